@@ -6,12 +6,16 @@ one superblock MatMult (the Sz-sector block-sparse Kronecker apply, == MatMult_K
 reorthogonalisation passes and the amortised thick restart.  Inputs (operators, vectors) are resident in HBM
 before the timed region.  value = MatMults/s of the whole job (all ranks work on ONE superblock: strong scaling).
 
-  python bench.py --gpus N --steps K --warmup W [--workload cfg4]
+  python bench.py --gpus N --steps K --warmup W [--workload cfg4] [--dump-outputs DIR] [--full]
   N > 1: launched by torch.distributed.run, one rank per GPU, RCCL all-gather / all-reduce over xGMI.
 
-The JSON line also carries `roofline` (dominant kernel = the grouped MFMA-f64 GEMM, timed with HIP events on
-its own stream inside the timed region) and `cpu_baseline` (the oracle's literal restatement of the
-reference's row loop, timed on this host's cores on a bounded row sample; N = 1, rank 0 only).
+A plain run sets up, warms up, times the K steps and prints the JSON line; it also carries `roofline` (dominant
+kernel = the grouped MFMA-f64 GEMM, timed with HIP events on its own stream inside the timed region).
+--dump-outputs DIR: after the timed steps, what the timed eigensolve returned (Ritz value, residual, Ritz vector in
+the reference's vector layout; a fixed seeded sample of the vector above DUMP_MAX_VALUES entries) as DIR/<name>.npy.
+--full adds everything that needs runs of its own: `matmult_isolated_per_s`, `cpu_baseline` (the factored CPU
+statement and the oracle's literal restatement of the reference's row loop, timed on this host's cores on a bounded
+row sample, both checked against the GPU MatMult; N = 1, rank 0 only) and the engine's sweep legs (`sweep`).
 """
 import argparse
 import json
@@ -27,6 +31,7 @@ sys.path.insert(0, ROOT)
 F64_PEAK_TFLOPS = 78.6   # MI355X dense f64 MFMA peak (AMD datasheet; v_mfma_f64_16x16x4 = 64 cycles/SIMD measured:
                          # 72-75 TF/s sustained at the clock the chip holds, profiles/r01_mfma_f64_probe.txt)
 HBM_PEAK_TBS = 8.0
+DUMP_MAX_VALUES = 4 << 20   # --dump-outputs: at most 32 MB of float64 per vector
 
 
 def cpu_baseline(sb, budget_s=15.0, gpu_apply=None):
@@ -351,6 +356,24 @@ def kernel_source_hash():
     return h.hexdigest()[:16]
 
 
+def dump_outputs(d, plan, e0, psi, stats):
+    """What the timed eigensolve returned, as float64 .npy files: e0 (Ritz value), residual (||H psi - e0 psi||) and psi in the
+    reference's vector layout -- psi.npy in full, or psi_sample.npy at DUMP_MAX_VALUES positions drawn with a fixed seed (sorted)."""
+    os.makedirs(d, exist_ok=True)
+    v = psi[:plan.info.n_states]                 # one rank: the layouts coincide
+    if plan.world_size > 1:
+        v = torch.empty(plan.info.n_states, dtype=torch.float64, device=psi.device)
+        plan.from_striped(psi, v)
+    v = v.cpu().numpy()
+    np.save(os.path.join(d, "e0.npy"), np.array([e0], dtype=np.float64))
+    np.save(os.path.join(d, "residual.npy"), np.array([stats.residual], dtype=np.float64))
+    if v.size > DUMP_MAX_VALUES:
+        idx = np.sort(np.random.default_rng(0).choice(v.size, DUMP_MAX_VALUES, replace=False))
+        np.save(os.path.join(d, "psi_sample.npy"), v[idx])
+    else:
+        np.save(os.path.join(d, "psi.npy"), v)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` as a plain command: start the N rank processes ourselves (what torch.distributed.run would
     do: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT), relay rank 0's JSON line, exit with the worst return code.
@@ -370,7 +393,7 @@ def launch_ranks(n):
     for p in procs[1:]:
         rc = p.wait() or rc
     text = out0.decode()
-    if rc == 0 and "--no-sweep" not in sys.argv:
+    if rc == 0 and "--full" in sys.argv and "--no-sweep" not in sys.argv:
         lines = text.strip().splitlines()
         try:
             line = json.loads(lines[-1])
@@ -392,9 +415,14 @@ def main():
     ap.add_argument("--workload", default="cfg4real", help="cfg4real (default: BASELINE configs[3], J1-J2 20x8, m=2048, on the sector tables of a real "
                     "mid-sweep step of the engine) | cfg1..cfg5 (SURVEY 8d's synthetic sigma=1.8 sector profile)")
     ap.add_argument("--ncv", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the engine legs (sites/sec per sweep, E0 rel-err)")
+    ap.add_argument("--full", action="store_true", help="also measure what needs runs of its own: the isolated MatMult rate, the CPU "
+                    "baselines with their parity checks and the engine legs (sites/sec per sweep, E0 rel-err)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: skip the engine legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed eigensolve returned in its last step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")     # dmabuf IPC for RCCL; must be in place before the first HIP call
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -446,7 +474,7 @@ def main():
     barrier()
     plan.timing(True)
     t0 = time.perf_counter()
-    _, _, stats = plan.eigs_lowest(ncv=args.ncv, tol=1e-300, seed=2, max_matvec=args.steps, **hooks)
+    e0, psi, stats = plan.eigs_lowest(ncv=args.ncv, tol=1e-300, seed=2, max_matvec=args.steps, **hooks)
     barrier()
     elapsed = time.perf_counter() - t0
     plan.timing(False)
@@ -466,19 +494,24 @@ def main():
         kernel, avg_ms, flops_per_launch = "dmrgx::ggemm_kernel_64", (ms4[1] + ms4[3]) / max(launches, 1), info.flops_alg / 2.0
     achieved = flops_per_launch / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
     gemm_all = info.flops_alg / max((ms1 + ms2) / max(napp, 1) * 1e-3, 1e-12) / 1e12     # all four GEMM launches together
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, plan, e0, psi, stats)
+    del psi
 
-    # K1 in isolation (MatMult only, no Lanczos vector work)
-    x = torch.randn(info.vec_len, dtype=torch.float64, device="cuda")
-    y = torch.zeros(info.vec_len, dtype=torch.float64, device="cuda")
-    yl = y[info.local_offset:info.local_offset + info.local_len]
-    for _ in range(3):
-        plan.apply(x, yl)
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(20):
-        plan.apply(x, yl)
-    barrier()
-    iso = 20 / (time.perf_counter() - t1)
+    iso = None
+    if args.full:
+        # K1 in isolation (MatMult only, no Lanczos vector work)
+        x = torch.randn(info.vec_len, dtype=torch.float64, device="cuda")
+        y = torch.zeros(info.vec_len, dtype=torch.float64, device="cuda")
+        yl = y[info.local_offset:info.local_offset + info.local_len]
+        for _ in range(3):
+            plan.apply(x, yl)
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(20):
+            plan.apply(x, yl)
+        barrier()
+        iso = 20 / (time.perf_counter() - t1)
 
     out = {
         "metric": "superblock MatMults/sec inside the ground-state eigensolve (Lanczos step = 1 MatMult + reorthogonalisation)",
@@ -516,7 +549,7 @@ def main():
             else:
                 out["roofline"]["traffic_source"] = ("profiles/traffic.json was measured on other kernel / plan sources (hash %s, running %s): not quoted; "
                                                      "regenerate with tools/profile.sh + tools/make_traffic_json.py" % (t.get("source_hash"), kernel_source_hash()))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # two CPU statements of the same MatMult on this host: the factored, operator-merged form -- the same
         # algorithm as the HIP plan, so value / cpu_baseline.value is hardware against hardware -- and beside it the literal
         # unfactored row loop the reference executes (sampled rows, extrapolated by its exact flop count)
@@ -541,7 +574,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     torch.cuda.empty_cache()                     # the engine legs below run in child processes on the same GPU(s)
-    if rank == 0 and not args.no_sweep and not (world > 1 and os.environ.get("DMRGX_BENCH_LAUNCHER") == "1"):
+    if rank == 0 and args.full and not args.no_sweep and not (world > 1 and os.environ.get("DMRGX_BENCH_LAUNCHER") == "1"):
         # sites/sec per sweep on the real engine: one rank -> the full set of legs; N ranks -> the configs[3] engine leg on N ranks
         # (and configs[2] for N = 2).  Started by `python bench.py --gpus N` the launcher process runs the N-rank legs after all ranks
         # have exited; under torch.distributed.run rank 0 does, after giving its siblings a moment to leave their GPUs.

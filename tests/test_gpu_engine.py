@@ -681,7 +681,7 @@ def test_bench_multi_rank_control_flow_rehearsal():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update(DMRGX_BENCH_REHEARSAL="1", PYTHONPATH=ROOT)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "24", "--warmup", "8", "--workload", "cfg2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "24", "--warmup", "8", "--workload", "cfg2", "--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
@@ -699,3 +699,32 @@ def test_bench_multi_rank_control_flow_rehearsal():
     bd = sw["step_breakdown_ms"]
     assert bd["t_allgather_ms"] > 0 and bd["t_apply_ms"] > 0 and bd["t_rdm_ms"] > 0 and bd["t_replicated_ms"] > 0, bd
     assert bd["t_allgather_ms"] + bd["t_apply_ms"] <= 1.05 * bd["t_solve_ms"] and bd["t_solve_ms"] + bd["t_rdm_ms"] <= 1.001 * bd["t_step_ms"], bd
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path, pkg):
+    """`python bench.py` without --full: one JSON line from the timed steps alone (no CPU baselines, isolated MatMult or engine legs),
+    and --dump-outputs writes what the timed eigensolve returned, checked against the CPU oracle's MatMult: psi is a unit vector in the
+    reference's layout, e0 its Rayleigh quotient and `residual` the norm of H psi - e0 psi."""
+    import sys
+    from dmrgx_amd.workloads import synthetic_superblock
+    from oracle.kron_factored import FactoredApplyCPU
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    d = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "4", "--workload", "cfg2", "--dump-outputs", str(d)]
+    p = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r["steps"] == 40 and r["warmup"] == 4 and r["n_gpus"] == 1 and r["unit"] == "MatMults/s" and r["dtype"] == "f64" and r["higher_is_better"] is True
+    assert r["value"] > 0 and abs(r["value"] * r["ms_per_step"] / 1e3 - 1.0) < 1e-9 and r["roofline"]["achieved"] > 0
+    assert r["cpu_baseline"] is None and r["matmult_isolated_per_s"] is None and "sweep" not in r
+    assert sorted(os.listdir(d)) == ["e0.npy", "psi.npy", "residual.npy"]
+    e0, res, psi = (np.load(d / (n + ".npy")) for n in ("e0", "residual", "psi"))
+    assert e0.dtype == res.dtype == psi.dtype == np.float64 and e0.shape == res.shape == (1,)
+    sb = synthetic_superblock("cfg2")
+    assert psi.shape == (sb.n_states,) and abs(np.linalg.norm(psi) - 1.0) < 1e-12
+    hpsi = FactoredApplyCPU(sb).apply(psi)
+    e0, res = float(e0[0]), float(res[0])
+    assert abs(float(psi @ hpsi) - e0) <= 1e-10 * abs(e0)
+    assert abs(float(np.linalg.norm(hpsi - e0 * psi)) - res) <= 1e-8 * abs(e0) + 1e-6 * res

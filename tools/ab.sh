@@ -7,7 +7,7 @@
 #   tools/ab.sh opts "optsA" "optsB" ...      the current build on configs[3] with several engine option sets (AB_NSWEEPS=1), twice, alternating
 #   tools/ab.sh c2opts "optsA" "optsB" ...    the same on configs[1] (12 sweeps: first sweep and the mean of sweeps 3-12)
 #   tools/ab.sh env "A=1,B=2" "-" ...         the current build on configs[3] under several environment settings ("-": none)
-#   tools/ab.sh bench NAME1 NAME2 ... [-- bench args]   bench.py --no-sweep --no-cpu-baseline with the library of each saved build (DMRGX_LIB), twice, alternating
+#   tools/ab.sh bench NAME1 NAME2 ... [-- bench args]   bench.py --full --no-sweep --no-cpu-baseline with the library of each saved build (DMRGX_LIB), twice, alternating
 set -o pipefail
 root=$(pwd); cmd=$1; shift
 c4="-Lx 20 -Ly 8 -J1 1 -Jz1 1 -J2 0.5 -Jz2 0.5 -mwarmup 2048 -nsweeps ${AB_NSWEEPS:-1} -H_eps_type gd"
@@ -45,7 +45,7 @@ env) out=$root/gpurun_out/ab_env; for rep in 1 2; do i=0; for e in "$@"; do i=$(
     ( [ "$e" = "-" ] || export $(echo $e | tr ',' ' '); run_engine $root/dmrg.x_amd/dmrgx-square-lattice $out/v$i "$c4" ) || exit 1; report $out/v$i "$e" $rep 156; done; done;;
 bench) names=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do names+=("$1"); shift; done; [ "$1" = "--" ] && shift
   for rep in 1 2; do for v in "${names[@]}"; do
-    DMRGX_LIB=$root/tools/ab/$v/libdmrgx_hip.so python3 bench.py --no-sweep --no-cpu-baseline "$@" 2>/dev/null | python3 -c "
+    DMRGX_LIB=$root/tools/ab/$v/libdmrgx_hip.so python3 bench.py --full --no-sweep --no-cpu-baseline "$@" 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('[$v] rep$rep: value %.1f MatMults/s  isolated %.1f  frac %.4f  stage1 %.4f ms  stage2 %.4f ms'%(d['value'],d['matmult_isolated_per_s'],r['frac'],r['stage1_ms_per_matmult'],r['stage2_ms_per_matmult']))"
   done; done;;
