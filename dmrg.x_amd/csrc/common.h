@@ -57,6 +57,10 @@ inline int32_t stripe_cut(int32_t n, int32_t W, int32_t w)
 hipError_t pool_malloc(void** out, size_t bytes);
 hipError_t pool_free(void* p);
 hipError_t zero_async(void* p, size_t bytes, hipStream_t st);
+// DMRGX_POOL_POISON=1 (read once): f64 workspaces are handed out filled with this quiet NaN ("BAD" payload), see pool.hip
+constexpr uint64_t POISON_F64_BITS = 0x7ff8badbadbadbadull;
+bool pool_poison();
+hipError_t poison_f64_async(void* p, size_t bytes, hipStream_t st);
 void pool_stats(size_t* in_use, size_t* cached, size_t* peak);
 hipError_t h2d_async(void* dst, const void* src, size_t bytes, hipStream_t st);   // pinned-ring staged, never blocks on the copy
 
@@ -79,6 +83,12 @@ struct DevBuf {
         hipError_t e = pool_malloc(&p, n);
         if (e != hipSuccess) { p = nullptr; set_error("hipMalloc(%zu) failed: %s", n, hipGetErrorString(e)); return DMRGX_ERR_MEM; }
         bytes = n;
+        return DMRGX_OK;
+    }
+    // `count` doubles of f64 payload only (never an index, a task table or a status word): poisoned on `st` under DMRGX_POOL_POISON=1
+    dmrgx_status alloc_f64(size_t count, hipStream_t st) {
+        DMRGX_CHK(alloc(count * sizeof(double)));
+        if (p && pool_poison()) DMRGX_HIP(poison_f64_async(p, bytes, st));
         return DMRGX_OK;
     }
     void release() { if (p && owned) (void)pool_free(p); p = nullptr; bytes = 0; owned = true; }

@@ -707,15 +707,15 @@ extern "C" dmrgx_status dmrgx_eigs_lowest(dmrgx_kron_plan* plan, const dmrgx_eig
     const auto t_begin = std::chrono::steady_clock::now();
 
     DevBuf dV, dW, dX, dTmp, dPartial, dScal, dQ;
-    DMRGX_CHK(dV.alloc((size_t)(m + 1) * n * sizeof(double)));
-    DMRGX_CHK(dW.alloc((size_t)n * sizeof(double)));
-    DMRGX_CHK(dTmp.alloc((size_t)(m / 2 + 2) * n * sizeof(double)));
-    if (dist) DMRGX_CHK(dX.alloc((size_t)I.vec_len * sizeof(double)));
-    DMRGX_CHK(dPartial.alloc((size_t)(MAX_NCV + DOT_CHUNK + 1) * DOT_BLOCKS * sizeof(double)));
+    DMRGX_CHK(dV.alloc_f64((size_t)(m + 1) * n, st));
+    DMRGX_CHK(dW.alloc_f64((size_t)n, st));
+    DMRGX_CHK(dTmp.alloc_f64((size_t)(m / 2 + 2) * n, st));
+    if (dist) DMRGX_CHK(dX.alloc_f64((size_t)I.vec_len, st));
+    DMRGX_CHK(dPartial.alloc_f64((size_t)(MAX_NCV + DOT_CHUNK + 1) * DOT_BLOCKS, st));
     // scalars: per step j a row of (m+2) doubles: h_j[0..m] accumulated coefficients, slot m+1: beta_j^2 ; + scratch c[]
     const int row = m + 2;
-    DMRGX_CHK(dScal.alloc((size_t)((m + 1) * row + 3 * (MAX_NCV + 2)) * sizeof(double)));
-    DMRGX_CHK(dQ.alloc((size_t)MAX_NCV * MAX_NCV * sizeof(double)));
+    DMRGX_CHK(dScal.alloc_f64((size_t)((m + 1) * row + 3 * (MAX_NCV + 2)), st));
+    DMRGX_CHK(dQ.alloc_f64((size_t)MAX_NCV * MAX_NCV, st));
     double* V = dV.as<double>();
     double* w = dW.as<double>();
     double* c1 = dScal.as<double>() + (size_t)(m + 1) * row;      // [nv+1]: V^T w, w.w
@@ -998,14 +998,14 @@ static dmrgx_status eigs_davidson(dmrgx_kron_plan* plan, const dmrgx_eigs_opts* 
     };
     mark("enter");
     DevBuf dV, dW, dT, dX, dD, dTmp, dPartial, dScal, dState;
-    DMRGX_CHK(dV.alloc((size_t)(m + 1) * ld * sizeof(double)));
-    DMRGX_CHK(dW.alloc((size_t)(m + 1) * ld * sizeof(double)));
-    DMRGX_CHK(dT.alloc((size_t)ld * sizeof(double)));
-    DMRGX_CHK(dD.alloc((size_t)ld * sizeof(double)));
-    DMRGX_CHK(dTmp.alloc((size_t)kk * ld * sizeof(double)));
-    if (dist) DMRGX_CHK(dX.alloc((size_t)I.vec_len * sizeof(double)));
-    DMRGX_CHK(dPartial.alloc((size_t)(MAX_NCV + DOT_CHUNK + 2) * DOT_BLOCKS * sizeof(double)));
-    DMRGX_CHK(dScal.alloc((size_t)(3 * (MAX_NCV + 2)) * sizeof(double)));
+    DMRGX_CHK(dV.alloc_f64((size_t)(m + 1) * ld, st));
+    DMRGX_CHK(dW.alloc_f64((size_t)(m + 1) * ld, st));
+    DMRGX_CHK(dT.alloc_f64((size_t)ld, st));
+    DMRGX_CHK(dD.alloc_f64((size_t)ld, st));
+    DMRGX_CHK(dTmp.alloc_f64((size_t)kk * ld, st));
+    if (dist) DMRGX_CHK(dX.alloc_f64((size_t)I.vec_len, st));
+    DMRGX_CHK(dPartial.alloc_f64((size_t)(MAX_NCV + DOT_CHUNK + 2) * DOT_BLOCKS, st));
+    DMRGX_CHK(dScal.alloc_f64((size_t)(3 * (MAX_NCV + 2)), st));
     DMRGX_CHK(dState.alloc(sizeof(GdState)));
     double* V = dV.as<double>();
     double* W = dW.as<double>();

@@ -57,12 +57,13 @@ struct CopyTile { int32_t task, ti, tj, pad; };
 
 // The column segments of the intermediates T_{g,k} that no right-operator cell reaches are read by stage 2 as zeros: they are the only part of
 // the arena that is zeroed (round 5; rounds 1-4 zeroed the whole arena -- 1.4 GB at m = 2048 -- and added every operator into it)
+// (one rectangle per blockIdx.x, its chunks over blockIdx.y: a plan can hold far more rectangles than the grid's y limit of 65535)
 struct ZeroRect { int64_t off; int32_t ld, nr, nc, pad; };
 __global__ void __launch_bounds__(256) zero_rects_kernel(const ZeroRect* __restrict__ rects, double* __restrict__ arena)
 {
-    const ZeroRect r = rects[blockIdx.y];
+    const ZeroRect r = rects[blockIdx.x];
     const int64_t n = (int64_t)r.nr * r.nc;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) arena[r.off + (e / r.nc) * r.ld + e % r.nc] = 0.0;
+    for (int64_t e = (int64_t)blockIdx.y * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.y * 256) arena[r.off + (e / r.nc) * r.ld + e % r.nc] = 0.0;
 }
 
 __global__ void __launch_bounds__(256)
@@ -670,7 +671,9 @@ extern "C" dmrgx_status dmrgx_kron_plan_create(const dmrgx_kron_desc* d, void* s
     ggemm_schedule(B.tiles2, B.groups);
     ggemm_schedule(B.tiles1b, B.groups, 2);
     ggemm_schedule(B.tiles2b, B.groups, 2);
-    if (const char* dump = getenv("DMRGX_PLAN_DUMP")) {   // developer aid: scheduled tile lists, one line per tile
+    // developer aid and test evidence: scheduled tile lists, one line per tile; then one line per zero rectangle of the intermediates
+    // ("zr i off ld nr nc") and one per split-K reduction task ("red i dst_off slab_off ldc M N nslab")
+    if (const char* dump = getenv("DMRGX_PLAN_DUMP")) {
         if (FILE* f = fopen(dump, "w")) {
             auto put = [&](const char* name, const std::vector<GTile>& tl) {
                 for (size_t i = 0; i < tl.size(); ++i) {
@@ -681,6 +684,14 @@ extern "C" dmrgx_status dmrgx_kron_plan_create(const dmrgx_kron_desc* d, void* s
                 }
             };
             put("s1", B.tiles1); put("s2", B.tiles2); put("s1b", B.tiles1b); put("s2b", B.tiles2b);
+            for (size_t i = 0; i < zero_rects.size(); ++i) {
+                const ZeroRect& z = zero_rects[i];
+                fprintf(f, "zr %zu %lld %d %d %d\n", i, (long long)z.off, z.ld, z.nr, z.nc);
+            }
+            for (size_t i = 0; i < B.red_tasks.size(); ++i) {
+                const RedTask& r = B.red_tasks[i];
+                fprintf(f, "red %zu %lld %lld %d %d %d %d\n", i, (long long)r.dst_off, (long long)r.slab_off, r.ldc, r.M, r.N, r.nslab);
+            }
             fclose(f);
         }
     }
@@ -690,7 +701,7 @@ extern "C" dmrgx_status dmrgx_kron_plan_create(const dmrgx_kron_desc* d, void* s
     if (!P) DMRGX_FAIL(DMRGX_ERR_MEM, "out of host memory");
     std::unique_ptr<dmrgx_kron_plan> guard(P);
     P->world = W; P->rank = me;
-    DMRGX_CHK(P->arena.alloc((size_t)std::max<int64_t>(arena_ops + arena_T + arena_slabs, 1) * sizeof(double)));
+    DMRGX_CHK(P->arena.alloc_f64((size_t)std::max<int64_t>(arena_ops + arena_T + arena_slabs, 1), st));
     P->n_red_tiles = (int32_t)B.red_tiles.size();
     {   // operator copies, one launch per accumulation round (round 0 writes); the unreached segments of the intermediates are zeroed.
         // Nothing else of the arena is read before it is written: every dense operator cell has a round-0 copy, stage 1 writes the reached
@@ -714,7 +725,8 @@ extern "C" dmrgx_status dmrgx_kron_plan_create(const dmrgx_kron_desc* d, void* s
         if (!zero_rects.empty()) {
             int64_t big = 1;
             for (const ZeroRect& r : zero_rects) big = std::max(big, (int64_t)r.nr * r.nc);
-            hipLaunchKernelGGL(zero_rects_kernel, dim3((unsigned)std::min<int64_t>((big + 2047) / 2048, 512), (unsigned)zero_rects.size()), dim3(256), 0, st,
+            if (zero_rects.size() >= ((size_t)1 << 23)) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_plan: %zu zero rectangles exceed the launch grid", zero_rects.size());
+            hipLaunchKernelGGL(zero_rects_kernel, dim3((unsigned)zero_rects.size(), (unsigned)std::min<int64_t>((big + 2047) / 2048, 512)), dim3(256), 0, st,
                                (const ZeroRect*)packed_at<ZeroRect>(d_tab, o_zero), P->arena.as<double>());
             DMRGX_HIP(hipGetLastError());
         }

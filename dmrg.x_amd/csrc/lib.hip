@@ -109,6 +109,10 @@ extern "C" dmrgx_status dmrgx_malloc(void** p, size_t bytes)
     if (bytes == 0) return DMRGX_OK;
     hipError_t e = dmrgx::pool_malloc(p, bytes);
     if (e != hipSuccess) { *p = nullptr; DMRGX_FAIL(DMRGX_ERR_MEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); }
+    if (dmrgx::pool_poison()) {                       // (the engine's SectorMat values: f64 only; no stream here, so the null stream and a wait)
+        DMRGX_HIP(dmrgx::poison_f64_async(*p, bytes, nullptr));
+        DMRGX_HIP(hipStreamSynchronize(nullptr));
+    }
     return DMRGX_OK;
 }
 extern "C" dmrgx_status dmrgx_mem_stats(size_t* in_use, size_t* cached, size_t* peak_in_use)
@@ -159,7 +163,7 @@ extern "C" dmrgx_status dmrgx_dot_async(int64_t n, const double* x_dev, const do
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) { DMRGX_HIP(zero_async(dev_out, sizeof(double), st)); return DMRGX_OK; }
     DevBuf part;                                      // returned to the pool on exit; recycling is stream-ordered
-    DMRGX_CHK(part.alloc(dmrgx::VDOT_BLOCKS * sizeof(double)));
+    DMRGX_CHK(part.alloc_f64(dmrgx::VDOT_BLOCKS, st));
     hipLaunchKernelGGL(dmrgx::vdot_partial_kernel, dim3(dmrgx::VDOT_BLOCKS), dim3(dmrgx::VDOT_THREADS), 0, st, x_dev, y_dev, n, part.as<double>());
     hipLaunchKernelGGL(dmrgx::vdot_final_kernel, dim3(1), dim3(64), 0, st, (const double*)part.as<double>(), dev_out);
     DMRGX_HIP(hipGetLastError());
@@ -173,7 +177,7 @@ extern "C" dmrgx_status dmrgx_dot(int64_t n, const double* x_dev, const double* 
     if (n == 0) return DMRGX_OK;
     hipStream_t st = (hipStream_t)stream;
     DevBuf part;
-    DMRGX_CHK(part.alloc(dmrgx::VDOT_BLOCKS * sizeof(double)));
+    DMRGX_CHK(part.alloc_f64(dmrgx::VDOT_BLOCKS, st));
     hipLaunchKernelGGL(dmrgx::vdot_partial_kernel, dim3(dmrgx::VDOT_BLOCKS), dim3(dmrgx::VDOT_THREADS), 0, st, x_dev, y_dev, n, part.as<double>());
     DMRGX_HIP(hipGetLastError());
     std::vector<double> h(dmrgx::VDOT_BLOCKS);
@@ -239,7 +243,7 @@ extern "C" dmrgx_status dmrgx_dot2d_batch(int32_t count, const dmrgx_dot2d_task*
     }
     first.push_back((int32_t)pieces.size());
     DevBuf tab, dpart;
-    DMRGX_CHK(dpart.alloc(std::max<size_t>(pieces.size(), 1) * sizeof(double)));
+    DMRGX_CHK(dpart.alloc_f64(std::max<size_t>(pieces.size(), 1), st));
     dmrgx::PackedUpload pk;
     const size_t opc = pk.add(pieces), oo = pk.add(outs), of = pk.add(first);
     DMRGX_CHK(pk.upload(tab, st));

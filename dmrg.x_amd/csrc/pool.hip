@@ -7,6 +7,9 @@
 // a block freed while work is still queued is only overwritten by work queued later ON THE SAME STREAM.  The engine and the
 // Python wrappers use one stream (the null stream); a caller that moves between streams synchronises in between
 // (dmrgx_stream_sync) -- see include/dmrgx.h.  DMRGX_POOL=0 disables caching (every free is a hipFree again).
+// DMRGX_POOL_POISON=1 (test switch): every block that holds only f64 payload (DevBuf::alloc_f64, dmrgx_malloc) is filled with a quiet
+// NaN each time it is handed out, fresh or recycled, so that a read of a location nobody wrote shows up as a NaN in the result instead
+// of as the zero that a fresh block usually holds.  Index tables, task lists and status words are never poisoned.
 #include "common.h"
 #include <chrono>
 #include <cstring>
@@ -61,9 +64,17 @@ struct Pool {
 };
 Pool& pool() { static Pool* p = new Pool(); return *p; }    // leaked on purpose: no teardown order issues with the HIP runtime
 
-__global__ void __launch_bounds__(256) zero_kernel(uint64_t* __restrict__ p, size_t n)
+__global__ void __launch_bounds__(256) fill_kernel(uint64_t* __restrict__ p, size_t n, uint64_t v)
 {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = v;
+}
+
+hipError_t fill_async(void* p, size_t bytes, uint64_t v, hipStream_t st)     // bytes: a multiple of 8, p 8-byte aligned
+{
+    const size_t n = bytes / 8;
+    const unsigned grid = (unsigned)std::min<size_t>(2048, (n + 255) / 256);
+    hipLaunchKernelGGL(fill_kernel, dim3(grid), dim3(256), 0, st, (uint64_t*)p, n, v);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -186,10 +197,20 @@ hipError_t zero_async(void* p, size_t bytes, hipStream_t st)
 {
     if (bytes == 0) return hipSuccess;
     if (((uintptr_t)p & 7) || (bytes & 7)) return hipMemsetAsync(p, 0, bytes, st);
-    const size_t n = bytes / 8;
-    const unsigned grid = (unsigned)std::min<size_t>(2048, (n + 255) / 256);
-    hipLaunchKernelGGL(zero_kernel, dim3(grid), dim3(256), 0, st, (uint64_t*)p, n);
-    return hipGetLastError();
+    return fill_async(p, bytes, 0, st);
+}
+
+bool pool_poison()
+{
+    static const bool on = getenv("DMRGX_POOL_POISON") && atoi(getenv("DMRGX_POOL_POISON")) != 0;
+    return on;
+}
+
+hipError_t poison_f64_async(void* p, size_t bytes, hipStream_t st)
+{
+    bytes &= ~(size_t)7;                              // (whole doubles only; pool blocks are 256-byte aligned)
+    if (bytes == 0 || ((uintptr_t)p & 7)) return hipSuccess;
+    return fill_async(p, bytes, POISON_F64_BITS, st);
 }
 
 }  // namespace dmrgx

@@ -646,7 +646,7 @@ static dmrgx_status rdm_create_impl(const dmrgx_sectors* left, const dmrgx_secto
     }
     std::vector<int64_t> warm_w(nm, -1), warm_et(nm, -1);
     for (int mi = 0; mi < nm; ++mi) if (warm_src[mi] || qmats[mi].n) { const int64_t nn = (int64_t)P->mats[mi].n * P->mats[mi].n; warm_w[mi] = total; total += nn; warm_et[mi] = total; total += nn; }
-    DMRGX_CHK(P->buf.alloc((size_t)total * sizeof(double)));
+    DMRGX_CHK(P->buf.alloc_f64((size_t)total, st));
     double* buf = P->buf.as<double>();
     // ---- tables of the set-up (matrix descriptors, Jacobi pair lists, transposition tiles, the Gram GEMMs) in ONE upload ----------
     DevBuf d_pairs, d_tiles, d_doff, d_pstart;          // views into P->d_tables

@@ -140,7 +140,7 @@ extern "C" dmrgx_status dmrgx_rotate_ops(const dmrgx_sectors* old_sectors, const
         }
     }
     DevBuf ws;
-    DMRGX_CHK(ws.alloc((size_t)std::max<int64_t>(ut_off[nn] + wtot, 1) * sizeof(double)));
+    DMRGX_CHK(ws.alloc_f64((size_t)std::max<int64_t>(ut_off[nn] + wtot, 1), st));
     double* UT = ws.as<double>();
     double* W = UT + ut_off[nn];
     {

@@ -1184,7 +1184,7 @@ dmrgx_status symeig_batched(const std::vector<SymEigMat>& mats_in, hipStream_t s
         w.ints = itot; itot += NINT * n;
     }
     DevBuf dbuf, ibuf;
-    DMRGX_CHK(dbuf.alloc((size_t)dtot * sizeof(double)));
+    DMRGX_CHK(dbuf.alloc_f64((size_t)dtot, st));
     DMRGX_CHK(ibuf.alloc((size_t)itot * sizeof(int32_t)));
     double* B = dbuf.as<double>();
     int32_t* I = ibuf.as<int32_t>();

@@ -68,7 +68,8 @@ class KronPlan:
         terms = (_capi.Term * max(len(sb.terms), 1))()
         for i, t in enumerate(sb.terms):
             terms[i].a, terms[i].left_op, terms[i].right_op = t[0], li[(t[1], t[2])], ri[(t[3], t[4])]
-        hl, hr = secop(sb.h_left), secop(sb.h_right)
+        hl = secop(sb.h_left) if sb.h_left is not None else None          # (None: no H_L / H_R term, a NULL in the descriptor)
+        hr = secop(sb.h_right) if sb.h_right is not None else None
         d = _capi.KronDesc()
         ls, rs = _i32(sb.left_sizes), _i32(sb.right_sizes)
         bil, bir = _i32([b[0] for b in sb.blocks]), _i32([b[1] for b in sb.blocks])
@@ -76,7 +77,8 @@ class KronPlan:
         d.right.nsec, d.right.size = len(sb.right_sizes), rs
         d.nblocks, d.block_il, d.block_ir = len(sb.blocks), bil, bir
         d.n_left_ops, d.n_right_ops, d.left_ops, d.right_ops = nl, nr, larr, rarr
-        d.h_left, d.h_right = C.pointer(hl), C.pointer(hr)
+        d.h_left = C.pointer(hl) if hl is not None else None
+        d.h_right = C.pointer(hr) if hr is not None else None
         d.nterms, d.terms = len(sb.terms), terms
         d.world_size, d.rank = world_size, rank
         self._handle = C.c_void_p()
@@ -188,6 +190,9 @@ class ReducedDensityMatrices:
         sl, sr = _capi.Sectors(len(left_sizes), ls), _capi.Sectors(len(right_sizes), rs)
         bil, bir = _i32([b[0] for b in blocks]), _i32([b[1] for b in blocks])
         self._handle = C.c_void_p()
+        # the library keeps only psi's address and reads psi again when the eigenvectors are formed (dmrgx_rdm_select or the first
+        # request): a temporary tensor would go back to torch's allocator and be handed out again before then
+        self._psi = psi
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         if warm:
             ptrs = (C.c_void_p * (2 * len(blocks)))()
@@ -214,6 +219,7 @@ class ReducedDensityMatrices:
         """Second phase (dmrgx_rdm_select): form the eigenvectors of the counts[2*k + side] largest eigenvalues of every density matrix only."""
         arr = (C.c_int32 * (2 * len(self.blocks)))(*[int(c) for c in counts])
         _capi.check(_capi.lib().dmrgx_rdm_select(self._handle, arr, None))
+        self._psi = None                        # (read by work queued on the stream psi was allocated on: stream-ordered release)
 
     def eigenvectors_batch(self, requests):
         """requests: [(side, k, count), ...] -> list of (count, n) tensors, all gathered by ONE launch (dmrgx_rdm_eigenvectors_batch)."""
@@ -223,6 +229,7 @@ class ReducedDensityMatrices:
             outs.append(torch.empty((count, n), dtype=torch.float64, device="cuda"))
             tasks[i].side, tasks[i].k, tasks[i].count, tasks[i].dst_dev, tasks[i].ld = side, k, count, outs[-1].data_ptr(), n
         _capi.check(_capi.lib().dmrgx_rdm_eigenvectors_batch(self._handle, len(requests), tasks, None))
+        self._psi = None
         return outs
 
     def eigenvectors(self, side, k, count):
@@ -230,11 +237,14 @@ class ReducedDensityMatrices:
         dst = torch.empty((count, n), dtype=torch.float64, device="cuda")
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         _capi.check(_capi.lib().dmrgx_rdm_eigenvectors(self._handle, side, k, count, C.c_void_p(dst.data_ptr()), n, st))
+        if count > 0:                           # (a request of nothing forms nothing)
+            self._psi = None
         return dst
 
     def destroy(self):
         if self._handle:
             h, self._handle = self._handle, C.c_void_p()      # (the object is gone whatever the verdict of its verification)
+            self._psi = None
             _capi.check(_capi.lib().dmrgx_rdm_destroy(h))
 
     def __del__(self):

@@ -1,0 +1,71 @@
+"""Child process of tests/test_gpu_poison.py: runs fixed-input kernels and writes their outputs to an .npz file, so that runs in
+separate processes -- clean or with DMRGX_POOL_POISON=1 -- can be compared bit for bit.
+
+    python tests/bitwise_worker.py OUT.npz apply,solvers
+"""
+import hashlib
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from __graft_entry__ import load_package  # noqa: E402
+
+load_package()
+from dmrgx_amd import superblock as sbm, workloads as wl  # noqa: E402
+
+
+def full_size_applies(out):
+    """dmrgx_kron_apply on the full-size BASELINE superblocks: the digest of y (80 MB at cfg5) and its NaN count."""
+    for cfg in ("cfg4real", "cfg5"):
+        sb = wl.synthetic_superblock(cfg)
+        x = torch.from_numpy(np.random.default_rng(4242).standard_normal(sb.n_states)).cuda()
+        y = torch.full_like(x, float("nan"))
+        plan = sbm.KronPlan(sb)
+        plan.apply(x, y)
+        torch.cuda.synchronize()
+        h = y.cpu().numpy()
+        out["apply_%s_sha" % cfg] = np.frombuffer(hashlib.sha256(h.tobytes()).digest(), dtype=np.uint8)
+        out["apply_%s_nonfinite" % cfg] = np.array(int((~np.isfinite(h)).sum()))
+        plan.destroy()
+        del x, y
+
+
+def solvers(out):
+    """Lanczos and generalized Davidson (an odd and an even number of states) from fixed start vectors, and the density-matrix
+    spectra + eigenvectors of a fixed state."""
+    kept = {0.5: 7, -0.5: 6, 1.5: 3, -1.5: 2}
+    for tag, kw in (("even", dict(m=32, Ly=2, seed=3)), ("odd", dict(Ly=2, seed=3, kept=(kept, kept)))):      # 844 and 341 states
+        sb = wl.synthetic_superblock("cfg2", **kw)
+        plan = sbm.KronPlan(sb)
+        out["n_states_%s" % tag] = np.array(sb.n_states)
+        e0, psi, _ = plan.eigs_lowest(tol=1e-12, seed=9)
+        out["lanczos_%s_e0" % tag], out["lanczos_%s_psi" % tag] = np.array(e0), psi.cpu().numpy()
+        psi0 = torch.from_numpy(np.random.default_rng(1).standard_normal(sb.n_states)).cuda()
+        e0, psi, _ = plan.eigs_lowest(tol=1e-12, method=1, psi0=psi0, ncv=6)
+        out["gd_%s_e0" % tag], out["gd_%s_psi" % tag] = np.array(e0), psi.cpu().numpy()
+        plan.destroy()
+    rng = np.random.default_rng(5)
+    ls, rs = [300, 77], [120, 260]
+    psi = rng.standard_normal(300 * 120 + 77 * 260)
+    psi /= np.linalg.norm(psi)
+    rdm = sbm.ReducedDensityMatrices(ls, rs, [(0, 0), (1, 1)], torch.from_numpy(psi).cuda())
+    for k in range(2):
+        for side in (0, 1):
+            out["rdm_w_%d_%d" % (k, side)] = rdm.eigenvalues(side, k)
+            out["rdm_u_%d_%d" % (k, side)] = rdm.eigenvectors(side, k, rdm.size(side, k)).cpu().numpy()
+    rdm.destroy()
+
+
+if __name__ == "__main__":
+    path, what = sys.argv[1], sys.argv[2].split(",")
+    res = {}
+    if "apply" in what:
+        full_size_applies(res)
+    if "solvers" in what:
+        solvers(res)
+    np.savez(path, **res)
+    print("bitwise worker ok", sorted(res))

@@ -323,6 +323,40 @@ def test_large_m_step_by_step_against_the_oracle(tmp_path, ranks, extra):
         assert run["TridLaunchPathCalls"] == run["RdmCalls"] and run["TridPersistentCalls"] == 0, run      # (ranks sharing one GPU: no persistent kernel)
 
 
+def _assert_run_is_finite(tmp_path):
+    """Every number of DMRGRun.json is finite (no NaN / Infinity constant, no non-finite float)."""
+    bad = []
+    run = json.load(open(os.path.join(str(tmp_path), "DMRGRun.json")), parse_constant=lambda c: bad.append(c) or 0.0)
+
+    def walk(v):
+        if isinstance(v, dict):
+            for x in v.values():
+                walk(x)
+        elif isinstance(v, list):
+            for x in v:
+                walk(x)
+        elif isinstance(v, float) and not np.isfinite(v):
+            bad.append(v)
+    walk(run)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("ranks", [1, 2])
+def test_medium_m_step_by_step_on_poisoned_workspaces(tmp_path, monkeypatch, ranks):
+    """The step-by-step comparison with the oracle with every f64 workspace of the engine processes NaN-poisoned (DMRGX_POOL_POISON=1:
+    csrc/pool.hip), so that a kernel reading a location nobody wrote shows as a wrong or non-finite step instead of a lucky zero."""
+    monkeypatch.setenv("DMRGX_POOL_POISON", "1")
+    test_medium_m_step_by_step_against_the_oracle(tmp_path, "j1j2_8x4_sz1", ranks, ())
+    _assert_run_is_finite(tmp_path)
+
+
+def test_large_m_step_by_step_on_poisoned_workspaces(tmp_path, monkeypatch):
+    """The production-size density-matrix paths and the generalized-Davidson solver inside a sweep, on poisoned workspaces."""
+    monkeypatch.setenv("DMRGX_POOL_POISON", "1")
+    test_large_m_step_by_step_against_the_oracle(tmp_path, 1, ("-H_eps_type", "gd"))
+    _assert_run_is_finite(tmp_path)
+
+
 def test_medium_m_tables_cover_the_sizes_they_are_for():
     """(no GPU needed, but kept beside its test) >= 100 strictly compared steps at m >= 24, one run with sectors above 32"""
     g = _medium_golden()

@@ -4,7 +4,8 @@ import sys, heapq, collections
 rows = collections.defaultdict(list)
 for l in open(sys.argv[1]):
     f = l.split()
-    rows[f[0]].append(tuple(int(x) for x in f[1:]))
+    if f[0] in ("s1", "s2", "s1b", "s2b"):          # (the zero-rectangle and reduction lines are not tiles)
+        rows[f[0]].append(tuple(int(x) for x in f[1:]))
 c0 = float(sys.argv[2]) if len(sys.argv) > 2 else 3.0
 for name, tl in rows.items():
     if not tl: continue
