@@ -84,4 +84,51 @@ inline void ggemm_schedule(std::vector<GTile>& tiles, const GroupVec& groups, in
     ggemm_schedule_core(tiles, p0, unit);
 }
 
+// Host-side batch of grouped GEMMs, for every user outside the superblock MatMult: one product table, one group table and any number
+// of GemmSets, the tile lists of one dependent step.  pack() schedules a set's 128 x 128 list with unit 2 and its 64 x 64 list with
+// unit 1, launch() runs them with the matching kernel, 128 x 128 first.  The tables go into the caller's PackedUpload, beside whatever
+// else it sends in that copy.
+struct GemmSet {
+    std::vector<GTile> big, small;          // 128 x 128 core tiles, 64 x 64 edge tiles
+    size_t off_big = 0, off_small = 0;      // in the PackedUpload the set was packed into
+};
+struct GemmBatch {
+    std::vector<GProd> prods;
+    std::vector<GGroup> groups;
+    bool skip_empty_k = false;              // gemm() with K <= 0 adds nothing (else a group without products: C = 0 unless it accumulates)
+    size_t off_prods = 0, off_groups = 0;
+    const GProd* d_prods = nullptr;
+    const GGroup* d_groups = nullptr;
+
+    // group g, whose products [g.prod_begin, g.prod_end) are already pushed (AXPY products first), with its tiles in s; cost: k-steps
+    void group(GemmSet& s, const GGroup& g, int32_t cost) {
+        groups.push_back(g);
+        ggemm_append_tiles_mixed(s.big, s.small, (int32_t)groups.size() - 1, g.M, g.N, cost);
+    }
+    // C[M x N] (=|+=) A[M x K] B[K x N], a group of its own; nothing when M or N <= 0
+    void gemm(GemmSet& s, double* C, int32_t ldc, int32_t M, int32_t N, const double* A, int32_t lda, const double* B, int32_t ldb, int32_t K, int32_t accumulate = 0) {
+        if (M <= 0 || N <= 0 || (K <= 0 && skip_empty_k)) return;
+        const int32_t p0 = (int32_t)prods.size();
+        if (K > 0) prods.push_back(GProd{A, B, lda, ldb, K, GPROD_GEMM, 1.0});
+        group(s, GGroup{C, ldc, M, N, p0, (int32_t)prods.size(), 0, accumulate}, (K + GG_BK - 1) / GG_BK);
+    }
+    void pack(PackedUpload& pk) {           // the product and group tables (a dummy entry in an empty one)
+        if (prods.empty()) prods.push_back(GProd{nullptr, nullptr, 0, 0, 0, GPROD_GEMM, 0.0});
+        if (groups.empty()) groups.push_back(GGroup{nullptr, 0, 0, 0, 0, 0, 0, 0});
+        off_prods = pk.add(prods); off_groups = pk.add(groups);
+    }
+    void pack(GemmSet& s, PackedUpload& pk) const {     // schedules the lists of s and adds them: once, after the last group of s
+        ggemm_schedule(s.big, groups, 2); ggemm_schedule(s.small, groups);
+        s.off_big = pk.add(s.big); s.off_small = pk.add(s.small);
+    }
+    // tab: the upload of the PackedUpload that pack(pk) went into
+    void bind(const DevBuf& tab) { d_prods = packed_at<GProd>(tab, off_prods); d_groups = packed_at<GGroup>(tab, off_groups); }
+    // tab: the upload that s was packed into (need not be the one of the tables)
+    dmrgx_status launch(const GemmSet& s, const DevBuf& tab, hipStream_t st) const {
+        if (!d_groups) DMRGX_FAIL(DMRGX_ERR_INTERNAL, "GemmBatch::launch before bind");
+        DMRGX_CHK(ggemm_launch(packed_at<GTile>(tab, s.off_big), d_groups, d_prods, (int32_t)s.big.size(), st, 1));
+        return ggemm_launch(packed_at<GTile>(tab, s.off_small), d_groups, d_prods, (int32_t)s.small.size(), st, 0);
+    }
+};
+
 }  // namespace dmrgx

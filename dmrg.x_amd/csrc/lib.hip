@@ -50,56 +50,41 @@ extern "C" dmrgx_status dmrgx_stripe_bounds_of_block(int32_t n_right, int32_t wo
     return DMRGX_OK;
 }
 
+static bool bad_gemm_task(const dmrgx_gemm_task& g)
+{
+    return g.M < 0 || g.N < 0 || g.K < 0 || (g.M && g.N && (!g.C || g.ldc < g.N)) || (g.M && g.N && g.K && (!g.A || !g.B || g.lda < g.K || g.ldb < g.N));
+}
+
+// checked tasks in one grouped launch: tasks with M == 0 or N == 0 are skipped, K == 0 writes C = 0 (or leaves it, accumulating)
+static dmrgx_status run_gemm_tasks(int32_t count, const dmrgx_gemm_task* t, hipStream_t st)
+{
+    GemmBatch b;
+    GemmSet s;
+    for (int32_t i = 0; i < count; ++i)
+        b.gemm(s, t[i].C, (int32_t)t[i].ldc, t[i].M, t[i].N, t[i].A, (int32_t)t[i].lda, t[i].B, (int32_t)t[i].ldb, t[i].K, t[i].accumulate ? 1 : 0);
+    if (b.groups.empty()) return DMRGX_OK;
+    DevBuf tab;
+    PackedUpload pk;
+    b.pack(pk); b.pack(s, pk);
+    DMRGX_CHK(pk.upload(tab, st));
+    b.bind(tab);
+    return b.launch(s, tab, st);
+}
+
 extern "C" dmrgx_status dmrgx_dgemm_nn(int32_t M, int32_t N, int32_t K, const double* A, int64_t lda,
                                        const double* B, int64_t ldb, double* C, int64_t ldc, void* stream)
 {
-    hipStream_t st = (hipStream_t)stream;
-    if (M < 0 || N < 0 || K < 0 || (M && N && (!C || ldc < N)) || (M && N && K && (!A || !B || lda < K || ldb < N)))
-        DMRGX_FAIL(DMRGX_ERR_ARG, "dgemm_nn: bad argument (M=%d N=%d K=%d)", M, N, K);
-    if (M == 0 || N == 0) return DMRGX_OK;
-    std::vector<GProd> prods;
-    if (K > 0) prods.push_back(GProd{A, B, (int32_t)lda, (int32_t)ldb, K, GPROD_GEMM, 1.0});
-    std::vector<GGroup> groups = {GGroup{C, (int32_t)ldc, M, N, 0, (int32_t)prods.size(), 0, 0}};
-    std::vector<GTile> tiles, big;
-    ggemm_append_tiles_mixed(big, tiles, 0, M, N, (K + GG_BK - 1) / GG_BK);
-    ggemm_schedule(tiles, groups); ggemm_schedule(big, groups, 2);
-    if (prods.empty()) prods.push_back(GProd{nullptr, nullptr, 0, 0, 0, GPROD_GEMM, 0.0});
-    DevBuf tab;
-    PackedUpload pk;
-    const size_t op = pk.add(prods), og = pk.add(groups), ot = pk.add(tiles), ob = pk.add(big);
-    DMRGX_CHK(pk.upload(tab, st));
-    DMRGX_CHK(ggemm_launch(packed_at<GTile>(tab, ob), packed_at<GGroup>(tab, og), packed_at<GProd>(tab, op), (int32_t)big.size(), st, 1));
-    DMRGX_CHK(ggemm_launch(packed_at<GTile>(tab, ot), packed_at<GGroup>(tab, og), packed_at<GProd>(tab, op), (int32_t)tiles.size(), st, 0));
-    return DMRGX_OK;
+    const dmrgx_gemm_task g{M, N, K, 0, A, lda, B, ldb, C, ldc};
+    if (bad_gemm_task(g)) DMRGX_FAIL(DMRGX_ERR_ARG, "dgemm_nn: bad argument (M=%d N=%d K=%d)", M, N, K);
+    return run_gemm_tasks(1, &g, (hipStream_t)stream);
 }
 
 extern "C" dmrgx_status dmrgx_dgemm_batch(int32_t count, const dmrgx_gemm_task* t, void* stream)
 {
-    hipStream_t st = (hipStream_t)stream;
     if (count < 0 || (count > 0 && !t)) DMRGX_FAIL(DMRGX_ERR_ARG, "dgemm_batch: bad argument");
-    std::vector<GProd> prods;
-    std::vector<GGroup> groups;
-    std::vector<GTile> tiles, big;
-    for (int32_t i = 0; i < count; ++i) {
-        const dmrgx_gemm_task& g = t[i];
-        if (g.M < 0 || g.N < 0 || g.K < 0 || (g.M && g.N && (!g.C || g.ldc < g.N)) || (g.M && g.N && g.K && (!g.A || !g.B || g.lda < g.K || g.ldb < g.N)))
-            DMRGX_FAIL(DMRGX_ERR_ARG, "dgemm_batch: bad task %d (M=%d N=%d K=%d)", i, g.M, g.N, g.K);
-        if (g.M == 0 || g.N == 0) continue;
-        const int32_t p0 = (int32_t)prods.size();
-        if (g.K > 0) prods.push_back(GProd{g.A, g.B, (int32_t)g.lda, (int32_t)g.ldb, g.K, GPROD_GEMM, 1.0});
-        groups.push_back(GGroup{g.C, (int32_t)g.ldc, g.M, g.N, p0, (int32_t)prods.size(), 0, g.accumulate ? 1 : 0});
-        ggemm_append_tiles_mixed(big, tiles, (int32_t)groups.size() - 1, g.M, g.N, (g.K + GG_BK - 1) / GG_BK);
-    }
-    if (groups.empty()) return DMRGX_OK;
-    if (prods.empty()) prods.push_back(GProd{nullptr, nullptr, 0, 0, 0, GPROD_GEMM, 0.0});
-    ggemm_schedule(tiles, groups); ggemm_schedule(big, groups, 2);
-    DevBuf tab;
-    PackedUpload pk;
-    const size_t op = pk.add(prods), og = pk.add(groups), ot = pk.add(tiles), ob = pk.add(big);
-    DMRGX_CHK(pk.upload(tab, st));
-    DMRGX_CHK(ggemm_launch(packed_at<GTile>(tab, ob), packed_at<GGroup>(tab, og), packed_at<GProd>(tab, op), (int32_t)big.size(), st, 1));
-    DMRGX_CHK(ggemm_launch(packed_at<GTile>(tab, ot), packed_at<GGroup>(tab, og), packed_at<GProd>(tab, op), (int32_t)tiles.size(), st, 0));
-    return DMRGX_OK;
+    for (int32_t i = 0; i < count; ++i)
+        if (bad_gemm_task(t[i])) DMRGX_FAIL(DMRGX_ERR_ARG, "dgemm_batch: bad task %d (M=%d N=%d K=%d)", i, t[i].M, t[i].N, t[i].K);
+    return run_gemm_tasks(count, t, (hipStream_t)stream);
 }
 
 extern "C" dmrgx_status dmrgx_malloc(void** p, size_t bytes)

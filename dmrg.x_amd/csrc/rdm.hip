@@ -658,35 +658,24 @@ static dmrgx_status rdm_create_impl(const dmrgx_sectors* left, const dmrgx_secto
         for (int ti = 0; ti < (nl + 31) / 32; ++ti) for (int tj = 0; tj < (nr + 31) / 32; ++tj)
             tt.push_back(TrTile{off[k], psiT_off + off[k], nl, nr, ti, tj});
     }
-    std::vector<GProd> gprods;
-    std::vector<GGroup> ggroups;
-    std::vector<GTile> gt, gb;
+    GemmBatch gram;
+    GemmSet gram_set;
     for (int32_t k = 0; k < nblocks; ++k) {
         const int32_t nl = left->size[block_il[k]], nr = right->size[block_ir[k]];
         const double* Psi = psi_dev + off[k];
         const double* PsiT = buf + psiT_off + off[k];
         const MatDesc& mL = P->mats[2 * k];
         const MatDesc& mR = P->mats[2 * k + 1];
-        if (P->selected[2 * k]) {
-            gprods.push_back(GProd{Psi, PsiT, nr, nl, nr, GPROD_GEMM, 1.0});       // rho_L = Psi Psi^T  (:1733)
-            ggroups.push_back(GGroup{buf + mL.a_off, mL.npad, nl, nl, (int32_t)gprods.size() - 1, (int32_t)gprods.size(), 0, 0});
-            ggemm_append_tiles_mixed(gb, gt, (int32_t)ggroups.size() - 1, nl, nl, (nr + GG_BK - 1) / GG_BK);
-        }
-        if (P->selected[2 * k + 1]) {
-            gprods.push_back(GProd{PsiT, Psi, nl, nr, nl, GPROD_GEMM, 1.0});       // rho_R = Psi^T Psi  (:1734)
-            ggroups.push_back(GGroup{buf + mR.a_off, mR.npad, nr, nr, (int32_t)gprods.size() - 1, (int32_t)gprods.size(), 0, 0});
-            ggemm_append_tiles_mixed(gb, gt, (int32_t)ggroups.size() - 1, nr, nr, (nl + GG_BK - 1) / GG_BK);
-        }
+        if (P->selected[2 * k]) gram.gemm(gram_set, buf + mL.a_off, mL.npad, nl, nl, Psi, nr, PsiT, nl, nr);             // rho_L = Psi Psi^T  (:1733)
+        if (P->selected[2 * k + 1]) gram.gemm(gram_set, buf + mR.a_off, mR.npad, nr, nr, PsiT, nl, Psi, nr, nl);         // rho_R = Psi^T Psi  (:1734)
     }
-    if (gprods.empty()) gprods.push_back(GProd{nullptr, nullptr, 0, 0, 0, GPROD_GEMM, 0.0});
-    if (ggroups.empty()) ggroups.push_back(GGroup{nullptr, 0, 0, 0, 0, 0, 0, 0});
-    ggemm_schedule(gt, ggroups); ggemm_schedule(gb, ggroups, 2);
-    size_t o_tt = 0, o_gp = 0, o_gg = 0, o_gt = 0, o_gb = 0;
+    size_t o_tt = 0;
     {
         PackedUpload pk;
         const size_t o_m = pk.add(P->mats), o_p = pk.add(pairs), o_t = pk.add(tiles), o_ps = pk.add(pair_start), o_d = pk.add(diag_off);
-        o_tt = pk.add(tt); o_gp = pk.add(gprods); o_gg = pk.add(ggroups); o_gt = pk.add(gt); o_gb = pk.add(gb);
+        o_tt = pk.add(tt); gram.pack(pk); gram.pack(gram_set, pk);
         DMRGX_CHK(pk.upload(P->d_tables, st));
+        gram.bind(P->d_tables);
         PackedUpload::view<MatDesc>(P->d_mats, P->d_tables, o_m, P->mats.size());
         PackedUpload::view<std::decay<decltype(pairs[0])>::type>(d_pairs, P->d_tables, o_p, pairs.size());
         PackedUpload::view<std::decay<decltype(tiles[0])>::type>(d_tiles, P->d_tables, o_t, tiles.size());
@@ -703,8 +692,7 @@ static dmrgx_status rdm_create_impl(const dmrgx_sectors* left, const dmrgx_secto
         // transpose reads psi (caller memory) and writes the arena: pass distinct base pointers
         if (!tt.empty()) hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)tt.size()), dim3(256), 0, st, (const TrTile*)packed_at<TrTile>(P->d_tables, o_tt), psi_dev, buf);
         DMRGX_HIP(hipGetLastError());
-        DMRGX_CHK(ggemm_launch(packed_at<GTile>(P->d_tables, o_gb), packed_at<GGroup>(P->d_tables, o_gg), packed_at<GProd>(P->d_tables, o_gp), (int32_t)gb.size(), st, 1));
-        DMRGX_CHK(ggemm_launch(packed_at<GTile>(P->d_tables, o_gt), packed_at<GGroup>(P->d_tables, o_gg), packed_at<GProd>(P->d_tables, o_gp), (int32_t)gt.size(), st, 0));
+        DMRGX_CHK(gram.launch(gram_set, P->d_tables, st));
     }
 
     stage("gram");
@@ -754,9 +742,8 @@ static dmrgx_status rdm_create_impl(const dmrgx_sectors* left, const dmrgx_secto
     for (int mi = 0; mi < nm; ++mi) any_warm = any_warm || warm_src[mi];
     if (any_warm) {
         std::vector<TrTile> tt;
-        std::vector<GProd> p1, p2;
-        std::vector<GGroup> g1, g2;
-        std::vector<GTile> t1, t1b, t2, t2b;
+        GemmBatch b1, b2;
+        GemmSet s1, s2;
         for (int mi = 0; mi < nm; ++mi) {
             if (!warm_src[mi]) continue;
             const MatDesc& m = P->mats[mi];
@@ -767,25 +754,20 @@ static dmrgx_status rdm_create_impl(const dmrgx_sectors* left, const dmrgx_secto
             double* ET = buf + warm_et[mi];
             for (int ti = 0; ti < (n + 31) / 32; ++ti) for (int tj = 0; tj < (n + 31) / 32; ++tj)
                 tt.push_back(TrTile{(int64_t)(E - buf), warm_et[mi], n, n, ti, tj});     // source addressed relative to the arena base
-            p1.push_back(GProd{E, buf + m.a_off, n, m.npad, n, GPROD_GEMM, 1.0});          // W = E A
-            g1.push_back(GGroup{Wt, n, n, n, (int32_t)p1.size() - 1, (int32_t)p1.size(), 0, 0});
-            ggemm_append_tiles_mixed(t1b, t1, (int32_t)g1.size() - 1, n, n, (n + GG_BK - 1) / GG_BK);
-            p2.push_back(GProd{Wt, ET, n, n, n, GPROD_GEMM, 1.0});                          // A = W E^T
-            g2.push_back(GGroup{buf + m.a_off, m.npad, n, n, (int32_t)p2.size() - 1, (int32_t)p2.size(), 0, 0});
-            ggemm_append_tiles_mixed(t2b, t2, (int32_t)g2.size() - 1, n, n, (n + GG_BK - 1) / GG_BK);
+            b1.gemm(s1, Wt, n, n, n, E, n, buf + m.a_off, m.npad, n);              // W = E A
+            b2.gemm(s2, buf + m.a_off, m.npad, n, n, Wt, n, ET, n, n);             // A = W E^T
         }
         if (!tt.empty()) {
-            DevBuf d_tt, dp1, dg1, dt1, db1, dp2, dg2, dt2, db2;
-            DMRGX_CHK(upload(d_tt, tt, st));
-            hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)tt.size()), dim3(256), 0, st, d_tt.as<TrTile>(), (const double*)buf, buf);
+            DevBuf tab;
+            PackedUpload pk;
+            const size_t o_tt = pk.add(tt);
+            b1.pack(pk); b1.pack(s1, pk); b2.pack(pk); b2.pack(s2, pk);
+            DMRGX_CHK(pk.upload(tab, st));
+            b1.bind(tab); b2.bind(tab);
+            hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)tt.size()), dim3(256), 0, st, (const TrTile*)packed_at<TrTile>(tab, o_tt), (const double*)buf, buf);
             DMRGX_HIP(hipGetLastError());
-            ggemm_schedule(t1, g1); ggemm_schedule(t1b, g1, 2); ggemm_schedule(t2, g2); ggemm_schedule(t2b, g2, 2);
-            DMRGX_CHK(upload(dp1, p1, st)); DMRGX_CHK(upload(dg1, g1, st)); DMRGX_CHK(upload(dt1, t1, st)); DMRGX_CHK(upload(db1, t1b, st));
-            DMRGX_CHK(upload(dp2, p2, st)); DMRGX_CHK(upload(dg2, g2, st)); DMRGX_CHK(upload(dt2, t2, st)); DMRGX_CHK(upload(db2, t2b, st));
-            DMRGX_CHK(ggemm_launch(db1.as<GTile>(), dg1.as<GGroup>(), dp1.as<GProd>(), (int32_t)t1b.size(), st, 1));
-            DMRGX_CHK(ggemm_launch(dt1.as<GTile>(), dg1.as<GGroup>(), dp1.as<GProd>(), (int32_t)t1.size(), st, 0));
-            DMRGX_CHK(ggemm_launch(db2.as<GTile>(), dg2.as<GGroup>(), dp2.as<GProd>(), (int32_t)t2b.size(), st, 1));
-            DMRGX_CHK(ggemm_launch(dt2.as<GTile>(), dg2.as<GGroup>(), dp2.as<GProd>(), (int32_t)t2.size(), st, 0));
+            DMRGX_CHK(b1.launch(s1, tab, st));
+            DMRGX_CHK(b2.launch(s2, tab, st));
             for (int mi = 0; mi < nm; ++mi) {
                 if (!warm_src[mi] || P->mats[mi].n == 0) continue;
                 const MatDesc& m = P->mats[mi];
@@ -914,9 +896,8 @@ static dmrgx_status rdm_rayleigh(dmrgx_rdm* P, const std::vector<int32_t>& cols,
     const int64_t dtot = P->dtot;
     std::vector<double> rq((size_t)dtot, 0.0);
     {
-        std::vector<GProd> prods;
-        std::vector<GGroup> groups;
-        std::vector<GTile> gt, gb;
+        GemmBatch wgemm;                                // W = Psi^T V_L, Psi V_R
+        GemmSet wset;
         std::vector<ColNormTask> cn;
         for (int32_t k = 0; k < nblocks; ++k) {
             const int32_t nl = P->nl[(size_t)k], nr = P->nr[(size_t)k];
@@ -929,28 +910,24 @@ static dmrgx_status rdm_rayleigh(dmrgx_rdm* P, const std::vector<int32_t>& cols,
             const int32_t cL = P->selected[2 * k] ? cols[(size_t)(2 * k)] : 0, cR = P->selected[2 * k + 1] ? cols[(size_t)(2 * k + 1)] : 0;
             if (cL > 0) {
                 const int32_t c0 = nl - cL;
-                prods.push_back(GProd{PsiT, buf + mL.v_off + c0, nl, mL.npad, nl, GPROD_GEMM, 1.0});
-                groups.push_back(GGroup{WL, cL, nr, cL, (int32_t)prods.size() - 1, (int32_t)prods.size(), 0, 0});
-                ggemm_append_tiles_mixed(gb, gt, (int32_t)groups.size() - 1, nr, cL, (nl + GG_BK - 1) / GG_BK);
+                wgemm.gemm(wset, WL, cL, nr, cL, PsiT, nl, buf + mL.v_off + c0, mL.npad, nl);
                 cn.push_back(ColNormTask{P->w_base + 2 * P->off[(size_t)k], P->rq_base + (P->diag_off[2 * k] - P->diag_base) + c0, nr, cL, cL, 0});
             }
             if (cR > 0) {
                 const int32_t c0 = nr - cR;
-                prods.push_back(GProd{Psi, buf + mR.v_off + c0, nr, mR.npad, nr, GPROD_GEMM, 1.0});
-                groups.push_back(GGroup{WR, cR, nl, cR, (int32_t)prods.size() - 1, (int32_t)prods.size(), 0, 0});
-                ggemm_append_tiles_mixed(gb, gt, (int32_t)groups.size() - 1, nl, cR, (nr + GG_BK - 1) / GG_BK);
+                wgemm.gemm(wset, WR, cR, nl, cR, Psi, nr, buf + mR.v_off + c0, mR.npad, nr);
                 cn.push_back(ColNormTask{P->w_base + 2 * P->off[(size_t)k] + (int64_t)nl * nr, P->rq_base + (P->diag_off[2 * k + 1] - P->diag_base) + c0, nl, cR, cR, 0});
             }
         }
-        if (prods.empty()) return DMRGX_OK;                 // (nothing selected on this rank)
-        ggemm_schedule(gt, groups); ggemm_schedule(gb, groups, 2);
+        if (cn.empty()) return DMRGX_OK;                    // (nothing selected on this rank)
         DevBuf dtab;
         PackedUpload pk;
-        const size_t o_p = pk.add(prods), o_g = pk.add(groups), o_t = pk.add(gt), o_b = pk.add(gb), o_c = pk.add(cn);
+        wgemm.pack(pk); wgemm.pack(wset, pk);
+        const size_t o_c = pk.add(cn);
         DMRGX_CHK(pk.upload(dtab, st));
+        wgemm.bind(dtab);
         DMRGX_HIP(zero_async(buf + P->rq_base, (size_t)dtot * sizeof(double), st));
-        DMRGX_CHK(ggemm_launch(packed_at<GTile>(dtab, o_b), packed_at<GGroup>(dtab, o_g), packed_at<GProd>(dtab, o_p), (int32_t)gb.size(), st, 1));
-        DMRGX_CHK(ggemm_launch(packed_at<GTile>(dtab, o_t), packed_at<GGroup>(dtab, o_g), packed_at<GProd>(dtab, o_p), (int32_t)gt.size(), st, 0));
+        DMRGX_CHK(wgemm.launch(wset, dtab, st));
         int maxc = 1;
         for (auto& c : cn) maxc = std::max(maxc, c.ncols);
         hipLaunchKernelGGL(colnorm_kernel, dim3((maxc + 63) / 64, (unsigned)cn.size()), dim3(256), 0, st, (const ColNormTask*)packed_at<ColNormTask>(dtab, o_c), buf, buf);

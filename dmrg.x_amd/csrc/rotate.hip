@@ -152,19 +152,17 @@ extern "C" dmrgx_status dmrgx_rotate_ops(const dmrgx_sectors* old_sectors, const
         }
         DMRGX_CHK(dmrgx_cells_axpy(nn, tr.data(), st));
     }
-    std::vector<GProd> prods;
-    std::vector<GGroup> groups;
-    std::vector<GTile> tA, tAb, tB, tBb;
+    GemmBatch gemms;
+    GemmSet sA, sB;
     // stage A
     for (const WRef& w : wrefs) {
         const dmrgx_cell& ce = src_ops[w.op].cells[w.cell];
         const int32_t nq = old_sectors->size[rot->old_sector[w.a]], m = rot->kept[w.a];
         const double* RTa = rot->rot_t[w.a] + ce.r0;
-        const int32_t pb = (int32_t)prods.size();
-        if (ce.kind == DMRGX_CELL_DENSE) prods.push_back(GProd{RTa, ce.data, nq, (int32_t)ce.ld, ce.nr, GPROD_GEMM, 1.0});
-        else prods.push_back(GProd{nullptr, RTa, 0, nq, 0, GPROD_AXPY, ce.scale});
-        groups.push_back(GGroup{W + w.off, ce.nc, m, ce.nc, pb, pb + 1, ce.kind == DMRGX_CELL_DENSE ? 0 : 1, 0});
-        ggemm_append_tiles_mixed(tAb, tA, (int32_t)groups.size() - 1, m, ce.nc, (ce.nr + GG_BK - 1) / GG_BK);
+        const int32_t pb = (int32_t)gemms.prods.size();
+        if (ce.kind == DMRGX_CELL_DENSE) gemms.prods.push_back(GProd{RTa, ce.data, nq, (int32_t)ce.ld, ce.nr, GPROD_GEMM, 1.0});
+        else gemms.prods.push_back(GProd{nullptr, RTa, 0, nq, 0, GPROD_AXPY, ce.scale});
+        gemms.group(sA, GGroup{W + w.off, ce.nc, m, ce.nc, pb, pb + 1, ce.kind == DMRGX_CELL_DENSE ? 0 : 1, 0}, (ce.nr + GG_BK - 1) / GG_BK);
     }
     // stage B: group per (op, a) destination
     std::map<std::pair<int32_t, int32_t>, std::vector<const WRef*>> by_dst;
@@ -179,51 +177,45 @@ extern "C" dmrgx_status dmrgx_rotate_ops(const dmrgx_sectors* old_sectors, const
     for (auto& kv : by_dst) {
         const int32_t o = kv.first.first, a = kv.first.second, ap = new_of_old[rot->old_sector[a] + src_ops[o].shift];
         const int32_t m = rot->kept[a], mp = rot->kept[ap];
-        const int32_t pb = (int32_t)prods.size();
+        const int32_t pb = (int32_t)gemms.prods.size();
         int32_t cost = 1;
         for (const WRef* w : kv.second) {
             const dmrgx_cell& ce = src_ops[o].cells[w->cell];
-            prods.push_back(GProd{W + w->off, UT + ut_off[ap] + (int64_t)ce.c0 * mp, ce.nc, mp, ce.nc, GPROD_GEMM, 1.0});
+            gemms.prods.push_back(GProd{W + w->off, UT + ut_off[ap] + (int64_t)ce.c0 * mp, ce.nc, mp, ce.nc, GPROD_GEMM, 1.0});
             cost += (ce.nc + GG_BK - 1) / GG_BK;
         }
-        groups.push_back(GGroup{dst_blocks[o][a], mp, m, mp, pb, (int32_t)prods.size(), 0, 0});
-        ggemm_append_tiles_mixed(tBb, tB, (int32_t)groups.size() - 1, m, mp, cost);
+        gemms.group(sB, GGroup{dst_blocks[o][a], mp, m, mp, pb, (int32_t)gemms.prods.size(), 0, 0}, cost);
     }
     const auto h1 = std::chrono::steady_clock::now();
     // stage A goes to the device before stage B's tile lists are scheduled: the host work of B (a sort over ~10^4 tiles) then
     // runs behind A's GEMMs instead of in front of an idle GPU
-    ggemm_schedule(tA, groups); ggemm_schedule(tAb, groups, 2);
-    const auto h2 = std::chrono::steady_clock::now();
     DevBuf dtabA, dtabB;
-    PackedUpload pkA;
-    const size_t o_p = pkA.add(prods), o_g = pkA.add(groups), o_1 = pkA.add(tAb), o_2 = pkA.add(tA);
+    PackedUpload pkA, pkB;
+    gemms.pack(sA, pkA);
+    const auto h2 = std::chrono::steady_clock::now();
+    gemms.pack(pkA);
     DMRGX_CHK(pkA.upload(dtabA, st));
-    const GProd* dp = packed_at<GProd>(dtabA, o_p);
-    const GGroup* dg = packed_at<GGroup>(dtabA, o_g);
+    gemms.bind(dtabA);
     const auto h3 = std::chrono::steady_clock::now();
     static const bool trace = getenv("DMRGX_ROT_TRACE") != nullptr;      // developer aid: flops and time of the two stages
     if (trace) fprintf(stderr, "[rotate] host: tables %.3f ms, schedule A %.3f ms, uploads A %.3f ms\n", std::chrono::duration<double, std::milli>(h1 - h0).count(),
                        std::chrono::duration<double, std::milli>(h2 - h1).count(), std::chrono::duration<double, std::milli>(h3 - h2).count());
     hipEvent_t ev[3];
     if (trace) { for (auto& e : ev) DMRGX_HIP(hipEventCreate(&e)); DMRGX_HIP(hipEventRecord(ev[0], st)); }
-    DMRGX_CHK(ggemm_launch(packed_at<GTile>(dtabA, o_1), dg, dp, (int32_t)tAb.size(), st, 1));
-    DMRGX_CHK(ggemm_launch(packed_at<GTile>(dtabA, o_2), dg, dp, (int32_t)tA.size(), st, 0));
+    DMRGX_CHK(gemms.launch(sA, dtabA, st));
     if (trace) DMRGX_HIP(hipEventRecord(ev[1], st));
-    ggemm_schedule(tB, groups); ggemm_schedule(tBb, groups, 2);
-    PackedUpload pkB;
-    const size_t o_3 = pkB.add(tBb), o_4 = pkB.add(tB);
+    gemms.pack(sB, pkB);
     DMRGX_CHK(pkB.upload(dtabB, st));
-    DMRGX_CHK(ggemm_launch(packed_at<GTile>(dtabB, o_3), dg, dp, (int32_t)tBb.size(), st, 1));
-    DMRGX_CHK(ggemm_launch(packed_at<GTile>(dtabB, o_4), dg, dp, (int32_t)tB.size(), st, 0));
+    DMRGX_CHK(gemms.launch(sB, dtabB, st));
     if (trace) {
         DMRGX_HIP(hipEventRecord(ev[2], st));
         DMRGX_HIP(hipEventSynchronize(ev[2]));
         double fa = 0, fb = 0;
-        for (const GGroup& g : groups) for (int32_t q = g.prod_begin + g.n_axpy; q < g.prod_end; ++q) ((&g - groups.data()) < (ptrdiff_t)wrefs.size() ? fa : fb) += 2.0 * g.M * g.N * prods[q].K;
+        for (const GGroup& g : gemms.groups) for (int32_t q = g.prod_begin + g.n_axpy; q < g.prod_end; ++q) ((&g - gemms.groups.data()) < (ptrdiff_t)wrefs.size() ? fa : fb) += 2.0 * g.M * g.N * gemms.prods[q].K;
         float ma = 0, mb = 0;
         DMRGX_HIP(hipEventElapsedTime(&ma, ev[0], ev[1])); DMRGX_HIP(hipEventElapsedTime(&mb, ev[1], ev[2]));
         fprintf(stderr, "[rotate] %d ops: stage A %.2f GF %.3f ms (%.1f TF/s, tiles %zu+%zu big), stage B %.2f GF %.3f ms (%.1f TF/s, tiles %zu+%zu big)\n", nops,
-                fa * 1e-9, ma, fa / (ma * 1e9), tA.size(), tAb.size(), fb * 1e-9, mb, fb / (mb * 1e9), tB.size(), tBb.size());
+                fa * 1e-9, ma, fa / (ma * 1e9), sA.small.size(), sA.big.size(), fb * 1e-9, mb, fb / (mb * 1e9), sB.small.size(), sB.big.size());
         for (auto& e : ev) (void)hipEventDestroy(e);
     }
     return DMRGX_OK;

@@ -1109,11 +1109,6 @@ std::vector<int> tree_bounds(int n, int level)
 bool g_coop_disabled = false;                       // set once a persistent round has timed out (process-wide)
 int32_t g_coop_timeouts = 0;                        // how often that happened
 
-struct GemmSet {                                   // the tile lists of one dependent GEMM step
-    size_t big_off = 0, small_off = 0;
-    int32_t nbig = 0, nsmall = 0;
-};
-
 template <class K> dmrgx_status set_dyn_lds(K kernel, size_t bytes)
 {
     if (bytes > 64 * 1024) DMRGX_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
@@ -1310,54 +1305,33 @@ dmrgx_status symeig_batched(const std::vector<SymEigMat>& mats_in, hipStream_t s
     hmark("trid launched");
 
     // ---- 3a. (independent of the eigenvectors) V = (V^T)^T, the Gram blocks, T factors and T V^T ---------------------------------
-    std::vector<GProd> prods;
-    std::vector<GGroup> groups;
-    std::vector<GTile> tiles;                         // all tile lists, one after the other
-    auto add_set = [&](std::vector<GTile>& big, std::vector<GTile>& small) {
-        GemmSet s;
-        ggemm_schedule(big, groups, 2); ggemm_schedule(small, groups);
-        s.big_off = tiles.size(); s.nbig = (int32_t)big.size(); tiles.insert(tiles.end(), big.begin(), big.end());
-        s.small_off = tiles.size(); s.nsmall = (int32_t)small.size(); tiles.insert(tiles.end(), small.begin(), small.end());
-        return s;
-    };
-    auto add_gemm = [&](std::vector<GTile>& big, std::vector<GTile>& small, double* C, int ldc, int Mr, int Nc, const double* A, int lda, const double* Bm, int ldb, int K, int accumulate) {
-        if (Mr <= 0 || Nc <= 0 || K <= 0) return;
-        prods.push_back(GProd{A, Bm, lda, ldb, K, GPROD_GEMM, 1.0});
-        groups.push_back(GGroup{C, ldc, Mr, Nc, (int32_t)prods.size() - 1, (int32_t)prods.size(), 0, accumulate});
-        ggemm_append_tiles_mixed(big, small, (int32_t)groups.size() - 1, Mr, Nc, (K + GG_BK - 1) / GG_BK);
-    };
+    GemmBatch gemms;                                  // every GEMM of the call; a GemmSet per dependent step
+    gemms.skip_empty_k = true;
     std::vector<SqPair> tp(nm);
     std::vector<WyBlock> wyb;
     GemmSet set_gram, set_tv, set_t12a, set_t12b;
     int max_nblk = 0;
-    {
-        std::vector<GTile> gb, gs, tb, tsm, pb_, ps_, qb_, qs_;
-        for (int i = 0; i < nm; ++i) {
-            const int n = M[i].n;
-            const Ws& w = ws[i];
-            max_nblk = std::max(max_nblk, w.nblk);
-            tp[i] = SqPair{B + w.VT, B + w.Vc, n, n, n, 0};
-            for (int b = 0; b < w.nblk; ++b) {
-                const int b0 = b * WY_NB, kb = std::min(WY_NB, n - 2 - b0), r0 = b0 + 1;      // reflectors b0 .. b0+kb-1 live in rows >= b0+1
-                double* G = B + w.G + (int64_t)b * WY_NB * WY_NB;
-                double* Tn = B + w.Tn + (int64_t)b * WY_NB * WY_NB;
-                add_gemm(gb, gs, G, WY_NB, kb, kb, B + w.VT + (int64_t)b0 * n + r0, n, B + w.Vc + (int64_t)r0 * n + b0, n, n - r0, 0);      // G = V_b^T V_b
-                const int k1 = std::min(kb, WY_SUB), k2 = kb - k1;
-                wyb.push_back(WyBlock{G, B + w.tau + b0, Tn, k1, WY_NB, k2, 0});
-                if (k2 > 0) {
-                    wyb.push_back(WyBlock{G + (int64_t)WY_SUB * WY_NB + WY_SUB, B + w.tau + b0 + WY_SUB, Tn + (int64_t)WY_SUB * WY_NB + WY_SUB, k2, WY_NB, 0, 0});
-                    // Tneg12 = Tneg1 . G12 . Tneg2 (= -T12): P = G12 . Tneg2 parked in the unused lower-left block of G, then Tneg12 = Tneg1 . P
-                    double* Pm = G + (int64_t)WY_SUB * WY_NB;
-                    add_gemm(pb_, ps_, Pm, WY_NB, k1, k2, G + WY_SUB, WY_NB, Tn + (int64_t)WY_SUB * WY_NB + WY_SUB, WY_NB, k2, 0);
-                    add_gemm(qb_, qs_, Tn + WY_SUB, WY_NB, k1, k2, Tn, WY_NB, Pm, WY_NB, k1, 0);
-                }
-                add_gemm(tb, tsm, B + w.TV + (int64_t)b0 * n, n, kb, n, Tn, WY_NB, B + w.VT + (int64_t)b0 * n, n, kb, 0);     // (T V^T)_b = Tneg_b . V_b^T
+    for (int i = 0; i < nm; ++i) {
+        const int n = M[i].n;
+        const Ws& w = ws[i];
+        max_nblk = std::max(max_nblk, w.nblk);
+        tp[i] = SqPair{B + w.VT, B + w.Vc, n, n, n, 0};
+        for (int b = 0; b < w.nblk; ++b) {
+            const int b0 = b * WY_NB, kb = std::min(WY_NB, n - 2 - b0), r0 = b0 + 1;      // reflectors b0 .. b0+kb-1 live in rows >= b0+1
+            double* G = B + w.G + (int64_t)b * WY_NB * WY_NB;
+            double* Tn = B + w.Tn + (int64_t)b * WY_NB * WY_NB;
+            gemms.gemm(set_gram, G, WY_NB, kb, kb, B + w.VT + (int64_t)b0 * n + r0, n, B + w.Vc + (int64_t)r0 * n + b0, n, n - r0);      // G = V_b^T V_b
+            const int k1 = std::min(kb, WY_SUB), k2 = kb - k1;
+            wyb.push_back(WyBlock{G, B + w.tau + b0, Tn, k1, WY_NB, k2, 0});
+            if (k2 > 0) {
+                wyb.push_back(WyBlock{G + (int64_t)WY_SUB * WY_NB + WY_SUB, B + w.tau + b0 + WY_SUB, Tn + (int64_t)WY_SUB * WY_NB + WY_SUB, k2, WY_NB, 0, 0});
+                // Tneg12 = Tneg1 . G12 . Tneg2 (= -T12): P = G12 . Tneg2 parked in the unused lower-left block of G, then Tneg12 = Tneg1 . P
+                double* Pm = G + (int64_t)WY_SUB * WY_NB;
+                gemms.gemm(set_t12a, Pm, WY_NB, k1, k2, G + WY_SUB, WY_NB, Tn + (int64_t)WY_SUB * WY_NB + WY_SUB, WY_NB, k2);
+                gemms.gemm(set_t12b, Tn + WY_SUB, WY_NB, k1, k2, Tn, WY_NB, Pm, WY_NB, k1);
             }
+            gemms.gemm(set_tv, B + w.TV + (int64_t)b0 * n, n, kb, n, Tn, WY_NB, B + w.VT + (int64_t)b0 * n, n, kb);     // (T V^T)_b = Tneg_b . V_b^T
         }
-        set_t12a = add_set(pb_, ps_);
-        set_t12b = add_set(qb_, qs_);
-        set_gram = add_set(gb, gs);
-        set_tv = add_set(tb, tsm);
     }
 
     // ---- 2. divide-and-conquer tables --------------------------------------------------------------------------------------
@@ -1393,7 +1367,6 @@ dmrgx_status symeig_batched(const std::vector<SymEigMat>& mats_in, hipStream_t s
     for (int t = 1; t <= dmax; ++t) {
         Step& s = steps[(size_t)t - 1];
         s.merge_off = merges.size();
-        std::vector<GTile> gb, gs;
         for (int i = 0; i < nm; ++i) {
             if (depth[i] < t) continue;
             const int lev = depth[i] - t, n = M[i].n;           // the level being produced; its children live at lev + 1
@@ -1407,46 +1380,40 @@ dmrgx_status symeig_batched(const std::vector<SymEigMat>& mats_in, hipStream_t s
                 double* Qd = dm[i].Q[dst]; const int ldd = dm[i].ldq[dst];
                 const double* Qs = dm[i].Q[src]; const int lds_ = dm[i].ldq[src];
                 const double* U = dm[i].U; const int ldu = dm[i].ldu;
-                add_gemm(gb, gs, Qd + (int64_t)lo * ldd + lo, ldd, mid - lo, hi - lo, Qs + (int64_t)lo * lds_ + lo, lds_, U + (int64_t)lo * ldu + lo, ldu, mid - lo, 0);
-                add_gemm(gb, gs, Qd + (int64_t)mid * ldd + lo, ldd, hi - mid, hi - lo, Qs + (int64_t)mid * lds_ + mid, lds_, U + (int64_t)mid * ldu + lo, ldu, hi - mid, 0);
+                gemms.gemm(s.gemm, Qd + (int64_t)lo * ldd + lo, ldd, mid - lo, hi - lo, Qs + (int64_t)lo * lds_ + lo, lds_, U + (int64_t)lo * ldu + lo, ldu, mid - lo);
+                gemms.gemm(s.gemm, Qd + (int64_t)mid * ldd + lo, ldd, hi - mid, hi - lo, Qs + (int64_t)mid * lds_ + mid, lds_, U + (int64_t)mid * ldu + lo, ldu, hi - mid);
             }
         }
         s.nmerge = (int)(merges.size() - s.merge_off);
-        s.gemm = add_set(gb, gs);
     }
 
     // ---- 3b. back-transformation steps (last block first), aligned at the end of every matrix's block list ------------------------
     std::vector<GemmSet> bt_w((size_t)max_nblk), bt_x((size_t)max_nblk);
     for (int s = 0; s < max_nblk && !deferred; ++s) {
-        std::vector<GTile> wb, wsm, xb, xs;
         for (int i = 0; i < nm; ++i) {
             const Ws& w = ws[i];
             const int b = w.nblk - 1 - s, n = M[i].n;
             if (b < 0) continue;
             const int b0 = b * WY_NB, kb = std::min(WY_NB, n - 2 - b0), r0 = b0 + 1;
             double* X = M[i].X; const int ldx = M[i].ldx;
-            add_gemm(wb, wsm, B + w.W, n, kb, n, B + w.TV + (int64_t)b0 * n + r0, n, X + (int64_t)r0 * ldx, ldx, n - r0, 0);          // W = -(T V^T) X
-            add_gemm(xb, xs, X + (int64_t)r0 * ldx, ldx, n - r0, n, B + w.Vc + (int64_t)r0 * n + b0, n, B + w.W, n, kb, 1);             // X += V W
+            gemms.gemm(bt_w[(size_t)s], B + w.W, n, kb, n, B + w.TV + (int64_t)b0 * n + r0, n, X + (int64_t)r0 * ldx, ldx, n - r0);          // W = -(T V^T) X
+            gemms.gemm(bt_x[(size_t)s], X + (int64_t)r0 * ldx, ldx, n - r0, n, B + w.Vc + (int64_t)r0 * n + b0, n, B + w.W, n, kb, 1);       // X += V W
         }
-        bt_w[(size_t)s] = add_set(wb, wsm);
-        bt_x[(size_t)s] = add_set(xb, xs);
     }
 
     hmark("tables built");
     // ---- uploads ---------------------------------------------------------------------------------------------------------------
-    if (prods.empty()) prods.push_back(GProd{nullptr, nullptr, 0, 0, 0, GPROD_GEMM, 0.0});
-    if (groups.empty()) groups.push_back(GGroup{nullptr, 0, 0, 0, 0, 0, 0, 0});
-    if (tiles.empty()) tiles.push_back(GTile{-1, 0, 0, 0});
     if (merges.empty()) merges.push_back(DcMerge{0, 0, 0, 0, 0, 0});
     if (wyb.empty()) wyb.push_back(WyBlock{nullptr, nullptr, nullptr, 0, 0, 0, 0});
-    DevBuf d_tab;                                      // all eight tables in one copy
+    DevBuf d_tab;                                      // every table in one copy
     PackedUpload pk;
-    const size_t o_prods = pk.add(prods), o_groups = pk.add(groups), o_tiles = pk.add(tiles), o_tp = pk.add(tp), o_wyb = pk.add(wyb), o_dm = pk.add(dm),
-                 o_leaves = pk.add(leaves), o_merges = pk.add(merges);
+    gemms.pack(pk);
+    for (GemmSet* s : {&set_t12a, &set_t12b, &set_gram, &set_tv}) gemms.pack(*s, pk);
+    for (Step& s : steps) gemms.pack(s.gemm, pk);
+    for (int s = 0; s < max_nblk && !deferred; ++s) { gemms.pack(bt_w[(size_t)s], pk); gemms.pack(bt_x[(size_t)s], pk); }
+    const size_t o_tp = pk.add(tp), o_wyb = pk.add(wyb), o_dm = pk.add(dm), o_leaves = pk.add(leaves), o_merges = pk.add(merges);
     DMRGX_CHK(pk.upload(d_tab, st));
-    const GProd* d_prods = packed_at<GProd>(d_tab, o_prods);
-    const GGroup* d_groups = packed_at<GGroup>(d_tab, o_groups);
-    const GTile* d_tiles = packed_at<GTile>(d_tab, o_tiles);
+    gemms.bind(d_tab);
     const SqPair* d_tp = packed_at<SqPair>(d_tab, o_tp);
     const WyBlock* d_wyb = packed_at<WyBlock>(d_tab, o_wyb);
     const DcMat* d_dm = packed_at<DcMat>(d_tab, o_dm);
@@ -1480,12 +1447,6 @@ dmrgx_status symeig_batched(const std::vector<SymEigMat>& mats_in, hipStream_t s
         }
     }
 
-    auto run_set = [&](const GemmSet& s) -> dmrgx_status {
-        DMRGX_CHK(ggemm_launch(d_tiles + s.big_off, d_groups, d_prods, s.nbig, st, 1));
-        DMRGX_CHK(ggemm_launch(d_tiles + s.small_off, d_groups, d_prods, s.nsmall, st, 0));
-        return DMRGX_OK;
-    };
-
     // ---- 3a: launches ----------------------------------------------------------------------------------------------------------
     // The WY factors (V^T, Gram matrix, T^-1 by one latency-bound workgroup per block, T12, T V^T) and the divide and conquer below both
     // need the tridiagonalisation only, and neither fills the chip: the WY chain goes to a second stream and joins in front of the
@@ -1501,20 +1462,15 @@ dmrgx_status symeig_batched(const std::vector<SymEigMat>& mats_in, hipStream_t s
         }
         DMRGX_HIP(hipEventRecord(ev_fork, st));
         DMRGX_HIP(hipStreamWaitEvent(side, ev_fork, 0));
-        auto run_set_side = [&](const GemmSet& s) -> dmrgx_status {
-            DMRGX_CHK(ggemm_launch(d_tiles + s.big_off, d_groups, d_prods, s.nbig, side, 1));
-            DMRGX_CHK(ggemm_launch(d_tiles + s.small_off, d_groups, d_prods, s.nsmall, side, 0));
-            return DMRGX_OK;
-        };
         const unsigned t32 = (unsigned)((nmax + 31) / 32);
         hipLaunchKernelGGL(transpose_sq_kernel, dim3(t32, t32, (unsigned)nm), dim3(256), 0, side, d_tp);
         DMRGX_HIP(hipGetLastError());
-        DMRGX_CHK(run_set_side(set_gram));
+        DMRGX_CHK(gemms.launch(set_gram, d_tab, side));
         hipLaunchKernelGGL(wy_tinv_kernel, dim3((unsigned)wyb.size()), dim3(WY_SUB), 0, side, d_wyb);
         DMRGX_HIP(hipGetLastError());
-        DMRGX_CHK(run_set_side(set_t12a));
-        DMRGX_CHK(run_set_side(set_t12b));
-        DMRGX_CHK(run_set_side(set_tv));
+        DMRGX_CHK(gemms.launch(set_t12a, d_tab, side));
+        DMRGX_CHK(gemms.launch(set_t12b, d_tab, side));
+        DMRGX_CHK(gemms.launch(set_tv, d_tab, side));
         DMRGX_HIP(hipEventRecord(ev_join, side));
     }
 
@@ -1547,14 +1503,14 @@ dmrgx_status symeig_batched(const std::vector<SymEigMat>& mats_in, hipStream_t s
         hipLaunchKernelGGL(dc_fill_u_kernel, dim3((unsigned)((nl + 63) / 64), (unsigned)((nl + 63) / 64), (unsigned)s.nmerge), dim3(256), 0, st, ddm, mp);
         hipLaunchKernelGGL(dc_rot_kernel, dim3((unsigned)((nl + 255) / 256), (unsigned)s.nmerge), dim3(256), lds_rot, st, ddm, mp, nl);
         DMRGX_HIP(hipGetLastError());
-        DMRGX_CHK(run_set(s.gemm));
+        DMRGX_CHK(gemms.launch(s.gemm, d_tab, st));
     }
     hipLaunchKernelGGL(dc_out_kernel, dim3((unsigned)((nmax + 255) / 256), (unsigned)nm), dim3(256), 0, st, ddm);
     DMRGX_HIP(hipGetLastError());
 
     // ---- 3b: launches ------------------------------------------------------------------------------------------------------------
     if (any_blk) DMRGX_HIP(hipStreamWaitEvent(st, ev_join, 0));
-    for (int s = 0; s < max_nblk && !deferred; ++s) { DMRGX_CHK(run_set(bt_w[(size_t)s])); DMRGX_CHK(run_set(bt_x[(size_t)s])); }
+    for (int s = 0; s < max_nblk && !deferred; ++s) { DMRGX_CHK(gemms.launch(bt_w[(size_t)s], d_tab, st)); DMRGX_CHK(gemms.launch(bt_x[(size_t)s], d_tab, st)); }
     if (deferred) {
         // everything symeig_finish needs: the matrices, where their factors sit in the workspace, and the workspace itself
         deferred->mats.clear();
@@ -1582,70 +1538,43 @@ dmrgx_status symeig_finish(SymEigDeferred& d, const std::vector<int32_t>& keep, 
     const int nm = (int)d.mats.size();
     if ((int)keep.size() != nm) DMRGX_FAIL(DMRGX_ERR_ARG, "symeig_finish: %d counts for %d matrices", (int)keep.size(), nm);
     double* B = d.dbuf.as<double>();
-    std::vector<GProd> prods;
-    std::vector<GGroup> groups;
-    std::vector<GTile> tiles;
-    auto add_set = [&](std::vector<GTile>& big, std::vector<GTile>& small) {
-        GemmSet s;
-        ggemm_schedule(big, groups, 2); ggemm_schedule(small, groups);
-        s.big_off = tiles.size(); s.nbig = (int32_t)big.size(); tiles.insert(tiles.end(), big.begin(), big.end());
-        s.small_off = tiles.size(); s.nsmall = (int32_t)small.size(); tiles.insert(tiles.end(), small.begin(), small.end());
-        return s;
-    };
-    auto add_gemm = [&](std::vector<GTile>& big, std::vector<GTile>& small, double* C, int ldc, int Mr, int Nc, const double* A, int lda, const double* Bm, int ldb, int K, int accumulate) {
-        if (Mr <= 0 || Nc <= 0 || K <= 0) return;
-        prods.push_back(GProd{A, Bm, lda, ldb, K, GPROD_GEMM, 1.0});
-        groups.push_back(GGroup{C, ldc, Mr, Nc, (int32_t)prods.size() - 1, (int32_t)prods.size(), 0, accumulate});
-        ggemm_append_tiles_mixed(big, small, (int32_t)groups.size() - 1, Mr, Nc, (K + GG_BK - 1) / GG_BK);
-    };
+    GemmBatch gemms;
+    gemms.skip_empty_k = true;
     int max_nblk = 0;
     GemmSet root;
-    {
-        std::vector<GTile> gb, gs;
-        for (int i = 0; i < nm; ++i) {
-            const SymEigDeferred::Mat& q = d.mats[(size_t)i];
-            const int n = q.m.n, c = keep[(size_t)i];
-            if (c < 0 || c > n) DMRGX_FAIL(DMRGX_ERR_ARG, "symeig_finish: matrix %d of order %d cannot keep %d eigenvectors", i, n, c);
-            if (c > 0) max_nblk = std::max(max_nblk, q.nblk);
-            if (q.depth < 1 || c == 0) continue;                  // (a single leaf: its eigenvectors are complete)
-            const int mid = tree_bounds(n, 1)[1], c0 = n - c;
-            double* X = q.m.X; const int ldx = q.m.ldx;
-            const double* Qs = B + q.Q1; const double* U = B + q.U;        // the root's children live in Q[1] (ld n), its merge matrix in U (ld n)
-            add_gemm(gb, gs, X + c0, ldx, mid, c, Qs, n, U + c0, n, mid, 0);
-            add_gemm(gb, gs, X + (int64_t)mid * ldx + c0, ldx, n - mid, c, Qs + (int64_t)mid * n + mid, n, U + (int64_t)mid * n + c0, n, n - mid, 0);
-        }
-        root = add_set(gb, gs);
+    for (int i = 0; i < nm; ++i) {
+        const SymEigDeferred::Mat& q = d.mats[(size_t)i];
+        const int n = q.m.n, c = keep[(size_t)i];
+        if (c < 0 || c > n) DMRGX_FAIL(DMRGX_ERR_ARG, "symeig_finish: matrix %d of order %d cannot keep %d eigenvectors", i, n, c);
+        if (c > 0) max_nblk = std::max(max_nblk, q.nblk);
+        if (q.depth < 1 || c == 0) continue;                  // (a single leaf: its eigenvectors are complete)
+        const int mid = tree_bounds(n, 1)[1], c0 = n - c;
+        double* X = q.m.X; const int ldx = q.m.ldx;
+        const double* Qs = B + q.Q1; const double* U = B + q.U;        // the root's children live in Q[1] (ld n), its merge matrix in U (ld n)
+        gemms.gemm(root, X + c0, ldx, mid, c, Qs, n, U + c0, n, mid);
+        gemms.gemm(root, X + (int64_t)mid * ldx + c0, ldx, n - mid, c, Qs + (int64_t)mid * n + mid, n, U + (int64_t)mid * n + c0, n, n - mid);
     }
     std::vector<GemmSet> bt_w((size_t)max_nblk), bt_x((size_t)max_nblk);
     for (int s = 0; s < max_nblk; ++s) {
-        std::vector<GTile> wb, wsm, xb, xs;
         for (int i = 0; i < nm; ++i) {
             const SymEigDeferred::Mat& q = d.mats[(size_t)i];
             const int b = q.nblk - 1 - s, n = q.m.n, c = keep[(size_t)i];
             if (b < 0 || c == 0) continue;
             const int b0 = b * WY_NB, kb = std::min(WY_NB, n - 2 - b0), r0 = b0 + 1, c0 = n - c;
             double* X = q.m.X; const int ldx = q.m.ldx;
-            add_gemm(wb, wsm, B + q.W, n, kb, c, B + q.TV + (int64_t)b0 * n + r0, n, X + (int64_t)r0 * ldx + c0, ldx, n - r0, 0);      // W = -(T V^T) X[:, kept]
-            add_gemm(xb, xs, X + (int64_t)r0 * ldx + c0, ldx, n - r0, c, B + q.Vc + (int64_t)r0 * n + b0, n, B + q.W, n, kb, 1);       // X[:, kept] += V W
+            gemms.gemm(bt_w[(size_t)s], B + q.W, n, kb, c, B + q.TV + (int64_t)b0 * n + r0, n, X + (int64_t)r0 * ldx + c0, ldx, n - r0);      // W = -(T V^T) X[:, kept]
+            gemms.gemm(bt_x[(size_t)s], X + (int64_t)r0 * ldx + c0, ldx, n - r0, c, B + q.Vc + (int64_t)r0 * n + b0, n, B + q.W, n, kb, 1);   // X[:, kept] += V W
         }
-        bt_w[(size_t)s] = add_set(wb, wsm);
-        bt_x[(size_t)s] = add_set(xb, xs);
     }
-    if (!tiles.empty()) {
+    if (!gemms.groups.empty()) {
         DevBuf d_tab;
         PackedUpload pk;
-        const size_t o_prods = pk.add(prods), o_groups = pk.add(groups), o_tiles = pk.add(tiles);
+        gemms.pack(pk); gemms.pack(root, pk);
+        for (int s = 0; s < max_nblk; ++s) { gemms.pack(bt_w[(size_t)s], pk); gemms.pack(bt_x[(size_t)s], pk); }
         DMRGX_CHK(pk.upload(d_tab, st));
-        const GProd* d_prods = packed_at<GProd>(d_tab, o_prods);
-        const GGroup* d_groups = packed_at<GGroup>(d_tab, o_groups);
-        const GTile* d_tiles = packed_at<GTile>(d_tab, o_tiles);
-        auto run_set = [&](const GemmSet& s) -> dmrgx_status {
-            DMRGX_CHK(ggemm_launch(d_tiles + s.big_off, d_groups, d_prods, s.nbig, st, 1));
-            DMRGX_CHK(ggemm_launch(d_tiles + s.small_off, d_groups, d_prods, s.nsmall, st, 0));
-            return DMRGX_OK;
-        };
-        DMRGX_CHK(run_set(root));
-        for (int s = 0; s < max_nblk; ++s) { DMRGX_CHK(run_set(bt_w[(size_t)s])); DMRGX_CHK(run_set(bt_x[(size_t)s])); }
+        gemms.bind(d_tab);
+        DMRGX_CHK(gemms.launch(root, d_tab, st));
+        for (int s = 0; s < max_nblk; ++s) { DMRGX_CHK(gemms.launch(bt_w[(size_t)s], d_tab, st)); DMRGX_CHK(gemms.launch(bt_x[(size_t)s], d_tab, st)); }
     }
     // (the tables and the workspace go back to the stream-ordered pool: later users are ordered behind the launches above)
     d.dbuf.release(); d.ibuf.release();
