@@ -82,6 +82,20 @@ class GemmTask(C.Structure):
                 ("A", C.c_void_p), ("lda", C.c_int64), ("B", C.c_void_p), ("ldb", C.c_int64), ("C", C.c_void_p), ("ldc", C.c_int64)]
 
 
+class GgemmProd(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("K", C.c_int32), ("A", C.c_void_p), ("lda", C.c_int64), ("B", C.c_void_p), ("ldb", C.c_int64),
+                ("alpha", C.c_double)]
+
+
+class GgemmGroup(C.Structure):
+    _fields_ = [("C", C.c_void_p), ("ldc", C.c_int64), ("M", C.c_int32), ("N", C.c_int32), ("accumulate", C.c_int32), ("nprods", C.c_int32),
+                ("prods", C.POINTER(GgemmProd))]
+
+
+class GgemmReport(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("tiles_big", "tiles_small", "entries_big", "entries_small", "slots_big", "slots_small")]
+
+
 class Rotation(C.Structure):
     _fields_ = [("n_new", C.c_int32), ("old_sector", C.POINTER(C.c_int32)), ("kept", C.POINTER(C.c_int32)), ("rot_t", C.POINTER(C.c_void_p))]
 
@@ -140,6 +154,7 @@ SIGNATURES = {
     "dmrgx_memset_zero": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "dmrgx_stream_sync": (C.c_int32, [C.c_void_p]),
     "dmrgx_dgemm_batch": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p]),
+    "dmrgx_ggemm_groups": (C.c_int32, [C.c_int32, C.POINTER(GgemmGroup), C.c_int32, C.POINTER(GgemmReport), C.c_void_p]),
     "dmrgx_dot": (C.c_int32, [C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "dmrgx_dot_async": (C.c_int32, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dmrgx_dot2d_batch": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

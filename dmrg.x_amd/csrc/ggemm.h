@@ -101,9 +101,10 @@ struct GemmBatch {
     const GGroup* d_groups = nullptr;
 
     // group g, whose products [g.prod_begin, g.prod_end) are already pushed (AXPY products first), with its tiles in s; cost: k-steps
-    void group(GemmSet& s, const GGroup& g, int32_t cost) {
+    // allow_big = false: 64 x 64 tiles only
+    void group(GemmSet& s, const GGroup& g, int32_t cost, bool allow_big = true) {
         groups.push_back(g);
-        ggemm_append_tiles_mixed(s.big, s.small, (int32_t)groups.size() - 1, g.M, g.N, cost);
+        ggemm_append_tiles_mixed(s.big, s.small, (int32_t)groups.size() - 1, g.M, g.N, cost, allow_big);
     }
     // C[M x N] (=|+=) A[M x K] B[K x N], a group of its own; nothing when M or N <= 0
     void gemm(GemmSet& s, double* C, int32_t ldc, int32_t M, int32_t N, const double* A, int32_t lda, const double* B, int32_t ldb, int32_t K, int32_t accumulate = 0) {

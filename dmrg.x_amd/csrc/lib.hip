@@ -87,6 +87,68 @@ extern "C" dmrgx_status dmrgx_dgemm_batch(int32_t count, const dmrgx_gemm_task* 
     return run_gemm_tasks(count, t, (hipStream_t)stream);
 }
 
+// 0: fine; else what is wrong with product q of group g (leading dimensions travel as int32 in the device tables)
+static const char* bad_ggemm_group(const dmrgx_ggemm_group& g, int32_t* q_bad)
+{
+    *q_bad = -1;
+    if (g.M < 0 || g.N < 0 || g.nprods < 0) return "negative size";
+    if (g.nprods > 0 && !g.prods) return "null product list";
+    const bool live = g.M > 0 && g.N > 0;
+    if (live && (!g.C || g.ldc < g.N || g.ldc > INT32_MAX)) return "null C or ldc < N";
+    for (int32_t q = 0; q < g.nprods; ++q) {
+        const dmrgx_ggemm_prod& p = g.prods[q];
+        *q_bad = q;
+        if (p.kind != GPROD_GEMM && p.kind != GPROD_AXPY) return "unknown kind";
+        if (p.kind == GPROD_AXPY) {
+            if (live && (!p.B || p.ldb < g.N || p.ldb > INT32_MAX)) return "scaled copy: null source or ldb < N";
+            continue;
+        }
+        if (p.K < 0) return "negative K";
+        if (live && p.K > 0 && (!p.A || !p.B || p.lda < p.K || p.ldb < g.N || p.lda > INT32_MAX || p.ldb > INT32_MAX)) return "null operand, lda < K or ldb < N";
+    }
+    return nullptr;
+}
+
+extern "C" dmrgx_status dmrgx_ggemm_groups(int32_t count, const dmrgx_ggemm_group* groups, int32_t tiling, dmrgx_ggemm_report* report, void* stream)
+{
+    if (count < 0 || (count > 0 && !groups) || (tiling != 0 && tiling != 1)) DMRGX_FAIL(DMRGX_ERR_ARG, "ggemm_groups: bad argument (count=%d tiling=%d)", count, tiling);
+    for (int32_t i = 0; i < count; ++i) {
+        int32_t q = -1;
+        if (const char* why = bad_ggemm_group(groups[i], &q))
+            DMRGX_FAIL(DMRGX_ERR_ARG, "ggemm_groups: bad group %d (M=%d N=%d nprods=%d, product %d): %s", i, groups[i].M, groups[i].N, groups[i].nprods, q, why);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    GemmBatch b;
+    GemmSet s;
+    for (int32_t i = 0; i < count; ++i) {
+        const dmrgx_ggemm_group& g = groups[i];
+        if (g.M == 0 || g.N == 0) continue;
+        const int32_t pb = (int32_t)b.prods.size();
+        int32_t cost = 0, n_axpy = 0;
+        // the scaled copies first, in their own order, then the GEMM products in theirs
+        for (int32_t q = 0; q < g.nprods; ++q)
+            if (g.prods[q].kind == GPROD_AXPY) { b.prods.push_back(GProd{nullptr, g.prods[q].B, 0, (int32_t)g.prods[q].ldb, 0, GPROD_AXPY, g.prods[q].alpha}); ++n_axpy; ++cost; }
+        for (int32_t q = 0; q < g.nprods; ++q) {
+            const dmrgx_ggemm_prod& p = g.prods[q];
+            if (p.kind != GPROD_GEMM || p.K == 0) continue;
+            b.prods.push_back(GProd{p.A, p.B, (int32_t)p.lda, (int32_t)p.ldb, p.K, GPROD_GEMM, 1.0});
+            cost += (p.K + GG_BK - 1) / GG_BK;
+        }
+        b.group(s, GGroup{g.C, (int32_t)g.ldc, g.M, g.N, pb, (int32_t)b.prods.size(), n_axpy, g.accumulate ? 1 : 0}, cost, tiling == 0);
+    }
+    if (report) {
+        *report = dmrgx_ggemm_report{(int32_t)s.big.size(), (int32_t)s.small.size(), 0, 0, ggemm_slots(2), ggemm_slots(1)};
+    }
+    if (b.groups.empty()) return DMRGX_OK;
+    DevBuf tab;
+    PackedUpload pk;
+    b.pack(pk); b.pack(s, pk);
+    if (report) { report->entries_big = (int32_t)s.big.size(); report->entries_small = (int32_t)s.small.size(); }
+    DMRGX_CHK(pk.upload(tab, st));
+    b.bind(tab);
+    return b.launch(s, tab, st);
+}
+
 extern "C" dmrgx_status dmrgx_malloc(void** p, size_t bytes)
 {
     if (!p) DMRGX_FAIL(DMRGX_ERR_ARG, "malloc: null argument");

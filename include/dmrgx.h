@@ -204,6 +204,31 @@ typedef struct {
     double* C; int64_t ldc;
 } dmrgx_gemm_task;
 dmrgx_status dmrgx_dgemm_batch(int32_t count, const dmrgx_gemm_task* tasks, void* stream);
+/* Whole groups of the grouped GEMM, as the MatMult, the density matrices and the rotations build them (tests/test_gpu_ggemm.py):
+ *   C[M x N] (=|+=) sum over the GEMM products A[M x K] * B[K x N]  +  sum over the scaled copies alpha * S[M x N]
+ * in ONE launch per tile size.  kind 0: GEMM product (a product with K == 0 adds nothing); kind 1: scaled copy, `B` is the source S
+ * and `ldb` its leading dimension, A / lda / K are ignored.  A group without products writes C = 0 (or leaves C, accumulating);
+ * groups with M == 0 or N == 0 are skipped.  Outputs must not overlap.  tiling 0: 128 x 128 cores and 64 x 64 edges (what every
+ * library user gets), 1: 64 x 64 tiles only (as the MatMult tiles).  report (may be NULL): the tiles of the launch, the lengths of
+ * the scheduled lists handed to the kernels (padded per XCD queue) and the resident workgroup slots they were scheduled for --
+ * a list longer than its slots is worked off by claiming.  Asynchronous on `stream`; the tables are consumed before returning. */
+typedef struct {
+    int32_t kind, K;
+    const double* A; int64_t lda;
+    const double* B; int64_t ldb;
+    double alpha;
+} dmrgx_ggemm_prod;
+typedef struct {
+    double* C; int64_t ldc;
+    int32_t M, N, accumulate, nprods;
+    const dmrgx_ggemm_prod* prods;
+} dmrgx_ggemm_group;
+typedef struct {
+    int32_t tiles_big, tiles_small;         /* real tiles: 128 x 128, 64 x 64           */
+    int32_t entries_big, entries_small;     /* list lengths handed to the kernels       */
+    int32_t slots_big, slots_small;         /* resident workgroups of a full launch     */
+} dmrgx_ggemm_report;
+dmrgx_status dmrgx_ggemm_groups(int32_t count, const dmrgx_ggemm_group* groups, int32_t tiling, dmrgx_ggemm_report* report, void* stream);
 
 /* ---- K2: lowest eigenpair of the planned superblock Hamiltonian -------------------------------------- */
 typedef struct {

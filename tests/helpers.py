@@ -91,3 +91,109 @@ def parse_desc2(desc2):
     from oracle.qn import OpSm, OpSz, OpSp
     kinds = {"Sz": OpSz, "Sp": OpSp, "Sm": OpSm}
     return [(kinds[k], int(i)) for k, i in re.findall(r"(S[zpm])_\{(\d+)\}", desc2)]
+
+
+# ---- grouped GEMM: groups with planted borders, a plain float64 reference and a derived bound (tests/test_gpu_ggemm.py) ---------------
+GGEMM_SENTINEL = -6.02214076e+123      # the band round an output; must come back bit for bit
+SCALED_COPY = "s"                      # entry of a product list: alpha * S (an int K is a GEMM product A[M x K] B[K x N])
+
+
+def ggemm_values(rng, shape):
+    """Magnitudes in [0.5, 1.5] with random signs: every single term a * b or alpha * s of an output element is >= 0.25 in magnitude."""
+    return rng.uniform(0.5, 1.5, size=shape) * rng.choice((-1.0, 1.0), size=shape)
+
+
+class GgemmOperand:
+    """A rows x cols matrix as a sub-view (row and column offset, ld > cols) of a larger buffer filled with `fill`."""
+
+    def __init__(self, rng, values, fill, tight=False):
+        rows, cols = values.shape
+        top, bottom, left, right = (1, 1, 1, 2) if tight else (int(v) for v in rng.integers(1, 6, size=4))
+        self.buf = np.full((rows + top + bottom, cols + left + right), fill, dtype=np.float64)
+        self.r0, self.c0, self.rows, self.cols = top, left, rows, cols
+        self.view[...] = values
+
+    @property
+    def view(self):
+        return self.buf[self.r0:self.r0 + self.rows, self.c0:self.c0 + self.cols]
+
+    @property
+    def ld(self):
+        return self.buf.shape[1]
+
+    @property
+    def first(self):          # element offset of view[0, 0] inside buf
+        return self.r0 * self.ld + self.c0
+
+
+class GgemmInstance:
+    """One group description with its operands: C[M x N] (=|+=) sum_p A_p B_p + sum_q alpha_q S_q.  `prods` lists K (GEMM product) or
+    SCALED_COPY in the caller's order.  A, B and S sit in NaN buffers (a read past the K edge, or outside S, poisons the result); the
+    output's initial content is C0 (magnitude rule) when accumulating and NaN otherwise, inside a band of GGEMM_SENTINEL.
+    R, S_abs, n: the float64 reference, sum of the magnitudes of the terms and the number of terms of an element."""
+
+    def __init__(self, rng, M, N, prods, accumulate=False, tight=False):
+        self.M, self.N, self.accumulate = M, N, bool(accumulate)
+        self.prods = []                # (kind, K, A operand or None, B / S operand, alpha)
+        for p in prods:
+            if p == SCALED_COPY:
+                self.prods.append((1, 0, None, GgemmOperand(rng, ggemm_values(rng, (M, N)), np.nan, tight), float(ggemm_values(rng, ()))))
+            else:
+                K = int(p)
+                self.prods.append((0, K, GgemmOperand(rng, ggemm_values(rng, (M, K)), np.nan, tight),
+                                   GgemmOperand(rng, ggemm_values(rng, (K, N)), np.nan, tight), 1.0))
+        self.C0 = ggemm_values(rng, (M, N)) if accumulate else None
+        self.c_pad = (1, 1, 1, 2) if tight else tuple(int(v) for v in rng.integers(1, 6, size=4))
+        self.R, self.S_abs, self.n = ggemm_reference(self)
+
+    def output_buffer(self):
+        """(buffer, r0, c0): a fresh output buffer in its sentinel band."""
+        top, bottom, left, right = self.c_pad
+        buf = np.full((self.M + top + bottom, self.N + left + right), GGEMM_SENTINEL, dtype=np.float64)
+        buf[top:top + self.M, left:left + self.N] = self.C0 if self.accumulate else np.nan
+        return buf, top, left
+
+
+def ggemm_reference(inst, dtype=np.float64):
+    """R = sum_p A_p B_p + sum_q alpha_q S_q (+ C0) in plain numpy at `dtype`, S = the same sum over magnitudes, n = terms per element."""
+    R, S, n = np.zeros((inst.M, inst.N), dtype=dtype), np.zeros((inst.M, inst.N), dtype=dtype), 0
+    for kind, K, A, B, alpha in inst.prods:
+        if kind == 1:
+            R = R + dtype(alpha) * B.view.astype(dtype)
+            S = S + abs(dtype(alpha)) * np.abs(B.view.astype(dtype))
+            n += 1
+        else:
+            R = R + A.view.astype(dtype) @ B.view.astype(dtype)
+            S = S + np.abs(A.view.astype(dtype)) @ np.abs(B.view.astype(dtype))
+            n += K
+    if inst.accumulate:
+        R, S, n = R + inst.C0.astype(dtype), S + np.abs(inst.C0.astype(dtype)), n + 1
+    return R, S, n
+
+
+def ggemm_bound(S_abs, n):
+    """|got - R| <= 2 (n + 2) eps S, element by element.  A sum of n products evaluated in ANY order, with or without fused
+    multiply-adds, is within gamma_n S of the exact value, gamma_n = n u / (1 - n u) with u = eps / 2 (Higham, Accuracy and Stability of
+    Numerical Algorithms, section 3.1); (n + 2) eps lies above gamma_n for every n < 2^50, and it is taken once for the kernel and once
+    for the numpy reference.  Derived, not measured."""
+    return 2.0 * (n + 2) * np.finfo(np.float64).eps * np.asarray(S_abs, dtype=np.float64)
+
+
+def ggemm_violations(got, R, S_abs, n):
+    """Boolean M x N array: the elements of `got` outside the bound (a NaN is outside)."""
+    got = np.asarray(got, dtype=np.float64)
+    assert got.shape == R.shape, (got.shape, R.shape)
+    return ~(np.abs(got - R) <= ggemm_bound(S_abs, n))
+
+
+def ggemm_check(got, inst, what=""):
+    """Asserts that `got` is the result of `inst` within the bound at every element; returns the worst |got - R| / bound (0 for 0 / 0)."""
+    bad = ggemm_violations(got, inst.R, inst.S_abs, inst.n)
+    if bad.any():
+        i, j = (int(v) for v in np.argwhere(bad)[0])
+        raise AssertionError("%s: %d of %d elements outside the bound, first at (%d, %d): got %r, want %r, bound %.3e (M=%d N=%d n=%d)"
+                             % (what, int(bad.sum()), bad.size, i, j, float(np.asarray(got)[i, j]), float(inst.R[i, j]),
+                                float(ggemm_bound(inst.S_abs, inst.n)[i, j]), inst.M, inst.N, inst.n))
+    bound = ggemm_bound(inst.S_abs, inst.n)
+    err = np.abs(np.asarray(got, dtype=np.float64) - inst.R)
+    return float(np.max(np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), 0.0))) if err.size else 0.0

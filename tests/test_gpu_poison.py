@@ -369,6 +369,14 @@ POISONED_NODES = [
     "tests/test_gpu_poison.py::test_generalized_davidson_odd_and_even_sizes",
     "tests/test_gpu_poison.py::test_rdm_verification_catches_a_changed_state",
     "tests/test_gpu_poison.py::test_rdm_keeps_a_temporary_state_alive",
+    "tests/test_gpu_ggemm.py::test_k_ladder_one_product",
+    "tests/test_gpu_ggemm.py::test_product_lists",
+    "tests/test_gpu_ggemm.py::test_scaled_copies",
+    "tests/test_gpu_ggemm.py::test_accumulate",
+    "tests/test_gpu_ggemm.py::test_tile_geometry_mixed_tiling",
+    "tests/test_gpu_ggemm.py::test_tile_geometry_64_only",
+    "tests/test_gpu_ggemm.py::test_launch_regimes_64",
+    "tests/test_gpu_ggemm.py::test_claiming_128",
 ]
 
 
