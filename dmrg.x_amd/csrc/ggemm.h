@@ -38,30 +38,29 @@ constexpr int GG_BM = 64, GG_BN = 64, GG_BK = 16, GG_THREADS = 256;
 // (coordinates still in 64-units), else 64 x 64.
 dmrgx_status ggemm_launch(const GTile* d_tiles, const GGroup* d_groups, const GProd* d_prods, int32_t ntiles, hipStream_t st, int big = 0);
 
+inline int32_t ggemm_ksteps(int32_t K) { return (K + GG_BK - 1) / GG_BK; }    // k-steps of one GEMM product: the unit of every tile cost
+
 // Host-side helper: append the tiles of group `g` (M x N) to a tile list in 8 x 8 clusters (tiles of a cluster share
 // A row-panels and B column-panels; the scheduler keeps a cluster on one XCD so they meet in its L2); `cost` (k-steps of
-// the group's product list) is stored in GTile::pad for the scheduler.
+// the group's product list) is stored in GTile::pad for the scheduler.  The leading core_m x core_n tiles are left out (ggemm_append_tiles_mixed).
 constexpr int GG_CLUSTER = 8;   // cluster edge in tiles (4 and 16 measured within 1-2 %, rounds 2 and 4)
-inline void ggemm_append_tiles(std::vector<GTile>& tiles, int32_t g, int32_t M, int32_t N, int32_t cost = 1) {
+inline void ggemm_append_tiles(std::vector<GTile>& tiles, int32_t g, int32_t M, int32_t N, int32_t cost = 1, int32_t core_m = 0, int32_t core_n = 0) {
     const int32_t TM = (M + GG_BM - 1) / GG_BM, TN = (N + GG_BN - 1) / GG_BN;
     for (int32_t bm = 0; bm < TM; bm += GG_CLUSTER)
         for (int32_t bn = 0; bn < TN; bn += GG_CLUSTER)
             for (int32_t tm = bm; tm < std::min(TM, bm + GG_CLUSTER); ++tm)
-                for (int32_t tn = bn; tn < std::min(TN, bn + GG_CLUSTER); ++tn) tiles.push_back(GTile{g, tm, tn, cost});
+                for (int32_t tn = bn; tn < std::min(TN, bn + GG_CLUSTER); ++tn)
+                    if (tm >= core_m || tn >= core_n) tiles.push_back(GTile{g, tm, tn, cost});
 }
 
+// The 128-aligned core of the group as 128 x 128 macro tiles in `big`, the edges as 64 x 64 tiles in `small`.
 inline void ggemm_append_tiles_mixed(std::vector<GTile>& big, std::vector<GTile>& small, int32_t g, int32_t M, int32_t N, int32_t cost = 1, bool allow_big = true) {
     const int32_t mb = allow_big ? (M / 128) * 2 : 0, nb = allow_big ? (N / 128) * 2 : 0;   // core extent in 64-units
     for (int32_t bm = 0; bm < mb; bm += 2 * GG_CLUSTER)
         for (int32_t bn = 0; bn < nb; bn += 2 * GG_CLUSTER)
             for (int32_t tm = bm; tm < std::min(mb, bm + 2 * GG_CLUSTER); tm += 2)
                 for (int32_t tn = bn; tn < std::min(nb, bn + 2 * GG_CLUSTER); tn += 2) big.push_back(GTile{g, tm, tn, 4 * cost});
-    const int32_t TM = (M + GG_BM - 1) / GG_BM, TN = (N + GG_BN - 1) / GG_BN;
-    for (int32_t bm = 0; bm < TM; bm += GG_CLUSTER)
-        for (int32_t bn = 0; bn < TN; bn += GG_CLUSTER)
-            for (int32_t tm = bm; tm < std::min(TM, bm + GG_CLUSTER); ++tm)
-                for (int32_t tn = bn; tn < std::min(TN, bn + GG_CLUSTER); ++tn)
-                    if (tm >= mb || tn >= nb) small.push_back(GTile{g, tm, tn, cost});
+    ggemm_append_tiles(small, g, M, N, cost, mb, nb);
 }
 
 // XCD-aware, cost-balanced launch order.  Blocks b, b+8, b+16.. run on one XCD (each XCD has its own L2), so the
@@ -111,7 +110,7 @@ struct GemmBatch {
         if (M <= 0 || N <= 0 || (K <= 0 && skip_empty_k)) return;
         const int32_t p0 = (int32_t)prods.size();
         if (K > 0) prods.push_back(GProd{A, B, lda, ldb, K, GPROD_GEMM, 1.0});
-        group(s, GGroup{C, ldc, M, N, p0, (int32_t)prods.size(), 0, accumulate}, (K + GG_BK - 1) / GG_BK);
+        group(s, GGroup{C, ldc, M, N, p0, (int32_t)prods.size(), 0, accumulate}, ggemm_ksteps(K));
     }
     void pack(PackedUpload& pk) {           // the product and group tables (a dummy entry in an empty one)
         if (prods.empty()) prods.push_back(GProd{nullptr, nullptr, 0, 0, 0, GPROD_GEMM, 0.0});

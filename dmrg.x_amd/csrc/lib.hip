@@ -132,7 +132,7 @@ extern "C" dmrgx_status dmrgx_ggemm_groups(int32_t count, const dmrgx_ggemm_grou
             const dmrgx_ggemm_prod& p = g.prods[q];
             if (p.kind != GPROD_GEMM || p.K == 0) continue;
             b.prods.push_back(GProd{p.A, p.B, (int32_t)p.lda, (int32_t)p.ldb, p.K, GPROD_GEMM, 1.0});
-            cost += (p.K + GG_BK - 1) / GG_BK;
+            cost += ggemm_ksteps(p.K);
         }
         b.group(s, GGroup{g.C, (int32_t)g.ldc, g.M, g.N, pb, (int32_t)b.prods.size(), n_axpy, g.accumulate ? 1 : 0}, cost, tiling == 0);
     }

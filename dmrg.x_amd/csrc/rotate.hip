@@ -162,7 +162,7 @@ extern "C" dmrgx_status dmrgx_rotate_ops(const dmrgx_sectors* old_sectors, const
         const int32_t pb = (int32_t)gemms.prods.size();
         if (ce.kind == DMRGX_CELL_DENSE) gemms.prods.push_back(GProd{RTa, ce.data, nq, (int32_t)ce.ld, ce.nr, GPROD_GEMM, 1.0});
         else gemms.prods.push_back(GProd{nullptr, RTa, 0, nq, 0, GPROD_AXPY, ce.scale});
-        gemms.group(sA, GGroup{W + w.off, ce.nc, m, ce.nc, pb, pb + 1, ce.kind == DMRGX_CELL_DENSE ? 0 : 1, 0}, (ce.nr + GG_BK - 1) / GG_BK);
+        gemms.group(sA, GGroup{W + w.off, ce.nc, m, ce.nc, pb, pb + 1, ce.kind == DMRGX_CELL_DENSE ? 0 : 1, 0}, ggemm_ksteps(ce.nr));
     }
     // stage B: group per (op, a) destination
     std::map<std::pair<int32_t, int32_t>, std::vector<const WRef*>> by_dst;
@@ -182,7 +182,7 @@ extern "C" dmrgx_status dmrgx_rotate_ops(const dmrgx_sectors* old_sectors, const
         for (const WRef* w : kv.second) {
             const dmrgx_cell& ce = src_ops[o].cells[w->cell];
             gemms.prods.push_back(GProd{W + w->off, UT + ut_off[ap] + (int64_t)ce.c0 * mp, ce.nc, mp, ce.nc, GPROD_GEMM, 1.0});
-            cost += (ce.nc + GG_BK - 1) / GG_BK;
+            cost += ggemm_ksteps(ce.nc);
         }
         gemms.group(sB, GGroup{dst_blocks[o][a], mp, m, mp, pb, (int32_t)gemms.prods.size(), 0, 0}, cost);
     }

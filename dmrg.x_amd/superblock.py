@@ -147,7 +147,7 @@ class KronPlan:
         _capi.check(_capi.lib().dmrgx_kron_plan_timing(self._handle, 1 if enable else 0))
 
     def timing_read(self):
-        """-> ([ms stage-1 128-tiles, ms stage-1 64-tiles, ms stage-2 128-tiles, ms stage-2 64-tiles], applies recorded)."""
+        """-> ([0, ms stage 1, 0, ms stage 2], applies recorded): slots 0 and 2 belong to 128 x 128 launches, which the MatMult does not make."""
         ms, n = (C.c_double * 4)(), C.c_int64(0)
         _capi.check(_capi.lib().dmrgx_kron_plan_timing_read(self._handle, ms, C.byref(n)))
         return list(ms), n.value

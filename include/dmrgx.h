@@ -156,8 +156,8 @@ typedef struct {
     double  bytes_workspace;   /* bytes of intermediates written+read per apply (not part of B_alg)     */
     int32_t n_groups;          /* merged (A,B) operator pairs                                           */
     int32_t n_tiles_stage1, n_tiles_stage2;
-    int32_t n_tiles_big;       /* of those, 128x128 macro tiles (the rest are 64x64)                      */
-    double  flops_alg_big;     /* part of flops_alg executed by the 128x128 kernel                        */
+    int32_t n_tiles_big;       /* of those, 128x128 macro tiles: 0, the MatMult runs 64x64 tiles only     */
+    double  flops_alg_big;     /* part of flops_alg executed by the 128x128 kernel: 0                     */
 } dmrgx_kron_info;
 
 dmrgx_status dmrgx_kron_plan_create(const dmrgx_kron_desc* desc, void* stream, dmrgx_kron_plan** out);
@@ -175,8 +175,9 @@ dmrgx_status dmrgx_kron_diag(dmrgx_kron_plan* plan, double* d_local_dev, void* s
  * (the reference's analogue is the -DDMRG_KRON_TIMINGS accumulators, include/MiscTools.hpp:17-59).
  * enable != 0 resets and starts recording (up to 4096 applies), enable == 0 stops. */
 dmrgx_status dmrgx_kron_plan_timing(dmrgx_kron_plan* plan, int32_t enable);
-/* Synchronises the recorded events and returns the summed kernel time in milliseconds of the four GEMM launches
- * of an apply: ms[0] stage-1 128x128 tiles, ms[1] stage-1 64x64 tiles, ms[2] stage-2 128x128, ms[3] stage-2 64x64. */
+/* Synchronises the recorded events (three per apply: before stage 1, between the stages, after stage 2) and returns the
+ * summed kernel time in milliseconds of the two GEMM launches of an apply: ms[1] stage 1, ms[3] stage 2.  ms[0] and ms[2]
+ * are the slots of 128x128 launches, which the MatMult does not make: always 0. */
 dmrgx_status dmrgx_kron_plan_timing_read(dmrgx_kron_plan* plan, double* ms4, int64_t* n_applies);
 /* Convert between the reference's vector layout (KronBlocks order, n_states doubles, host or device) and the
  * striped full-vector layout (identity copy when world_size == 1). */

@@ -1,7 +1,7 @@
 """Child process of tests/test_gpu_poison.py: runs fixed-input kernels and writes their outputs to an .npz file, so that runs in
 separate processes -- clean or with DMRGX_POOL_POISON=1 -- can be compared bit for bit.
 
-    python tests/bitwise_worker.py OUT.npz apply,solvers
+    python tests/bitwise_worker.py OUT.npz apply,solvers,striped
 """
 import hashlib
 import os
@@ -60,6 +60,27 @@ def solvers(out):
     rdm.destroy()
 
 
+def striped(out):
+    """Multi-rank plans with every rank emulated in this process: to_striped, each rank's apply into a NaN-filled ys, from_striped.
+    m = 60 at W = 3: right sectors [1, 4, 10, 18, 27, 27, 18, 10, 4, 1], every stripe an even split and some of them empty.
+    m = 256, Ly = 4 at W = 2 (40 940 states): right sectors of 110 >= 48 W, where stripe_cut snaps to 64, beside 78 < 48 W, the even split."""
+    for tag, kw, world in (("m60_w3", dict(m=60, Ly=3, seed=11), 3), ("m256_w2", dict(m=256, Ly=4), 2)):
+        sb = wl.synthetic_superblock("cfg2", **kw)
+        plans = [sbm.KronPlan(sb, world_size=world, rank=r) for r in range(world)]
+        x = torch.from_numpy(np.random.default_rng(77).standard_normal(sb.n_states)).cuda()
+        xs = torch.zeros(plans[0].info.vec_len, dtype=torch.float64, device="cuda")
+        plans[0].to_striped(x, xs)
+        ys = torch.full_like(xs, float("nan"))
+        for p in plans:
+            p.apply(xs, ys[p.info.local_offset:p.info.local_offset + p.info.local_len])
+        y = torch.full_like(x, float("nan"))
+        plans[0].from_striped(ys, y)
+        torch.cuda.synchronize()
+        out["striped_%s" % tag] = y.cpu().numpy()
+        for p in plans:
+            p.destroy()
+
+
 if __name__ == "__main__":
     path, what = sys.argv[1], sys.argv[2].split(",")
     res = {}
@@ -67,5 +88,7 @@ if __name__ == "__main__":
         full_size_applies(res)
     if "solvers" in what:
         solvers(res)
+    if "striped" in what:
+        striped(res)
     np.savez(path, **res)
     print("bitwise worker ok", sorted(res))
