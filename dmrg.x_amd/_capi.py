@@ -96,6 +96,10 @@ class GgemmReport(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("tiles_big", "tiles_small", "entries_big", "entries_small", "slots_big", "slots_small")]
 
 
+class GramReport(C.Structure):
+    _fields_ = [("tiles", C.c_int32), ("slices", C.c_int32), ("slab_doubles", C.c_int64)]
+
+
 class Rotation(C.Structure):
     _fields_ = [("n_new", C.c_int32), ("old_sector", C.POINTER(C.c_int32)), ("kept", C.POINTER(C.c_int32)), ("rot_t", C.POINTER(C.c_void_p))]
 
@@ -158,6 +162,11 @@ SIGNATURES = {
     "dmrgx_dot": (C.c_int32, [C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "dmrgx_dot_async": (C.c_int32, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dmrgx_dot2d_batch": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dmrgx_vec_gram": (C.c_int32, [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                   C.c_int32, C.POINTER(GramReport), C.c_void_p]),
+    "dmrgx_kron_op_gram": (C.c_int32, [C.POINTER(Sectors), C.POINTER(Sectors), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
+                                       C.c_int32, C.POINTER(SecOp), C.c_int32, C.POINTER(SecOp), C.c_size_t, C.c_void_p, C.c_int64,
+                                       C.POINTER(GramReport), C.c_void_p]),
     "dmrgx_eigs_comm_timing": (C.c_int32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),
     "dmrgx_eigs_lowest": (C.c_int32, [C.c_void_p, C.POINTER(EigsOpts), C.POINTER(C.c_double), C.c_void_p,
                                       C.POINTER(EigsStats), C.c_void_p]),

@@ -945,3 +945,177 @@ extern "C" dmrgx_status dmrgx_kron_diag(dmrgx_kron_plan* P, double* d_local, voi
     }
     return DMRGX_OK;
 }
+
+// ---- all-pairs correlators: G = Gram matrix of the operator images O_a psi -------------------------------------------------------
+// The image of psi under A (x) 1 (or 1 (x) B) is formed block by block as grouped-GEMM products (dense cells) and scaled copies
+// (identity cells), exactly like a stage-2 (stage-1) row of the MatMult without the other factor; dmrgx_vec_gram then takes every
+// inner product at once.  The images are never held whole: the image blocks are worked off in slices that fit the workspace bound.
+namespace {
+struct UCell { int32_t r0, c0, nr, nc, kind; double scale; const double* data; int32_t ld; int64_t trans_off; };      // data: row-major in the shape the NN GEMM reads; trans_off >= 0: materialised there
+struct ImgBlock { int32_t a, b, src_left, src_right; int64_t size, off; int32_t slice; };
+}  // namespace
+
+extern "C" dmrgx_status dmrgx_kron_op_gram(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
+                                           const int32_t* block_il, const int32_t* block_ir, const double* psi_dev,
+                                           int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
+                                           size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, void* stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (!left || !right || left->nsec <= 0 || right->nsec <= 0 || !left->size || !right->size) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_op_gram: empty sector table");
+    const dmrgx_sectors& SL = *left;
+    const dmrgx_sectors& SR = *right;
+    for (int i = 0; i < SL.nsec; ++i) if (SL.size[i] <= 0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_op_gram: left sector %d has size %d", i, SL.size[i]);
+    for (int i = 0; i < SR.nsec; ++i) if (SR.size[i] <= 0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_op_gram: right sector %d has size %d", i, SR.size[i]);
+    if (nblocks <= 0 || !block_il || !block_ir) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_op_gram: no KronBlocks");
+    if (!psi_dev) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_op_gram: null psi");
+    if (n_left_ops < 0 || n_right_ops < 0 || n_left_ops + n_right_ops < 1 || (n_left_ops > 0 && !left_ops) || (n_right_ops > 0 && !right_ops))
+        DMRGX_FAIL(DMRGX_ERR_ARG, "kron_op_gram: bad operator lists (%d left, %d right)", n_left_ops, n_right_ops);
+    const int32_t nops = n_left_ops + n_right_ops;
+    if (!G_dev || ldg < nops) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_op_gram: null G or ldg %lld below the %d operators", (long long)ldg, nops);
+    std::map<std::pair<int32_t, int32_t>, int32_t> kmap;
+    std::vector<int64_t> ref_off(nblocks + 1, 0);
+    for (int32_t k = 0; k < nblocks; ++k) {
+        const int32_t il = block_il[k], ir = block_ir[k];
+        if (il < 0 || il >= SL.nsec || ir < 0 || ir >= SR.nsec) DMRGX_FAIL(DMRGX_ERR_OUTOFRANGE, "kron_op_gram: KronBlock %d = (%d,%d) out of range", k, il, ir);
+        if (!kmap.emplace(std::make_pair(il, ir), k).second) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_op_gram: KronBlock (%d,%d) listed twice", il, ir);
+        ref_off[k + 1] = ref_off[k] + (int64_t)SL.size[il] * SR.size[ir];
+    }
+    auto op_at = [&](int32_t v) -> const dmrgx_secop& { return v < n_left_ops ? left_ops[v] : right_ops[v - n_left_ops]; };
+    const int32_t shift = op_at(0).shift;
+    for (int32_t v = 1; v < nops; ++v)
+        if (op_at(v).shift != shift) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_op_gram: operator %d has shift %d, operator 0 has %d: one call takes one shift", v, op_at(v).shift, shift);
+    std::vector<std::vector<NCell>> cells(nops);
+    for (int32_t v = 0; v < nops; ++v) DMRGX_CHK(normalise_op(&op_at(v), v < n_left_ops ? SL : SR, v < n_left_ops ? "kron_op_gram left op" : "kron_op_gram right op", cells[v]));
+
+    // image blocks, in KronBlock order (left image, then right image of each)
+    std::vector<ImgBlock> imgs;
+    std::map<std::pair<int32_t, int32_t>, int32_t> imap;
+    auto image = [&](int32_t a, int32_t b) -> ImgBlock& {
+        auto it = imap.emplace(std::make_pair(a, b), (int32_t)imgs.size());
+        if (it.second) imgs.push_back(ImgBlock{a, b, -1, -1, (int64_t)SL.size[a] * SR.size[b], 0, 0});
+        return imgs[it.first->second];
+    };
+    for (int32_t k = 0; k < nblocks; ++k) {
+        const int32_t a = block_il[k] - shift, b = block_ir[k] - shift;
+        if (n_left_ops > 0 && a >= 0 && a < SL.nsec) image(a, block_ir[k]).src_left = k;
+        if (n_right_ops > 0 && b >= 0 && b < SR.nsec) image(block_il[k], b).src_right = k;
+    }
+    // slices of image blocks that fit the workspace
+    const int64_t bound = (int64_t)((workspace_bytes ? workspace_bytes : ((size_t)1 << 30)) / sizeof(double)) / nops;
+    std::vector<int64_t> slice_len;
+    for (ImgBlock& im : imgs) {
+        if (im.size > bound)
+            DMRGX_FAIL(DMRGX_ERR_ARG, "kron_op_gram: image block (%d,%d) of %d x %d needs %lld bytes for the %d operators, workspace_bytes allows %lld",
+                       im.a, im.b, SL.size[im.a], SR.size[im.b], (long long)(im.size * nops * (int64_t)sizeof(double)), nops, (long long)(bound * nops * (int64_t)sizeof(double)));
+        if (slice_len.empty() || slice_len.back() + im.size > bound) slice_len.push_back(0);
+        im.slice = (int32_t)slice_len.size() - 1;
+        im.off = slice_len.back();
+        slice_len.back() += im.size;
+    }
+    const int32_t nslices = (int32_t)slice_len.size();
+    if (nslices == 0) {                               // no shifted sector exists: every image is zero
+        DMRGX_CHK(dmrgx_vec_gram(nops, nops, 0, nullptr, 0, nullptr, 0, G_dev, ldg, 0, report, stream));
+        return DMRGX_OK;
+    }
+    DevBuf W, trans, tab;
+    DMRGX_CHK(W.alloc_f64((size_t)(*std::max_element(slice_len.begin(), slice_len.end())) * nops, st));
+
+    // the NN GEMM reads a left cell as A (row-major nr x nc) and a right cell as B = cell^T (row-major nc x nr): cells stored the other
+    // way round are materialised once per call (as the plan's cell_copy writes B^T)
+    std::vector<std::vector<UCell>> ucells(nops);
+    std::vector<CopyTask> copies;
+    std::vector<CopyTile> copy_tiles;
+    int64_t trans_doubles = 0;
+    for (int32_t v = 0; v < nops; ++v)
+        for (const NCell& c : cells[v]) {
+            const bool is_left = v < n_left_ops;
+            UCell u{c.r0, c.c0, c.nr, c.nc, c.kind, c.scale, c.data, 0, -1};
+            if (c.kind == DMRGX_CELL_DENSE) {
+                if (c.ld > INT32_MAX) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_op_gram: operator %d: leading dimension %lld of a cell too large", v, (long long)c.ld);
+                u.ld = (int32_t)c.ld;
+                if (c.tr == is_left) {                  // left and stored transposed, or right and stored plainly
+                    const int32_t dr = is_left ? c.nr : c.nc, dc = is_left ? c.nc : c.nr;
+                    copies.push_back(CopyTask{trans_doubles, c.data, c.ld, dr, dc, dc, 1, 1.0, 0});
+                    for (int32_t ti = 0; ti < (dr + 31) / 32; ++ti)
+                        for (int32_t tj = 0; tj < (dc + 31) / 32; ++tj) copy_tiles.push_back(CopyTile{(int32_t)copies.size() - 1, ti, tj, 0});
+                    u.trans_off = trans_doubles;
+                    u.ld = dc;
+                    trans_doubles += (int64_t)dr * dc;
+                }
+            }
+            ucells[v].push_back(u);
+        }
+    if (trans_doubles > 0) DMRGX_CHK(trans.alloc_f64((size_t)trans_doubles, st));
+    for (auto& list : ucells)
+        for (UCell& u : list)
+            if (u.trans_off >= 0) u.data = trans.as<double>() + u.trans_off;
+
+    GemmBatch gb;
+    std::vector<GemmSet> sets(nslices);
+    std::vector<int32_t> cuts, hit;
+    for (const ImgBlock& im : imgs) {
+        const int32_t nLa = SL.size[im.a], nRb = SR.size[im.b];
+        const int64_t ldw = slice_len[im.slice];
+        for (int32_t v = 0; v < nops; ++v) {
+            const bool is_left = v < n_left_ops;
+            double* Y = W.as<double>() + (int64_t)v * ldw + im.off;
+            const int32_t src = is_left ? im.src_left : im.src_right;
+            const int32_t q = is_left ? im.a : im.b, n = is_left ? nLa : nRb;     // the operator's row sector and its size: the index cut in segments
+            // segments of that index between the borders of the cells that reach it: every segment gets one group (no products: zeros)
+            cuts.assign({0, n});
+            hit.clear();
+            if (src >= 0)
+                for (size_t i = 0; i < cells[v].size(); ++i)
+                    if (cells[v][i].q == q) { hit.push_back((int32_t)i); cuts.push_back(cells[v][i].r0); cuts.push_back(cells[v][i].r0 + cells[v][i].nr); }
+            std::sort(cuts.begin(), cuts.end());
+            cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+            const double* X = src >= 0 ? psi_dev + ref_off[src] : nullptr;
+            const int32_t ldx = src >= 0 ? SR.size[block_ir[src]] : 0;
+            for (size_t s = 0; s + 1 < cuts.size(); ++s) {
+                const int32_t p = cuts[s], e = cuts[s + 1];
+                const int32_t pb = (int32_t)gb.prods.size();
+                int32_t cost = 0, n_axpy = 0;
+                for (int pass = 0; pass < 2; ++pass)            // scaled copies first, then the GEMM products
+                    for (int32_t i : hit) {
+                        const UCell& u = ucells[v][i];
+                        if (u.r0 > p || u.r0 + u.nr < e || (u.kind == DMRGX_CELL_IDENT) != (pass == 0)) continue;
+                        const int32_t d = p - u.r0;
+                        if (u.kind == DMRGX_CELL_IDENT) {
+                            gb.prods.push_back(GProd{nullptr, is_left ? X + (int64_t)(u.c0 + d) * ldx : X + u.c0 + d, 0, ldx, 0, GPROD_AXPY, u.scale});
+                            ++n_axpy; ++cost;
+                        } else if (is_left) {
+                            gb.prods.push_back(GProd{u.data + (int64_t)d * u.ld, X + (int64_t)u.c0 * ldx, u.ld, ldx, u.nc, GPROD_GEMM, 1.0});
+                            cost += ggemm_ksteps(u.nc);
+                        } else {
+                            gb.prods.push_back(GProd{X + u.c0, u.data + d, ldx, u.ld, u.nc, GPROD_GEMM, 1.0});
+                            cost += ggemm_ksteps(u.nc);
+                        }
+                    }
+                const GGroup g = is_left ? GGroup{Y + (int64_t)p * nRb, nRb, e - p, nRb, pb, (int32_t)gb.prods.size(), n_axpy, 0}
+                                         : GGroup{Y + p, nRb, nLa, e - p, pb, (int32_t)gb.prods.size(), n_axpy, 0};
+                gb.group(sets[im.slice], g, std::max(cost, 1));
+            }
+        }
+    }
+    PackedUpload pk;
+    gb.pack(pk);
+    for (GemmSet& s : sets) gb.pack(s, pk);
+    const size_t o_tasks = pk.add(copies), o_tiles = pk.add(copy_tiles);
+    DMRGX_CHK(pk.upload(tab, st));
+    gb.bind(tab);
+    if (!copy_tiles.empty()) {
+        hipLaunchKernelGGL(cell_copy_kernel, dim3((unsigned)copy_tiles.size()), dim3(256), 0, st, (const CopyTile*)packed_at<CopyTile>(tab, o_tiles),
+                           (const CopyTask*)packed_at<CopyTask>(tab, o_tasks), trans.as<double>());
+        DMRGX_HIP(hipGetLastError());
+    }
+    dmrgx_gram_report total{0, nslices, 0};
+    for (int32_t s = 0; s < nslices; ++s) {               // fixed order: slice s is added to the sum of the slices before it
+        DMRGX_CHK(gb.launch(sets[s], tab, st));
+        dmrgx_gram_report r{};
+        DMRGX_CHK(dmrgx_vec_gram(nops, nops, slice_len[s], W.as<double>(), slice_len[s], W.as<double>(), slice_len[s], G_dev, ldg, s > 0 ? 1 : 0, &r, stream));
+        total.tiles = r.tiles;
+        total.slab_doubles = std::max(total.slab_doubles, r.slab_doubles);
+    }
+    if (report) *report = total;
+    return DMRGX_OK;
+}

@@ -194,6 +194,7 @@ public:
         ierr = PetscOptionsGetBool(NULL, NULL, "-wavefunction_guess_overlap", &use_guess_overlap, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-rdm_warm_start", &use_rdm_warm, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-corr_batch", &use_corr_batch, NULL); CHKERRQ(ierr);
+        ierr = PetscOptionsGetBool(NULL, NULL, "-corr_matrix", &use_corr_matrix, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-prune_ops", &prune_ops, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-step_profile", &step_profile, NULL); CHKERRQ(ierr);
 
@@ -442,6 +443,7 @@ public:
         spectra_writer.Drain();
         if (fp_entanglement) { fprintf(fp_entanglement, "\n]\n"); fclose(fp_entanglement); fp_entanglement = NULL; }
         if (fp_kron) { fprintf(fp_kron, "\n]\n"); fclose(fp_kron); fp_kron = NULL; }
+        if (fp_spin) { fprintf(fp_spin, "\n]\n"); fclose(fp_spin); fp_spin = NULL; }
         if (fp_corr) {
             if (!corr_headers_printed) { PetscErrorCode e2 = PrintCorrelationHeaders(); CHKERRQ(e2); }
             fprintf(fp_corr, "\n  ]\n}\n"); fclose(fp_corr); fp_corr = NULL;
@@ -1312,6 +1314,131 @@ public:
             fprintf(fp_corr, " ]");
             fflush(fp_corr);
         }
+        if (use_corr_matrix) { ierr = CalculateCorrelationMatrix(KronBlocks, gsv_r); CHKERRQ(ierr); }
+        return 0;
+    }
+
+    /** -corr_matrix 1 (engine extension): the full tables < Sz_i Sz_j >, < Sm_i Sp_j > and < Sp_i Sm_j > over all pairs of lattice sites,
+        the spin correlation function < S_i . S_j > and its Fourier transform, the static structure factor, at every measurement point.
+        < psi | O_i^T O_j | psi > = < O_i psi , O_j psi >: a table is the Gram matrix of the vectors O_i psi, so each is ONE
+        dmrgx_kron_op_gram call -- the identity (which adds < Sz_i > and the norm) and Sz of every site of both blocks, shift 0; Sp of
+        every site, shift +1; Sm of every site (Sp read transposed), shift -1 -- instead of a plan, a MatMult and a dot product per pair.
+        < Sp_i Sm_j > is a table of its own because two TRUNCATED operators of one block do not commute: it equals < Sm_j Sp_i > only
+        across the cut or when nothing was truncated, and the registered correlators multiply the operators in the order they name.
+        Site s of the right block is lattice site N - 1 - s, as in SetUpCorrelation.  On several ranks every rank computes the same
+        tables from the replicated psi (no collective); rank 0 writes one record per measurement to SpinCorrelations.json. */
+    PetscErrorCode CalculateCorrelationMatrix(KronBlocks_t& KronBlocks, const Vec& gsv_r)
+    {
+        PetscLogDouble t0, t1;
+        PetscTime(&t0);
+        Block& L = KronBlocks.LeftBlockRefMod();
+        Block& R = KronBlocks.RightBlockRefMod();
+        const PetscInt nls = L.NumSites(), nrs = R.NumSites(), N = num_sites;
+        if (nls + nrs != N) SETERRQ3(mpi_comm, 1, "Correlation matrix: the blocks hold %lld + %lld sites, the lattice %lld.", LLD(nls), LLD(nrs), LLD(N));
+        const std::vector<int32_t> ls = L.Magnetization.Sizes32(), rs = R.Magnetization.Sizes32();
+        std::vector<int32_t> bil, bir;
+        for (PetscInt k = 0; k < KronBlocks.size(); ++k) { bil.push_back((int32_t)KronBlocks.LeftIdx(k)); bir.push_back((int32_t)KronBlocks.RightIdx(k)); }
+        const dmrgx_sectors sl{(int32_t)ls.size(), ls.data()}, sr{(int32_t)rs.size(), rs.data()};
+        std::vector<PetscInt> site;                                 /* lattice site of vector a of a family (identity: -1) */
+        /* one family: [identity] + the operator of every left site + of every right site */
+        auto family = [&](Op_t type, bool with_identity, std::vector<double>& G, PetscInt& n) -> PetscErrorCode {
+            std::vector<dmrgx_secop> lops, rops;
+            std::vector<std::vector<dmrgx_cell>> store;
+            store.reserve((size_t)N + 1);
+            site.clear();
+            if (with_identity) {
+                store.emplace_back();
+                for (int32_t q = 0; q < (int32_t)ls.size(); ++q) store.back().push_back(dmrgx_cell{q, 0, 0, ls[(size_t)q], ls[(size_t)q], DMRGX_CELL_IDENT, 1.0, nullptr, 0});
+                lops.push_back(dmrgx_secop{0, 0, (int32_t)store.back().size(), store.back().data()});
+                site.push_back(-1);
+            }
+            for (int side = 0; side < 2; ++side) {
+                Block& blk = side == 0 ? L : R;
+                for (PetscInt i = 0; i < blk.NumSites(); ++i) {
+                    Mat m = type == OpSz ? blk.Sz(i) : blk.Sp(i);                   /* (Sm is never stored) */
+                    /* a pruned operator must never read as zero */
+                    if (!m) SETERRQ3(mpi_comm, PETSC_ERR_ARG_WRONGSTATE, "Correlation matrix: operator %s(%lld) of the %s block is not resident (pruned).", OpToCStr(type == OpSz ? OpSz : OpSp), LLD(i), side == 0 ? "left" : "right");
+                    store.emplace_back();
+                    dmrgx_secop so;
+                    if (type == OpSm) m->to_secop(so, store.back(), true, -1);      /* Sm(i) = Sp(i) read transposed */
+                    else m->to_secop(so, store.back());
+                    (side == 0 ? lops : rops).push_back(so);
+                    site.push_back(side == 0 ? i : N - 1 - i);
+                }
+            }
+            n = (PetscInt)site.size();
+            dmrgx_host::DevBuffer g((size_t)(n * n), dmrgx_host::DevBuffer::device_only_t{});
+            if (dmrgx_kron_op_gram(&sl, &sr, (int32_t)bil.size(), bil.data(), bir.data(), gsv_r->buf->dev_ro(), (int32_t)lops.size(), lops.data(), (int32_t)rops.size(), rops.data(),
+                                   0, g.dev_uninitialised(), n, nullptr, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_op_gram: %s", dmrgx_last_error());
+            G.assign((size_t)(n * n), 0.0);
+            if (dmrgx_memcpy_d2h(G.data(), g.dev_ro(), G.size() * sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
+            return 0;
+        };
+        std::vector<double> G, SzSz((size_t)(N * N), 0.0), SmSp((size_t)(N * N), 0.0), SpSm((size_t)(N * N), 0.0), Sz((size_t)N, 0.0);
+        PetscInt n = 0;
+        PetscErrorCode ierr = family(OpSz, true, G, n); CHKERRQ(ierr);
+        const double norm = G[0];
+        for (PetscInt a = 1; a < n; ++a) {
+            Sz[(size_t)site[(size_t)a]] = G[(size_t)a];             /* < psi , Sz_i psi > */
+            for (PetscInt b = 1; b < n; ++b) SzSz[(size_t)(site[(size_t)a] * N + site[(size_t)b])] = G[(size_t)(a * n + b)];
+        }
+        ierr = family(OpSp, false, G, n); CHKERRQ(ierr);
+        for (PetscInt a = 0; a < n; ++a) for (PetscInt b = 0; b < n; ++b) SmSp[(size_t)(site[(size_t)a] * N + site[(size_t)b])] = G[(size_t)(a * n + b)];
+        ierr = family(OpSm, false, G, n); CHKERRQ(ierr);
+        for (PetscInt a = 0; a < n; ++a) for (PetscInt b = 0; b < n; ++b) SpSm[(size_t)(site[(size_t)a] * N + site[(size_t)b])] = G[(size_t)(a * n + b)];
+        /* S_i . S_j = Sz_i Sz_j + (Sp_i Sm_j + Sm_i Sp_j) / 2: off the diagonal the spins commute and the state is real, so both halves equal
+           < Sm_i Sp_j >; on the diagonal Sp Sm = Sm Sp + 2 Sz */
+        std::vector<double> SS((size_t)(N * N), 0.0);
+        for (PetscInt i = 0; i < N; ++i) for (PetscInt j = 0; j < N; ++j) SS[(size_t)(i * N + j)] = SzSz[(size_t)(i * N + j)] + SmSp[(size_t)(i * N + j)] + (i == j ? Sz[(size_t)i] : 0.0);
+        /* S(q) = (1/N) sum_ij cos(q . (r_i - r_j)) SS_ij,  q = (2 pi nx / Lx, 2 pi ny / Ly) */
+        const PetscInt Lx = Ham.Lx(), Ly = Ham.Ly();
+        std::vector<PetscInt> rx((size_t)N), ry((size_t)N);
+        for (PetscInt i = 0; i < N; ++i) { ierr = Ham.To2D(i, rx[(size_t)i], ry[(size_t)i]); CHKERRQ(ierr); }
+        std::vector<double> Sq((size_t)(Lx * Ly), 0.0);
+        const double two_pi = 6.283185307179586476925286766559;
+        for (PetscInt nx = 0; nx < Lx; ++nx) for (PetscInt ny = 0; ny < Ly; ++ny) {
+            double acc = 0.0;
+            for (PetscInt i = 0; i < N; ++i) for (PetscInt j = 0; j < N; ++j)
+                acc += std::cos(two_pi * ((double)(nx * (rx[(size_t)i] - rx[(size_t)j])) / (double)Lx + (double)(ny * (ry[(size_t)i] - ry[(size_t)j])) / (double)Ly)) * SS[(size_t)(i * N + j)];
+            Sq[(size_t)(nx * Ly + ny)] = acc / (double)N;
+        }
+        PetscTime(&t1);
+        if (!mpi_rank && verbose) {
+            /* what the two Gram kernels must read: vectors x length of the image space (shift 0: the target sector itself) */
+            int64_t len_shifted[2] = {0, 0};                         /* image space of Sp (sector shift +1), of Sm (-1) */
+            for (int d = 0; d < 2; ++d) {
+                const int32_t sh = d == 0 ? 1 : -1;
+                std::set<std::pair<int32_t, int32_t>> img;
+                for (size_t k = 0; k < bil.size(); ++k) {
+                    const int32_t a = bil[k] - sh, b = bir[k] - sh;
+                    if (a >= 0 && a < (int32_t)ls.size()) img.insert({a, bir[k]});
+                    if (b >= 0 && b < (int32_t)rs.size()) img.insert({bil[k], b});
+                }
+                for (const auto& ab : img) len_shifted[d] += (int64_t)ls[(size_t)ab.first] * rs[(size_t)ab.second];
+            }
+            printf("  * Correlation matrix: %lld x %lld pairs, Gram of %lld vectors x %lld (Sz), %lld x %lld (Sp), %lld x %lld (Sm), tCorrMatrix %.6f s\n", LLD(N), LLD(N), LLD(N + 1), LLD(gsv_r->n),
+                   LLD(N), LLD(len_shifted[0]), LLD(N), LLD(len_shifted[1]), t1 - t0);
+        }
+        if (mpi_rank) return 0;
+        if (!fp_spin) {
+            fp_spin = fopen((data_dir + "SpinCorrelations.json").c_str(), "w");
+            if (!fp_spin) SETERRQ1(mpi_comm, PETSC_ERR_FILE_OPEN, "Cannot open %sSpinCorrelations.json", data_dir.c_str());
+            fprintf(fp_spin, "[\n");
+            spin_printed_first = PETSC_FALSE;
+        }
+        auto row = [&](const double* v, PetscInt cnt) { fprintf(fp_spin, "["); for (PetscInt i = 0; i < cnt; ++i) fprintf(fp_spin, "%s%.15g", i ? ", " : "", v[i]); fprintf(fp_spin, "]"); };
+        auto table = [&](const char* name, const std::vector<double>& T, PetscInt nr, PetscInt nc, const char* end) {
+            fprintf(fp_spin, "   \"%s\": [\n", name);
+            for (PetscInt i = 0; i < nr; ++i) { fprintf(fp_spin, "     "); row(T.data() + i * nc, nc); fprintf(fp_spin, "%s\n", i + 1 < nr ? "," : ""); }
+            fprintf(fp_spin, "   ]%s", end);
+        };
+        fprintf(fp_spin, "%s  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"tCorrMatrix\": %.9g, \"Norm\": %.15g,\n   \"Sz\": ", spin_printed_first ? ",\n" : "", LLD(GlobIdx),
+                LoopType == WarmupStep ? "Warmup" : "Sweep", t1 - t0, norm);
+        row(Sz.data(), N);
+        fprintf(fp_spin, ",\n");
+        table("SzSz", SzSz, N, N, ",\n"); table("SmSp", SmSp, N, N, ",\n"); table("SpSm", SpSm, N, N, ",\n"); table("SS", SS, N, N, ",\n"); table("StructureFactor", Sq, Lx, Ly, "}");
+        spin_printed_first = PETSC_TRUE;
+        fflush(fp_spin);
         return 0;
     }
 
@@ -1590,6 +1717,7 @@ public:
             for (const Op& o : c.SysOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
             for (const Op& o : c.EnvOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
         }
+        if (use_corr_matrix) corr_sites.assign((size_t)N, 1);      /* -corr_matrix: Sz and Sp of every site of both centre blocks, on every rank */
         need_built = true;
         return 0;
     }
@@ -1791,6 +1919,9 @@ private:
     struct WarmBasis { std::vector<int32_t> sizes; std::map<int32_t, std::shared_ptr<dmrgx_host::DevBuffer>> E; };
     std::map<std::pair<PetscInt, int>, WarmBasis> rdm_basis;
     PetscBool use_rdm_warm = PETSC_FALSE;
+    PetscBool use_corr_matrix = PETSC_FALSE;    /* -corr_matrix 1: all-pairs tables through dmrgx_kron_op_gram, SpinCorrelations.json (CalculateCorrelationMatrix) */
+    FILE* fp_spin = NULL;                       /* opened at the first measurement with -corr_matrix, rank 0 only */
+    PetscBool spin_printed_first = PETSC_FALSE;
     PetscBool use_corr_batch = PETSC_TRUE;      /* -corr_batch 0: every correlator through its own MatMult + dot, as the reference does */
 };
 

@@ -178,6 +178,77 @@ def dgemm_nn(A, B, out=None):
     return out
 
 
+def vec_gram(U, V, accumulate=False, out=None):
+    """G[i, j] (= | +=) <U[i, :], V[j, :]> through the MFMA Gram kernel (dmrgx_vec_gram).  U, V: 2-D f64 device tensors with unit stride
+    along the vector (row stride >= length; views of larger buffers are fine).  Passing the same tensor twice takes the same-family
+    path: one triangle computed, G bitwise symmetric.  Returns (G, report); G is `out` (any row stride >= nv) when given."""
+    assert U.dtype == torch.float64 and V.dtype == torch.float64 and U.dim() == 2 and V.dim() == 2 and U.shape[1] == V.shape[1]
+    (nu, n), nv = U.shape, V.shape[0]
+    assert n == 0 or (U.stride(1) == 1 and V.stride(1) == 1)
+    if out is None:
+        assert not accumulate, "accumulate needs the matrix to add to"
+        out = torch.empty((nu, nv), dtype=torch.float64, device=U.device)
+    assert out.dtype == torch.float64 and out.shape == (nu, nv) and (nv == 1 or out.stride(1) == 1)
+    ldu, ldv = (U.stride(0) if nu > 1 else max(n, 1)), (V.stride(0) if nv > 1 else max(n, 1))
+    report = _capi.GramReport()
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _capi.check(_capi.lib().dmrgx_vec_gram(nu, nv, n, C.c_void_p(U.data_ptr()), ldu, C.c_void_p(V.data_ptr()), ldv, C.c_void_p(out.data_ptr()),
+                                           out.stride(0) if nu > 1 else max(nv, 1), 1 if accumulate else 0, C.byref(report), st))
+    return out, report
+
+
+def op_gram(sb_or_layout, psi, left_ops, right_ops, workspace_bytes=0):
+    """G[a, b] = <O_a psi, O_b psi> for O_a = A_a (x) 1 (left_ops) and 1 (x) B_a (right_ops), left ones first (dmrgx_kron_op_gram): with
+    Sz(i) of every site the whole table <Sz_i Sz_j>, with Sp(i) the table <Sm_i Sp_j>.  sb_or_layout: a Superblock or
+    (left_sizes, right_sizes, blocks); psi: the state in the reference's vector layout (device tensor or numpy array).  An operator is a
+    SectorOperator, or (SectorOperator, True) for its transpose (Sm(i) from the stored Sp(i)); all must carry the same shift as used.
+    workspace_bytes bounds the storage of the images (0: 1 GiB).  Returns (G, report)."""
+    _capi.require_device()
+    if hasattr(sb_or_layout, "blocks"):
+        left_sizes, right_sizes, blocks = sb_or_layout.left_sizes, sb_or_layout.right_sizes, sb_or_layout.blocks
+    else:
+        left_sizes, right_sizes, blocks = sb_or_layout
+    if not torch.is_tensor(psi):
+        psi = torch.from_numpy(np.ascontiguousarray(psi, dtype=np.float64)).cuda()
+    assert psi.dtype == torch.float64 and psi.is_contiguous()
+    assert psi.numel() == sum(left_sizes[il] * right_sizes[ir] for il, ir in blocks)
+    keep = []
+
+    def secops(ops):
+        lst = []
+        for op in ops:
+            op, transposed = op if isinstance(op, tuple) else (op, False)
+            cells = (_capi.Cell * max(len(op.cells), 1))()
+            for i, c in enumerate(op.cells):
+                cells[i].row_sector, cells[i].r0, cells[i].c0, cells[i].nr, cells[i].nc = c.row_sector, c.r0, c.c0, c.nr, c.nc
+                cells[i].kind, cells[i].scale = c.kind, c.scale
+                if c.kind == CELL_DENSE:
+                    t = torch.from_numpy(np.ascontiguousarray(c.array, dtype=np.float64)).to(psi.device)
+                    keep.append(t)
+                    cells[i].data, cells[i].ld = t.data_ptr(), c.nc
+            keep.append(cells)
+            s = _capi.SecOp()
+            s.shift, s.transposed, s.ncells, s.cells = (-op.shift if transposed else op.shift), (1 if transposed else 0), len(op.cells), cells
+            lst.append(s)
+        arr = (_capi.SecOp * max(len(lst), 1))(*lst)
+        keep.append(arr)
+        return arr, len(lst)
+
+    larr, nl = secops(left_ops)
+    rarr, nr = secops(right_ops)
+    ls, rs = _i32(left_sizes), _i32(right_sizes)
+    sl, sr = _capi.Sectors(len(left_sizes), ls), _capi.Sectors(len(right_sizes), rs)
+    bil, bir = _i32([b[0] for b in blocks]), _i32([b[1] for b in blocks])
+    n = nl + nr
+    G = torch.empty((max(n, 1), max(n, 1)), dtype=torch.float64, device=psi.device)
+    report = _capi.GramReport()
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _capi.check(_capi.lib().dmrgx_kron_op_gram(C.byref(sl), C.byref(sr), len(blocks), bil, bir, C.c_void_p(psi.data_ptr()), nl, larr, nr, rarr,
+                                               workspace_bytes, C.c_void_p(G.data_ptr()), max(n, 1), C.byref(report), st))
+    torch.cuda.current_stream().synchronize()       # the operator copies in `keep` are read by the queued work
+    return G, report
+
+
 class ReducedDensityMatrices:
     """Device RDM blocks + spectra of a superblock state (GetTruncation's rank-0 loop,
     include/DMRGBlockContainer.hpp:1715-1775).  psi: device tensor in the reference's vector layout."""

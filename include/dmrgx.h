@@ -21,6 +21,8 @@
  *   dmrgx_cells_axpy         <- the explicit KronSum that assembles an enlarged block's H (src/DMRGKron.cpp:612 ->
  *                               KronSumFillMatrix :1440-1446); the site operators of an enlarged block
  *                               (MatKronEyeConstruct, src/DMRGKron.cpp:52-456) are views and need no device call
+ *   dmrgx_kron_op_gram       <- all two-site correlators of one kind at once: the per-correlator KronConstruct + MatMult + VecDot
+ *   dmrgx_vec_gram              of include/DMRGBlockContainer.hpp:2287-2293, as one Gram matrix of the operator images O_i psi
  *   dmrgx_comm_*             <- the communicator of the reference's MPI path: VecScatter-to-all of x inside every MatMult
  *                               (src/DMRGKron.cpp:1833-1834) and the MPI_Allreduce behind SLEPc's VecDot / VecNorm
  *
@@ -397,6 +399,31 @@ dmrgx_status dmrgx_dot_async(int64_t n, const double* x_dev, const double* y_dev
  * system-block correlators at once (the MatMult + VecDot pairs of include/DMRGBlockContainer.hpp:2287-2293). */
 typedef struct { const double* a; int64_t lda; const double* b; int64_t ldb; int32_t nr, nc, out, pad; } dmrgx_dot2d_task;
 dmrgx_status dmrgx_dot2d_batch(int32_t count, const dmrgx_dot2d_task* tasks, double* dev_out, void* stream);
+
+/* ---- all-pairs correlators: Gram matrices of operator images ------------------------------------------------- */
+/* G[i*ldg + j] (= | +=) sum_{n < len} U[i*ldu + n] * V[j*ldv + n],  i < nu, j < nv: the inner products of two families of long
+ * vectors (len contiguous) on the f64 MFMA, split over len into slices whose partial tiles are added in slice order -- no atomics,
+ * the result repeats bit for bit.  nu, nv >= 1; len >= 0 (len == 0 writes zeros, or leaves G when accumulating); any ld >= len;
+ * pointers only 8-byte aligned.  Same family (same pointer, ld and count): G is bitwise symmetric.  G must not overlap U or V.
+ * report (may be NULL): output tiles computed (one triangle for the same family), slices of len, doubles of slab workspace. */
+typedef struct { int32_t tiles, slices; int64_t slab_doubles; } dmrgx_gram_report;
+dmrgx_status dmrgx_vec_gram(int32_t nu, int32_t nv, int64_t len, const double* U_dev, int64_t ldu,
+                            const double* V_dev, int64_t ldv, double* G_dev, int64_t ldg,
+                            int32_t accumulate, dmrgx_gram_report* report /* may be NULL */, void* stream);
+/* G[a*ldg + b] = < O_a psi , O_b psi >  for the n_left + n_right operators (left ones first): O_a = A_a (x) 1 or 1 (x) B_a.
+ * All operators carry the same sector shift (as used, after `transposed`).  psi: reference vector layout over the given KronBlocks.
+ * With O = Sz(i) this is the whole table <Sz_i Sz_j>, with O = Sp(i) the table <Sm_i Sp_j>, over all sites of both blocks at once:
+ * it replaces one KronConstruct + MatMult + VecDot per correlator (include/DMRGBlockContainer.hpp:2287-2293).
+ * The images live on the sector pairs reached from a KronBlock (IL, IR) by the shift: (IL - shift, IR) for a left operator,
+ * (IL, IR - shift) for a right one; a pair whose shifted sector does not exist contributes nothing.  Every image block is a list of
+ * grouped-GEMM products (dense cells) and scaled copies (identity cells).  workspace_bytes bounds the storage of the images (0: 1 GiB):
+ * the image blocks are worked off in slices that fit, each accumulated into G in fixed order; an image block that does not fit on
+ * its own is refused with DMRGX_ERR_ARG, as are operators of different shifts; a cell outside its sector block gives
+ * DMRGX_ERR_OUTOFRANGE.  report (may be NULL): tiles of G, number of workspace slices, largest slab of a slice. */
+dmrgx_status dmrgx_kron_op_gram(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
+                                const int32_t* block_il, const int32_t* block_ir, const double* psi_dev,
+                                int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
+                                size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, void* stream);
 
 #ifdef __cplusplus
 }
