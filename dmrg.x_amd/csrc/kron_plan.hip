@@ -946,13 +946,319 @@ extern "C" dmrgx_status dmrgx_kron_diag(dmrgx_kron_plan* P, double* d_local, voi
     return DMRGX_OK;
 }
 
-// ---- all-pairs correlators: G = Gram matrix of the operator images O_a psi -------------------------------------------------------
-// The image of psi under A (x) 1 (or 1 (x) B) is formed block by block as grouped-GEMM products (dense cells) and scaled copies
-// (identity cells), exactly like a stage-2 (stage-1) row of the MatMult without the other factor; dmrgx_vec_gram then takes every
-// inner product at once.  The images are never held whole: the image blocks are worked off in slices that fit the workspace bound.
+// ---- all-pairs correlators: G = Gram matrix of operator images of psi ---------------------------------------------------------------
+// An image v = sum_t c_t (A_t (x) B_t) psi is formed block by block.  A one-sided term is a list of grouped-GEMM products (dense cells)
+// and scaled copies (identity cells), exactly like a stage-2 (stage-1) row of the MatMult without the other factor.  A two-sided term
+// is the MatMult's two stages: T = X_k B^T goes to pool scratch in a first grouped launch, A T is accumulated into the image by the
+// second.  All terms of a vector that land in one image block -- from whichever source KronBlock -- are products of the same groups, so
+// they are summed inside the GEMM and every image element is written exactly once.  dmrgx_vec_gram then takes every inner product at
+// once.  The images are never held whole: the image blocks are worked off in slices that fit the workspace bound.
+//
+// The coefficient of a term is applied once: as the scale of a scaled copy, or folded into the one operand of the term that is
+// materialised for it (the left one of a two-sided term) -- a GEMM product itself carries none.  For a scaled-identity cell the scale of the
+// copy is the rounded product c * scale: exact whenever scale is 1 or c a power of two (every case the engine has: c in {1, 1/2}), one
+// rounding more than c * scale * x otherwise.
 namespace {
-struct UCell { int32_t r0, c0, nr, nc, kind; double scale; const double* data; int32_t ld; int64_t trans_off; };      // data: row-major in the shape the NN GEMM reads; trans_off >= 0: materialised there
-struct ImgBlock { int32_t a, b, src_left, src_right; int64_t size, off; int32_t slice; };
+struct UCell { int32_t q, r0, c0, nr, nc, kind; double scale; const double* data; int32_t ld; int64_t trans_off; };      // data: row-major in the shape the NN GEMM reads; trans_off >= 0: materialised there; scale: coefficient included
+struct ImgBlock { int32_t a, b; int64_t size, off; int32_t slice; };
+enum : int { SIDE_LEFT = 0, SIDE_RIGHT = 1 };
+
+// One contribution to (image block, vector): the cells of an operator (row sector = the image's) applied to a source matrix.
+//   left kind:  Y[r0.., :] += cell * S[c0.., :]        S: rows of the operator's column sector x n_R(b), leading dimension lds
+//   right kind: Y[:, r0..] += S[:, c0..] * cell^T      S: n_L(a) x columns of the operator's column sector
+struct ImgContrib { const std::vector<UCell>* cells; const double* S; int32_t lds; };
+
+struct GramLayout {
+    const dmrgx_sectors* SL; const dmrgx_sectors* SR;
+    int32_t nblocks; const int32_t* il; const int32_t* ir;
+    std::map<std::pair<int32_t, int32_t>, int32_t> kmap;
+    std::vector<int64_t> ref_off;
+};
+
+dmrgx_status gram_layout(const char* fn, const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks, const int32_t* block_il, const int32_t* block_ir,
+                         const double* psi_dev, GramLayout& L)
+{
+    if (!left || !right || left->nsec <= 0 || right->nsec <= 0 || !left->size || !right->size) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: empty sector table", fn);
+    for (int i = 0; i < left->nsec; ++i) if (left->size[i] <= 0) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: left sector %d has size %d", fn, i, left->size[i]);
+    for (int i = 0; i < right->nsec; ++i) if (right->size[i] <= 0) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: right sector %d has size %d", fn, i, right->size[i]);
+    if (nblocks <= 0 || !block_il || !block_ir) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: no KronBlocks", fn);
+    if (!psi_dev) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null psi", fn);
+    L.SL = left; L.SR = right; L.nblocks = nblocks; L.il = block_il; L.ir = block_ir;
+    L.ref_off.assign((size_t)nblocks + 1, 0);
+    for (int32_t k = 0; k < nblocks; ++k) {
+        const int32_t il = block_il[k], ir = block_ir[k];
+        if (il < 0 || il >= left->nsec || ir < 0 || ir >= right->nsec) DMRGX_FAIL(DMRGX_ERR_OUTOFRANGE, "%s: KronBlock %d = (%d,%d) out of range", fn, k, il, ir);
+        if (!L.kmap.emplace(std::make_pair(il, ir), k).second) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: KronBlock (%d,%d) listed twice", fn, il, ir);
+        L.ref_off[k + 1] = L.ref_off[k] + (int64_t)left->size[il] * right->size[ir];
+    }
+    return DMRGX_OK;
+}
+
+// The groups of one output block Y (nLa x nRb, leading dimension ldc): the rows are cut at the borders of the left-kind cells, the columns
+// at the borders of the right-kind cells, and every rectangle of that grid is one group -- scaled copies first, then the GEMM products --
+// of the cells that reach it.  A rectangle that no cell reaches is a group without products: zeros.  With contributions of one kind only
+// the grid is a list of row (column) segments.
+// (the cells of the contributions that live in the block's row sector are picked once per block, as the segments are walked per rectangle)
+struct CellHit { const UCell* u; const double* S; int32_t lds; };
+struct EmitScratch { std::vector<int32_t> rcuts, ccuts; std::vector<CellHit> lhit, rhit; };
+void emit_groups(GemmBatch& gb, GemmSet& set, double* Y, int32_t ldc, int32_t nLa, int32_t nRb, int32_t a, int32_t b,
+                 const std::vector<ImgContrib>& lefts, const std::vector<ImgContrib>& rights, EmitScratch& w)
+{
+    w.rcuts.assign({0, nLa});
+    w.ccuts.assign({0, nRb});
+    w.lhit.clear(); w.rhit.clear();
+    for (const ImgContrib& c : lefts) for (const UCell& u : *c.cells) if (u.q == a) { w.lhit.push_back(CellHit{&u, c.S, c.lds}); w.rcuts.push_back(u.r0); w.rcuts.push_back(u.r0 + u.nr); }
+    for (const ImgContrib& c : rights) for (const UCell& u : *c.cells) if (u.q == b) { w.rhit.push_back(CellHit{&u, c.S, c.lds}); w.ccuts.push_back(u.r0); w.ccuts.push_back(u.r0 + u.nr); }
+    for (std::vector<int32_t>* cuts : {&w.rcuts, &w.ccuts}) { std::sort(cuts->begin(), cuts->end()); cuts->erase(std::unique(cuts->begin(), cuts->end()), cuts->end()); }
+    for (size_t s = 0; s + 1 < w.rcuts.size(); ++s)
+        for (size_t t = 0; t + 1 < w.ccuts.size(); ++t) {
+            const int32_t p = w.rcuts[s], e = w.rcuts[s + 1], p2 = w.ccuts[t], e2 = w.ccuts[t + 1];
+            const int32_t pb = (int32_t)gb.prods.size();
+            int32_t cost = 0, n_axpy = 0;
+            for (int pass = 0; pass < 2; ++pass) {              // scaled copies first, then the GEMM products
+                for (const CellHit& h : w.lhit) {
+                    const UCell& u = *h.u;
+                    if (u.r0 > p || u.r0 + u.nr < e || (u.kind == DMRGX_CELL_IDENT) != (pass == 0)) continue;
+                    const int32_t d = p - u.r0;
+                    if (u.kind == DMRGX_CELL_IDENT) {
+                        gb.prods.push_back(GProd{nullptr, h.S + (int64_t)(u.c0 + d) * h.lds + p2, 0, h.lds, 0, GPROD_AXPY, u.scale});
+                        ++n_axpy; ++cost;
+                    } else {
+                        gb.prods.push_back(GProd{u.data + (int64_t)d * u.ld, h.S + (int64_t)u.c0 * h.lds + p2, u.ld, h.lds, u.nc, GPROD_GEMM, 1.0});
+                        cost += ggemm_ksteps(u.nc);
+                    }
+                }
+                for (const CellHit& h : w.rhit) {
+                    const UCell& u = *h.u;
+                    if (u.r0 > p2 || u.r0 + u.nr < e2 || (u.kind == DMRGX_CELL_IDENT) != (pass == 0)) continue;
+                    const int32_t d = p2 - u.r0;
+                    if (u.kind == DMRGX_CELL_IDENT) {
+                        gb.prods.push_back(GProd{nullptr, h.S + (int64_t)p * h.lds + u.c0 + d, 0, h.lds, 0, GPROD_AXPY, u.scale});
+                        ++n_axpy; ++cost;
+                    } else {
+                        gb.prods.push_back(GProd{h.S + (int64_t)p * h.lds + u.c0, u.data + d, h.lds, u.ld, u.nc, GPROD_GEMM, 1.0});
+                        cost += ggemm_ksteps(u.nc);
+                    }
+                }
+            }
+            gb.group(set, GGroup{Y + (int64_t)p * ldc + p2, ldc, e - p, e2 - p2, pb, (int32_t)gb.prods.size(), n_axpy, 0}, std::max(cost, 1));
+        }
+}
+
+// The builder behind dmrgx_kron_term_gram and dmrgx_kron_op_gram (one one-sided term per vector).  `fn` names the caller in messages.
+dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* psi_dev,
+                             int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
+                             int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
+                             size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, hipStream_t st)
+{
+    const dmrgx_sectors& SL = *L.SL;
+    const dmrgx_sectors& SR = *L.SR;
+    const int32_t nterms = vec_first[nvec];
+    auto shift_l = [&](const dmrgx_term& t) { return t.left_op < 0 ? 0 : left_ops[t.left_op].shift; };
+    auto shift_r = [&](const dmrgx_term& t) { return t.right_op < 0 ? 0 : right_ops[t.right_op].shift; };
+    std::vector<std::vector<NCell>> cellsL((size_t)n_left_ops), cellsR((size_t)n_right_ops);
+    {
+        const std::string wl = std::string(fn) + " left op", wr = std::string(fn) + " right op";
+        for (int32_t i = 0; i < n_left_ops; ++i) DMRGX_CHK(normalise_op(&left_ops[i], SL, wl.c_str(), cellsL[i]));
+        for (int32_t i = 0; i < n_right_ops; ++i) DMRGX_CHK(normalise_op(&right_ops[i], SR, wr.c_str(), cellsR[i]));
+    }
+
+    // image blocks: in KronBlock order, and for each KronBlock in the order the (left, right) shift pairs first appear among the terms
+    std::vector<std::pair<int32_t, int32_t>> pairs;
+    for (int32_t t = 0; t < nterms; ++t) {
+        const auto p = std::make_pair(shift_l(terms[t]), shift_r(terms[t]));
+        if (std::find(pairs.begin(), pairs.end(), p) == pairs.end()) pairs.push_back(p);
+    }
+    std::vector<ImgBlock> imgs;
+    std::map<std::pair<int32_t, int32_t>, int32_t> imap;
+    for (int32_t k = 0; k < L.nblocks; ++k)
+        for (const auto& p : pairs) {
+            const int32_t a = L.il[k] - p.first, b = L.ir[k] - p.second;
+            if (a < 0 || a >= SL.nsec || b < 0 || b >= SR.nsec) continue;
+            if (imap.emplace(std::make_pair(a, b), (int32_t)imgs.size()).second) imgs.push_back(ImgBlock{a, b, (int64_t)SL.size[a] * SR.size[b], 0, 0});
+        }
+    // slices of image blocks that fit the workspace
+    const int64_t bound = (int64_t)((workspace_bytes ? workspace_bytes : ((size_t)1 << 30)) / sizeof(double)) / nvec;
+    std::vector<int64_t> slice_len;
+    for (ImgBlock& im : imgs) {
+        if (im.size > bound)
+            DMRGX_FAIL(DMRGX_ERR_ARG, "%s: image block (%d,%d) of %d x %d needs %lld bytes for the %d vectors, workspace_bytes allows %lld",
+                       fn, im.a, im.b, SL.size[im.a], SR.size[im.b], (long long)(im.size * nvec * (int64_t)sizeof(double)), nvec, (long long)(bound * nvec * (int64_t)sizeof(double)));
+        if (slice_len.empty() || slice_len.back() + im.size > bound) slice_len.push_back(0);
+        im.slice = (int32_t)slice_len.size() - 1;
+        im.off = slice_len.back();
+        slice_len.back() += im.size;
+    }
+    const int32_t nslices = (int32_t)slice_len.size();
+    if (nslices == 0) {                               // no shifted sector pair exists: every image is zero
+        DMRGX_CHK(dmrgx_vec_gram(nvec, nvec, 0, nullptr, 0, nullptr, 0, G_dev, ldg, 0, report, st));
+        return DMRGX_OK;
+    }
+    // the source KronBlock of term t in image block im (-1: none)
+    auto source = [&](const dmrgx_term& t, const ImgBlock& im) -> int32_t {
+        auto it = L.kmap.find(std::make_pair(im.a + shift_l(t), im.b + shift_r(t)));
+        return it == L.kmap.end() ? -1 : it->second;
+    };
+
+    // Operands.  The NN GEMM reads a left cell as A (row-major nr x nc) and a right cell as B = cell^T (row-major nc x nr): cells stored the
+    // other way round, and cells that carry a coefficient, are materialised once per call (as the plan's cell_copy writes B^T).  One
+    // entry per (side, operator, coefficient) in use.
+    std::map<std::tuple<int, int32_t, uint64_t>, std::vector<UCell>> uses;
+    std::vector<CopyTask> copies;
+    std::vector<CopyTile> copy_tiles;
+    int64_t trans_doubles = 0;
+    auto bits_of = [](double coeff) { uint64_t bits; memcpy(&bits, &coeff, sizeof bits); return bits; };      // a coefficient as a map key
+    auto use_of = [&](int side, int32_t op, double coeff, const std::vector<UCell>** out) -> dmrgx_status {
+        auto ins = uses.emplace(std::make_tuple(side, op, bits_of(coeff)), std::vector<UCell>());
+        *out = &ins.first->second;
+        if (!ins.second) return DMRGX_OK;
+        const bool is_left = side == SIDE_LEFT;
+        for (const NCell& c : (is_left ? cellsL : cellsR)[op]) {
+            UCell u{c.q, c.r0, c.c0, c.nr, c.nc, c.kind, c.scale * coeff, c.data, 0, -1};
+            if (c.kind == DMRGX_CELL_DENSE) {
+                if (c.ld > INT32_MAX) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: %s operator %d: leading dimension %lld of a cell too large", fn, is_left ? "left" : "right", op, (long long)c.ld);
+                u.ld = (int32_t)c.ld;
+                const bool flip = c.tr == is_left;      // left and stored transposed, or right and stored plainly
+                if (flip || coeff != 1.0) {
+                    const int32_t dr = is_left ? c.nr : c.nc, dc = is_left ? c.nc : c.nr;
+                    copies.push_back(CopyTask{trans_doubles, c.data, c.ld, dr, dc, dc, flip ? 1 : 0, coeff, 0});
+                    for (int32_t ti = 0; ti < (dr + 31) / 32; ++ti)
+                        for (int32_t tj = 0; tj < (dc + 31) / 32; ++tj) copy_tiles.push_back(CopyTile{(int32_t)copies.size() - 1, ti, tj, 0});
+                    u.trans_off = trans_doubles;
+                    u.ld = dc;
+                    trans_doubles += (int64_t)dr * dc;
+                }
+            }
+            ins.first->second.push_back(u);
+        }
+        return DMRGX_OK;
+    };
+    // identity (x) identity: one scaled-identity cell per left sector, per coefficient
+    std::map<uint64_t, std::vector<UCell>> ident_uses;
+    auto ident_of = [&](double coeff) -> const std::vector<UCell>* {
+        auto ins = ident_uses.emplace(bits_of(coeff), std::vector<UCell>());
+        if (ins.second) for (int32_t q = 0; q < SL.nsec; ++q) ins.first->second.push_back(UCell{q, 0, 0, SL.size[q], SL.size[q], DMRGX_CELL_IDENT, coeff, nullptr, 0, -1});
+        return &ins.first->second;
+    };
+    // per term: the cells of its left factor (coefficient included) and, for a two-sided term, of its right factor
+    struct TermUse { const std::vector<UCell>* left; const std::vector<UCell>* right; };
+    std::vector<TermUse> tuse((size_t)nterms, TermUse{nullptr, nullptr});
+    for (int32_t t = 0; t < nterms; ++t) {
+        const dmrgx_term& T = terms[t];
+        if (T.left_op >= 0) DMRGX_CHK(use_of(SIDE_LEFT, T.left_op, T.a, &tuse[t].left));
+        if (T.right_op >= 0) DMRGX_CHK(use_of(SIDE_RIGHT, T.right_op, T.left_op >= 0 ? 1.0 : T.a, &tuse[t].right));
+        if (T.left_op < 0 && T.right_op < 0) tuse[t].left = ident_of(T.a);
+    }
+    // intermediates T = X_k B^T of the two-sided terms, one per (slice, right operator, source KronBlock): n_L(IL_k) x n_R(IR_k - shift)
+    std::map<std::tuple<int32_t, int32_t, int32_t>, int64_t> toff;
+    std::vector<int64_t> scratch_len((size_t)nslices, 0);
+    for (const ImgBlock& im : imgs)
+        for (int32_t t = 0; t < nterms; ++t) {
+            const dmrgx_term& T = terms[t];
+            if (T.left_op < 0 || T.right_op < 0) continue;
+            const int32_t k = source(T, im);
+            if (k < 0) continue;
+            if (toff.emplace(std::make_tuple(im.slice, T.right_op, k), scratch_len[im.slice]).second)
+                scratch_len[im.slice] += (int64_t)SL.size[L.il[k]] * SR.size[im.b];
+        }
+
+    DevBuf W, trans, scratch, tab;
+    DMRGX_CHK(W.alloc_f64((size_t)(*std::max_element(slice_len.begin(), slice_len.end())) * nvec, st));
+    if (trans_doubles > 0) DMRGX_CHK(trans.alloc_f64((size_t)trans_doubles, st));
+    const int64_t scratch_max = *std::max_element(scratch_len.begin(), scratch_len.end());
+    if (scratch_max > 0) DMRGX_CHK(scratch.alloc_f64((size_t)scratch_max, st));
+    for (auto& kv : uses)
+        for (UCell& u : kv.second)
+            if (u.trans_off >= 0) u.data = trans.as<double>() + u.trans_off;
+
+    GemmBatch gb;
+    std::vector<GemmSet> sets1(nslices), sets2(nslices);      // stage 1: the intermediates of a slice; stage 2: its images
+    EmitScratch emit;
+    std::vector<ImgContrib> lefts, rights;
+    for (const auto& kv : toff) {                              // (ordered by slice, right operator, KronBlock)
+        const int32_t s = std::get<0>(kv.first), r = std::get<1>(kv.first), k = std::get<2>(kv.first);
+        const int32_t nl = SL.size[L.il[k]], b = L.ir[k] - right_ops[r].shift, ldx = SR.size[L.ir[k]];
+        lefts.clear();
+        rights.assign(1, ImgContrib{&uses.at(std::make_tuple((int)SIDE_RIGHT, r, bits_of(1.0))), psi_dev + L.ref_off[k], ldx});
+        emit_groups(gb, sets1[s], scratch.as<double>() + kv.second, SR.size[b], nl, SR.size[b], -1, b, lefts, rights, emit);
+    }
+    for (const ImgBlock& im : imgs) {
+        const int32_t nLa = SL.size[im.a], nRb = SR.size[im.b];
+        const int64_t ldw = slice_len[im.slice];
+        for (int32_t v = 0; v < nvec; ++v) {
+            lefts.clear(); rights.clear();
+            for (int32_t t = vec_first[v]; t < vec_first[v + 1]; ++t) {
+                const dmrgx_term& T = terms[t];
+                const int32_t k = source(T, im);
+                if (k < 0) continue;
+                if (T.left_op >= 0 && T.right_op >= 0) lefts.push_back(ImgContrib{tuse[t].left, scratch.as<double>() + toff.at(std::make_tuple(im.slice, T.right_op, k)), nRb});
+                else if (T.right_op >= 0) rights.push_back(ImgContrib{tuse[t].right, psi_dev + L.ref_off[k], SR.size[L.ir[k]]});
+                else lefts.push_back(ImgContrib{tuse[t].left, psi_dev + L.ref_off[k], nRb});
+            }
+            emit_groups(gb, sets2[im.slice], W.as<double>() + (int64_t)v * ldw + im.off, nRb, nLa, nRb, im.a, im.b, lefts, rights, emit);
+        }
+    }
+    PackedUpload pk;
+    gb.pack(pk);
+    for (GemmSet& s : sets1) gb.pack(s, pk);
+    for (GemmSet& s : sets2) gb.pack(s, pk);
+    const size_t o_tasks = pk.add(copies), o_tiles = pk.add(copy_tiles);
+    DMRGX_CHK(pk.upload(tab, st));
+    gb.bind(tab);
+    if (!copy_tiles.empty()) {
+        hipLaunchKernelGGL(cell_copy_kernel, dim3((unsigned)copy_tiles.size()), dim3(256), 0, st, (const CopyTile*)packed_at<CopyTile>(tab, o_tiles),
+                           (const CopyTask*)packed_at<CopyTask>(tab, o_tasks), trans.as<double>());
+        DMRGX_HIP(hipGetLastError());
+    }
+    dmrgx_gram_report total{0, nslices, 0};
+    for (int32_t s = 0; s < nslices; ++s) {               // fixed order: slice s is added to the sum of the slices before it
+        DMRGX_CHK(gb.launch(sets1[s], tab, st));
+        DMRGX_CHK(gb.launch(sets2[s], tab, st));
+        dmrgx_gram_report r{};
+        DMRGX_CHK(dmrgx_vec_gram(nvec, nvec, slice_len[s], W.as<double>(), slice_len[s], W.as<double>(), slice_len[s], G_dev, ldg, s > 0 ? 1 : 0, &r, st));
+        total.tiles = r.tiles;
+        total.slab_doubles = std::max(total.slab_doubles, r.slab_doubles);
+    }
+    if (report) *report = total;
+    return DMRGX_OK;
+}
+}  // namespace
+
+extern "C" dmrgx_status dmrgx_kron_term_gram(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
+                                             const int32_t* block_il, const int32_t* block_ir, const double* psi_dev,
+                                             int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
+                                             int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
+                                             size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, void* stream)
+{
+    const char* fn = "kron_term_gram";
+    GramLayout L;
+    DMRGX_CHK(gram_layout(fn, left, right, nblocks, block_il, block_ir, psi_dev, L));
+    if (n_left_ops < 0 || n_right_ops < 0 || (n_left_ops > 0 && !left_ops) || (n_right_ops > 0 && !right_ops))
+        DMRGX_FAIL(DMRGX_ERR_ARG, "%s: bad operator lists (%d left, %d right)", fn, n_left_ops, n_right_ops);
+    if (nvec < 1 || !vec_first || vec_first[0] != 0) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: no vectors, or vec_first does not start at 0", fn);
+    for (int32_t v = 0; v < nvec; ++v)
+        if (vec_first[v + 1] <= vec_first[v]) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: vector %d is empty (vec_first %d, %d): every vector has at least one term", fn, v, vec_first[v], vec_first[v + 1]);
+    if (!terms) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null term list", fn);
+    if (!G_dev || ldg < nvec) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null G or ldg %lld below the %d vectors", fn, (long long)ldg, nvec);
+    int32_t shift = 0;
+    for (int32_t v = 0; v < nvec; ++v)
+        for (int32_t t = vec_first[v]; t < vec_first[v + 1]; ++t) {
+            const dmrgx_term& T = terms[t];
+            if (T.left_op < -1 || T.left_op >= n_left_ops || T.right_op < -1 || T.right_op >= n_right_ops)
+                DMRGX_FAIL(DMRGX_ERR_OUTOFRANGE, "%s: term %d of vector %d references operator (%d,%d) outside the %d left and %d right operators", fn, t - vec_first[v], v, T.left_op, T.right_op, n_left_ops, n_right_ops);
+            const int32_t s = (T.left_op < 0 ? 0 : left_ops[T.left_op].shift) + (T.right_op < 0 ? 0 : right_ops[T.right_op].shift);
+            if (t == 0) shift = s;
+            else if (s != shift) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: term %d of vector %d has total shift %d, the first term has %d: one call takes one shift", fn, t - vec_first[v], v, s, shift);
+        }
+    return term_gram_build(fn, L, psi_dev, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, workspace_bytes, G_dev, ldg, report, (hipStream_t)stream);
+}
+
+// dmrgx_kron_op_gram: one operator per vector, A (x) 1 or 1 (x) B.  It keeps its own builder: the same image blocks, groups and products
+// as one one-sided term per vector gives above (the shared parts are normalise_op, the cell copies, GemmBatch and dmrgx_vec_gram), with
+// the cells of an operator picked per image block before its segments are walked.
+namespace {
+struct OpUCell { int32_t r0, c0, nr, nc, kind; double scale; const double* data; int32_t ld; int64_t trans_off; };      // data: row-major in the shape the NN GEMM reads; trans_off >= 0: materialised there
+struct OpImgBlock { int32_t a, b, src_left, src_right; int64_t size, off; int32_t slice; };
 }  // namespace
 
 extern "C" dmrgx_status dmrgx_kron_op_gram(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
@@ -988,11 +1294,11 @@ extern "C" dmrgx_status dmrgx_kron_op_gram(const dmrgx_sectors* left, const dmrg
     for (int32_t v = 0; v < nops; ++v) DMRGX_CHK(normalise_op(&op_at(v), v < n_left_ops ? SL : SR, v < n_left_ops ? "kron_op_gram left op" : "kron_op_gram right op", cells[v]));
 
     // image blocks, in KronBlock order (left image, then right image of each)
-    std::vector<ImgBlock> imgs;
+    std::vector<OpImgBlock> imgs;
     std::map<std::pair<int32_t, int32_t>, int32_t> imap;
-    auto image = [&](int32_t a, int32_t b) -> ImgBlock& {
+    auto image = [&](int32_t a, int32_t b) -> OpImgBlock& {
         auto it = imap.emplace(std::make_pair(a, b), (int32_t)imgs.size());
-        if (it.second) imgs.push_back(ImgBlock{a, b, -1, -1, (int64_t)SL.size[a] * SR.size[b], 0, 0});
+        if (it.second) imgs.push_back(OpImgBlock{a, b, -1, -1, (int64_t)SL.size[a] * SR.size[b], 0, 0});
         return imgs[it.first->second];
     };
     for (int32_t k = 0; k < nblocks; ++k) {
@@ -1003,7 +1309,7 @@ extern "C" dmrgx_status dmrgx_kron_op_gram(const dmrgx_sectors* left, const dmrg
     // slices of image blocks that fit the workspace
     const int64_t bound = (int64_t)((workspace_bytes ? workspace_bytes : ((size_t)1 << 30)) / sizeof(double)) / nops;
     std::vector<int64_t> slice_len;
-    for (ImgBlock& im : imgs) {
+    for (OpImgBlock& im : imgs) {
         if (im.size > bound)
             DMRGX_FAIL(DMRGX_ERR_ARG, "kron_op_gram: image block (%d,%d) of %d x %d needs %lld bytes for the %d operators, workspace_bytes allows %lld",
                        im.a, im.b, SL.size[im.a], SR.size[im.b], (long long)(im.size * nops * (int64_t)sizeof(double)), nops, (long long)(bound * nops * (int64_t)sizeof(double)));
@@ -1022,14 +1328,14 @@ extern "C" dmrgx_status dmrgx_kron_op_gram(const dmrgx_sectors* left, const dmrg
 
     // the NN GEMM reads a left cell as A (row-major nr x nc) and a right cell as B = cell^T (row-major nc x nr): cells stored the other
     // way round are materialised once per call (as the plan's cell_copy writes B^T)
-    std::vector<std::vector<UCell>> ucells(nops);
+    std::vector<std::vector<OpUCell>> ucells(nops);
     std::vector<CopyTask> copies;
     std::vector<CopyTile> copy_tiles;
     int64_t trans_doubles = 0;
     for (int32_t v = 0; v < nops; ++v)
         for (const NCell& c : cells[v]) {
             const bool is_left = v < n_left_ops;
-            UCell u{c.r0, c.c0, c.nr, c.nc, c.kind, c.scale, c.data, 0, -1};
+            OpUCell u{c.r0, c.c0, c.nr, c.nc, c.kind, c.scale, c.data, 0, -1};
             if (c.kind == DMRGX_CELL_DENSE) {
                 if (c.ld > INT32_MAX) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_op_gram: operator %d: leading dimension %lld of a cell too large", v, (long long)c.ld);
                 u.ld = (int32_t)c.ld;
@@ -1047,13 +1353,13 @@ extern "C" dmrgx_status dmrgx_kron_op_gram(const dmrgx_sectors* left, const dmrg
         }
     if (trans_doubles > 0) DMRGX_CHK(trans.alloc_f64((size_t)trans_doubles, st));
     for (auto& list : ucells)
-        for (UCell& u : list)
+        for (OpUCell& u : list)
             if (u.trans_off >= 0) u.data = trans.as<double>() + u.trans_off;
 
     GemmBatch gb;
     std::vector<GemmSet> sets(nslices);
     std::vector<int32_t> cuts, hit;
-    for (const ImgBlock& im : imgs) {
+    for (const OpImgBlock& im : imgs) {
         const int32_t nLa = SL.size[im.a], nRb = SR.size[im.b];
         const int64_t ldw = slice_len[im.slice];
         for (int32_t v = 0; v < nops; ++v) {
@@ -1077,7 +1383,7 @@ extern "C" dmrgx_status dmrgx_kron_op_gram(const dmrgx_sectors* left, const dmrg
                 int32_t cost = 0, n_axpy = 0;
                 for (int pass = 0; pass < 2; ++pass)            // scaled copies first, then the GEMM products
                     for (int32_t i : hit) {
-                        const UCell& u = ucells[v][i];
+                        const OpUCell& u = ucells[v][i];
                         if (u.r0 > p || u.r0 + u.nr < e || (u.kind == DMRGX_CELL_IDENT) != (pass == 0)) continue;
                         const int32_t d = p - u.r0;
                         if (u.kind == DMRGX_CELL_IDENT) {

@@ -26,6 +26,7 @@
 #include <map>
 #include <set>
 #include <string>
+#include <tuple>
 #include <vector>
 #include <condition_variable>
 #include <deque>
@@ -195,6 +196,7 @@ public:
         ierr = PetscOptionsGetBool(NULL, NULL, "-rdm_warm_start", &use_rdm_warm, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-corr_batch", &use_corr_batch, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-corr_matrix", &use_corr_matrix, NULL); CHKERRQ(ierr);
+        ierr = PetscOptionsGetBool(NULL, NULL, "-corr_dimer", &use_corr_dimer, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-prune_ops", &prune_ops, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-step_profile", &step_profile, NULL); CHKERRQ(ierr);
 
@@ -444,6 +446,7 @@ public:
         if (fp_entanglement) { fprintf(fp_entanglement, "\n]\n"); fclose(fp_entanglement); fp_entanglement = NULL; }
         if (fp_kron) { fprintf(fp_kron, "\n]\n"); fclose(fp_kron); fp_kron = NULL; }
         if (fp_spin) { fprintf(fp_spin, "\n]\n"); fclose(fp_spin); fp_spin = NULL; }
+        if (fp_dimer) { fprintf(fp_dimer, "\n]\n"); fclose(fp_dimer); fp_dimer = NULL; }
         if (fp_corr) {
             if (!corr_headers_printed) { PetscErrorCode e2 = PrintCorrelationHeaders(); CHKERRQ(e2); }
             fprintf(fp_corr, "\n  ]\n}\n"); fclose(fp_corr); fp_corr = NULL;
@@ -1315,6 +1318,7 @@ public:
             fflush(fp_corr);
         }
         if (use_corr_matrix) { ierr = CalculateCorrelationMatrix(KronBlocks, gsv_r); CHKERRQ(ierr); }
+        if (use_corr_dimer) { ierr = CalculateDimerCorrelations(KronBlocks, gsv_r); CHKERRQ(ierr); }
         return 0;
     }
 
@@ -1439,6 +1443,256 @@ public:
         table("SzSz", SzSz, N, N, ",\n"); table("SmSp", SmSp, N, N, ",\n"); table("SpSm", SpSm, N, N, ",\n"); table("SS", SS, N, N, ",\n"); table("StructureFactor", Sq, Lx, Ly, "}");
         spin_printed_first = PETSC_TRUE;
         fflush(fp_spin);
+        return 0;
+    }
+
+    /** A nearest-neighbour bond of the lattice: sites i < j, the site (ix, jy) from which NearestNeighbors generates it, 'x' if the two
+        sites differ in column, else 'y'. */
+    struct DimerBond { PetscInt i, j, ix, jy; char orient; };
+    /** The distinct pairs of Ham.NeighborPairs(), in order of first appearance (on Ly = 2 with the periodic y boundary every vertical pair
+        appears twice).  The generating site is the one whose "above" (y) or "right" (x) neighbour is the other site; where that holds
+        for both -- two sites round a periodic direction -- the lower-numbered one is visited first. */
+    std::vector<DimerBond> DimerBonds()
+    {
+        std::vector<DimerBond> bonds;
+        std::set<std::pair<PetscInt, PetscInt>> seen;
+        const PetscInt Lx = Ham.Lx(), Ly = Ham.Ly();
+        for (const std::vector<PetscInt>& p : Ham.NeighborPairs()) {
+            if (!seen.insert({p[0], p[1]}).second) continue;
+            PetscInt x0, y0, x1, y1;
+            Ham.To2D(p[0], x0, y0); Ham.To2D(p[1], x1, y1);
+            DimerBond b;
+            b.i = p[0]; b.j = p[1]; b.orient = x0 != x1 ? 'x' : 'y';
+            const bool from_i = b.orient == 'x' ? (x0 + 1) % Lx == x1 : (y0 + 1) % Ly == y1;
+            b.ix = from_i ? x0 : x1; b.jy = from_i ? y0 : y1;
+            bonds.push_back(b);
+        }
+        return bonds;
+    }
+
+    /** -corr_dimer 1 (engine extension): the dimer-dimer table < D_b D_b' > over all pairs of nearest-neighbour bonds, D_b = S_i . S_j
+        = Sz_i Sz_j + (Sp_i Sm_j + Sm_i Sp_j) / 2, its connected part and the dimer structure factors of the x and the y bonds, at every
+        measurement point.  < psi | D_b^T D_b' | psi > = < D_b psi , D_b' psi >: the whole table is ONE dmrgx_kron_term_gram call over the
+        bond images D_b psi -- vector 0 is psi itself (norm and < D_b >), vector 1 + b the image of bond b -- instead of a plan, a MatMult
+        and a dot product per pair of bonds.  D_b is built from the stored, truncated block operators, the operator of site i first:
+        a bond inside the left block is A_b (x) 1 with A_b formed on the device in dense per-sector form (one grouped GEMM per chunk of
+        bonds: every sector block of every bond is one group of three products; the site operators are densified once per measurement
+        and released when the bond operators exist), a bond inside the right block is 1 (x) B_b, a bond across the cut is three
+        two-sided terms.  Sm is Sp read transposed.  Site s of the right block is lattice site N - 1 - s.
+        DD[b][b'] is < psi | D_b^T D_b' | psi >: it equals < D_b D_b' > when nothing was truncated or the two bonds sit in different
+        blocks -- truncated operators of one block do not commute, the caveat of the SpSm table.  On several ranks every rank
+        computes the same table from the replicated psi (no collective); rank 0 writes one record per measurement to
+        DimerCorrelations.json. */
+    PetscErrorCode CalculateDimerCorrelations(KronBlocks_t& KronBlocks, const Vec& gsv_r)
+    {
+        PetscLogDouble t0, t1;
+        PetscTime(&t0);
+        Block& L = KronBlocks.LeftBlockRefMod();
+        Block& R = KronBlocks.RightBlockRefMod();
+        const PetscInt nls = L.NumSites(), nrs = R.NumSites(), N = num_sites;
+        if (nls + nrs != N) SETERRQ3(mpi_comm, 1, "Dimer correlations: the blocks hold %lld + %lld sites, the lattice %lld.", LLD(nls), LLD(nrs), LLD(N));
+        const std::vector<int32_t> ls = L.Magnetization.Sizes32(), rs = R.Magnetization.Sizes32();
+        std::vector<int32_t> bil, bir;
+        for (PetscInt k = 0; k < KronBlocks.size(); ++k) { bil.push_back((int32_t)KronBlocks.LeftIdx(k)); bir.push_back((int32_t)KronBlocks.RightIdx(k)); }
+        const dmrgx_sectors sl{(int32_t)ls.size(), ls.data()}, sr{(int32_t)rs.size(), rs.data()};
+        const std::vector<DimerBond> bonds = DimerBonds();
+        const PetscInt nb = (PetscInt)bonds.size();
+        /* a pruned operator must never read as zero */
+        auto site_op = [&](int side, Op_t type, PetscInt s, Mat& m) -> PetscErrorCode {
+            Block& blk = side == 0 ? L : R;
+            m = type == OpSz ? blk.Sz(s) : blk.Sp(s);
+            if (!m) SETERRQ3(mpi_comm, PETSC_ERR_ARG_WRONGSTATE, "Dimer correlations: operator %s(%lld) of the %s block is not resident (pruned).", OpToCStr(type), LLD(s), side == 0 ? "left" : "right");
+            return 0;
+        };
+        auto block_site = [&](int side, PetscInt lattice_site) { return side == 0 ? lattice_site : N - 1 - lattice_site; };
+        auto side_of = [&](const DimerBond& b) { return b.j < nls ? 0 : (b.i >= nls ? 1 : 2); };      /* 2: across the cut */
+
+        /* ---- bond operators inside a block, dense per sector: C[q] = Sz_i[q] Sz_j[q] + (Sp_i / 2)[q -> q+1] Sm_j[q+1 -> q] + (Sm_i / 2)[q -> q-1] Sp_j[q-1 -> q] */
+        std::vector<Mat> bond_op((size_t)nb);
+        int64_t bond_doubles = 0;
+        for (int side = 0; side < 2; ++side) {
+            const std::vector<int32_t>& sz = side == 0 ? ls : rs;
+            const int32_t ns = (int32_t)sz.size();
+            enum { DSz = 0, DSp = 1, DSm = 2, DHalfSp = 3, DHalfSm = 4 };
+            std::map<std::pair<int, PetscInt>, Mat> dense;          /* (kind, block site) -> dense form, for this measurement */
+            auto densify = [&](int kind, PetscInt s, Mat& d) -> PetscErrorCode {
+                auto it = dense.find({kind, s});
+                if (it != dense.end()) { d = it->second; return 0; }
+                Mat m;
+                PetscErrorCode e = site_op(side, kind == DSz ? OpSz : OpSp, s, m); CHKERRQ(e);
+                if (kind == DSm || kind == DHalfSm) {               /* Sm(s) = Sp(s) read transposed */
+                    auto v = std::make_shared<dmrgx_host::SectorMat>();
+                    v->transpose_of = m; v->shift = OpSm; v->sizes = m->sizes;
+                    m = v;
+                }
+                if (dmrgx_host::SectorMatDensify(m, d, kind >= DHalfSp ? 0.5 : 1.0)) SETERRQ1(mpi_comm, 1, "Dimer correlations: densifying a site operator: %s", dmrgx_last_error());
+                dense[{kind, s}] = d;
+                return 0;
+            };
+            auto cell_at = [](const Mat& M, int32_t q) -> const dmrgx_host::MatCell* { for (const dmrgx_host::MatCell& c : M->cells) if (c.q == q) return &c; return nullptr; };
+            std::vector<dmrgx_ggemm_group> groups;
+            std::vector<dmrgx_ggemm_prod> prods;
+            std::vector<size_t> first_prod;
+            int64_t chunk_elems = 0, total = 0;
+            for (int32_t q = 0; q < ns; ++q) total += (int64_t)sz[(size_t)q] * sz[(size_t)q];
+            const int64_t chunk_limit = (int64_t)1 << 28;           /* 2 GiB of bond operators per grouped launch */
+            auto flush = [&]() -> PetscErrorCode {
+                for (size_t g = 0; g < groups.size(); ++g) groups[g].prods = prods.data() + first_prod[g];
+                if (!groups.empty() && dmrgx_ggemm_groups((int32_t)groups.size(), groups.data(), 0, nullptr, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_ggemm_groups: %s", dmrgx_last_error());
+                groups.clear(); prods.clear(); first_prod.clear(); chunk_elems = 0;
+                return 0;
+            };
+            for (PetscInt b = 0; b < nb; ++b) {
+                if (side_of(bonds[(size_t)b]) != side) continue;
+                const PetscInt si = block_site(side, bonds[(size_t)b].i), sj = block_site(side, bonds[(size_t)b].j);
+                Mat zi, zj, hpi, hmi, pj, mj;
+                PetscErrorCode ierr;
+                ierr = densify(DSz, si, zi); CHKERRQ(ierr); ierr = densify(DSz, sj, zj); CHKERRQ(ierr);
+                ierr = densify(DHalfSp, si, hpi); CHKERRQ(ierr); ierr = densify(DSm, sj, mj); CHKERRQ(ierr);
+                ierr = densify(DHalfSm, si, hmi); CHKERRQ(ierr); ierr = densify(DSp, sj, pj); CHKERRQ(ierr);
+                if (chunk_elems + total > chunk_limit) { ierr = flush(); CHKERRQ(ierr); }
+                Mat C = std::make_shared<dmrgx_host::SectorMat>();
+                C->shift = 0; C->sizes = sz;
+                auto arena = std::make_shared<dmrgx_host::DevBuffer>((size_t)std::max<int64_t>(total, 1), dmrgx_host::DevBuffer::device_only_t{});
+                int64_t cursor = 0;
+                for (int32_t q = 0; q < ns; ++q) {
+                    const int32_t n = sz[(size_t)q];
+                    dmrgx_host::MatCell c;
+                    c.q = q; c.nr = c.nc = n; c.ld = n; c.buf = arena; c.off = cursor;
+                    C->cells.push_back(c);
+                    first_prod.push_back(prods.size());
+                    int32_t np = 0;
+                    auto product = [&](const Mat& A, const Mat& B, int32_t qmid) {        /* A[q -> qmid] B[qmid -> q] */
+                        if (qmid < 0 || qmid >= ns) return;
+                        const dmrgx_host::MatCell* a = cell_at(A, q);
+                        const dmrgx_host::MatCell* bb = cell_at(B, qmid);
+                        if (!a || !bb) return;
+                        prods.push_back(dmrgx_ggemm_prod{0, sz[(size_t)qmid], a->buf->dev_ro() + a->off, a->ld, bb->buf->dev_ro() + bb->off, bb->ld, 1.0});
+                        ++np;
+                    };
+                    product(zi, zj, q); product(hpi, mj, q + 1); product(hmi, pj, q - 1);
+                    groups.push_back(dmrgx_ggemm_group{arena->dev_uninitialised() + cursor, n, n, n, 0, np, nullptr});
+                    cursor += (int64_t)n * n;
+                }
+                chunk_elems += total;
+                bond_doubles += total;
+                bond_op[(size_t)b] = C;
+            }
+            PetscErrorCode ierr = flush(); CHKERRQ(ierr);
+        }                                                           /* (the dense site operators go back to the pool here: stream-ordered) */
+
+        /* ---- the vectors: psi, then the image of every bond */
+        std::deque<std::vector<dmrgx_cell>> store;
+        std::vector<dmrgx_secop> ops[2];
+        std::map<std::tuple<int, int, PetscInt>, int32_t> site_index;       /* (side, Sz / Sp / Sm, block site) -> index in ops[side] */
+        auto site_secop = [&](int side, Op_t type, PetscInt s, int32_t& idx) -> PetscErrorCode {
+            auto it = site_index.find(std::make_tuple(side, (int)type, s));
+            if (it != site_index.end()) { idx = it->second; return 0; }
+            Mat m;
+            PetscErrorCode e = site_op(side, type == OpSz ? OpSz : OpSp, s, m); CHKERRQ(e);
+            store.emplace_back();
+            dmrgx_secop so;
+            if (type == OpSm) m->to_secop(so, store.back(), true, -1);
+            else m->to_secop(so, store.back());
+            idx = (int32_t)ops[side].size();
+            ops[side].push_back(so);
+            site_index[std::make_tuple(side, (int)type, s)] = idx;
+            return 0;
+        };
+        std::vector<int32_t> vec_first{0};
+        std::vector<dmrgx_term> terms;
+        terms.push_back(dmrgx_term{1.0, -1, -1});
+        vec_first.push_back((int32_t)terms.size());
+        for (PetscInt b = 0; b < nb; ++b) {
+            const int side = side_of(bonds[(size_t)b]);
+            if (side < 2) {
+                store.emplace_back();
+                dmrgx_secop so;
+                bond_op[(size_t)b]->to_secop(so, store.back());
+                ops[side].push_back(so);
+                const int32_t idx = (int32_t)ops[side].size() - 1;
+                terms.push_back(side == 0 ? dmrgx_term{1.0, idx, -1} : dmrgx_term{1.0, -1, idx});
+            } else {
+                const PetscInt si = bonds[(size_t)b].i, sj = block_site(1, bonds[(size_t)b].j);
+                const Op_t left_type[3] = {OpSz, OpSp, OpSm}, right_type[3] = {OpSz, OpSm, OpSp};
+                const double coeff[3] = {1.0, 0.5, 0.5};
+                for (int t = 0; t < 3; ++t) {
+                    int32_t il, ir;
+                    PetscErrorCode ierr = site_secop(0, left_type[t], si, il); CHKERRQ(ierr);
+                    ierr = site_secop(1, right_type[t], sj, ir); CHKERRQ(ierr);
+                    terms.push_back(dmrgx_term{coeff[t], il, ir});
+                }
+            }
+            vec_first.push_back((int32_t)terms.size());
+        }
+        const PetscInt nv = nb + 1;
+        /* the workspace holds at least the largest image block of every vector: the blocks (IL, IR), (IL - 1, IR + 1), (IL + 1, IR - 1) */
+        int64_t largest = 1;
+        for (size_t k = 0; k < bil.size(); ++k)
+            for (int32_t d = -1; d <= 1; ++d) {
+                const int32_t a = bil[k] - d, c = bir[k] + d;
+                if (a >= 0 && a < (int32_t)ls.size() && c >= 0 && c < (int32_t)rs.size()) largest = std::max<int64_t>(largest, (int64_t)ls[(size_t)a] * rs[(size_t)c]);
+            }
+        const size_t workspace = std::max<size_t>((size_t)1 << 30, (size_t)largest * (size_t)nv * sizeof(double));
+        std::vector<double> G((size_t)(nv * nv), 0.0);
+        {
+            dmrgx_host::DevBuffer g((size_t)(nv * nv), dmrgx_host::DevBuffer::device_only_t{});
+            if (dmrgx_kron_term_gram(&sl, &sr, (int32_t)bil.size(), bil.data(), bir.data(), gsv_r->buf->dev_ro(), (int32_t)ops[0].size(), ops[0].data(), (int32_t)ops[1].size(), ops[1].data(),
+                                     (int32_t)nv, vec_first.data(), terms.data(), workspace, g.dev_uninitialised(), nv, nullptr, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_gram: %s", dmrgx_last_error());
+            if (dmrgx_memcpy_d2h(G.data(), g.dev_ro(), G.size() * sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
+        }
+        bond_op.clear();
+        const double norm = G[0];
+        std::vector<double> D((size_t)nb, 0.0), DD((size_t)(nb * nb), 0.0), Conn((size_t)(nb * nb), 0.0);
+        for (PetscInt b = 0; b < nb; ++b) {
+            D[(size_t)b] = G[(size_t)(1 + b)];
+            for (PetscInt c = 0; c < nb; ++c) DD[(size_t)(b * nb + c)] = G[(size_t)((1 + b) * nv + 1 + c)];
+        }
+        for (PetscInt b = 0; b < nb; ++b) for (PetscInt c = 0; c < nb; ++c) Conn[(size_t)(b * nb + c)] = DD[(size_t)(b * nb + c)] / norm - D[(size_t)b] * D[(size_t)c] / (norm * norm);
+        /* S_a(q) = (1/N_a) sum over the bonds b, b' of orientation a of cos(q . (r_b - r_b')) Connected[b][b'],  q = (2 pi nx / Lx, 2 pi ny / Ly) */
+        const PetscInt Lx = Ham.Lx(), Ly = Ham.Ly();
+        std::vector<double> Sq[2] = {std::vector<double>((size_t)(Lx * Ly), 0.0), std::vector<double>((size_t)(Lx * Ly), 0.0)};
+        const double two_pi = 6.283185307179586476925286766559;
+        for (int o = 0; o < 2; ++o) {
+            std::vector<PetscInt> of;
+            for (PetscInt b = 0; b < nb; ++b) if (bonds[(size_t)b].orient == (o == 0 ? 'x' : 'y')) of.push_back(b);
+            if (of.empty()) continue;
+            for (PetscInt nx = 0; nx < Lx; ++nx) for (PetscInt ny = 0; ny < Ly; ++ny) {
+                double acc = 0.0;
+                for (PetscInt b : of) for (PetscInt c : of)
+                    acc += std::cos(two_pi * ((double)(nx * (bonds[(size_t)b].ix - bonds[(size_t)c].ix)) / (double)Lx + (double)(ny * (bonds[(size_t)b].jy - bonds[(size_t)c].jy)) / (double)Ly)) * Conn[(size_t)(b * nb + c)];
+                Sq[o][(size_t)(nx * Ly + ny)] = acc / (double)of.size();
+            }
+        }
+        PetscTime(&t1);
+        if (!mpi_rank && verbose)
+            printf("  * Dimer correlations: %lld bonds, Gram of %lld vectors x %lld, %lld bytes of bond operators held, tDimer %.6f s\n", LLD(nb), LLD(nv), LLD(gsv_r->n), LLD(bond_doubles * (int64_t)sizeof(double)), t1 - t0);
+        if (mpi_rank) return 0;
+        if (!fp_dimer) {
+            fp_dimer = fopen((data_dir + "DimerCorrelations.json").c_str(), "w");
+            if (!fp_dimer) SETERRQ1(mpi_comm, PETSC_ERR_FILE_OPEN, "Cannot open %sDimerCorrelations.json", data_dir.c_str());
+            fprintf(fp_dimer, "[\n");
+            dimer_printed_first = PETSC_FALSE;
+        }
+        auto row = [&](const double* v, PetscInt cnt) { fprintf(fp_dimer, "["); for (PetscInt i = 0; i < cnt; ++i) fprintf(fp_dimer, "%s%.15g", i ? ", " : "", v[i]); fprintf(fp_dimer, "]"); };
+        auto table = [&](const char* name, const std::vector<double>& T, PetscInt nr, PetscInt nc, const char* end) {
+            fprintf(fp_dimer, "   \"%s\": [\n", name);
+            for (PetscInt i = 0; i < nr; ++i) { fprintf(fp_dimer, "     "); row(T.data() + i * nc, nc); fprintf(fp_dimer, "%s\n", i + 1 < nr ? "," : ""); }
+            fprintf(fp_dimer, "   ]%s", end);
+        };
+        fprintf(fp_dimer, "%s  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"tDimer\": %.9g, \"Norm\": %.15g,\n   \"Bonds\": [", dimer_printed_first ? ",\n" : "", LLD(GlobIdx),
+                LoopType == WarmupStep ? "Warmup" : "Sweep", t1 - t0, norm);
+        for (PetscInt b = 0; b < nb; ++b) fprintf(fp_dimer, "%s[%lld, %lld]", b ? ", " : "", LLD(bonds[(size_t)b].i), LLD(bonds[(size_t)b].j));
+        fprintf(fp_dimer, "],\n   \"Orientation\": [");
+        for (PetscInt b = 0; b < nb; ++b) fprintf(fp_dimer, "%s\"%c\"", b ? ", " : "", bonds[(size_t)b].orient);
+        fprintf(fp_dimer, "],\n   \"Position\": [");
+        for (PetscInt b = 0; b < nb; ++b) fprintf(fp_dimer, "%s[%lld, %lld]", b ? ", " : "", LLD(bonds[(size_t)b].ix), LLD(bonds[(size_t)b].jy));
+        fprintf(fp_dimer, "],\n   \"D\": ");
+        row(D.data(), nb);
+        fprintf(fp_dimer, ",\n");
+        table("DD", DD, nb, nb, ",\n"); table("Connected", Conn, nb, nb, ",\n"); table("StructureFactorX", Sq[0], Lx, Ly, ",\n"); table("StructureFactorY", Sq[1], Lx, Ly, "}");
+        dimer_printed_first = PETSC_TRUE;
+        fflush(fp_dimer);
         return 0;
     }
 
@@ -1717,7 +1971,7 @@ public:
             for (const Op& o : c.SysOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
             for (const Op& o : c.EnvOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
         }
-        if (use_corr_matrix) corr_sites.assign((size_t)N, 1);      /* -corr_matrix: Sz and Sp of every site of both centre blocks, on every rank */
+        if (use_corr_matrix || use_corr_dimer) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer: Sz and Sp of every site of both centre blocks, on every rank */
         need_built = true;
         return 0;
     }
@@ -1922,6 +2176,9 @@ private:
     PetscBool use_corr_matrix = PETSC_FALSE;    /* -corr_matrix 1: all-pairs tables through dmrgx_kron_op_gram, SpinCorrelations.json (CalculateCorrelationMatrix) */
     FILE* fp_spin = NULL;                       /* opened at the first measurement with -corr_matrix, rank 0 only */
     PetscBool spin_printed_first = PETSC_FALSE;
+    PetscBool use_corr_dimer = PETSC_FALSE;     /* -corr_dimer 1: dimer-dimer table over all bond pairs through dmrgx_kron_term_gram, DimerCorrelations.json (CalculateDimerCorrelations) */
+    FILE* fp_dimer = NULL;                      /* opened at the first measurement with -corr_dimer, rank 0 only */
+    PetscBool dimer_printed_first = PETSC_FALSE;
     PetscBool use_corr_batch = PETSC_TRUE;      /* -corr_batch 0: every correlator through its own MatMult + dot, as the reference does */
 };
 

@@ -203,8 +203,9 @@ inline PetscErrorCode MatGetSize(const Mat& m, PetscInt* M, PetscInt* N) { if (!
 /** Dense form of an operator: one device-resident dense cell per sector block (q -> q+shift), the cells of `src`
     accumulated into it on the device (dmrgx_cells_axpy: dense, identity and -- for a transposed view such as Sm(i) --
     transposed sources).  Used for operator products inside one block basis (correlators,
-    include/DMRGBlockContainer.hpp:2333-2410 of the reference); never on the superblock path. */
-inline PetscErrorCode SectorMatDensify(const Mat& src_in, Mat& out)
+    include/DMRGBlockContainer.hpp:2333-2410 of the reference); never on the superblock path.  alpha: the dense form is
+    alpha times the operator (the grouped GEMM's products carry no coefficient: 1/2 Sp(i) is densified as such). */
+inline PetscErrorCode SectorMatDensify(const Mat& src_in, Mat& out, const double alpha = 1.0)
 {
     if (!src_in) return PETSC_ERR_ARG_CORRUPT;
     const bool tr = (bool)src_in->transpose_of;
@@ -246,8 +247,8 @@ inline PetscErrorCode SectorMatDensify(const Mat& src_in, Mat& out)
         t.transposed = tr ? 1 : 0;
         if (tr) { t.dst = blk + (int64_t)c.c0 * d.ld + c.r0; t.nr = c.nc; t.nc = c.nr; }
         else    { t.dst = blk + (int64_t)c.r0 * d.ld + c.c0; t.nr = c.nr; t.nc = c.nc; }
-        if (c.kind == DMRGX_CELL_DENSE) { t.src = c.buf->dev_ro() + c.off; t.lds = c.ld; t.alpha = 1.0; }
-        else { t.src = nullptr; t.lds = 0; t.alpha = c.scale; }
+        if (c.kind == DMRGX_CELL_DENSE) { t.src = c.buf->dev_ro() + c.off; t.lds = c.ld; t.alpha = alpha; }
+        else { t.src = nullptr; t.lds = 0; t.alpha = alpha * c.scale; }
         tasks.push_back(t);
     }
     if (!tasks.empty() && dmrgx_cells_axpy((int32_t)tasks.size(), tasks.data(), nullptr)) return 1;

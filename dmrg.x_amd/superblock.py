@@ -197,13 +197,9 @@ def vec_gram(U, V, accumulate=False, out=None):
     return out, report
 
 
-def op_gram(sb_or_layout, psi, left_ops, right_ops, workspace_bytes=0):
-    """G[a, b] = <O_a psi, O_b psi> for O_a = A_a (x) 1 (left_ops) and 1 (x) B_a (right_ops), left ones first (dmrgx_kron_op_gram): with
-    Sz(i) of every site the whole table <Sz_i Sz_j>, with Sp(i) the table <Sm_i Sp_j>.  sb_or_layout: a Superblock or
-    (left_sizes, right_sizes, blocks); psi: the state in the reference's vector layout (device tensor or numpy array).  An operator is a
-    SectorOperator, or (SectorOperator, True) for its transpose (Sm(i) from the stored Sp(i)); all must carry the same shift as used.
-    workspace_bytes bounds the storage of the images (0: 1 GiB).  Returns (G, report)."""
-    _capi.require_device()
+def _gram_arguments(sb_or_layout, psi, left_ops, right_ops):
+    """The arguments dmrgx_kron_op_gram and dmrgx_kron_term_gram share, as ctypes values: (sectors, sectors, nblocks, il, ir, psi pointer, n_left,
+    left operators, n_right, right operators), psi as a device tensor, and the list that keeps every buffer behind them alive."""
     if hasattr(sb_or_layout, "blocks"):
         left_sizes, right_sizes, blocks = sb_or_layout.left_sizes, sb_or_layout.right_sizes, sb_or_layout.blocks
     else:
@@ -239,12 +235,45 @@ def op_gram(sb_or_layout, psi, left_ops, right_ops, workspace_bytes=0):
     ls, rs = _i32(left_sizes), _i32(right_sizes)
     sl, sr = _capi.Sectors(len(left_sizes), ls), _capi.Sectors(len(right_sizes), rs)
     bil, bir = _i32([b[0] for b in blocks]), _i32([b[1] for b in blocks])
-    n = nl + nr
+    keep += [ls, rs, sl, sr, bil, bir]
+    return (C.byref(sl), C.byref(sr), len(blocks), bil, bir, C.c_void_p(psi.data_ptr()), nl, larr, nr, rarr), psi, keep
+
+
+def op_gram(sb_or_layout, psi, left_ops, right_ops, workspace_bytes=0):
+    """G[a, b] = <O_a psi, O_b psi> for O_a = A_a (x) 1 (left_ops) and 1 (x) B_a (right_ops), left ones first (dmrgx_kron_op_gram): with
+    Sz(i) of every site the whole table <Sz_i Sz_j>, with Sp(i) the table <Sm_i Sp_j>.  sb_or_layout: a Superblock or
+    (left_sizes, right_sizes, blocks); psi: the state in the reference's vector layout (device tensor or numpy array).  An operator is a
+    SectorOperator, or (SectorOperator, True) for its transpose (Sm(i) from the stored Sp(i)); all must carry the same shift as used.
+    workspace_bytes bounds the storage of the images (0: 1 GiB).  Returns (G, report)."""
+    _capi.require_device()
+    args, psi, keep = _gram_arguments(sb_or_layout, psi, left_ops, right_ops)
+    n = len(left_ops) + len(right_ops)
     G = torch.empty((max(n, 1), max(n, 1)), dtype=torch.float64, device=psi.device)
     report = _capi.GramReport()
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _capi.check(_capi.lib().dmrgx_kron_op_gram(C.byref(sl), C.byref(sr), len(blocks), bil, bir, C.c_void_p(psi.data_ptr()), nl, larr, nr, rarr,
-                                               workspace_bytes, C.c_void_p(G.data_ptr()), max(n, 1), C.byref(report), st))
+    _capi.check(_capi.lib().dmrgx_kron_op_gram(*args, workspace_bytes, C.c_void_p(G.data_ptr()), max(n, 1), C.byref(report), st))
+    torch.cuda.current_stream().synchronize()       # the operator copies in `keep` are read by the queued work
+    return G, report
+
+
+def term_gram(sb_or_layout, psi, left_ops, right_ops, vectors, workspace_bytes=0):
+    """G[a, b] = <v_a, v_b> for v_a = sum over the terms (c, l, r) of vectors[a] of c * (left_ops[l] (x) right_ops[r]) psi
+    (dmrgx_kron_term_gram); l or r None: the identity on that side, both None: c * psi.  With the bond operators S_i . S_j -- one operator
+    of a block, or three two-sided terms across the cut -- the whole table of dimer-dimer correlations.  Layout, psi, operators
+    (a SectorOperator, or (SectorOperator, True) for its transpose) and workspace_bytes as in op_gram; every term of the call must have
+    the same total sector shift.  Returns (G, report)."""
+    _capi.require_device()
+    args, psi, keep = _gram_arguments(sb_or_layout, psi, left_ops, right_ops)
+    n = len(vectors)
+    first = _i32(list(np.cumsum([0] + [len(v) for v in vectors])))
+    flat = [t for v in vectors for t in v]
+    terms = (_capi.Term * max(len(flat), 1))()
+    for i, (c, l, r) in enumerate(flat):
+        terms[i].a, terms[i].left_op, terms[i].right_op = float(c), (-1 if l is None else int(l)), (-1 if r is None else int(r))
+    G = torch.empty((max(n, 1), max(n, 1)), dtype=torch.float64, device=psi.device)
+    report = _capi.GramReport()
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _capi.check(_capi.lib().dmrgx_kron_term_gram(*args, n, first, terms, workspace_bytes, C.c_void_p(G.data_ptr()), max(n, 1), C.byref(report), st))
     torch.cuda.current_stream().synchronize()       # the operator copies in `keep` are read by the queued work
     return G, report
 

@@ -23,6 +23,8 @@
  *                               (MatKronEyeConstruct, src/DMRGKron.cpp:52-456) are views and need no device call
  *   dmrgx_kron_op_gram       <- all two-site correlators of one kind at once: the per-correlator KronConstruct + MatMult + VecDot
  *   dmrgx_vec_gram              of include/DMRGBlockContainer.hpp:2287-2293, as one Gram matrix of the operator images O_i psi
+ *   dmrgx_kron_term_gram     <- the same for images that are sums of terms c A (x) B (bond operators S_i . S_j inside a block or across
+ *                               the cut): the whole table < D_b D_b' > of dimer-dimer correlations as one Gram matrix
  *   dmrgx_comm_*             <- the communicator of the reference's MPI path: VecScatter-to-all of x inside every MatMult
  *                               (src/DMRGKron.cpp:1833-1834) and the MPI_Allreduce behind SLEPc's VecDot / VecNorm
  *
@@ -424,6 +426,28 @@ dmrgx_status dmrgx_kron_op_gram(const dmrgx_sectors* left, const dmrgx_sectors* 
                                 const int32_t* block_il, const int32_t* block_ir, const double* psi_dev,
                                 int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
                                 size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, void* stream);
+/* G[a*ldg + b] = < v_a , v_b >,  v_a = sum over the terms t of vector a of  c_t (A_t (x) B_t) psi,  a, b < nvec.
+ * Vector a owns terms[vec_first[a] .. vec_first[a+1]) (vec_first[0] = 0, every vector at least one term); a term names its operators by
+ * index into left_ops / right_ops, -1 meaning the identity on that side (both -1: c psi).  Sector tables, KronBlocks, psi, operators
+ * (cells, `transposed`), workspace_bytes, G, ldg and report are those of dmrgx_kron_op_gram, which is this function with one one-sided
+ * term per vector.  A term with left shift sA and right shift sB maps KronBlock (IL, IR) to the image block (IL - sA, IR - sB); where
+ * either shifted sector does not exist it contributes nothing.  Every term of one call must have the same total sA + sB (the identity
+ * counts 0), else DMRGX_ERR_ARG; an operator index outside its list gives DMRGX_ERR_OUTOFRANGE, an empty vector or a vec_first that
+ * does not grow DMRGX_ERR_ARG.  Terms of one vector that reach the same image block from different KronBlocks are summed there.
+ * A one-sided term is built as in dmrgx_kron_op_gram; a two-sided term takes two grouped launches per workspace slice, like the
+ * MatMult: T = X_k B^T into scratch, then A T accumulated into the image.  The coefficient is applied once: as the scale of a scaled
+ * copy, or folded into a materialised copy of the (left) operand.
+ * Memory on top of workspace_bytes, all from the library's pool: (1) the intermediates T of ONE slice, one n_L(IL) x n_R(IR - sB)
+ * matrix per distinct (right operator, source KronBlock) of the two-sided terms that reach the slice -- at most, when one slice holds
+ * every image block, sum over the distinct right operators r of two-sided terms of sum_k n_L(IL_k) n_R(IR_k - s_r) doubles: about one
+ * superblock vector per such operator (the Ly operators next to the cut for nearest-neighbour bonds); (2) one copy of every dense cell that is stored the other way round than the GEMM
+ * reads it (left operators used transposed, right operators stored plainly) or that carries a coefficient other than 1.
+ * No atomics: the result repeats bit for bit and is bitwise symmetric. */
+dmrgx_status dmrgx_kron_term_gram(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
+                                  const int32_t* block_il, const int32_t* block_ir, const double* psi_dev,
+                                  int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
+                                  int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
+                                  size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, void* stream);
 
 #ifdef __cplusplus
 }
