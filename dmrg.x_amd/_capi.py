@@ -170,6 +170,11 @@ SIGNATURES = {
     "dmrgx_kron_term_gram": (C.c_int32, [C.POINTER(Sectors), C.POINTER(Sectors), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
                                          C.c_int32, C.POINTER(SecOp), C.c_int32, C.POINTER(SecOp), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Term),
                                          C.c_size_t, C.c_void_p, C.c_int64, C.POINTER(GramReport), C.c_void_p]),
+    "dmrgx_kron_term_apply": (C.c_int32, [C.POINTER(Sectors), C.POINTER(Sectors), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
+                                          C.c_int32, C.POINTER(SecOp), C.c_int32, C.POINTER(SecOp), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Term),
+                                          C.c_void_p, C.c_int64, C.c_void_p]),
+    "dmrgx_kron_lanczos_coeffs": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                              C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p]),
     "dmrgx_eigs_comm_timing": (C.c_int32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),
     "dmrgx_eigs_lowest": (C.c_int32, [C.c_void_p, C.POINTER(EigsOpts), C.POINTER(C.c_double), C.c_void_p,
                                       C.POINTER(EigsStats), C.c_void_p]),

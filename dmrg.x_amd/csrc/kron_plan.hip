@@ -1045,11 +1045,15 @@ void emit_groups(GemmBatch& gb, GemmSet& set, double* Y, int32_t ldc, int32_t nL
         }
 }
 
-// The builder behind dmrgx_kron_term_gram and dmrgx_kron_op_gram (one one-sided term per vector).  `fn` names the caller in messages.
+// The builder behind dmrgx_kron_term_gram and dmrgx_kron_term_apply.  `fn` names the caller in messages.
+// Output mode (Y_dev != nullptr, dmrgx_kron_term_apply): the images themselves are the result.  The image blocks are then the KronBlocks
+// at their offsets in the reference layout, all in one slice whose "workspace" is the caller's Y (vector stride ldy), and no Gram
+// matrix is taken; the groups, products and cell copies are emitted exactly as for the Gram matrix.
 dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* psi_dev,
                              int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
                              int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
-                             size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, hipStream_t st)
+                             size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, hipStream_t st,
+                             double* Y_dev = nullptr, int64_t ldy = 0)
 {
     const dmrgx_sectors& SL = *L.SL;
     const dmrgx_sectors& SR = *L.SR;
@@ -1071,16 +1075,23 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
     }
     std::vector<ImgBlock> imgs;
     std::map<std::pair<int32_t, int32_t>, int32_t> imap;
-    for (int32_t k = 0; k < L.nblocks; ++k)
+    std::vector<int64_t> slice_len;
+    for (int32_t k = 0; k < L.nblocks; ++k) {
         for (const auto& p : pairs) {
             const int32_t a = L.il[k] - p.first, b = L.ir[k] - p.second;
             if (a < 0 || a >= SL.nsec || b < 0 || b >= SR.nsec) continue;
-            if (imap.emplace(std::make_pair(a, b), (int32_t)imgs.size()).second) imgs.push_back(ImgBlock{a, b, (int64_t)SL.size[a] * SR.size[b], 0, 0});
+            if (Y_dev && !L.kmap.count(std::make_pair(a, b)))
+                DMRGX_FAIL(DMRGX_ERR_ARG, "%s: shifts (%d,%d) map KronBlock %d = (%d,%d) to the sector pair (%d,%d), which is not one of the KronBlocks", fn, p.first, p.second, k, L.il[k], L.ir[k], a, b);
+            if (!Y_dev && imap.emplace(std::make_pair(a, b), (int32_t)imgs.size()).second) imgs.push_back(ImgBlock{a, b, (int64_t)SL.size[a] * SR.size[b], 0, 0});
         }
+        // output mode: every KronBlock is an image block where the layout has it, reached or not
+        if (Y_dev) imgs.push_back(ImgBlock{L.il[k], L.ir[k], L.ref_off[k + 1] - L.ref_off[k], L.ref_off[k], 0});
+    }
+    if (Y_dev) slice_len.assign(1, ldy);              // one slice: the caller's vectors, stride ldy
     // slices of image blocks that fit the workspace
     const int64_t bound = (int64_t)((workspace_bytes ? workspace_bytes : ((size_t)1 << 30)) / sizeof(double)) / nvec;
-    std::vector<int64_t> slice_len;
     for (ImgBlock& im : imgs) {
+        if (Y_dev) break;
         if (im.size > bound)
             DMRGX_FAIL(DMRGX_ERR_ARG, "%s: image block (%d,%d) of %d x %d needs %lld bytes for the %d vectors, workspace_bytes allows %lld",
                        fn, im.a, im.b, SL.size[im.a], SR.size[im.b], (long long)(im.size * nvec * (int64_t)sizeof(double)), nvec, (long long)(bound * nvec * (int64_t)sizeof(double)));
@@ -1163,7 +1174,8 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
         }
 
     DevBuf W, trans, scratch, tab;
-    DMRGX_CHK(W.alloc_f64((size_t)(*std::max_element(slice_len.begin(), slice_len.end())) * nvec, st));
+    if (Y_dev) W.view(Y_dev, (size_t)((nvec - 1) * ldy + L.ref_off[L.nblocks]) * sizeof(double));
+    else DMRGX_CHK(W.alloc_f64((size_t)(*std::max_element(slice_len.begin(), slice_len.end())) * nvec, st));
     if (trans_doubles > 0) DMRGX_CHK(trans.alloc_f64((size_t)trans_doubles, st));
     const int64_t scratch_max = *std::max_element(scratch_len.begin(), scratch_len.end());
     if (scratch_max > 0) DMRGX_CHK(scratch.alloc_f64((size_t)scratch_max, st));
@@ -1214,6 +1226,7 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
     for (int32_t s = 0; s < nslices; ++s) {               // fixed order: slice s is added to the sum of the slices before it
         DMRGX_CHK(gb.launch(sets1[s], tab, st));
         DMRGX_CHK(gb.launch(sets2[s], tab, st));
+        if (Y_dev) continue;
         dmrgx_gram_report r{};
         DMRGX_CHK(dmrgx_vec_gram(nvec, nvec, slice_len[s], W.as<double>(), slice_len[s], W.as<double>(), slice_len[s], G_dev, ldg, s > 0 ? 1 : 0, &r, st));
         total.tiles = r.tiles;
@@ -1224,22 +1237,16 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
 }
 }  // namespace
 
-extern "C" dmrgx_status dmrgx_kron_term_gram(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
-                                             const int32_t* block_il, const int32_t* block_ir, const double* psi_dev,
-                                             int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
-                                             int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
-                                             size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, void* stream)
+// The checks dmrgx_kron_term_gram and dmrgx_kron_term_apply share: operator lists, vectors, term indices, one total shift (-> *shift_out).
+static dmrgx_status term_list_check(const char* fn, int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
+                                    int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms, int32_t* shift_out)
 {
-    const char* fn = "kron_term_gram";
-    GramLayout L;
-    DMRGX_CHK(gram_layout(fn, left, right, nblocks, block_il, block_ir, psi_dev, L));
     if (n_left_ops < 0 || n_right_ops < 0 || (n_left_ops > 0 && !left_ops) || (n_right_ops > 0 && !right_ops))
         DMRGX_FAIL(DMRGX_ERR_ARG, "%s: bad operator lists (%d left, %d right)", fn, n_left_ops, n_right_ops);
     if (nvec < 1 || !vec_first || vec_first[0] != 0) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: no vectors, or vec_first does not start at 0", fn);
     for (int32_t v = 0; v < nvec; ++v)
         if (vec_first[v + 1] <= vec_first[v]) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: vector %d is empty (vec_first %d, %d): every vector has at least one term", fn, v, vec_first[v], vec_first[v + 1]);
     if (!terms) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null term list", fn);
-    if (!G_dev || ldg < nvec) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null G or ldg %lld below the %d vectors", fn, (long long)ldg, nvec);
     int32_t shift = 0;
     for (int32_t v = 0; v < nvec; ++v)
         for (int32_t t = vec_first[v]; t < vec_first[v + 1]; ++t) {
@@ -1250,7 +1257,42 @@ extern "C" dmrgx_status dmrgx_kron_term_gram(const dmrgx_sectors* left, const dm
             if (t == 0) shift = s;
             else if (s != shift) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: term %d of vector %d has total shift %d, the first term has %d: one call takes one shift", fn, t - vec_first[v], v, s, shift);
         }
+    *shift_out = shift;
+    return DMRGX_OK;
+}
+
+extern "C" dmrgx_status dmrgx_kron_term_gram(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
+                                             const int32_t* block_il, const int32_t* block_ir, const double* psi_dev,
+                                             int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
+                                             int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
+                                             size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, void* stream)
+{
+    const char* fn = "kron_term_gram";
+    GramLayout L;
+    DMRGX_CHK(gram_layout(fn, left, right, nblocks, block_il, block_ir, psi_dev, L));
+    int32_t shift = 0;
+    DMRGX_CHK(term_list_check(fn, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, &shift));
+    if (!G_dev || ldg < nvec) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null G or ldg %lld below the %d vectors", fn, (long long)ldg, nvec);
     return term_gram_build(fn, L, psi_dev, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, workspace_bytes, G_dev, ldg, report, (hipStream_t)stream);
+}
+
+// dmrgx_kron_term_apply: the images themselves, written once each into the caller's Y (the builder's output mode).
+extern "C" dmrgx_status dmrgx_kron_term_apply(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
+                                              const int32_t* block_il, const int32_t* block_ir, const double* psi_dev,
+                                              int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
+                                              int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
+                                              double* Y_dev, int64_t ldy, void* stream)
+{
+    const char* fn = "kron_term_apply";
+    GramLayout L;
+    DMRGX_CHK(gram_layout(fn, left, right, nblocks, block_il, block_ir, psi_dev, L));
+    int32_t shift = 0;
+    DMRGX_CHK(term_list_check(fn, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, &shift));
+    if (shift != 0) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: the terms have total shift %d: an image in the layout of psi needs total shift 0", fn, shift);
+    const int64_t N = L.ref_off[nblocks];
+    if (!Y_dev || ldy < N) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null Y or ldy %lld below the %lld states", fn, (long long)ldy, (long long)N);
+    if (Y_dev < psi_dev + N && psi_dev < Y_dev + (int64_t)(nvec - 1) * ldy + N) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: Y overlaps psi", fn);
+    return term_gram_build(fn, L, psi_dev, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, 0, nullptr, 0, nullptr, (hipStream_t)stream, Y_dev, ldy);
 }
 
 // dmrgx_kron_op_gram: one operator per vector, A (x) 1 or 1 (x) B.  It keeps its own builder: the same image blocks, groups and products

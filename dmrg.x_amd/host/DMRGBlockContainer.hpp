@@ -35,6 +35,7 @@
 #include <thread>
 #include "DMRGKron.hpp"
 #include "CorrelatorDealing.hpp"
+#include "TridiagQL.hpp"
 
 /** One eigenpair of a reduced-density-matrix block */
 struct Eigen_t
@@ -198,6 +199,20 @@ public:
         ierr = PetscOptionsGetBool(NULL, NULL, "-corr_matrix", &use_corr_matrix, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-corr_dimer", &use_corr_dimer, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-prune_ops", &prune_ops, NULL); CHKERRQ(ierr);
+        ierr = PetscOptionsGetBool(NULL, NULL, "-dsf", &use_dsf, NULL); CHKERRQ(ierr);
+        if (use_dsf) {   /* -dsf 1: S^zz(q, w) at every measurement point (CalculateDynamicalStructureFactor) */
+            if (mpi_size > 1) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-dsf 1 is not available on more than one rank (got %d): the Lanczos run behind S(q,w) has no collectives.", (int)mpi_size);
+            PetscBool have_q = PETSC_FALSE;
+            PetscInt nq = 2048;
+            dsf_q.assign((size_t)nq, 0);
+            ierr = PetscOptionsGetIntArray(NULL, NULL, "-dsf_q", dsf_q.data(), &nq, &have_q); CHKERRQ(ierr);
+            dsf_q.resize((size_t)nq);
+            if (!have_q || nq < 2 || nq % 2) SETERRQ1(mpi_comm, PETSC_ERR_ARG_WRONG, "-dsf 1 needs -dsf_q nx0,ny0,nx1,ny1,...: pairs of integers, q = (2 pi nx / Lx, 2 pi ny / Ly). Got %lld numbers.", LLD(nq));
+            ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_steps", &dsf_steps, NULL); CHKERRQ(ierr);
+            if (dsf_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_steps must be at least 1. Got %lld.", LLD(dsf_steps));
+            ierr = PetscOptionsGetReal(NULL, NULL, "-dsf_breakdown_tol", &dsf_breakdown_tol, NULL); CHKERRQ(ierr);
+            if (!(dsf_breakdown_tol >= 0.0) || dsf_breakdown_tol >= 1.0) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_breakdown_tol must lie in [0, 1). Got %g.", dsf_breakdown_tol);
+        }
         ierr = PetscOptionsGetBool(NULL, NULL, "-step_profile", &step_profile, NULL); CHKERRQ(ierr);
 
         PetscBool opt = PETSC_FALSE;
@@ -447,6 +462,7 @@ public:
         if (fp_kron) { fprintf(fp_kron, "\n]\n"); fclose(fp_kron); fp_kron = NULL; }
         if (fp_spin) { fprintf(fp_spin, "\n]\n"); fclose(fp_spin); fp_spin = NULL; }
         if (fp_dimer) { fprintf(fp_dimer, "\n]\n"); fclose(fp_dimer); fp_dimer = NULL; }
+        if (fp_dsf) { fprintf(fp_dsf, "\n]\n"); fclose(fp_dsf); fp_dsf = NULL; }
         if (fp_corr) {
             if (!corr_headers_printed) { PetscErrorCode e2 = PrintCorrelationHeaders(); CHKERRQ(e2); }
             fprintf(fp_corr, "\n  ]\n}\n"); fclose(fp_corr); fp_corr = NULL;
@@ -573,6 +589,7 @@ public:
             ierr = SaveKronStats(kinfo, SysBlock, EnvBlock, (PetscInt)Terms.size(), st.n_matvec, st.seconds, ms4, napp); CHKERRQ(ierr);
         }
         step.GSEnergy = gse_r;
+        if (use_dsf && do_measurements) { ierr = CalculateDynamicalStructureFactor(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* needs the plan */
         ierr = MatDestroy_KronSumShell(&H); CHKERRQ(ierr);
         ierr = MatDestroy(&H); CHKERRQ(ierr);
         ierr = PetscTime(&tdiag); CHKERRQ(ierr);
@@ -1446,6 +1463,129 @@ public:
         return 0;
     }
 
+    /** -dsf 1 (engine extension): the dynamical spin structure factor S^zz(q, w) of the ground state at every measurement point, by the
+        Lanczos-vector (continued-fraction) method.  With O_q = N^(-1/2) sum_r e^(-i q.r) Sz_r = C_q - i S_q (cosine and sine part) and a
+        real psi,  S^zz(q, w) = sum_n ( |<n|C_q|0>|^2 + |<n|S_q|0>|^2 ) delta(w - E_n + E_0):  two real runs per q.  A run forms
+        v = C_q psi with ONE dmrgx_kron_term_apply over Sz of every site of both blocks, then dmrgx_kron_lanczos_coeffs gives |v|^2 and
+        the tridiagonal T of H from v without a host round trip per step; T is diagonalised here (TridiagQL.hpp): poles w = theta - E0,
+        weights |v|^2 z_k^2 / <psi|psi>.  It runs right after the eigensolve, while the plan of the superblock Hamiltonian still exists.
+        The block bases were optimised for the ground state alone (single target): |v|^2 -- the static S^zz(q) -- and the first moments
+        are exact in the superblock basis, the line shape is as good as that basis represents the excited states.
+        cos and sin are taken of the exact fraction 2 pi p / (Lx Ly) with their exact zeros, so that a part that vanishes by symmetry
+        vanishes in the coefficients too; a part whose |v|^2 <= 1e-20 <psi|psi> (rounding of Sz_tot psi at q = 0, for instance) holds no
+        weight a double could resolve next to the others and is recorded without a run: StepsDone 0.
+        Site s of the right block is lattice site N - 1 - s, as in SetUpCorrelation.  One rank only (refused at start-up otherwise). */
+    PetscErrorCode CalculateDynamicalStructureFactor(KronBlocks_t& KronBlocks, const Vec& gsv_r, Mat& H, PetscScalar E0)
+    {
+        PetscLogDouble t0, t1;
+        PetscTime(&t0);
+        Block& L = KronBlocks.LeftBlockRefMod();
+        Block& R = KronBlocks.RightBlockRefMod();
+        const PetscInt nls = L.NumSites(), nrs = R.NumSites(), N = num_sites, Lx = Ham.Lx(), Ly = Ham.Ly();
+        if (nls + nrs != N) SETERRQ3(mpi_comm, 1, "Dynamical structure factor: the blocks hold %lld + %lld sites, the lattice %lld.", LLD(nls), LLD(nrs), LLD(N));
+        const std::vector<int32_t> ls = L.Magnetization.Sizes32(), rs = R.Magnetization.Sizes32();
+        std::vector<int32_t> bil, bir;
+        for (PetscInt k = 0; k < KronBlocks.size(); ++k) { bil.push_back((int32_t)KronBlocks.LeftIdx(k)); bir.push_back((int32_t)KronBlocks.RightIdx(k)); }
+        const dmrgx_sectors sl{(int32_t)ls.size(), ls.data()}, sr{(int32_t)rs.size(), rs.data()};
+        /* Sz of every site of both blocks, and where the site sits on the lattice */
+        std::vector<dmrgx_secop> ops[2];
+        std::vector<std::vector<dmrgx_cell>> store;
+        store.reserve((size_t)N);
+        std::vector<PetscInt> rx, ry;
+        for (int side = 0; side < 2; ++side) {
+            Block& blk = side == 0 ? L : R;
+            for (PetscInt i = 0; i < blk.NumSites(); ++i) {
+                Mat m = blk.Sz(i);
+                /* a pruned operator must never read as zero */
+                if (!m) SETERRQ2(mpi_comm, PETSC_ERR_ARG_WRONGSTATE, "Dynamical structure factor: operator Sz(%lld) of the %s block is not resident (pruned).", LLD(i), side == 0 ? "left" : "right");
+                store.emplace_back();
+                dmrgx_secop so;
+                m->to_secop(so, store.back());
+                ops[side].push_back(so);
+                PetscInt x, y;
+                PetscErrorCode ierr = Ham.To2D(side == 0 ? i : N - 1 - i, x, y); CHKERRQ(ierr);
+                rx.push_back(x); ry.push_back(y);
+            }
+        }
+        std::vector<dmrgx_term> terms;
+        terms.reserve((size_t)N);
+        const int64_t n = gsv_r->n;
+        const double* psi = gsv_r->buf->dev_ro();
+        double norm = 0.0;
+        if (dmrgx_dot(n, psi, psi, &norm, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
+        dmrgx_host::DevBuffer v((size_t)n, dmrgx_host::DevBuffer::device_only_t{});
+        const double two_pi = 6.283185307179586476925286766559;
+        const PetscInt M = Lx * Ly;
+
+        struct Part { double norm2 = 0.0; int32_t done = 0; std::vector<double> alpha, beta, theta, z; };
+        struct Point { PetscInt nx, ny; Part part[2]; std::vector<double> poles, weights; double total = 0.0; };
+        std::vector<Point> points(dsf_q.size() / 2);
+        PetscInt matmults = 0;
+        for (size_t iq = 0; iq < points.size(); ++iq) {
+            Point& P = points[iq];
+            P.nx = dsf_q[2 * iq]; P.ny = dsf_q[2 * iq + 1];
+            for (int part = 0; part < 2; ++part) {
+                Part& A = P.part[part];
+                terms.clear();
+                for (PetscInt i = 0; i < N; ++i) {
+                    /* q . r = 2 pi p / M exactly; the zeros of cos and sin are taken from p, not from a rounded angle */
+                    const PetscInt p = (((P.nx * rx[(size_t)i] * Ly + P.ny * ry[(size_t)i] * Lx) % M) + M) % M;
+                    double c;
+                    if (part == 0) c = ((4 * p) % M == 0 && (2 * p) % M != 0) ? 0.0 : std::cos(two_pi * (double)p / (double)M);
+                    else c = (2 * p) % M == 0 ? 0.0 : std::sin(two_pi * (double)p / (double)M);
+                    /* a site whose coefficient is exactly zero takes no part: its Sz cells are neither copied nor multiplied */
+                    if (c == 0.0) continue;
+                    terms.push_back(i < nls ? dmrgx_term{c / std::sqrt((double)N), (int32_t)i, -1} : dmrgx_term{c / std::sqrt((double)N), -1, (int32_t)(i - nls)});
+                }
+                if (terms.empty()) continue;                            /* the part vanishes on the lattice: Norm2 0, no run */
+                const int32_t vec_first[2] = {0, (int32_t)terms.size()};
+                if (dmrgx_kron_term_apply(&sl, &sr, (int32_t)bil.size(), bil.data(), bir.data(), psi, (int32_t)ops[0].size(), ops[0].data(), (int32_t)ops[1].size(), ops[1].data(),
+                                          1, vec_first, terms.data(), v.dev_uninitialised(), n, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_apply: %s", dmrgx_last_error());
+                if (dmrgx_dot(n, v.dev_ro(), v.dev_ro(), &A.norm2, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
+                if (A.norm2 != A.norm2) SETERRQ3(mpi_comm, 1, "Dynamical structure factor: the %s part of q = (%lld,%lld) is not a number.", part == 0 ? "cosine" : "sine", LLD(P.nx), LLD(P.ny));
+                if (!(A.norm2 > dsf_no_weight * norm)) continue;        /* no weight: no run */
+                A.alpha.assign((size_t)dsf_steps, 0.0); A.beta.assign((size_t)dsf_steps, 0.0);
+                if (dmrgx_kron_lanczos_coeffs(H->plan, v.dev_ro(), (int32_t)dsf_steps, dsf_breakdown_tol, &A.norm2, A.alpha.data(), A.beta.data(), &A.done, nullptr))
+                    SETERRQ1(mpi_comm, 1, "dmrgx_kron_lanczos_coeffs: %s", dmrgx_last_error());
+                matmults += dsf_steps;
+                A.alpha.resize((size_t)A.done); A.beta.resize((size_t)A.done);
+                A.theta = A.alpha;
+                if (!dmrgx_host::TridiagQLFirstRow(A.theta, A.beta, A.z)) SETERRQ2(mpi_comm, 1, "Dynamical structure factor: the QL iteration on the Lanczos matrix of q = (%lld,%lld) did not converge.", LLD(P.nx), LLD(P.ny));
+            }
+            /* the poles of both parts, ascending */
+            std::vector<std::pair<double, double>> pw;
+            for (const Part& A : P.part) for (size_t k = 0; k < A.theta.size(); ++k) pw.push_back({A.theta[k] - E0, A.norm2 * A.z[k] * A.z[k] / norm});
+            std::sort(pw.begin(), pw.end());
+            for (const auto& x : pw) { P.poles.push_back(x.first); P.weights.push_back(x.second); P.total += x.second; }
+        }
+        PetscTime(&t1);
+        if (verbose) printf("  * Dynamical structure factor: %lld q points, %lld Lanczos steps per run, %lld MatMults on %lld states, tDsf %.6f s\n", LLD(points.size()), LLD(dsf_steps), LLD(matmults), LLD(n), t1 - t0);
+        if (!fp_dsf) {
+            fp_dsf = fopen((data_dir + "DynamicalStructureFactor.json").c_str(), "w");
+            if (!fp_dsf) SETERRQ1(mpi_comm, PETSC_ERR_FILE_OPEN, "Cannot open %sDynamicalStructureFactor.json", data_dir.c_str());
+            fprintf(fp_dsf, "[\n");
+            dsf_printed_first = PETSC_FALSE;
+        }
+        auto row = [&](const std::vector<double>& x) { fprintf(fp_dsf, "["); for (size_t i = 0; i < x.size(); ++i) fprintf(fp_dsf, "%s%.17g", i ? ", " : "", x[i]); fprintf(fp_dsf, "]"); };
+        fprintf(fp_dsf, "%s  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"E0\": %.17g, \"Norm\": %.17g, \"Steps\": %lld, \"tDsf\": %.9g, \"MatMults\": %lld,\n   \"Points\": [\n", dsf_printed_first ? ",\n" : "", LLD(GlobIdx),
+                LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, norm, LLD(dsf_steps), t1 - t0, LLD(matmults));
+        for (size_t iq = 0; iq < points.size(); ++iq) {
+            const Point& P = points[iq];
+            fprintf(fp_dsf, "     {\"q\": [%lld, %lld],\n", LLD(P.nx), LLD(P.ny));
+            for (int part = 0; part < 2; ++part) {
+                const Part& A = P.part[part];
+                fprintf(fp_dsf, "      \"%s\": {\"Norm2\": %.17g, \"StepsDone\": %d, \"Alpha\": ", part == 0 ? "Cos" : "Sin", A.norm2, (int)A.done);
+                row(A.alpha); fprintf(fp_dsf, ", \"Beta\": "); row(A.beta); fprintf(fp_dsf, "},\n");
+            }
+            fprintf(fp_dsf, "      \"Poles\": "); row(P.poles); fprintf(fp_dsf, ",\n      \"Weights\": "); row(P.weights);
+            fprintf(fp_dsf, ",\n      \"StaticSzz\": %.17g}%s\n", P.total, iq + 1 < points.size() ? "," : "");
+        }
+        fprintf(fp_dsf, "   ]}");
+        dsf_printed_first = PETSC_TRUE;
+        fflush(fp_dsf);
+        return 0;
+    }
+
     /** A nearest-neighbour bond of the lattice: sites i < j, the site (ix, jy) from which NearestNeighbors generates it, 'x' if the two
         sites differ in column, else 'y'. */
     struct DimerBond { PetscInt i, j, ix, jy; char orient; };
@@ -1971,7 +2111,7 @@ public:
             for (const Op& o : c.SysOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
             for (const Op& o : c.EnvOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
         }
-        if (use_corr_matrix || use_corr_dimer) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer: Sz and Sp of every site of both centre blocks, on every rank */
+        if (use_corr_matrix || use_corr_dimer || use_dsf) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer, -dsf: Sz and Sp of every site of both centre blocks, on every rank */
         need_built = true;
         return 0;
     }
@@ -2178,6 +2318,13 @@ private:
     PetscBool spin_printed_first = PETSC_FALSE;
     PetscBool use_corr_dimer = PETSC_FALSE;     /* -corr_dimer 1: dimer-dimer table over all bond pairs through dmrgx_kron_term_gram, DimerCorrelations.json (CalculateDimerCorrelations) */
     FILE* fp_dimer = NULL;                      /* opened at the first measurement with -corr_dimer, rank 0 only */
+    PetscBool use_dsf = PETSC_FALSE;            /* -dsf 1: S^zz(q, w) by the Lanczos-vector method, DynamicalStructureFactor.json (CalculateDynamicalStructureFactor) */
+    std::vector<PetscInt> dsf_q;                /* -dsf_q: nx0, ny0, nx1, ny1, ... */
+    PetscInt dsf_steps = 100;                   /* -dsf_steps: Lanczos steps per run */
+    PetscReal dsf_breakdown_tol = 0.0;          /* -dsf_breakdown_tol: 0 = the library's default, 1e-7 */
+    static constexpr double dsf_no_weight = 1e-20; /* a part with |v|^2 <= dsf_no_weight <psi|psi> (rounding noise, as Sz_tot psi at q = 0) is recorded with StepsDone 0, without a run */
+    FILE* fp_dsf = NULL;                        /* opened at the first measurement with -dsf */
+    PetscBool dsf_printed_first = PETSC_FALSE;
     PetscBool dimer_printed_first = PETSC_FALSE;
     PetscBool use_corr_batch = PETSC_TRUE;      /* -corr_batch 0: every correlator through its own MatMult + dot, as the reference does */
 };

@@ -10,6 +10,7 @@
 #include "Hamiltonians.hpp"
 #include "DMRGKron.hpp"
 #include "CorrelatorDealing.hpp"
+#include "TridiagQL.hpp"
 
 static void dump_mat(const char* tag, PetscInt site, const Mat& m)
 {
@@ -145,6 +146,15 @@ int main()
             for (int o : owner) printf(" %d", o);
             printf("\ncarried");
             for (double c : carried) printf(" %.17g", c);
+            printf("\n");
+        } else if (cmd == "tridiag") {           /* tridiag n d_0 .. d_{n-1} e_0 .. e_{n-2}  ->  eigenvalues and first eigenvector components */
+            size_t n; is >> n;
+            std::vector<double> d(n), e(n ? n - 1 : 0), z;
+            for (double& x : d) is >> x;
+            for (double& x : e) is >> x;
+            const bool ok = dmrgx_host::TridiagQLFirstRow(d, e, z);
+            printf("tridiag %d", (int)ok);
+            for (size_t i = 0; i < n; ++i) printf(" %.17g,%.17g", d[i], z[i]);
             printf("\n");
         } else printf("unknown %s\n", cmd.c_str());
         fflush(stdout);

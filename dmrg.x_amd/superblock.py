@@ -143,6 +143,18 @@ class KronPlan:
             _capi.check(rc)
         return e0.value, psi, stats
 
+    def lanczos_coeffs(self, v0, nsteps, breakdown_tol=0.0, stream=None):
+        """Lanczos coefficients of H from the start vector v0 (dmrgx_kron_lanczos_coeffs): plain three-term recursion, device-resident,
+        breakdown decided on the device.  v0: f64 device tensor of n_states (reference layout, only read).  Returns
+        (norm2, alpha[nsteps], beta[nsteps], nsteps_done); after a breakdown T of order nsteps_done is the whole answer."""
+        assert v0.dtype == torch.float64 and v0.is_contiguous() and v0.numel() >= self.info.n_states
+        n = max(int(nsteps), 0)
+        norm2, done = C.c_double(0.0), C.c_int32(0)
+        alpha, beta = (C.c_double * max(n, 1))(), (C.c_double * max(n, 1))()
+        _capi.check(_capi.lib().dmrgx_kron_lanczos_coeffs(self._handle, C.c_void_p(v0.data_ptr()), int(nsteps), float(breakdown_tol),
+                                                          C.byref(norm2), alpha, beta, C.byref(done), self._stream_ptr(stream)))
+        return norm2.value, np.array(alpha[:n]), np.array(beta[:n]), done.value
+
     def timing(self, enable):
         _capi.check(_capi.lib().dmrgx_kron_plan_timing(self._handle, 1 if enable else 0))
 
@@ -276,6 +288,29 @@ def term_gram(sb_or_layout, psi, left_ops, right_ops, vectors, workspace_bytes=0
     _capi.check(_capi.lib().dmrgx_kron_term_gram(*args, n, first, terms, workspace_bytes, C.c_void_p(G.data_ptr()), max(n, 1), C.byref(report), st))
     torch.cuda.current_stream().synchronize()       # the operator copies in `keep` are read by the queued work
     return G, report
+
+
+def term_apply(sb_or_layout, psi, left_ops, right_ops, vectors, out=None):
+    """Y[a, :n_states] = v_a = sum over the terms (c, l, r) of vectors[a] of c * (left_ops[l] (x) right_ops[r]) psi, in the layout of psi
+    (dmrgx_kron_term_apply).  Arguments as in term_gram; every term must have total sector shift 0.  out: a 2-D f64 device tensor with
+    unit stride along the vector and a row stride >= n_states whose columns beyond n_states are left alone; default: a new
+    (len(vectors), n_states) tensor.  Returns Y."""
+    _capi.require_device()
+    args, psi, keep = _gram_arguments(sb_or_layout, psi, left_ops, right_ops)
+    n, ns = len(vectors), psi.numel()
+    first = _i32(list(np.cumsum([0] + [len(v) for v in vectors])))
+    flat = [t for v in vectors for t in v]
+    terms = (_capi.Term * max(len(flat), 1))()
+    for i, (c, l, r) in enumerate(flat):
+        terms[i].a, terms[i].left_op, terms[i].right_op = float(c), (-1 if l is None else int(l)), (-1 if r is None else int(r))
+    if out is None:
+        out = torch.empty((max(n, 1), ns), dtype=torch.float64, device=psi.device)
+    assert out.dtype == torch.float64 and out.dim() == 2 and out.shape[0] >= n and (out.shape[1] <= 1 or out.stride(1) == 1)
+    ldy = out.stride(0) if out.shape[0] > 1 else out.shape[1]
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _capi.check(_capi.lib().dmrgx_kron_term_apply(*args, n, first, terms, C.c_void_p(out.data_ptr()), ldy, st))
+    torch.cuda.current_stream().synchronize()       # the operator copies in `keep` are read by the queued work
+    return out
 
 
 class ReducedDensityMatrices:

@@ -25,6 +25,9 @@
  *   dmrgx_vec_gram              of include/DMRGBlockContainer.hpp:2287-2293, as one Gram matrix of the operator images O_i psi
  *   dmrgx_kron_term_gram     <- the same for images that are sums of terms c A (x) B (bond operators S_i . S_j inside a block or across
  *                               the cut): the whole table < D_b D_b' > of dimer-dimer correlations as one Gram matrix
+ *   dmrgx_kron_term_apply    <- nothing in the reference: engine extensions like the Gram calls.  The image vectors sum_t c_t (A_t (x) B_t) psi
+ *   dmrgx_kron_lanczos_coeffs   themselves (the Gram calls only hand back their inner products) and the Lanczos coefficients of the planned
+ *                               superblock Hamiltonian from such a vector: the continued fraction behind a dynamical structure factor
  *   dmrgx_comm_*             <- the communicator of the reference's MPI path: VecScatter-to-all of x inside every MatMult
  *                               (src/DMRGKron.cpp:1833-1834) and the MPI_Allreduce behind SLEPc's VecDot / VecNorm
  *
@@ -448,6 +451,38 @@ dmrgx_status dmrgx_kron_term_gram(const dmrgx_sectors* left, const dmrgx_sectors
                                   int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
                                   int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
                                   size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, void* stream);
+/* Y[a*ldy + n] = v_a[n], n < n_states:  the images v_a = sum_t c_t (A_t (x) B_t) psi of dmrgx_kron_term_gram themselves, in the reference
+ * vector layout of the same KronBlocks.  Sector tables, KronBlocks, psi, operators, vectors and terms, and their checks, are those of
+ * dmrgx_kron_term_gram; it is the same builder with the caller's Y in place of the workspace and no Gram matrix taken.  The images must
+ * live where psi lives: every term has total shift 0 (DMRGX_ERR_ARG otherwise), and a term that maps a KronBlock to an existing sector pair
+ * that is not one of the KronBlocks is refused (DMRGX_ERR_ARG), not dropped.  Every element [0, n_states) of every vector is written
+ * exactly once -- KronBlocks that no term reaches as zeros --, the columns from n_states to ldy are not touched.  ldy >= n_states; Y must
+ * not overlap psi.  Memory from the pool: the intermediates and cell copies of dmrgx_kron_term_gram, (1) and (2) there.  No atomics: two
+ * calls give the same bits. */
+dmrgx_status dmrgx_kron_term_apply(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
+                                   const int32_t* block_il, const int32_t* block_ir, const double* psi_dev,
+                                   int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
+                                   int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
+                                   double* Y_dev, int64_t ldy, void* stream);
+
+/* ---- Lanczos coefficients from a given start vector (continued fractions: S(q, w)) ------------------------------------ */
+/* The plain three-term recursion with q_0 = v0 / |v0| on the planned Hamiltonian (world_size == 1; a striped plan is refused with
+ * DMRGX_ERR_ARG):  w = H q_j - beta_{j-1} q_{j-1};  alpha_j = q_j . w;  w -= alpha_j q_j;  beta_j = |w|;  q_{j+1} = w / beta_j.
+ * No basis is kept and nothing is reorthogonalised: three vectors of n_states doubles from the pool, v0 (reference layout, n_states
+ * doubles) is only read.  All nsteps steps (>= 1, may exceed n_states) are enqueued without looking at the device; the call ends with
+ * one copy and one synchronisation.  Host outputs: *norm2 = |v0|^2, alpha[0..nsteps), beta[0..nsteps), *nsteps_done.
+ * Breakdown is decided on the device: at the first j with beta_j <= breakdown_tol * max(|alpha_i| (i <= j), beta_i (i < j)) the run is dead,
+ * *nsteps_done = j + 1, and T_{j+1} = tridiag(alpha_0..alpha_j; beta_0..beta_{j-1}) is the whole answer.  beta[j] of that step is the small
+ * value found; every later vector is exactly zero, every later coefficient 0, and nothing is ever divided by such a beta (the later
+ * MatMults run on zero vectors).  Without a breakdown *nsteps_done = nsteps.  breakdown_tol == 0: 1e-7 (genuine betas of the lattices
+ * here are O(1), the beta of an exhausted Krylov space is rounding noise of 1e-8 .. 1e-12); values outside [0, 1): DMRGX_ERR_ARG.
+ * A start vector whose squared norm is not a positive finite number (zero, NaN, overflow) gives *norm2 = 0, *nsteps_done = 0 and zero
+ * coefficients.  A sum that turns NaN or infinite inside step j (overflow, a NaN operator) ends the run before that step counts:
+ * *nsteps_done = j, alpha[j], beta[j] and all later coefficients are 0: no output is ever NaN.  Fixed-order sums, no atomics: two runs
+ * give the same bits. */
+dmrgx_status dmrgx_kron_lanczos_coeffs(dmrgx_kron_plan* plan, const double* v0_dev, int32_t nsteps, double breakdown_tol,
+                                       double* norm2, double* alpha /* [nsteps] */, double* beta /* [nsteps] */,
+                                       int32_t* nsteps_done, void* stream);
 
 #ifdef __cplusplus
 }
