@@ -26,7 +26,6 @@
 #include <map>
 #include <set>
 #include <string>
-#include <tuple>
 #include <vector>
 #include <condition_variable>
 #include <deque>
@@ -36,6 +35,7 @@
 #include "DMRGKron.hpp"
 #include "CorrelatorDealing.hpp"
 #include "TridiagQL.hpp"
+#include "Measurements.hpp"
 
 /** One eigenpair of a reduced-density-matrix block */
 struct Eigen_t
@@ -460,9 +460,7 @@ public:
         spectra_writer.Drain();
         if (fp_entanglement) { fprintf(fp_entanglement, "\n]\n"); fclose(fp_entanglement); fp_entanglement = NULL; }
         if (fp_kron) { fprintf(fp_kron, "\n]\n"); fclose(fp_kron); fp_kron = NULL; }
-        if (fp_spin) { fprintf(fp_spin, "\n]\n"); fclose(fp_spin); fp_spin = NULL; }
-        if (fp_dimer) { fprintf(fp_dimer, "\n]\n"); fclose(fp_dimer); fp_dimer = NULL; }
-        if (fp_dsf) { fprintf(fp_dsf, "\n]\n"); fclose(fp_dsf); fp_dsf = NULL; }
+        spin_file.Close(); dimer_file.Close(); dsf_file.Close();
         if (fp_corr) {
             if (!corr_headers_printed) { PetscErrorCode e2 = PrintCorrelationHeaders(); CHKERRQ(e2); }
             fprintf(fp_corr, "\n  ]\n}\n"); fclose(fp_corr); fp_corr = NULL;
@@ -1352,61 +1350,33 @@ public:
     {
         PetscLogDouble t0, t1;
         PetscTime(&t0);
-        Block& L = KronBlocks.LeftBlockRefMod();
-        Block& R = KronBlocks.RightBlockRefMod();
-        const PetscInt nls = L.NumSites(), nrs = R.NumSites(), N = num_sites;
-        if (nls + nrs != N) SETERRQ3(mpi_comm, 1, "Correlation matrix: the blocks hold %lld + %lld sites, the lattice %lld.", LLD(nls), LLD(nrs), LLD(N));
-        const std::vector<int32_t> ls = L.Magnetization.Sizes32(), rs = R.Magnetization.Sizes32();
-        std::vector<int32_t> bil, bir;
-        for (PetscInt k = 0; k < KronBlocks.size(); ++k) { bil.push_back((int32_t)KronBlocks.LeftIdx(k)); bir.push_back((int32_t)KronBlocks.RightIdx(k)); }
-        const dmrgx_sectors sl{(int32_t)ls.size(), ls.data()}, sr{(int32_t)rs.size(), rs.data()};
+        dmrgx_host::CentreFrame F;
+        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, "Correlation matrix"); CHKERRQ(ierr);
+        const PetscInt N = F.N;
         std::vector<PetscInt> site;                                 /* lattice site of vector a of a family (identity: -1) */
-        /* one family: [identity] + the operator of every left site + of every right site */
-        auto family = [&](Op_t type, bool with_identity, std::vector<double>& G, PetscInt& n) -> PetscErrorCode {
-            std::vector<dmrgx_secop> lops, rops;
-            std::vector<std::vector<dmrgx_cell>> store;
-            store.reserve((size_t)N + 1);
+        std::vector<double> G;
+        /* one family: [identity] + the operator of every left site + of every right site; its Gram matrix G, and as a table over lattice sites */
+        auto family = [&](Op_t type, bool with_identity, std::vector<double>& table) -> PetscErrorCode {
+            dmrgx_host::SiteOperators T(F);
             site.clear();
-            if (with_identity) {
-                store.emplace_back();
-                for (int32_t q = 0; q < (int32_t)ls.size(); ++q) store.back().push_back(dmrgx_cell{q, 0, 0, ls[(size_t)q], ls[(size_t)q], DMRGX_CELL_IDENT, 1.0, nullptr, 0});
-                lops.push_back(dmrgx_secop{0, 0, (int32_t)store.back().size(), store.back().data()});
-                site.push_back(-1);
-            }
-            for (int side = 0; side < 2; ++side) {
-                Block& blk = side == 0 ? L : R;
-                for (PetscInt i = 0; i < blk.NumSites(); ++i) {
-                    Mat m = type == OpSz ? blk.Sz(i) : blk.Sp(i);                   /* (Sm is never stored) */
-                    /* a pruned operator must never read as zero */
-                    if (!m) SETERRQ3(mpi_comm, PETSC_ERR_ARG_WRONGSTATE, "Correlation matrix: operator %s(%lld) of the %s block is not resident (pruned).", OpToCStr(type == OpSz ? OpSz : OpSp), LLD(i), side == 0 ? "left" : "right");
-                    store.emplace_back();
-                    dmrgx_secop so;
-                    if (type == OpSm) m->to_secop(so, store.back(), true, -1);      /* Sm(i) = Sp(i) read transposed */
-                    else m->to_secop(so, store.back());
-                    (side == 0 ? lops : rops).push_back(so);
-                    site.push_back(side == 0 ? i : N - 1 - i);
-                }
-            }
-            n = (PetscInt)site.size();
+            if (with_identity) { T.AddIdentity(0); site.push_back(-1); }
+            PetscErrorCode e = T.AllSites(type, site); CHKERRQ(e);
+            const PetscInt n = (PetscInt)site.size();
             dmrgx_host::DevBuffer g((size_t)(n * n), dmrgx_host::DevBuffer::device_only_t{});
-            if (dmrgx_kron_op_gram(&sl, &sr, (int32_t)bil.size(), bil.data(), bir.data(), gsv_r->buf->dev_ro(), (int32_t)lops.size(), lops.data(), (int32_t)rops.size(), rops.data(),
+            if (dmrgx_kron_op_gram(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), gsv_r->buf->dev_ro(), (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
                                    0, g.dev_uninitialised(), n, nullptr, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_op_gram: %s", dmrgx_last_error());
             G.assign((size_t)(n * n), 0.0);
             if (dmrgx_memcpy_d2h(G.data(), g.dev_ro(), G.size() * sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
+            const PetscInt first = with_identity ? 1 : 0;
+            for (PetscInt a = first; a < n; ++a) for (PetscInt b = first; b < n; ++b) table[(size_t)(site[(size_t)a] * N + site[(size_t)b])] = G[(size_t)(a * n + b)];
             return 0;
         };
-        std::vector<double> G, SzSz((size_t)(N * N), 0.0), SmSp((size_t)(N * N), 0.0), SpSm((size_t)(N * N), 0.0), Sz((size_t)N, 0.0);
-        PetscInt n = 0;
-        PetscErrorCode ierr = family(OpSz, true, G, n); CHKERRQ(ierr);
+        std::vector<double> SzSz((size_t)(N * N), 0.0), SmSp((size_t)(N * N), 0.0), SpSm((size_t)(N * N), 0.0), Sz((size_t)N, 0.0);
+        ierr = family(OpSz, true, SzSz); CHKERRQ(ierr);
         const double norm = G[0];
-        for (PetscInt a = 1; a < n; ++a) {
-            Sz[(size_t)site[(size_t)a]] = G[(size_t)a];             /* < psi , Sz_i psi > */
-            for (PetscInt b = 1; b < n; ++b) SzSz[(size_t)(site[(size_t)a] * N + site[(size_t)b])] = G[(size_t)(a * n + b)];
-        }
-        ierr = family(OpSp, false, G, n); CHKERRQ(ierr);
-        for (PetscInt a = 0; a < n; ++a) for (PetscInt b = 0; b < n; ++b) SmSp[(size_t)(site[(size_t)a] * N + site[(size_t)b])] = G[(size_t)(a * n + b)];
-        ierr = family(OpSm, false, G, n); CHKERRQ(ierr);
-        for (PetscInt a = 0; a < n; ++a) for (PetscInt b = 0; b < n; ++b) SpSm[(size_t)(site[(size_t)a] * N + site[(size_t)b])] = G[(size_t)(a * n + b)];
+        for (PetscInt a = 1; a <= N; ++a) Sz[(size_t)site[(size_t)a]] = G[(size_t)a];     /* < psi , Sz_i psi > */
+        ierr = family(OpSp, false, SmSp); CHKERRQ(ierr);
+        ierr = family(OpSm, false, SpSm); CHKERRQ(ierr);
         /* S_i . S_j = Sz_i Sz_j + (Sp_i Sm_j + Sm_i Sp_j) / 2: off the diagonal the spins commute and the state is real, so both halves equal
            < Sm_i Sp_j >; on the diagonal Sp Sm = Sm Sp + 2 Sz */
         std::vector<double> SS((size_t)(N * N), 0.0);
@@ -1415,14 +1385,7 @@ public:
         const PetscInt Lx = Ham.Lx(), Ly = Ham.Ly();
         std::vector<PetscInt> rx((size_t)N), ry((size_t)N);
         for (PetscInt i = 0; i < N; ++i) { ierr = Ham.To2D(i, rx[(size_t)i], ry[(size_t)i]); CHKERRQ(ierr); }
-        std::vector<double> Sq((size_t)(Lx * Ly), 0.0);
-        const double two_pi = 6.283185307179586476925286766559;
-        for (PetscInt nx = 0; nx < Lx; ++nx) for (PetscInt ny = 0; ny < Ly; ++ny) {
-            double acc = 0.0;
-            for (PetscInt i = 0; i < N; ++i) for (PetscInt j = 0; j < N; ++j)
-                acc += std::cos(two_pi * ((double)(nx * (rx[(size_t)i] - rx[(size_t)j])) / (double)Lx + (double)(ny * (ry[(size_t)i] - ry[(size_t)j])) / (double)Ly)) * SS[(size_t)(i * N + j)];
-            Sq[(size_t)(nx * Ly + ny)] = acc / (double)N;
-        }
+        const std::vector<double> Sq = dmrgx_host::LatticeFourier(Lx, Ly, rx.data(), ry.data(), SS.data(), N, (double)N);
         PetscTime(&t1);
         if (!mpi_rank && verbose) {
             /* what the two Gram kernels must read: vectors x length of the image space (shift 0: the target sector itself) */
@@ -1430,36 +1393,23 @@ public:
             for (int d = 0; d < 2; ++d) {
                 const int32_t sh = d == 0 ? 1 : -1;
                 std::set<std::pair<int32_t, int32_t>> img;
-                for (size_t k = 0; k < bil.size(); ++k) {
-                    const int32_t a = bil[k] - sh, b = bir[k] - sh;
-                    if (a >= 0 && a < (int32_t)ls.size()) img.insert({a, bir[k]});
-                    if (b >= 0 && b < (int32_t)rs.size()) img.insert({bil[k], b});
+                for (size_t k = 0; k < F.bil.size(); ++k) {
+                    const int32_t a = F.bil[k] - sh, b = F.bir[k] - sh;
+                    if (a >= 0 && a < (int32_t)F.sizes[0].size()) img.insert({a, F.bir[k]});
+                    if (b >= 0 && b < (int32_t)F.sizes[1].size()) img.insert({F.bil[k], b});
                 }
-                for (const auto& ab : img) len_shifted[d] += (int64_t)ls[(size_t)ab.first] * rs[(size_t)ab.second];
+                for (const auto& ab : img) len_shifted[d] += (int64_t)F.sizes[0][(size_t)ab.first] * F.sizes[1][(size_t)ab.second];
             }
             printf("  * Correlation matrix: %lld x %lld pairs, Gram of %lld vectors x %lld (Sz), %lld x %lld (Sp), %lld x %lld (Sm), tCorrMatrix %.6f s\n", LLD(N), LLD(N), LLD(N + 1), LLD(gsv_r->n),
                    LLD(N), LLD(len_shifted[0]), LLD(N), LLD(len_shifted[1]), t1 - t0);
         }
         if (mpi_rank) return 0;
-        if (!fp_spin) {
-            fp_spin = fopen((data_dir + "SpinCorrelations.json").c_str(), "w");
-            if (!fp_spin) SETERRQ1(mpi_comm, PETSC_ERR_FILE_OPEN, "Cannot open %sSpinCorrelations.json", data_dir.c_str());
-            fprintf(fp_spin, "[\n");
-            spin_printed_first = PETSC_FALSE;
-        }
-        auto row = [&](const double* v, PetscInt cnt) { fprintf(fp_spin, "["); for (PetscInt i = 0; i < cnt; ++i) fprintf(fp_spin, "%s%.15g", i ? ", " : "", v[i]); fprintf(fp_spin, "]"); };
-        auto table = [&](const char* name, const std::vector<double>& T, PetscInt nr, PetscInt nc, const char* end) {
-            fprintf(fp_spin, "   \"%s\": [\n", name);
-            for (PetscInt i = 0; i < nr; ++i) { fprintf(fp_spin, "     "); row(T.data() + i * nc, nc); fprintf(fp_spin, "%s\n", i + 1 < nr ? "," : ""); }
-            fprintf(fp_spin, "   ]%s", end);
-        };
-        fprintf(fp_spin, "%s  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"tCorrMatrix\": %.9g, \"Norm\": %.15g,\n   \"Sz\": ", spin_printed_first ? ",\n" : "", LLD(GlobIdx),
-                LoopType == WarmupStep ? "Warmup" : "Sweep", t1 - t0, norm);
-        row(Sz.data(), N);
-        fprintf(fp_spin, ",\n");
-        table("SzSz", SzSz, N, N, ",\n"); table("SmSp", SmSp, N, N, ",\n"); table("SpSm", SpSm, N, N, ",\n"); table("SS", SS, N, N, ",\n"); table("StructureFactor", Sq, Lx, Ly, "}");
-        spin_printed_first = PETSC_TRUE;
-        fflush(fp_spin);
+        ierr = spin_file.Begin(data_dir + "SpinCorrelations.json"); CHKERRQ(ierr);
+        fprintf(spin_file.fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"tCorrMatrix\": %.9g, \"Norm\": %.15g,\n   \"Sz\": ", LLD(GlobIdx), LoopType == WarmupStep ? "Warmup" : "Sweep", t1 - t0, norm);
+        spin_file.Row(Sz);
+        fprintf(spin_file.fp, ",\n");
+        spin_file.Table("SzSz", SzSz, N, N, ",\n"); spin_file.Table("SmSp", SmSp, N, N, ",\n"); spin_file.Table("SpSm", SpSm, N, N, ",\n"); spin_file.Table("SS", SS, N, N, ",\n"); spin_file.Table("StructureFactor", Sq, Lx, Ly, "}");
+        fflush(spin_file.fp);
         return 0;
     }
 
@@ -1479,34 +1429,14 @@ public:
     {
         PetscLogDouble t0, t1;
         PetscTime(&t0);
-        Block& L = KronBlocks.LeftBlockRefMod();
-        Block& R = KronBlocks.RightBlockRefMod();
-        const PetscInt nls = L.NumSites(), nrs = R.NumSites(), N = num_sites, Lx = Ham.Lx(), Ly = Ham.Ly();
-        if (nls + nrs != N) SETERRQ3(mpi_comm, 1, "Dynamical structure factor: the blocks hold %lld + %lld sites, the lattice %lld.", LLD(nls), LLD(nrs), LLD(N));
-        const std::vector<int32_t> ls = L.Magnetization.Sizes32(), rs = R.Magnetization.Sizes32();
-        std::vector<int32_t> bil, bir;
-        for (PetscInt k = 0; k < KronBlocks.size(); ++k) { bil.push_back((int32_t)KronBlocks.LeftIdx(k)); bir.push_back((int32_t)KronBlocks.RightIdx(k)); }
-        const dmrgx_sectors sl{(int32_t)ls.size(), ls.data()}, sr{(int32_t)rs.size(), rs.data()};
+        dmrgx_host::CentreFrame F;
+        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, "Dynamical structure factor"); CHKERRQ(ierr);
+        const PetscInt nls = F.nsites[0], N = F.N, Lx = Ham.Lx(), Ly = Ham.Ly(), M = Lx * Ly;
         /* Sz of every site of both blocks, and where the site sits on the lattice */
-        std::vector<dmrgx_secop> ops[2];
-        std::vector<std::vector<dmrgx_cell>> store;
-        store.reserve((size_t)N);
-        std::vector<PetscInt> rx, ry;
-        for (int side = 0; side < 2; ++side) {
-            Block& blk = side == 0 ? L : R;
-            for (PetscInt i = 0; i < blk.NumSites(); ++i) {
-                Mat m = blk.Sz(i);
-                /* a pruned operator must never read as zero */
-                if (!m) SETERRQ2(mpi_comm, PETSC_ERR_ARG_WRONGSTATE, "Dynamical structure factor: operator Sz(%lld) of the %s block is not resident (pruned).", LLD(i), side == 0 ? "left" : "right");
-                store.emplace_back();
-                dmrgx_secop so;
-                m->to_secop(so, store.back());
-                ops[side].push_back(so);
-                PetscInt x, y;
-                PetscErrorCode ierr = Ham.To2D(side == 0 ? i : N - 1 - i, x, y); CHKERRQ(ierr);
-                rx.push_back(x); ry.push_back(y);
-            }
-        }
+        dmrgx_host::SiteOperators T(F);
+        std::vector<PetscInt> site, rx((size_t)N), ry((size_t)N);
+        ierr = T.AllSites(OpSz, site); CHKERRQ(ierr);
+        for (PetscInt i = 0; i < N; ++i) { ierr = Ham.To2D(site[(size_t)i], rx[(size_t)i], ry[(size_t)i]); CHKERRQ(ierr); }
         std::vector<dmrgx_term> terms;
         terms.reserve((size_t)N);
         const int64_t n = gsv_r->n;
@@ -1514,8 +1444,6 @@ public:
         double norm = 0.0;
         if (dmrgx_dot(n, psi, psi, &norm, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
         dmrgx_host::DevBuffer v((size_t)n, dmrgx_host::DevBuffer::device_only_t{});
-        const double two_pi = 6.283185307179586476925286766559;
-        const PetscInt M = Lx * Ly;
 
         struct Part { double norm2 = 0.0; int32_t done = 0; std::vector<double> alpha, beta, theta, z; };
         struct Point { PetscInt nx, ny; Part part[2]; std::vector<double> poles, weights; double total = 0.0; };
@@ -1528,18 +1456,15 @@ public:
                 Part& A = P.part[part];
                 terms.clear();
                 for (PetscInt i = 0; i < N; ++i) {
-                    /* q . r = 2 pi p / M exactly; the zeros of cos and sin are taken from p, not from a rounded angle */
-                    const PetscInt p = (((P.nx * rx[(size_t)i] * Ly + P.ny * ry[(size_t)i] * Lx) % M) + M) % M;
-                    double c;
-                    if (part == 0) c = ((4 * p) % M == 0 && (2 * p) % M != 0) ? 0.0 : std::cos(two_pi * (double)p / (double)M);
-                    else c = (2 * p) % M == 0 ? 0.0 : std::sin(two_pi * (double)p / (double)M);
+                    const PetscInt p = (((P.nx * rx[(size_t)i] * Ly + P.ny * ry[(size_t)i] * Lx) % M) + M) % M;      /* q . r = 2 pi p / M exactly */
+                    const double c = dmrgx_host::DsfPhaseCoefficient(part, p, M);
                     /* a site whose coefficient is exactly zero takes no part: its Sz cells are neither copied nor multiplied */
                     if (c == 0.0) continue;
                     terms.push_back(i < nls ? dmrgx_term{c / std::sqrt((double)N), (int32_t)i, -1} : dmrgx_term{c / std::sqrt((double)N), -1, (int32_t)(i - nls)});
                 }
                 if (terms.empty()) continue;                            /* the part vanishes on the lattice: Norm2 0, no run */
                 const int32_t vec_first[2] = {0, (int32_t)terms.size()};
-                if (dmrgx_kron_term_apply(&sl, &sr, (int32_t)bil.size(), bil.data(), bir.data(), psi, (int32_t)ops[0].size(), ops[0].data(), (int32_t)ops[1].size(), ops[1].data(),
+                if (dmrgx_kron_term_apply(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
                                           1, vec_first, terms.data(), v.dev_uninitialised(), n, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_apply: %s", dmrgx_last_error());
                 if (dmrgx_dot(n, v.dev_ro(), v.dev_ro(), &A.norm2, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
                 if (A.norm2 != A.norm2) SETERRQ3(mpi_comm, 1, "Dynamical structure factor: the %s part of q = (%lld,%lld) is not a number.", part == 0 ? "cosine" : "sine", LLD(P.nx), LLD(P.ny));
@@ -1560,14 +1485,9 @@ public:
         }
         PetscTime(&t1);
         if (verbose) printf("  * Dynamical structure factor: %lld q points, %lld Lanczos steps per run, %lld MatMults on %lld states, tDsf %.6f s\n", LLD(points.size()), LLD(dsf_steps), LLD(matmults), LLD(n), t1 - t0);
-        if (!fp_dsf) {
-            fp_dsf = fopen((data_dir + "DynamicalStructureFactor.json").c_str(), "w");
-            if (!fp_dsf) SETERRQ1(mpi_comm, PETSC_ERR_FILE_OPEN, "Cannot open %sDynamicalStructureFactor.json", data_dir.c_str());
-            fprintf(fp_dsf, "[\n");
-            dsf_printed_first = PETSC_FALSE;
-        }
-        auto row = [&](const std::vector<double>& x) { fprintf(fp_dsf, "["); for (size_t i = 0; i < x.size(); ++i) fprintf(fp_dsf, "%s%.17g", i ? ", " : "", x[i]); fprintf(fp_dsf, "]"); };
-        fprintf(fp_dsf, "%s  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"E0\": %.17g, \"Norm\": %.17g, \"Steps\": %lld, \"tDsf\": %.9g, \"MatMults\": %lld,\n   \"Points\": [\n", dsf_printed_first ? ",\n" : "", LLD(GlobIdx),
+        ierr = dsf_file.Begin(data_dir + "DynamicalStructureFactor.json"); CHKERRQ(ierr);
+        FILE* fp_dsf = dsf_file.fp;
+        fprintf(fp_dsf, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"E0\": %.17g, \"Norm\": %.17g, \"Steps\": %lld, \"tDsf\": %.9g, \"MatMults\": %lld,\n   \"Points\": [\n", LLD(GlobIdx),
                 LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, norm, LLD(dsf_steps), t1 - t0, LLD(matmults));
         for (size_t iq = 0; iq < points.size(); ++iq) {
             const Point& P = points[iq];
@@ -1575,39 +1495,14 @@ public:
             for (int part = 0; part < 2; ++part) {
                 const Part& A = P.part[part];
                 fprintf(fp_dsf, "      \"%s\": {\"Norm2\": %.17g, \"StepsDone\": %d, \"Alpha\": ", part == 0 ? "Cos" : "Sin", A.norm2, (int)A.done);
-                row(A.alpha); fprintf(fp_dsf, ", \"Beta\": "); row(A.beta); fprintf(fp_dsf, "},\n");
+                dsf_file.Row(A.alpha); fprintf(fp_dsf, ", \"Beta\": "); dsf_file.Row(A.beta); fprintf(fp_dsf, "},\n");
             }
-            fprintf(fp_dsf, "      \"Poles\": "); row(P.poles); fprintf(fp_dsf, ",\n      \"Weights\": "); row(P.weights);
+            fprintf(fp_dsf, "      \"Poles\": "); dsf_file.Row(P.poles); fprintf(fp_dsf, ",\n      \"Weights\": "); dsf_file.Row(P.weights);
             fprintf(fp_dsf, ",\n      \"StaticSzz\": %.17g}%s\n", P.total, iq + 1 < points.size() ? "," : "");
         }
         fprintf(fp_dsf, "   ]}");
-        dsf_printed_first = PETSC_TRUE;
         fflush(fp_dsf);
         return 0;
-    }
-
-    /** A nearest-neighbour bond of the lattice: sites i < j, the site (ix, jy) from which NearestNeighbors generates it, 'x' if the two
-        sites differ in column, else 'y'. */
-    struct DimerBond { PetscInt i, j, ix, jy; char orient; };
-    /** The distinct pairs of Ham.NeighborPairs(), in order of first appearance (on Ly = 2 with the periodic y boundary every vertical pair
-        appears twice).  The generating site is the one whose "above" (y) or "right" (x) neighbour is the other site; where that holds
-        for both -- two sites round a periodic direction -- the lower-numbered one is visited first. */
-    std::vector<DimerBond> DimerBonds()
-    {
-        std::vector<DimerBond> bonds;
-        std::set<std::pair<PetscInt, PetscInt>> seen;
-        const PetscInt Lx = Ham.Lx(), Ly = Ham.Ly();
-        for (const std::vector<PetscInt>& p : Ham.NeighborPairs()) {
-            if (!seen.insert({p[0], p[1]}).second) continue;
-            PetscInt x0, y0, x1, y1;
-            Ham.To2D(p[0], x0, y0); Ham.To2D(p[1], x1, y1);
-            DimerBond b;
-            b.i = p[0]; b.j = p[1]; b.orient = x0 != x1 ? 'x' : 'y';
-            const bool from_i = b.orient == 'x' ? (x0 + 1) % Lx == x1 : (y0 + 1) % Ly == y1;
-            b.ix = from_i ? x0 : x1; b.jy = from_i ? y0 : y1;
-            bonds.push_back(b);
-        }
-        return bonds;
     }
 
     /** -corr_dimer 1 (engine extension): the dimer-dimer table < D_b D_b' > over all pairs of nearest-neighbour bonds, D_b = S_i . S_j
@@ -1627,31 +1522,17 @@ public:
     {
         PetscLogDouble t0, t1;
         PetscTime(&t0);
-        Block& L = KronBlocks.LeftBlockRefMod();
-        Block& R = KronBlocks.RightBlockRefMod();
-        const PetscInt nls = L.NumSites(), nrs = R.NumSites(), N = num_sites;
-        if (nls + nrs != N) SETERRQ3(mpi_comm, 1, "Dimer correlations: the blocks hold %lld + %lld sites, the lattice %lld.", LLD(nls), LLD(nrs), LLD(N));
-        const std::vector<int32_t> ls = L.Magnetization.Sizes32(), rs = R.Magnetization.Sizes32();
-        std::vector<int32_t> bil, bir;
-        for (PetscInt k = 0; k < KronBlocks.size(); ++k) { bil.push_back((int32_t)KronBlocks.LeftIdx(k)); bir.push_back((int32_t)KronBlocks.RightIdx(k)); }
-        const dmrgx_sectors sl{(int32_t)ls.size(), ls.data()}, sr{(int32_t)rs.size(), rs.data()};
-        const std::vector<DimerBond> bonds = DimerBonds();
+        dmrgx_host::CentreFrame F;
+        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, "Dimer correlations"); CHKERRQ(ierr);
+        const std::vector<dmrgx_host::DimerBond> bonds = dmrgx_host::DimerBonds(Ham);
         const PetscInt nb = (PetscInt)bonds.size();
-        /* a pruned operator must never read as zero */
-        auto site_op = [&](int side, Op_t type, PetscInt s, Mat& m) -> PetscErrorCode {
-            Block& blk = side == 0 ? L : R;
-            m = type == OpSz ? blk.Sz(s) : blk.Sp(s);
-            if (!m) SETERRQ3(mpi_comm, PETSC_ERR_ARG_WRONGSTATE, "Dimer correlations: operator %s(%lld) of the %s block is not resident (pruned).", OpToCStr(type), LLD(s), side == 0 ? "left" : "right");
-            return 0;
-        };
-        auto block_site = [&](int side, PetscInt lattice_site) { return side == 0 ? lattice_site : N - 1 - lattice_site; };
-        auto side_of = [&](const DimerBond& b) { return b.j < nls ? 0 : (b.i >= nls ? 1 : 2); };      /* 2: across the cut */
+        auto side_of = [&](const dmrgx_host::DimerBond& b) { return b.j < F.nsites[0] ? 0 : (b.i >= F.nsites[0] ? 1 : 2); };      /* 2: across the cut */
 
         /* ---- bond operators inside a block, dense per sector: C[q] = Sz_i[q] Sz_j[q] + (Sp_i / 2)[q -> q+1] Sm_j[q+1 -> q] + (Sm_i / 2)[q -> q-1] Sp_j[q-1 -> q] */
         std::vector<Mat> bond_op((size_t)nb);
         int64_t bond_doubles = 0;
         for (int side = 0; side < 2; ++side) {
-            const std::vector<int32_t>& sz = side == 0 ? ls : rs;
+            const std::vector<int32_t>& sz = F.sizes[side];
             const int32_t ns = (int32_t)sz.size();
             enum { DSz = 0, DSp = 1, DSm = 2, DHalfSp = 3, DHalfSm = 4 };
             std::map<std::pair<int, PetscInt>, Mat> dense;          /* (kind, block site) -> dense form, for this measurement */
@@ -1659,7 +1540,7 @@ public:
                 auto it = dense.find({kind, s});
                 if (it != dense.end()) { d = it->second; return 0; }
                 Mat m;
-                PetscErrorCode e = site_op(side, kind == DSz ? OpSz : OpSp, s, m); CHKERRQ(e);
+                PetscErrorCode e = F.resident(side, kind == DSz ? OpSz : OpSp, s, m); CHKERRQ(e);
                 if (kind == DSm || kind == DHalfSm) {               /* Sm(s) = Sp(s) read transposed */
                     auto v = std::make_shared<dmrgx_host::SectorMat>();
                     v->transpose_of = m; v->shift = OpSm; v->sizes = m->sizes;
@@ -1684,9 +1565,8 @@ public:
             };
             for (PetscInt b = 0; b < nb; ++b) {
                 if (side_of(bonds[(size_t)b]) != side) continue;
-                const PetscInt si = block_site(side, bonds[(size_t)b].i), sj = block_site(side, bonds[(size_t)b].j);
+                const PetscInt si = F.block_site(side, bonds[(size_t)b].i), sj = F.block_site(side, bonds[(size_t)b].j);
                 Mat zi, zj, hpi, hmi, pj, mj;
-                PetscErrorCode ierr;
                 ierr = densify(DSz, si, zi); CHKERRQ(ierr); ierr = densify(DSz, sj, zj); CHKERRQ(ierr);
                 ierr = densify(DHalfSp, si, hpi); CHKERRQ(ierr); ierr = densify(DSm, sj, mj); CHKERRQ(ierr);
                 ierr = densify(DHalfSm, si, hmi); CHKERRQ(ierr); ierr = densify(DSp, sj, pj); CHKERRQ(ierr);
@@ -1718,27 +1598,11 @@ public:
                 bond_doubles += total;
                 bond_op[(size_t)b] = C;
             }
-            PetscErrorCode ierr = flush(); CHKERRQ(ierr);
+            ierr = flush(); CHKERRQ(ierr);
         }                                                           /* (the dense site operators go back to the pool here: stream-ordered) */
 
         /* ---- the vectors: psi, then the image of every bond */
-        std::deque<std::vector<dmrgx_cell>> store;
-        std::vector<dmrgx_secop> ops[2];
-        std::map<std::tuple<int, int, PetscInt>, int32_t> site_index;       /* (side, Sz / Sp / Sm, block site) -> index in ops[side] */
-        auto site_secop = [&](int side, Op_t type, PetscInt s, int32_t& idx) -> PetscErrorCode {
-            auto it = site_index.find(std::make_tuple(side, (int)type, s));
-            if (it != site_index.end()) { idx = it->second; return 0; }
-            Mat m;
-            PetscErrorCode e = site_op(side, type == OpSz ? OpSz : OpSp, s, m); CHKERRQ(e);
-            store.emplace_back();
-            dmrgx_secop so;
-            if (type == OpSm) m->to_secop(so, store.back(), true, -1);
-            else m->to_secop(so, store.back());
-            idx = (int32_t)ops[side].size();
-            ops[side].push_back(so);
-            site_index[std::make_tuple(side, (int)type, s)] = idx;
-            return 0;
-        };
+        dmrgx_host::SiteOperators T(F);
         std::vector<int32_t> vec_first{0};
         std::vector<dmrgx_term> terms;
         terms.push_back(dmrgx_term{1.0, -1, -1});
@@ -1746,20 +1610,16 @@ public:
         for (PetscInt b = 0; b < nb; ++b) {
             const int side = side_of(bonds[(size_t)b]);
             if (side < 2) {
-                store.emplace_back();
-                dmrgx_secop so;
-                bond_op[(size_t)b]->to_secop(so, store.back());
-                ops[side].push_back(so);
-                const int32_t idx = (int32_t)ops[side].size() - 1;
+                const int32_t idx = T.Add(side, bond_op[(size_t)b]);
                 terms.push_back(side == 0 ? dmrgx_term{1.0, idx, -1} : dmrgx_term{1.0, -1, idx});
             } else {
-                const PetscInt si = bonds[(size_t)b].i, sj = block_site(1, bonds[(size_t)b].j);
+                const PetscInt si = bonds[(size_t)b].i, sj = F.block_site(1, bonds[(size_t)b].j);
                 const Op_t left_type[3] = {OpSz, OpSp, OpSm}, right_type[3] = {OpSz, OpSm, OpSp};
                 const double coeff[3] = {1.0, 0.5, 0.5};
                 for (int t = 0; t < 3; ++t) {
                     int32_t il, ir;
-                    PetscErrorCode ierr = site_secop(0, left_type[t], si, il); CHKERRQ(ierr);
-                    ierr = site_secop(1, right_type[t], sj, ir); CHKERRQ(ierr);
+                    ierr = T.Site(0, left_type[t], si, il); CHKERRQ(ierr);
+                    ierr = T.Site(1, right_type[t], sj, ir); CHKERRQ(ierr);
                     terms.push_back(dmrgx_term{coeff[t], il, ir});
                 }
             }
@@ -1768,16 +1628,16 @@ public:
         const PetscInt nv = nb + 1;
         /* the workspace holds at least the largest image block of every vector: the blocks (IL, IR), (IL - 1, IR + 1), (IL + 1, IR - 1) */
         int64_t largest = 1;
-        for (size_t k = 0; k < bil.size(); ++k)
+        for (size_t k = 0; k < F.bil.size(); ++k)
             for (int32_t d = -1; d <= 1; ++d) {
-                const int32_t a = bil[k] - d, c = bir[k] + d;
-                if (a >= 0 && a < (int32_t)ls.size() && c >= 0 && c < (int32_t)rs.size()) largest = std::max<int64_t>(largest, (int64_t)ls[(size_t)a] * rs[(size_t)c]);
+                const int32_t a = F.bil[k] - d, c = F.bir[k] + d;
+                if (a >= 0 && a < (int32_t)F.sizes[0].size() && c >= 0 && c < (int32_t)F.sizes[1].size()) largest = std::max<int64_t>(largest, (int64_t)F.sizes[0][(size_t)a] * F.sizes[1][(size_t)c]);
             }
         const size_t workspace = std::max<size_t>((size_t)1 << 30, (size_t)largest * (size_t)nv * sizeof(double));
         std::vector<double> G((size_t)(nv * nv), 0.0);
         {
             dmrgx_host::DevBuffer g((size_t)(nv * nv), dmrgx_host::DevBuffer::device_only_t{});
-            if (dmrgx_kron_term_gram(&sl, &sr, (int32_t)bil.size(), bil.data(), bir.data(), gsv_r->buf->dev_ro(), (int32_t)ops[0].size(), ops[0].data(), (int32_t)ops[1].size(), ops[1].data(),
+            if (dmrgx_kron_term_gram(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), gsv_r->buf->dev_ro(), (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
                                      (int32_t)nv, vec_first.data(), terms.data(), workspace, g.dev_uninitialised(), nv, nullptr, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_gram: %s", dmrgx_last_error());
             if (dmrgx_memcpy_d2h(G.data(), g.dev_ro(), G.size() * sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
         }
@@ -1792,46 +1652,30 @@ public:
         /* S_a(q) = (1/N_a) sum over the bonds b, b' of orientation a of cos(q . (r_b - r_b')) Connected[b][b'],  q = (2 pi nx / Lx, 2 pi ny / Ly) */
         const PetscInt Lx = Ham.Lx(), Ly = Ham.Ly();
         std::vector<double> Sq[2] = {std::vector<double>((size_t)(Lx * Ly), 0.0), std::vector<double>((size_t)(Lx * Ly), 0.0)};
-        const double two_pi = 6.283185307179586476925286766559;
         for (int o = 0; o < 2; ++o) {
-            std::vector<PetscInt> of;
-            for (PetscInt b = 0; b < nb; ++b) if (bonds[(size_t)b].orient == (o == 0 ? 'x' : 'y')) of.push_back(b);
+            std::vector<PetscInt> of, x, y;
+            for (PetscInt b = 0; b < nb; ++b) if (bonds[(size_t)b].orient == (o == 0 ? 'x' : 'y')) { of.push_back(b); x.push_back(bonds[(size_t)b].ix); y.push_back(bonds[(size_t)b].jy); }
             if (of.empty()) continue;
-            for (PetscInt nx = 0; nx < Lx; ++nx) for (PetscInt ny = 0; ny < Ly; ++ny) {
-                double acc = 0.0;
-                for (PetscInt b : of) for (PetscInt c : of)
-                    acc += std::cos(two_pi * ((double)(nx * (bonds[(size_t)b].ix - bonds[(size_t)c].ix)) / (double)Lx + (double)(ny * (bonds[(size_t)b].jy - bonds[(size_t)c].jy)) / (double)Ly)) * Conn[(size_t)(b * nb + c)];
-                Sq[o][(size_t)(nx * Ly + ny)] = acc / (double)of.size();
-            }
+            std::vector<double> C;                                  /* Connected among the bonds of this orientation */
+            for (PetscInt b : of) for (PetscInt c : of) C.push_back(Conn[(size_t)(b * nb + c)]);
+            Sq[o] = dmrgx_host::LatticeFourier(Lx, Ly, x.data(), y.data(), C.data(), (PetscInt)of.size(), (double)of.size());
         }
         PetscTime(&t1);
         if (!mpi_rank && verbose)
             printf("  * Dimer correlations: %lld bonds, Gram of %lld vectors x %lld, %lld bytes of bond operators held, tDimer %.6f s\n", LLD(nb), LLD(nv), LLD(gsv_r->n), LLD(bond_doubles * (int64_t)sizeof(double)), t1 - t0);
         if (mpi_rank) return 0;
-        if (!fp_dimer) {
-            fp_dimer = fopen((data_dir + "DimerCorrelations.json").c_str(), "w");
-            if (!fp_dimer) SETERRQ1(mpi_comm, PETSC_ERR_FILE_OPEN, "Cannot open %sDimerCorrelations.json", data_dir.c_str());
-            fprintf(fp_dimer, "[\n");
-            dimer_printed_first = PETSC_FALSE;
-        }
-        auto row = [&](const double* v, PetscInt cnt) { fprintf(fp_dimer, "["); for (PetscInt i = 0; i < cnt; ++i) fprintf(fp_dimer, "%s%.15g", i ? ", " : "", v[i]); fprintf(fp_dimer, "]"); };
-        auto table = [&](const char* name, const std::vector<double>& T, PetscInt nr, PetscInt nc, const char* end) {
-            fprintf(fp_dimer, "   \"%s\": [\n", name);
-            for (PetscInt i = 0; i < nr; ++i) { fprintf(fp_dimer, "     "); row(T.data() + i * nc, nc); fprintf(fp_dimer, "%s\n", i + 1 < nr ? "," : ""); }
-            fprintf(fp_dimer, "   ]%s", end);
-        };
-        fprintf(fp_dimer, "%s  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"tDimer\": %.9g, \"Norm\": %.15g,\n   \"Bonds\": [", dimer_printed_first ? ",\n" : "", LLD(GlobIdx),
-                LoopType == WarmupStep ? "Warmup" : "Sweep", t1 - t0, norm);
+        ierr = dimer_file.Begin(data_dir + "DimerCorrelations.json"); CHKERRQ(ierr);
+        FILE* fp_dimer = dimer_file.fp;
+        fprintf(fp_dimer, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"tDimer\": %.9g, \"Norm\": %.15g,\n   \"Bonds\": [", LLD(GlobIdx), LoopType == WarmupStep ? "Warmup" : "Sweep", t1 - t0, norm);
         for (PetscInt b = 0; b < nb; ++b) fprintf(fp_dimer, "%s[%lld, %lld]", b ? ", " : "", LLD(bonds[(size_t)b].i), LLD(bonds[(size_t)b].j));
         fprintf(fp_dimer, "],\n   \"Orientation\": [");
         for (PetscInt b = 0; b < nb; ++b) fprintf(fp_dimer, "%s\"%c\"", b ? ", " : "", bonds[(size_t)b].orient);
         fprintf(fp_dimer, "],\n   \"Position\": [");
         for (PetscInt b = 0; b < nb; ++b) fprintf(fp_dimer, "%s[%lld, %lld]", b ? ", " : "", LLD(bonds[(size_t)b].ix), LLD(bonds[(size_t)b].jy));
         fprintf(fp_dimer, "],\n   \"D\": ");
-        row(D.data(), nb);
+        dimer_file.Row(D);
         fprintf(fp_dimer, ",\n");
-        table("DD", DD, nb, nb, ",\n"); table("Connected", Conn, nb, nb, ",\n"); table("StructureFactorX", Sq[0], Lx, Ly, ",\n"); table("StructureFactorY", Sq[1], Lx, Ly, "}");
-        dimer_printed_first = PETSC_TRUE;
+        dimer_file.Table("DD", DD, nb, nb, ",\n"); dimer_file.Table("Connected", Conn, nb, nb, ",\n"); dimer_file.Table("StructureFactorX", Sq[0], Lx, Ly, ",\n"); dimer_file.Table("StructureFactorY", Sq[1], Lx, Ly, "}");
         fflush(fp_dimer);
         return 0;
     }
@@ -2314,18 +2158,15 @@ private:
     std::map<std::pair<PetscInt, int>, WarmBasis> rdm_basis;
     PetscBool use_rdm_warm = PETSC_FALSE;
     PetscBool use_corr_matrix = PETSC_FALSE;    /* -corr_matrix 1: all-pairs tables through dmrgx_kron_op_gram, SpinCorrelations.json (CalculateCorrelationMatrix) */
-    FILE* fp_spin = NULL;                       /* opened at the first measurement with -corr_matrix, rank 0 only */
-    PetscBool spin_printed_first = PETSC_FALSE;
+    dmrgx_host::JsonRecordFile spin_file{"%.15g"};      /* created at the first measurement with -corr_matrix, rank 0 only */
     PetscBool use_corr_dimer = PETSC_FALSE;     /* -corr_dimer 1: dimer-dimer table over all bond pairs through dmrgx_kron_term_gram, DimerCorrelations.json (CalculateDimerCorrelations) */
-    FILE* fp_dimer = NULL;                      /* opened at the first measurement with -corr_dimer, rank 0 only */
+    dmrgx_host::JsonRecordFile dimer_file{"%.15g"};     /* created at the first measurement with -corr_dimer, rank 0 only */
     PetscBool use_dsf = PETSC_FALSE;            /* -dsf 1: S^zz(q, w) by the Lanczos-vector method, DynamicalStructureFactor.json (CalculateDynamicalStructureFactor) */
     std::vector<PetscInt> dsf_q;                /* -dsf_q: nx0, ny0, nx1, ny1, ... */
     PetscInt dsf_steps = 100;                   /* -dsf_steps: Lanczos steps per run */
     PetscReal dsf_breakdown_tol = 0.0;          /* -dsf_breakdown_tol: 0 = the library's default, 1e-7 */
     static constexpr double dsf_no_weight = 1e-20; /* a part with |v|^2 <= dsf_no_weight <psi|psi> (rounding noise, as Sz_tot psi at q = 0) is recorded with StepsDone 0, without a run */
-    FILE* fp_dsf = NULL;                        /* opened at the first measurement with -dsf */
-    PetscBool dsf_printed_first = PETSC_FALSE;
-    PetscBool dimer_printed_first = PETSC_FALSE;
+    dmrgx_host::JsonRecordFile dsf_file{"%.17g"};       /* created at the first measurement with -dsf */
     PetscBool use_corr_batch = PETSC_TRUE;      /* -corr_batch 0: every correlator through its own MatMult + dot, as the reference does */
 };
 

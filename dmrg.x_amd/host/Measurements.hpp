@@ -1,0 +1,158 @@
+#ifndef DMRGX_HOST_MEASUREMENTS_HPP
+#define DMRGX_HOST_MEASUREMENTS_HPP
+/** What -corr_matrix, -corr_dimer and -dsf share (DMRGBlockContainer.hpp: CalculateCorrelationMatrix, CalculateDimerCorrelations,
+    CalculateDynamicalStructureFactor): the two blocks as the library sees them, the site operators of one Gram / term call, the bond
+    list, the lattice Fourier sum, the phase coefficients of -dsf, the JSON record file.  host_tool.cpp runs the pure parts without a GPU. */
+#include <cmath>
+#include <deque>
+#include "DMRGKron.hpp"
+
+namespace dmrgx_host {
+
+constexpr double two_pi = 6.283185307179586476925286766559;
+
+/** The left (side 0) and the right (side 1) block of a KronBlocks_t, their sector sizes and the (left, right) sector of every
+    KronBlock.  sectors[] points into sizes[]: not copyable.  Site s of the right block is lattice site N - 1 - s, as in SetUpCorrelation. */
+struct CentreFrame {
+    const char* name = "";                                      /* the measurement, as its messages call it */
+    Block::SpinBase* blk[2] = {nullptr, nullptr};
+    PetscInt nsites[2] = {0, 0}, N = 0;
+    std::vector<int32_t> sizes[2], bil, bir;
+    dmrgx_sectors sectors[2] = {{0, nullptr}, {0, nullptr}};
+    CentreFrame() = default;
+    CentreFrame(const CentreFrame&) = delete;
+    PetscErrorCode Init(KronBlocks_t& KronBlocks, PetscInt num_sites, const char* display_name)
+    {
+        name = display_name; blk[0] = &KronBlocks.LeftBlockRefMod(); blk[1] = &KronBlocks.RightBlockRefMod();
+        nsites[0] = blk[0]->NumSites(); nsites[1] = blk[1]->NumSites(); N = num_sites;
+        if (nsites[0] + nsites[1] != N) SETERRQ4(PETSC_COMM_SELF, 1, "%s: the blocks hold %lld + %lld sites, the lattice %lld.", name, LLD(nsites[0]), LLD(nsites[1]), LLD(N));
+        for (int side = 0; side < 2; ++side) { sizes[side] = blk[side]->Magnetization.Sizes32(); sectors[side] = dmrgx_sectors{(int32_t)sizes[side].size(), sizes[side].data()}; }
+        for (PetscInt k = 0; k < KronBlocks.size(); ++k) { bil.push_back((int32_t)KronBlocks.LeftIdx(k)); bir.push_back((int32_t)KronBlocks.RightIdx(k)); }
+        return 0;
+    }
+    PetscInt lattice_site(int side, PetscInt block_site) const { return side == 0 ? block_site : N - 1 - block_site; }
+    PetscInt block_site(int side, PetscInt lattice_site) const { return side == 0 ? lattice_site : N - 1 - lattice_site; }
+    /** Sz(s) or Sp(s) of a block (Sm is never stored).  A pruned operator must never read as zero. */
+    PetscErrorCode resident(int side, Op_t type, PetscInt s, Mat& m) const
+    {
+        m = type == OpSz ? blk[side]->Sz(s) : blk[side]->Sp(s);
+        if (!m) SETERRQ4(PETSC_COMM_SELF, PETSC_ERR_ARG_WRONGSTATE, "%s: operator %s(%lld) of the %s block is not resident (pruned).", name, OpToCStr(type), LLD(s), side == 0 ? "left" : "right");
+        return 0;
+    }
+};
+
+/** The operators of one dmrgx_kron_op_gram / term_apply / term_gram call: ops[0] on the left block, ops[1] on the right, in the order
+    they were asked for (the order of the Gram vectors).  The cells behind a dmrgx_secop stay where they are while the table lives. */
+class SiteOperators {
+public:
+    explicit SiteOperators(const CentreFrame& F) : F(F) {}
+    SiteOperators(const SiteOperators&) = delete;                /* ops point into store */
+    std::vector<dmrgx_secop> ops[2];
+    /** idx: where Sz, Sp or Sm of block site s stands in ops[side]; appended at its first use.  Sm(s) is Sp(s) read transposed. */
+    PetscErrorCode Site(int side, Op_t type, PetscInt s, int32_t& idx)
+    {
+        auto it = index.find(std::make_tuple(side, (int)type, s));
+        if (it != index.end()) { idx = it->second; return 0; }
+        Mat m;
+        PetscErrorCode ierr = F.resident(side, type == OpSz ? OpSz : OpSp, s, m); CHKERRQ(ierr);
+        index[std::make_tuple(side, (int)type, s)] = idx = Add(side, m, type == OpSm);
+        return 0;
+    }
+    /** A ready operator of the block (a bond operator), or read transposed with sector shift -1 (Sm from Sp). */
+    int32_t Add(int side, const Mat& m, bool transposed = false) { dmrgx_secop so; store.emplace_back(); m->to_secop(so, store.back(), transposed, -1); ops[side].push_back(so); return (int32_t)ops[side].size() - 1; }
+    /** Sz, Sp or Sm of every site of the left, then of the right block; `lattice` gains the lattice site of each. */
+    PetscErrorCode AllSites(Op_t type, std::vector<PetscInt>& lattice)
+    {
+        for (int side = 0; side < 2; ++side) for (PetscInt s = 0; s < F.nsites[side]; ++s) {
+            int32_t idx;
+            PetscErrorCode ierr = Site(side, type, s, idx); CHKERRQ(ierr);
+            lattice.push_back(F.lattice_site(side, s));
+        }
+        return 0;
+    }
+    /** The identity of the block. */
+    void AddIdentity(int side)
+    {
+        const std::vector<int32_t>& sz = F.sizes[side];
+        store.emplace_back();
+        for (int32_t q = 0; q < (int32_t)sz.size(); ++q) store.back().push_back(dmrgx_cell{q, 0, 0, sz[(size_t)q], sz[(size_t)q], DMRGX_CELL_IDENT, 1.0, nullptr, 0});
+        ops[side].push_back(dmrgx_secop{0, 0, (int32_t)store.back().size(), store.back().data()});
+    }
+private:
+    const CentreFrame& F;
+    std::deque<std::vector<dmrgx_cell>> store;                  /* a deque: its elements never move */
+    std::map<std::tuple<int, int, PetscInt>, int32_t> index;    /* (side, Sz / Sp / Sm, block site) -> index in ops[side] */
+};
+
+/** S[nx][ny] = (1 / norm) sum_ab cos(q . (r_a - r_b)) T[a][b] over n points r_a = (x[a], y[a]) of the Lx x Ly lattice,
+    q = (2 pi nx / Lx, 2 pi ny / Ly); T is n x n, the result Lx x Ly, both row-major. */
+inline std::vector<double> LatticeFourier(PetscInt Lx, PetscInt Ly, const PetscInt* x, const PetscInt* y, const double* T, PetscInt n, double norm)
+{
+    std::vector<double> S((size_t)(Lx * Ly), 0.0);
+    for (PetscInt nx = 0; nx < Lx; ++nx) for (PetscInt ny = 0; ny < Ly; ++ny) {
+        double acc = 0.0;
+        for (PetscInt a = 0; a < n; ++a) for (PetscInt b = 0; b < n; ++b)
+            acc += std::cos(two_pi * ((double)(nx * (x[a] - x[b])) / (double)Lx + (double)(ny * (y[a] - y[b])) / (double)Ly)) * T[a * n + b];
+        S[(size_t)(nx * Ly + ny)] = acc / norm;
+    }
+    return S;
+}
+
+/** cos (part 0) or sin (part 1) of the exact fraction 2 pi p / M, 0 <= p < M, with the exact zeros taken from p, not from a rounded
+    angle: a part of O_q that vanishes by symmetry vanishes in its coefficients too. */
+inline double DsfPhaseCoefficient(int part, PetscInt p, PetscInt M)
+{
+    if (part == 0) return ((4 * p) % M == 0 && (2 * p) % M != 0) ? 0.0 : std::cos(two_pi * (double)p / (double)M);
+    return (2 * p) % M == 0 ? 0.0 : std::sin(two_pi * (double)p / (double)M);
+}
+
+/** A nearest-neighbour bond of the lattice: sites i < j, the site (ix, jy) from which NearestNeighbors generates it, 'x' if the two
+    sites differ in column, else 'y'. */
+struct DimerBond { PetscInt i, j, ix, jy; char orient; };
+/** The distinct pairs of Ham.NeighborPairs(), in order of first appearance (on Ly = 2 with the periodic y boundary every vertical pair
+    appears twice).  The generating site is the one whose "above" (y) or "right" (x) neighbour is the other site; where that holds
+    for both -- two sites round a periodic direction -- the lower-numbered one is visited first. */
+template<class Hamiltonian> std::vector<DimerBond> DimerBonds(const Hamiltonian& Ham)
+{
+    std::vector<DimerBond> bonds;
+    std::set<std::pair<PetscInt, PetscInt>> seen;
+    for (const std::vector<PetscInt>& p : Ham.NeighborPairs()) {
+        if (!seen.insert({p[0], p[1]}).second) continue;
+        PetscInt x0, y0, x1, y1;
+        Ham.To2D(p[0], x0, y0); Ham.To2D(p[1], x1, y1);
+        const char orient = x0 != x1 ? 'x' : 'y';
+        const bool from_i = orient == 'x' ? (x0 + 1) % Ham.Lx() == x1 : (y0 + 1) % Ham.Ly() == y1;
+        bonds.push_back(DimerBond{p[0], p[1], from_i ? x0 : x1, from_i ? y0 : y1, orient});
+    }
+    return bonds;
+}
+
+/** A JSON file that holds one list of records, one per measurement: created by the first Begin(), finished by Close().  The caller
+    writes the record itself to fp; numbers of Row() and Table() go through `number`, a printf format for one double. */
+struct JsonRecordFile {
+    const char* const number;
+    FILE* fp = NULL;
+    explicit JsonRecordFile(const char* number) : number(number) {}
+    JsonRecordFile(const JsonRecordFile&) = delete;
+    ~JsonRecordFile() { if (fp) fclose(fp); }                   /* (an error path: the list stays open-ended) */
+    /** Start a record: "[\n" in a new file, ",\n" after the record before. */
+    PetscErrorCode Begin(const std::string& path)
+    {
+        const bool first = !fp;
+        if (first && !(fp = fopen(path.c_str(), "w"))) SETERRQ1(PETSC_COMM_SELF, PETSC_ERR_FILE_OPEN, "Cannot open %s", path.c_str());
+        fprintf(fp, first ? "[\n" : ",\n");
+        return 0;
+    }
+    void Row(const double* v, PetscInt cnt) const { fprintf(fp, "["); for (PetscInt i = 0; i < cnt; ++i) { fprintf(fp, "%s", i ? ", " : ""); fprintf(fp, number, v[i]); } fprintf(fp, "]"); }
+    void Row(const std::vector<double>& v) const { Row(v.data(), (PetscInt)v.size()); }
+    void Table(const char* name, const std::vector<double>& T, PetscInt nr, PetscInt nc, const char* end) const
+    {
+        fprintf(fp, "   \"%s\": [\n", name);
+        for (PetscInt i = 0; i < nr; ++i) { fprintf(fp, "     "); Row(T.data() + i * nc, nc); fprintf(fp, "%s\n", i + 1 < nr ? "," : ""); }
+        fprintf(fp, "   ]%s", end);
+    }
+    void Close() { if (fp) { fprintf(fp, "\n]\n"); fclose(fp); fp = NULL; } }
+};
+
+}  // namespace dmrgx_host
+#endif

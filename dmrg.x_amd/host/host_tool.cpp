@@ -11,6 +11,7 @@
 #include "DMRGKron.hpp"
 #include "CorrelatorDealing.hpp"
 #include "TridiagQL.hpp"
+#include "Measurements.hpp"
 
 static void dump_mat(const char* tag, PetscInt site, const Mat& m)
 {
@@ -156,6 +157,45 @@ int main()
             printf("tridiag %d", (int)ok);
             for (size_t i = 0; i < n; ++i) printf(" %.17g,%.17g", d[i], z[i]);
             printf("\n");
+        } else if (cmd == "dsfcoef") {           /* dsfcoef Lx Ly nx ny  ->  cosine,sine coefficient of O_q (without 1/sqrt N) at every site, in the order of ham.To2D */
+            PetscInt Lx, Ly, nx, ny; is >> Lx >> Ly >> nx >> ny;
+            const PetscInt M = Lx * Ly;
+            printf("dsfcoef");
+            for (PetscInt i = 0; i < M; ++i) {
+                PetscInt x, y; ham.To2D(i, x, y);
+                const PetscInt p = (((nx * x * Ly + ny * y * Lx) % M) + M) % M;
+                printf(" %.17g,%.17g", dmrgx_host::DsfPhaseCoefficient(0, p, M), dmrgx_host::DsfPhaseCoefficient(1, p, M));
+            }
+            printf("\n");
+        } else if (cmd == "bonds") {             /* the nearest-neighbour bonds of ham: i,j,orientation,ix,jy */
+            printf("bonds");
+            for (const dmrgx_host::DimerBond& b : dmrgx_host::DimerBonds(ham)) printf(" %lld,%lld,%c,%lld,%lld", LLD(b.i), LLD(b.j), b.orient, LLD(b.ix), LLD(b.jy));
+            printf("\n");
+        } else if (cmd == "fourier") {           /* fourier Lx Ly n x_0 .. x_{n-1} y_0 .. y_{n-1} T_00 .. T_{n-1,n-1}  ->  the Lx x Ly table, norm n */
+            PetscInt Lx, Ly, n; is >> Lx >> Ly >> n;
+            std::vector<PetscInt> x((size_t)n), y((size_t)n);
+            std::vector<double> T((size_t)(n * n));
+            for (PetscInt& v : x) is >> v;
+            for (PetscInt& v : y) is >> v;
+            for (double& v : T) is >> v;
+            printf("fourier");
+            for (double v : dmrgx_host::LatticeFourier(Lx, Ly, x.data(), y.data(), T.data(), n, (double)n)) printf(" %.17g", v);
+            printf("\n");
+        } else if (cmd == "jsonrec") {           /* jsonrec path format nrec: nrec records {"K": k, "R": row of 3, "T": 2 x 3 table} of thirds, then Close() */
+            std::string path, fmt; PetscInt nrec; is >> path >> fmt >> nrec;
+            dmrgx_host::JsonRecordFile J(fmt.c_str());
+            for (PetscInt k = 0; k < nrec && !ierr; ++k) {
+                std::vector<double> T;
+                for (int i = 0; i < 6; ++i) T.push_back((double)(k * 6 + i) / 3.0);
+                ierr = J.Begin(path);
+                if (ierr) break;
+                fprintf(J.fp, "  {\"K\": %lld,\n   \"R\": ", LLD(k));
+                J.Row(T.data() + 1, 3);
+                fprintf(J.fp, ",\n");
+                J.Table("T", T, 2, 3, "}");
+            }
+            J.Close();
+            printf("rc %d\n", ierr);
         } else printf("unknown %s\n", cmd.c_str());
         fflush(stdout);
     }
