@@ -12,6 +12,7 @@
 // Every scalar the next kernel needs -- beta_{j-1}, alpha_j, 1/beta_j, the dead flag -- lives in a small device array, so the whole run
 // is enqueued without looking at the device; one copy and one synchronisation at the end bring the coefficients back.  Fixed grids and
 // fixed-order sums of block partials, no atomics: two runs give the same bits.
+// dmrgx_kron_lanczos_basis, further down, is the same run with the basis kept and fully reorthogonalised.
 #include "common.h"
 #include <cmath>
 
@@ -124,6 +125,149 @@ __global__ void __launch_bounds__(LZ_THREADS) lz_reduce_kernel(const double* __r
     }
 }
 
+
+// ---- the basis-keeping, fully reorthogonalised run (dmrgx_kron_lanczos_basis) ---------------------------------------------------------
+// Row j of V is q_j.  After the three-term step above (pass 1, alpha, pass 2 -- the same kernels), w is orthogonalised against all of
+// q_0..q_j twice by classical Gram-Schmidt:  h = V_{0..j} w  (multi-dot, then one reduction per k),  w -= V_{0..j}^T h  (multi-axpy).
+// alpha_j is everything removed along q_j (the three-term alpha plus h_j of both passes), beta_j = |w| after the second pass.
+// Both kernels are streaming reads of V_{0..j}: a workgroup owns LB_RANGE contiguous elements of the vector, keeps its piece of w in
+// registers (LB_PER doubles per thread) and lets the rows go past in 16-byte loads -- V_{0..j} and w are read once per kernel.
+constexpr int LB_PER = 8, LB_RANGE = LZ_THREADS * LB_PER, LB_KC = 64;
+
+// elements e, e + 1 of p (e even); beyond n: zeros.  VEC: p + e is 16-byte aligned
+template <bool VEC> __device__ __forceinline__ double2 lb_load2(const double* __restrict__ p, int64_t e, int64_t n)
+{
+    if (VEC && e + 1 < n) return *reinterpret_cast<const double2*>(p + e);
+    double2 r;
+    r.x = e < n ? p[e] : 0.0;
+    r.y = e + 1 < n ? p[e + 1] : 0.0;
+    return r;
+}
+
+// partial[k * gridDim.x + b] = sum over block b's range of V[k * ldv + e] * w[e],  k < nk.  Wave sums go to LDS per k and are added in
+// wave order once per LB_KC rows, so that there is no barrier per row.
+template <bool VEC> __global__ void __launch_bounds__(LZ_THREADS) lb_multidot_kernel(const double* __restrict__ w, const double* __restrict__ V, int64_t ldv, int nk, int64_t n,
+                                                                                     double* __restrict__ partial)
+{
+    __shared__ double red[LB_KC][LZ_THREADS / 64];
+    const int64_t base = (int64_t)blockIdx.x * LB_RANGE + 2 * threadIdx.x;
+    double2 wr[LB_PER / 2];
+#pragma unroll
+    for (int t = 0; t < LB_PER / 2; ++t) wr[t] = lb_load2<true>(w, base + (int64_t)t * 2 * LZ_THREADS, n);      // (w: a pool block, 256-byte aligned)
+    for (int k0 = 0; k0 < nk; k0 += LB_KC) {
+        const int kc = min(LB_KC, nk - k0);
+        for (int kk = 0; kk < kc; ++kk) {
+            const double* __restrict__ row = V + (int64_t)(k0 + kk) * ldv;
+            double2 v[LB_PER / 2];
+#pragma unroll
+            for (int t = 0; t < LB_PER / 2; ++t) v[t] = lb_load2<VEC>(row, base + (int64_t)t * 2 * LZ_THREADS, n);
+            double acc = 0.0;
+#pragma unroll
+            for (int t = 0; t < LB_PER / 2; ++t) { acc += v[t].x * wr[t].x; acc += v[t].y * wr[t].y; }
+            acc = lz_wave_sum(acc);
+            if ((threadIdx.x & 63) == 0) red[kk][threadIdx.x >> 6] = acc;
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < kc) {
+            double s = 0.0;
+#pragma unroll
+            for (int i = 0; i < LZ_THREADS / 64; ++i) s += red[threadIdx.x][i];
+            partial[(int64_t)(k0 + threadIdx.x) * gridDim.x + blockIdx.x] = s;
+        }
+        __syncthreads();
+    }
+}
+
+// block k: h[k] = the partials of row k added in block order
+__global__ void __launch_bounds__(LZ_THREADS) lb_hreduce_kernel(const double* __restrict__ partial, int nblk, double* __restrict__ h)
+{
+    const double* __restrict__ p = partial + (int64_t)blockIdx.x * nblk;
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += LZ_THREADS) s += p[b];
+    s = lz_block_sum(s);
+    if (threadIdx.x == 0) h[blockIdx.x] = s;
+}
+
+// w -= sum_{k < nk} h[k] V[k];  NORM: partial[b] = w . w over block b's range afterwards
+template <bool VEC, bool NORM> __global__ void __launch_bounds__(LZ_THREADS) lb_multiaxpy_kernel(double* __restrict__ w, const double* __restrict__ V, int64_t ldv, int nk, int64_t n,
+                                                                                                 const double* __restrict__ h, double* __restrict__ partial)
+{
+    const int64_t base = (int64_t)blockIdx.x * LB_RANGE + 2 * threadIdx.x;
+    double2 wr[LB_PER / 2];
+#pragma unroll
+    for (int t = 0; t < LB_PER / 2; ++t) wr[t] = lb_load2<true>(w, base + (int64_t)t * 2 * LZ_THREADS, n);
+    for (int k = 0; k < nk; ++k) {
+        const double* __restrict__ row = V + (int64_t)k * ldv;
+        const double hk = h[k];
+        double2 v[LB_PER / 2];
+#pragma unroll
+        for (int t = 0; t < LB_PER / 2; ++t) v[t] = lb_load2<VEC>(row, base + (int64_t)t * 2 * LZ_THREADS, n);
+#pragma unroll
+        for (int t = 0; t < LB_PER / 2; ++t) { wr[t].x -= hk * v[t].x; wr[t].y -= hk * v[t].y; }
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int t = 0; t < LB_PER / 2; ++t) {
+        const int64_t e = base + (int64_t)t * 2 * LZ_THREADS;
+        if (e + 1 < n) *reinterpret_cast<double2*>(w + e) = wr[t];
+        else if (e < n) w[e] = wr[t].x;
+        if (NORM) { acc += wr[t].x * wr[t].x; acc += wr[t].y * wr[t].y; }      // (beyond n the registers hold zeros)
+    }
+    if (NORM) {
+        acc = lz_block_sum(acc);
+        if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+    }
+}
+
+// One workgroup: stage 2 of lz_reduce_kernel for the reorthogonalised step.  alpha_j = the three-term alpha + h_j of both passes;
+// beta_j = sqrt of the partials added in block order; the same breakdown rule, the same end on a sum that is not a finite number.
+__global__ void __launch_bounds__(LZ_THREADS) lb_beta_kernel(const double* __restrict__ partial, int nblk, double* __restrict__ S, const double* __restrict__ h1,
+                                                             const double* __restrict__ h2, int j, int nsteps, double tol)
+{
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += LZ_THREADS) s += partial[b];
+    s = lz_block_sum(s);
+    if (threadIdx.x != 0) return;
+    const bool dead = S[LZ_DEAD] != 0.0;
+    double beta = 0.0, inv = 0.0, a = 0.0;
+    if (!dead) {
+        a = S[LZ_ALPHA] + h1[j] + h2[j];
+        if (!(fabs(a) < INFINITY) || !(s >= 0.0 && s < INFINITY)) { S[LZ_DEAD] = 1.0; S[LZ_BETA_PREV] = 0.0; a = 0.0; }      // step j does not count
+        else {
+            const double scale = fmax(S[LZ_SCALE], fabs(a));
+            beta = sqrt(s);
+            S[LZ_DONE] = (double)(j + 1);
+            if (beta > tol * scale) { inv = 1.0 / beta; S[LZ_SCALE] = fmax(scale, beta); S[LZ_BETA_PREV] = beta; }
+            else { S[LZ_DEAD] = 1.0; S[LZ_BETA_PREV] = 0.0; }
+        }
+    }
+    S[LZ_ALPHA] = a;
+    S[LZ_COEF + j] = a;
+    S[LZ_INV] = inv;
+    S[LZ_COEF + nsteps + j] = beta;
+}
+
+// row = x = src / beta, or exact zeros when there is no next vector (whatever src holds)
+__global__ void __launch_bounds__(LZ_THREADS) lb_scale2_kernel(const double* __restrict__ src, double* __restrict__ row, double* __restrict__ x, int64_t n, const double* __restrict__ S)
+{
+    const double inv = S[LZ_INV];
+    for (int64_t e = (int64_t)blockIdx.x * LZ_THREADS + threadIdx.x; e < n; e += (int64_t)gridDim.x * LZ_THREADS) {
+        const double q = inv != 0.0 ? src[e] * inv : 0.0;
+        row[e] = q;
+        x[e] = q;
+    }
+}
+
+// A run that a non-finite sum ended inside step j leaves q_j in row j although step j does not count: rows >= steps done are zeros.
+// (After a breakdown that row holds zeros already; a run that went through has no such row.)
+__global__ void __launch_bounds__(LZ_THREADS) lb_zero_uncounted_row_kernel(double* __restrict__ V, int64_t ldv, int64_t n, int nsteps, const double* __restrict__ S)
+{
+    const int done = (int)S[LZ_DONE];
+    if (S[LZ_DEAD] == 0.0 || done >= nsteps) return;
+    double* __restrict__ row = V + (int64_t)done * ldv;
+    for (int64_t e = (int64_t)blockIdx.x * LZ_THREADS + threadIdx.x; e < n; e += (int64_t)gridDim.x * LZ_THREADS) row[e] = 0.0;
+}
+
 }  // namespace
 }  // namespace dmrgx
 
@@ -170,6 +314,86 @@ extern "C" dmrgx_status dmrgx_kron_lanczos_coeffs(dmrgx_kron_plan* plan, const d
         DMRGX_HIP(hipGetLastError());
         double* t = qprev; qprev = qcur; qcur = w; w = t;               // three buffers, three (x, y) pairs: the plan patches its tables once each
     }
+    std::vector<double> host(nscal);
+    DMRGX_HIP(hipMemcpyAsync(host.data(), S, nscal * sizeof(double), hipMemcpyDeviceToHost, st));
+    DMRGX_HIP(hipStreamSynchronize(st));
+    *norm2 = host[LZ_NORM2];
+    *nsteps_done = (int32_t)host[LZ_DONE];
+    for (int32_t j = 0; j < nsteps; ++j) { alpha[j] = host[LZ_COEF + j]; beta[j] = host[LZ_COEF + nsteps + j]; }
+    return DMRGX_OK;
+}
+
+extern "C" dmrgx_status dmrgx_kron_lanczos_basis(dmrgx_kron_plan* plan, const double* v0_dev, int32_t nsteps, double breakdown_tol, double* V_dev, int64_t ldv,
+                                                 double* norm2, double* alpha, double* beta, int32_t* nsteps_done, void* stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (!plan || !v0_dev || !V_dev || !norm2 || !alpha || !beta || !nsteps_done) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_basis: null argument");
+    if (nsteps < 1) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_basis: nsteps %d, at least one step is needed", nsteps);
+    if (!(breakdown_tol >= 0.0) || breakdown_tol >= 1.0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_basis: breakdown_tol %g outside [0, 1)", breakdown_tol);
+    dmrgx_kron_info I;
+    DMRGX_CHK(dmrgx_kron_plan_info(plan, &I));
+    if (I.vec_len != I.n_states || I.local_len != I.n_states)
+        DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_basis: the plan is striped over ranks (world_size > 1): the recursion has no collectives");
+    const int64_t n = I.n_states;
+    if (ldv < n) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_basis: ldv %lld is smaller than n_states %lld", (long long)ldv, (long long)n);
+    {
+        const uintptr_t v_lo = (uintptr_t)V_dev, v_hi = v_lo + ((size_t)(nsteps - 1) * (size_t)ldv + (size_t)n) * sizeof(double);
+        const uintptr_t s_lo = (uintptr_t)v0_dev, s_hi = s_lo + (size_t)n * sizeof(double);
+        if (v_lo < s_hi && s_lo < v_hi) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_basis: V overlaps v0");
+    }
+    const double tol = breakdown_tol > 0.0 ? breakdown_tol : 1e-7;
+    const size_t nscal = (size_t)LZ_COEF + 2 * (size_t)nsteps;
+    const int nblk = (int)std::max<int64_t>(1, (n + LB_RANGE - 1) / LB_RANGE);
+    const bool vec = ((uintptr_t)V_dev & 15) == 0 && (ldv & 1) == 0;      // every row 16-byte aligned
+
+    // x = q_j and w = H q_j are fixed buffers: the plan sees one (x, y) pair for the whole run, and never a row of V
+    DevBuf dX, dW, dPartial, dRowPartial, dH, dS;
+    DMRGX_CHK(dX.alloc_f64((size_t)n, st));
+    DMRGX_CHK(dW.alloc_f64((size_t)n, st));
+    DMRGX_CHK(dPartial.alloc_f64((size_t)std::max(LZ_BLOCKS, nblk), st));
+    DMRGX_CHK(dRowPartial.alloc_f64((size_t)nsteps * (size_t)nblk, st));
+    DMRGX_CHK(dH.alloc_f64((size_t)2 * (size_t)nsteps, st));
+    DMRGX_CHK(dS.alloc(nscal * sizeof(double)));
+    DMRGX_HIP(zero_async(dS.p, dS.bytes, st));
+    double* S = dS.as<double>();
+    double* P = dPartial.as<double>();
+    double* RP = dRowPartial.as<double>();
+    double* h1 = dH.as<double>();
+    double* h2 = h1 + nsteps;
+    double* x = dX.as<double>();
+    double* w = dW.as<double>();
+
+    hipLaunchKernelGGL(lz_norm2_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, v0_dev, n, P);
+    hipLaunchKernelGGL(lz_reduce_kernel, dim3(1), dim3(LZ_THREADS), 0, st, (const double*)P, LZ_BLOCKS, S, 0, 0, nsteps, tol);
+    hipLaunchKernelGGL(lb_scale2_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, v0_dev, V_dev, x, n, (const double*)S);
+    DMRGX_HIP(hipGetLastError());
+    for (int32_t j = 0; j < nsteps; ++j) {
+        const double* qcur = V_dev + (int64_t)j * ldv;
+        const double* qprev = j ? V_dev + (int64_t)(j - 1) * ldv : qcur;      // beta_{-1} = 0 multiplies a finite vector
+        const int nk = j + 1;
+        DMRGX_CHK(dmrgx_kron_apply(plan, x, w, st));
+        hipLaunchKernelGGL(lz_pass1_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, w, qprev, qcur, n, (const double*)S, P);
+        hipLaunchKernelGGL(lz_reduce_kernel, dim3(1), dim3(LZ_THREADS), 0, st, (const double*)P, LZ_BLOCKS, S, 1, j, nsteps, tol);
+        hipLaunchKernelGGL(lz_pass2_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, w, qcur, n, (const double*)S, P);
+        for (int pass = 0; pass < 2; ++pass) {
+            double* h = pass ? h2 : h1;                                       // entries [0, j] are rewritten every step; entry j is what the beta kernel reads
+            if (vec) hipLaunchKernelGGL(lb_multidot_kernel<true>, dim3(nblk), dim3(LZ_THREADS), 0, st, (const double*)w, (const double*)V_dev, ldv, nk, n, RP);
+            else hipLaunchKernelGGL(lb_multidot_kernel<false>, dim3(nblk), dim3(LZ_THREADS), 0, st, (const double*)w, (const double*)V_dev, ldv, nk, n, RP);
+            hipLaunchKernelGGL(lb_hreduce_kernel, dim3(nk), dim3(LZ_THREADS), 0, st, (const double*)RP, nblk, h);
+            if (pass == 0) {
+                if (vec) hipLaunchKernelGGL((lb_multiaxpy_kernel<true, false>), dim3(nblk), dim3(LZ_THREADS), 0, st, w, (const double*)V_dev, ldv, nk, n, (const double*)h, P);
+                else hipLaunchKernelGGL((lb_multiaxpy_kernel<false, false>), dim3(nblk), dim3(LZ_THREADS), 0, st, w, (const double*)V_dev, ldv, nk, n, (const double*)h, P);
+            } else {
+                if (vec) hipLaunchKernelGGL((lb_multiaxpy_kernel<true, true>), dim3(nblk), dim3(LZ_THREADS), 0, st, w, (const double*)V_dev, ldv, nk, n, (const double*)h, P);
+                else hipLaunchKernelGGL((lb_multiaxpy_kernel<false, true>), dim3(nblk), dim3(LZ_THREADS), 0, st, w, (const double*)V_dev, ldv, nk, n, (const double*)h, P);
+            }
+        }
+        hipLaunchKernelGGL(lb_beta_kernel, dim3(1), dim3(LZ_THREADS), 0, st, (const double*)P, nblk, S, (const double*)h1, (const double*)h2, j, nsteps, tol);
+        if (j + 1 < nsteps) hipLaunchKernelGGL(lb_scale2_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, (const double*)w, V_dev + (int64_t)(j + 1) * ldv, x, n, (const double*)S);
+        DMRGX_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(lb_zero_uncounted_row_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, V_dev, ldv, n, nsteps, (const double*)S);
+    DMRGX_HIP(hipGetLastError());
     std::vector<double> host(nscal);
     DMRGX_HIP(hipMemcpyAsync(host.data(), S, nscal * sizeof(double), hipMemcpyDeviceToHost, st));
     DMRGX_HIP(hipStreamSynchronize(st));

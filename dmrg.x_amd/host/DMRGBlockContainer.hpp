@@ -213,6 +213,22 @@ public:
             ierr = PetscOptionsGetReal(NULL, NULL, "-dsf_breakdown_tol", &dsf_breakdown_tol, NULL); CHKERRQ(ierr);
             if (!(dsf_breakdown_tol >= 0.0) || dsf_breakdown_tol >= 1.0) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_breakdown_tol must lie in [0, 1). Got %g.", dsf_breakdown_tol);
         }
+        {   /* -dsf_sites c0,c1,...: the real-space dynamical correlations G_ic(w) from every listed site c (CalculateDynamicalCorrelations) */
+            PetscBool have_sites = PETSC_FALSE;
+            PetscInt nc = 4096;
+            dsf_sites.assign((size_t)nc, 0);
+            ierr = PetscOptionsGetIntArray(NULL, NULL, "-dsf_sites", dsf_sites.data(), &nc, &have_sites); CHKERRQ(ierr);
+            dsf_sites.resize(have_sites ? (size_t)nc : 0);
+            use_dsf_sites = (have_sites && nc > 0) ? PETSC_TRUE : PETSC_FALSE;
+        }
+        if (use_dsf_sites) {
+            if (mpi_size > 1) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-dsf_sites is not available on more than one rank (got %d): the Lanczos run behind G_ic(w) has no collectives.", (int)mpi_size);
+            for (PetscInt c : dsf_sites) if (c < 0 || c >= num_sites) SETERRQ2(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_sites: site %lld is outside [0, %lld), the lattice sites in the numbering of To1D.", LLD(c), LLD(num_sites));
+            ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_steps", &dsf_steps, NULL); CHKERRQ(ierr);
+            if (dsf_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_steps must be at least 1. Got %lld.", LLD(dsf_steps));
+            ierr = PetscOptionsGetReal(NULL, NULL, "-dsf_breakdown_tol", &dsf_breakdown_tol, NULL); CHKERRQ(ierr);
+            if (!(dsf_breakdown_tol >= 0.0) || dsf_breakdown_tol >= 1.0) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_breakdown_tol must lie in [0, 1). Got %g.", dsf_breakdown_tol);
+        }
         ierr = PetscOptionsGetBool(NULL, NULL, "-step_profile", &step_profile, NULL); CHKERRQ(ierr);
 
         PetscBool opt = PETSC_FALSE;
@@ -460,7 +476,7 @@ public:
         spectra_writer.Drain();
         if (fp_entanglement) { fprintf(fp_entanglement, "\n]\n"); fclose(fp_entanglement); fp_entanglement = NULL; }
         if (fp_kron) { fprintf(fp_kron, "\n]\n"); fclose(fp_kron); fp_kron = NULL; }
-        spin_file.Close(); dimer_file.Close(); dsf_file.Close();
+        spin_file.Close(); dimer_file.Close(); dsf_file.Close(); dsf_sites_file.Close();
         if (fp_corr) {
             if (!corr_headers_printed) { PetscErrorCode e2 = PrintCorrelationHeaders(); CHKERRQ(e2); }
             fprintf(fp_corr, "\n  ]\n}\n"); fclose(fp_corr); fp_corr = NULL;
@@ -588,6 +604,7 @@ public:
         }
         step.GSEnergy = gse_r;
         if (use_dsf && do_measurements) { ierr = CalculateDynamicalStructureFactor(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* needs the plan */
+        if (use_dsf_sites && do_measurements) { ierr = CalculateDynamicalCorrelations(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
         ierr = MatDestroy_KronSumShell(&H); CHKERRQ(ierr);
         ierr = MatDestroy(&H); CHKERRQ(ierr);
         ierr = PetscTime(&tdiag); CHKERRQ(ierr);
@@ -1505,6 +1522,130 @@ public:
         return 0;
     }
 
+    /** -dsf_sites c0,c1,... (engine extension): the real-space dynamical correlations of the ground state from every listed site c,
+            G_ic(w) = sum_n <0|Sz_i|n> <n|Sz_c|0> delta(w - E_n + E_0)   for ALL sites i,
+        from ONE Lanczos run per c, where -dsf needs two runs per wave vector.  v = Sz_c psi is one dmrgx_kron_term_apply;
+        dmrgx_kron_lanczos_basis runs the recursion from v with the basis V kept and fully reorthogonalised, so that T = V H V^T and
+        V V^T = 1 hold to rounding; the images u_i = Sz_i psi of all N sites are formed by dmrgx_kron_term_apply in chunks of at most 1 GiB
+        and their overlaps M[i][k] = <u_i, q_k> are one dmrgx_vec_gram(chunk, V) each.  With T = S Theta S^T (TridiagQL.hpp, all
+        eigenvectors) the Galerkin approximation of G in the Krylov space of v is
+            Poles[n] = theta_n - E0,   Amplitudes[i][n] = (M S)[i][n] |v| S[0][n] / <psi|psi>,
+        and Sqw[q][n] = sum_i cos(q . (r_i - r_c)) Amplitudes[i][n] at all Lx Ly wave vectors q = (2 pi nx / Lx, 2 pi ny / Ly), row
+        nx Ly + ny: (1/N) sum_c Sqw is S^zz(q, w).  Static[i] = sum_n Amplitudes[i][n] = <Sz_i Sz_c> exactly (S is orthogonal), and the
+        moments sum_n Amplitudes[i][n] Poles[n]^p equal <u_i, (H - E0)^p v> for p < steps done.
+        The psi component of v is left in: it shows as a pole at w = 0 whose amplitude at i is <Sz_i> <Sz_c>.  Amplitudes[c] are the
+        weights |v|^2 S[0][n]^2 >= 0 of the continued fraction of v; for i != c they carry either sign, and Sqw of ONE site is an
+        estimator that need not be positive where the lattice is not translation invariant (an open cylinder) -- only the average over c
+        is S^zz(q, w).  The block bases were optimised for the ground state alone: the caveat of -dsf applies unchanged.
+        Memory: the basis, steps x N_sb doubles on the device for the whole measurement (2.6 GB at 20 x 8, m = 2048, 100 steps), beside
+        one chunk of images.  Site s of the right block is lattice site N - 1 - s.  One rank only (refused at start-up otherwise). */
+    PetscErrorCode CalculateDynamicalCorrelations(KronBlocks_t& KronBlocks, const Vec& gsv_r, Mat& H, PetscScalar E0)
+    {
+        PetscLogDouble t0, t1;
+        PetscTime(&t0);
+        dmrgx_host::CentreFrame F;
+        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, "Dynamical correlations"); CHKERRQ(ierr);
+        const PetscInt nls = F.nsites[0], N = F.N, Lx = Ham.Lx(), Ly = Ham.Ly(), M = Lx * Ly, K = dsf_steps;
+        dmrgx_host::SiteOperators T(F);
+        std::vector<PetscInt> site, rx((size_t)N), ry((size_t)N);      /* site[a]: lattice site of operator a of the table; (rx, ry)[s]: where lattice site s sits */
+        ierr = T.AllSites(OpSz, site); CHKERRQ(ierr);
+        for (PetscInt s = 0; s < N; ++s) { ierr = Ham.To2D(s, rx[(size_t)s], ry[(size_t)s]); CHKERRQ(ierr); }
+        auto term_of = [&](PetscInt a) { return a < nls ? dmrgx_term{1.0, (int32_t)a, -1} : dmrgx_term{1.0, -1, (int32_t)(a - nls)}; };
+        const int64_t n = gsv_r->n, ld = n + (n & 1);                 /* even rows: the library streams them in 16-byte loads */
+        const double* psi = gsv_r->buf->dev_ro();
+        double norm = 0.0;
+        if (dmrgx_dot(n, psi, psi, &norm, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
+        const PetscInt chunk = std::max<PetscInt>(1, std::min<PetscInt>(N, (PetscInt)((((int64_t)1 << 30) / (int64_t)sizeof(double)) / ld)));
+        std::unique_ptr<dmrgx_host::DevBuffer> v, V, U, Mdev;
+        try {
+            v.reset(new dmrgx_host::DevBuffer((size_t)n, dmrgx_host::DevBuffer::device_only_t{}));
+            V.reset(new dmrgx_host::DevBuffer((size_t)(K * ld), dmrgx_host::DevBuffer::device_only_t{}));
+            U.reset(new dmrgx_host::DevBuffer((size_t)(chunk * ld), dmrgx_host::DevBuffer::device_only_t{}));
+            Mdev.reset(new dmrgx_host::DevBuffer((size_t)(chunk * K), dmrgx_host::DevBuffer::device_only_t{}));
+        } catch (const std::exception& e) { SETERRQ3(mpi_comm, PETSC_ERR_MEM, "Dynamical correlations: no memory for the basis of %lld steps x %lld states: %s", LLD(K), LLD(n), e.what()); }
+
+        struct Run { PetscInt c = 0; double norm2 = 0.0; int32_t done = 0; std::vector<double> alpha, beta, poles, amp, stat, sqw; };
+        std::vector<Run> runs(dsf_sites.size());
+        std::vector<double> Mh((size_t)(N * K)), Mchunk((size_t)(chunk * K)), theta, vec, coskr((size_t)(M * N));
+        std::vector<dmrgx_term> terms;
+        std::vector<int32_t> vec_first;
+        PetscInt matmults = 0;
+        double t_runs = 0.0;
+        for (size_t ir = 0; ir < runs.size(); ++ir) {
+            Run& R = runs[ir];
+            R.c = dsf_sites[ir];
+            PetscInt ac = -1;
+            for (PetscInt a = 0; a < N; ++a) if (site[(size_t)a] == R.c) ac = a;
+            if (ac < 0) SETERRQ1(mpi_comm, 1, "Dynamical correlations: site %lld is in neither block.", LLD(R.c));
+            /* v = Sz_c psi, then the run from it */
+            const dmrgx_term tc = term_of(ac);
+            const int32_t one_vec[2] = {0, 1};
+            if (dmrgx_kron_term_apply(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
+                                      1, one_vec, &tc, v->dev_uninitialised(), n, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_apply: %s", dmrgx_last_error());
+            R.alpha.assign((size_t)K, 0.0); R.beta.assign((size_t)K, 0.0);
+            PetscLogDouble tr0 = 0.0, tr1 = 0.0;
+            if (verbose) { if (dmrgx_stream_sync(nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error()); PetscTime(&tr0); }      /* the run alone, for the log */
+            if (dmrgx_kron_lanczos_basis(H->plan, v->dev_ro(), (int32_t)K, dsf_breakdown_tol, V->dev_uninitialised(), ld, &R.norm2, R.alpha.data(), R.beta.data(), &R.done, nullptr))
+                SETERRQ1(mpi_comm, 1, "dmrgx_kron_lanczos_basis: %s", dmrgx_last_error());
+            if (verbose) { PetscTime(&tr1); t_runs += tr1 - tr0; }
+            matmults += K;
+            /* M[s][k] = < Sz_s psi , q_k > for every lattice site s */
+            for (PetscInt a0 = 0; a0 < N; a0 += chunk) {
+                const PetscInt cnt = std::min<PetscInt>(chunk, N - a0);
+                terms.clear(); vec_first.assign(1, 0);
+                for (PetscInt a = a0; a < a0 + cnt; ++a) { terms.push_back(term_of(a)); vec_first.push_back((int32_t)terms.size()); }
+                if (dmrgx_kron_term_apply(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
+                                          (int32_t)cnt, vec_first.data(), terms.data(), U->dev_uninitialised(), ld, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_apply: %s", dmrgx_last_error());
+                if (dmrgx_vec_gram((int32_t)cnt, (int32_t)K, n, U->dev_ro(), ld, V->dev_ro(), ld, Mdev->dev_uninitialised(), K, 0, nullptr, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_vec_gram: %s", dmrgx_last_error());
+                if (dmrgx_memcpy_d2h(Mchunk.data(), Mdev->dev_ro(), (size_t)(cnt * K) * sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
+                for (PetscInt a = a0; a < a0 + cnt; ++a) std::copy(Mchunk.begin() + (a - a0) * K, Mchunk.begin() + (a - a0 + 1) * K, Mh.begin() + site[(size_t)a] * K);
+            }
+            /* T = S Theta S^T on the host, the poles ascending */
+            const PetscInt D = R.done;
+            R.alpha.resize((size_t)D); R.beta.resize((size_t)D);
+            theta = R.alpha;
+            if (!dmrgx_host::TridiagQLVectors(theta, R.beta, vec)) SETERRQ1(mpi_comm, 1, "Dynamical correlations: the QL iteration on the Lanczos matrix of site %lld did not converge.", LLD(R.c));
+            std::vector<PetscInt> order((size_t)D);
+            for (PetscInt k = 0; k < D; ++k) order[(size_t)k] = k;
+            std::sort(order.begin(), order.end(), [&](PetscInt a, PetscInt b) { return theta[(size_t)a] < theta[(size_t)b]; });
+            const double vnorm = std::sqrt(R.norm2);
+            R.poles.resize((size_t)D); R.amp.assign((size_t)(N * D), 0.0); R.stat.assign((size_t)N, 0.0); R.sqw.assign((size_t)(M * D), 0.0);
+            for (PetscInt p = 0; p < D; ++p) {
+                const double* z = vec.data() + order[(size_t)p] * D;            /* eigenvector of pole p: z[k] = S[k][n] */
+                R.poles[(size_t)p] = theta[(size_t)order[(size_t)p]] - (double)E0;
+                for (PetscInt s = 0; s < N; ++s) {
+                    double acc = 0.0;
+                    for (PetscInt k = 0; k < D; ++k) acc += Mh[(size_t)(s * K + k)] * z[k];
+                    R.amp[(size_t)(s * D + p)] = acc * vnorm * z[0] / norm;
+                }
+            }
+            for (PetscInt s = 0; s < N; ++s) for (PetscInt p = 0; p < D; ++p) R.stat[(size_t)s] += R.amp[(size_t)(s * D + p)];
+            for (PetscInt nx = 0; nx < Lx; ++nx) for (PetscInt ny = 0; ny < Ly; ++ny) for (PetscInt s = 0; s < N; ++s)
+                coskr[(size_t)((nx * Ly + ny) * N + s)] = std::cos(dmrgx_host::two_pi * ((double)(nx * (rx[(size_t)s] - rx[(size_t)R.c])) / (double)Lx + (double)(ny * (ry[(size_t)s] - ry[(size_t)R.c])) / (double)Ly));
+            for (PetscInt q = 0; q < M; ++q) for (PetscInt s = 0; s < N; ++s) {
+                const double cq = coskr[(size_t)(q * N + s)];
+                for (PetscInt p = 0; p < D; ++p) R.sqw[(size_t)(q * D + p)] += cq * R.amp[(size_t)(s * D + p)];
+            }
+        }
+        PetscTime(&t1);
+        if (verbose) printf("  * Dynamical correlations: %lld reference sites, %lld Lanczos steps per run with the basis kept, %lld MatMults on %lld states, images in chunks of %lld, tDsfSites %.6f s, of it the Lanczos runs %.6f s\n", LLD(runs.size()), LLD(K), LLD(matmults), LLD(n), LLD(chunk), t1 - t0, t_runs);
+        ierr = dsf_sites_file.Begin(data_dir + "DynamicalCorrelations.json"); CHKERRQ(ierr);
+        FILE* fp = dsf_sites_file.fp;
+        fprintf(fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"E0\": %.17g, \"Norm\": %.17g, \"Steps\": %lld, \"tDsfSites\": %.9g, \"MatMults\": %lld,\n   \"Sites\": [\n", LLD(GlobIdx),
+                LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, norm, LLD(K), t1 - t0, LLD(matmults));
+        for (size_t ir = 0; ir < runs.size(); ++ir) {
+            const Run& R = runs[ir];
+            const PetscInt D = R.done;
+            fprintf(fp, "   {\"Site\": %lld, \"r\": [%lld, %lld], \"Norm2\": %.17g, \"StepsDone\": %d,\n   \"Alpha\": ", LLD(R.c), LLD(rx[(size_t)R.c]), LLD(ry[(size_t)R.c]), R.norm2, (int)R.done);
+            dsf_sites_file.Row(R.alpha); fprintf(fp, ",\n   \"Beta\": "); dsf_sites_file.Row(R.beta); fprintf(fp, ",\n   \"Poles\": "); dsf_sites_file.Row(R.poles);
+            fprintf(fp, ",\n   \"Static\": "); dsf_sites_file.Row(R.stat); fprintf(fp, ",\n");
+            dsf_sites_file.Table("Amplitudes", R.amp, N, D, ",\n"); dsf_sites_file.Table("Sqw", R.sqw, M, D, ir + 1 < runs.size() ? "},\n" : "}\n");
+        }
+        fprintf(fp, "   ]}");
+        fflush(fp);
+        return 0;
+    }
+
     /** -corr_dimer 1 (engine extension): the dimer-dimer table < D_b D_b' > over all pairs of nearest-neighbour bonds, D_b = S_i . S_j
         = Sz_i Sz_j + (Sp_i Sm_j + Sm_i Sp_j) / 2, its connected part and the dimer structure factors of the x and the y bonds, at every
         measurement point.  < psi | D_b^T D_b' | psi > = < D_b psi , D_b' psi >: the whole table is ONE dmrgx_kron_term_gram call over the
@@ -1955,7 +2096,7 @@ public:
             for (const Op& o : c.SysOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
             for (const Op& o : c.EnvOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
         }
-        if (use_corr_matrix || use_corr_dimer || use_dsf) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer, -dsf: Sz and Sp of every site of both centre blocks, on every rank */
+        if (use_corr_matrix || use_corr_dimer || use_dsf || use_dsf_sites) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer, -dsf, -dsf_sites: Sz and Sp of every site of both centre blocks, on every rank */
         need_built = true;
         return 0;
     }
@@ -2167,6 +2308,9 @@ private:
     PetscReal dsf_breakdown_tol = 0.0;          /* -dsf_breakdown_tol: 0 = the library's default, 1e-7 */
     static constexpr double dsf_no_weight = 1e-20; /* a part with |v|^2 <= dsf_no_weight <psi|psi> (rounding noise, as Sz_tot psi at q = 0) is recorded with StepsDone 0, without a run */
     dmrgx_host::JsonRecordFile dsf_file{"%.17g"};       /* created at the first measurement with -dsf */
+    PetscBool use_dsf_sites = PETSC_FALSE;      /* -dsf_sites c0,c1,...: G_ic(w) and its Fourier transform from a kept Lanczos basis, DynamicalCorrelations.json (CalculateDynamicalCorrelations) */
+    std::vector<PetscInt> dsf_sites;            /* the reference sites c, lattice numbering of To1D; shares -dsf_steps and -dsf_breakdown_tol */
+    dmrgx_host::JsonRecordFile dsf_sites_file{"%.17g"}; /* created at the first measurement with -dsf_sites */
     PetscBool use_corr_batch = PETSC_TRUE;      /* -corr_batch 0: every correlator through its own MatMult + dot, as the reference does */
 };
 

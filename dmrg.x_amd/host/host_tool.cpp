@@ -157,6 +157,18 @@ int main()
             printf("tridiag %d", (int)ok);
             for (size_t i = 0; i < n; ++i) printf(" %.17g,%.17g", d[i], z[i]);
             printf("\n");
+        } else if (cmd == "tridiagvec") {        /* tridiagvec n d_0 .. d_{n-1} e_0 .. e_{n-2}  ->  one line per eigenvalue: the eigenvalue, then its eigenvector */
+            size_t n; is >> n;
+            std::vector<double> d(n), e(n ? n - 1 : 0), vec;
+            for (double& x : d) is >> x;
+            for (double& x : e) is >> x;
+            const bool ok = dmrgx_host::TridiagQLVectors(d, e, vec);
+            printf("tridiagvec %d %zu\n", (int)ok, n);
+            for (size_t k = 0; k < n; ++k) {
+                printf("eig %.17g", d[k]);
+                for (size_t i = 0; i < n; ++i) printf(" %.17g", vec[k * n + i]);
+                printf("\n");
+            }
         } else if (cmd == "dsfcoef") {           /* dsfcoef Lx Ly nx ny  ->  cosine,sine coefficient of O_q (without 1/sqrt N) at every site, in the order of ham.To2D */
             PetscInt Lx, Ly, nx, ny; is >> Lx >> Ly >> nx >> ny;
             const PetscInt M = Lx * Ly;

@@ -155,6 +155,22 @@ class KronPlan:
                                                           C.byref(norm2), alpha, beta, C.byref(done), self._stream_ptr(stream)))
         return norm2.value, np.array(alpha[:n]), np.array(beta[:n]), done.value
 
+    def lanczos_basis(self, v0, nsteps, breakdown_tol=0.0, V=None, stream=None):
+        """The Lanczos run of lanczos_coeffs with the basis kept and fully reorthogonalised (dmrgx_kron_lanczos_basis).  Returns
+        (norm2, alpha[nsteps], beta[nsteps], nsteps_done, V): row j of V is q_j, the rows from nsteps_done on are zeros.  V: an f64 device
+        tensor of nsteps rows whose elements are contiguous (its row stride is the library's ldv), any contents; None: a new nsteps x n_states."""
+        assert v0.dtype == torch.float64 and v0.is_contiguous() and v0.numel() >= self.info.n_states
+        n = max(int(nsteps), 0)
+        if V is None:
+            V = torch.empty((max(n, 1), self.info.n_states), dtype=torch.float64, device=v0.device)
+        assert V.dtype == torch.float64 and V.dim() == 2 and V.shape[0] >= n and (V.shape[1] <= 1 or V.stride(1) == 1)
+        norm2, done = C.c_double(0.0), C.c_int32(0)
+        alpha, beta = (C.c_double * max(n, 1))(), (C.c_double * max(n, 1))()
+        _capi.check(_capi.lib().dmrgx_kron_lanczos_basis(self._handle, C.c_void_p(v0.data_ptr()), int(nsteps), float(breakdown_tol),
+                                                         C.c_void_p(V.data_ptr()), int(V.stride(0)), C.byref(norm2), alpha, beta, C.byref(done),
+                                                         self._stream_ptr(stream)))
+        return norm2.value, np.array(alpha[:n]), np.array(beta[:n]), done.value, V
+
     def timing(self, enable):
         _capi.check(_capi.lib().dmrgx_kron_plan_timing(self._handle, 1 if enable else 0))
 

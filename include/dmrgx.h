@@ -28,6 +28,7 @@
  *   dmrgx_kron_term_apply    <- nothing in the reference: engine extensions like the Gram calls.  The image vectors sum_t c_t (A_t (x) B_t) psi
  *   dmrgx_kron_lanczos_coeffs   themselves (the Gram calls only hand back their inner products) and the Lanczos coefficients of the planned
  *                               superblock Hamiltonian from such a vector: the continued fraction behind a dynamical structure factor
+ *   dmrgx_kron_lanczos_basis    (-dsf); the same run with the basis kept and reorthogonalised, for overlaps with it (-dsf_sites)
  *   dmrgx_comm_*             <- the communicator of the reference's MPI path: VecScatter-to-all of x inside every MatMult
  *                               (src/DMRGKron.cpp:1833-1834) and the MPI_Allreduce behind SLEPc's VecDot / VecNorm
  *
@@ -483,6 +484,22 @@ dmrgx_status dmrgx_kron_term_apply(const dmrgx_sectors* left, const dmrgx_sector
 dmrgx_status dmrgx_kron_lanczos_coeffs(dmrgx_kron_plan* plan, const double* v0_dev, int32_t nsteps, double breakdown_tol,
                                        double* norm2, double* alpha /* [nsteps] */, double* beta /* [nsteps] */,
                                        int32_t* nsteps_done, void* stream);
+/* The same recursion with the basis kept and fully reorthogonalised: row j of V (V_dev[j*ldv + e], e < n_states; the caller's device
+ * memory, nsteps rows, ldv >= n_states) is q_j.  After the three-term step w is orthogonalised against all of q_0..q_j twice by
+ * classical Gram-Schmidt (h = V_{0..j} w, w -= V_{0..j}^T h; h stays on the device); alpha_j is the sum of everything removed along
+ * q_j, beta_j = |w| after the second pass.  So V V^T = 1 and V H V^T = tridiag(alpha; beta) hold to rounding over all steps done, which
+ * the overlaps <u, q_k> of other vectors with the basis need (the real-space dynamical correlations of -dsf_sites), and an exhausted
+ * Krylov space is noticed: beta falls to rounding noise and the run breaks down.  Arguments, refusals, the breakdown rule, the treatment
+ * of a zero, NaN or overflowing v0 and of a sum that turns non-finite, the host outputs and the single copy and synchronisation at the
+ * end are those of dmrgx_kron_lanczos_coeffs; refused in addition (DMRGX_ERR_ARG): V_dev NULL, ldv < n_states, V overlapping v0.
+ * Every row [0, nsteps) of V is written, the rows >= *nsteps_done as exact zeros (V may hold anything on entry); the columns from
+ * n_states to ldv are not touched.  The rows stream in 16-byte loads when V_dev is 16-byte aligned and ldv even, else in 8-byte loads.
+ * The MatMult runs from and into two fixed pool vectors -- the plan sees one (x, y) pair, never a row of V.  Memory from the pool: those
+ * two vectors, nsteps * ceil(n_states / 2048) doubles of partial sums, 2 nsteps of h.  Fixed grids, fixed-order sums, no atomics: two
+ * runs give the same bits in alpha, beta and V. */
+dmrgx_status dmrgx_kron_lanczos_basis(dmrgx_kron_plan* plan, const double* v0_dev, int32_t nsteps, double breakdown_tol,
+                                      double* V_dev, int64_t ldv, double* norm2, double* alpha /* [nsteps] */, double* beta /* [nsteps] */,
+                                      int32_t* nsteps_done, void* stream);
 
 #ifdef __cplusplus
 }

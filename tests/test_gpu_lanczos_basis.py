@@ -1,0 +1,230 @@
+"""dmrgx_kron_lanczos_basis: the basis-keeping, twice-reorthogonalised device-resident Lanczos run against numpy on the dense
+Hamiltonian (-m gpu).  The synthetic superblocks and the dense H of test_gpu_lanczos_coeffs (once per module)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from test_gpu_lanczos_coeffs import CASES, ERR_ARG, _lanczos_reorth
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def mods(pkg):
+    from dmrgx_amd import superblock, workloads, _capi
+    _capi.require_device()
+    return superblock, workloads, _capi
+
+
+def _dense(wl, name, m, Ly, seed):
+    sb = wl.synthetic_superblock(name, m=m, Ly=Ly, seed=seed)
+    H = np.stack([wl.apply_factored_numpy(sb, e) for e in np.eye(sb.n_states)], axis=1)
+    w, v = np.linalg.eigh(H)
+    for a in (H, w, v):
+        a.setflags(write=False)
+    return sb, H, w, v
+
+
+@pytest.fixture(scope="module")
+def dense(mods):
+    """name -> (superblock, dense H, eigenvalues, eigenvectors); read-only"""
+    _, wl, _ = mods
+    out = {key: _dense(wl, kw["name"], kw["m"], kw["Ly"], kw["seed"]) for key, kw in CASES.items()}
+    out["tiny"] = _dense(wl, "cfg1", 4, 1, 3)
+    return out
+
+
+def _lanczos_plain(H, v0, K):
+    """The three-term recursion without reorthogonalisation (what dmrgx_kron_lanczos_coeffs runs)."""
+    q, qp, bp = v0 / np.linalg.norm(v0), np.zeros_like(v0), 0.0
+    alpha, beta = [], []
+    for _ in range(K):
+        x = H @ q - bp * qp
+        a = q @ x
+        x = x - a * q
+        b = np.linalg.norm(x)
+        alpha.append(a)
+        beta.append(b)
+        qp, q, bp = q, x / b, b
+    return np.array(alpha), np.array(beta)
+
+
+def _tridiag(alpha, beta):
+    K = len(alpha)
+    return np.diag(alpha) + np.diag(beta[:K - 1], 1) + np.diag(beta[:K - 1], -1)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint64)
+
+
+def _invariants(plan, sb, H, v0, K, V=None):
+    """One run, twice: coefficients against numpy, V V^T = 1 and V H V^T = T to 1e-12, repeatability, v0 untouched."""
+    n2, a, b = _lanczos_reorth(H, v0, K)
+    normH = np.linalg.norm(H, 2)
+    v0d = torch.from_numpy(v0).cuda()
+    norm2, alpha, beta, done, Vd = plan.lanczos_basis(v0d, K, V=V)
+    Vh = Vd.cpu().numpy()[:, :sb.n_states].copy()
+    norm2b, alphab, betab, doneb, Vb = plan.lanczos_basis(v0d, K)
+    Vhb = Vb.cpu().numpy()
+    tol = 1e-10 * np.abs(a).max()
+    T = _tridiag(alpha, beta)
+    orth, galerkin = np.abs(Vh @ Vh.T - np.eye(K)).max(), np.abs(Vh @ H @ Vh.T - T).max()
+    print("n", sb.n_states, "K", K, "norm2 err", abs(norm2 - n2), "alpha err", np.abs(alpha - a).max(), "beta err", np.abs(beta[:K - 1] - b[:K - 1]).max(), "tol", tol,
+          "|VV^T - 1|", orth, "|VHV^T - T|", galerkin, "|H|", normH)
+    assert done == K and np.isfinite(alpha).all() and np.isfinite(beta).all() and np.isfinite(Vh).all()
+    assert abs(norm2 - n2) <= tol
+    assert np.abs(alpha - a).max() <= tol and np.abs(beta[:K - 1] - b[:K - 1]).max() <= tol
+    assert orth <= 1e-12
+    assert galerkin <= 1e-12 * normH
+    assert norm2 == norm2b and done == doneb
+    assert np.array_equal(_bits(alpha), _bits(alphab)) and np.array_equal(_bits(beta), _bits(betab)) and np.array_equal(_bits(Vh), _bits(Vhb))
+    assert np.array_equal(_bits(v0d.cpu().numpy()), _bits(v0))
+    return alpha, beta
+
+
+def test_120_steps_where_the_plain_recursion_has_lost_orthogonality(mods, dense):
+    """cfg1, m = 12, seed 4 (148 states), 120 steps.  In numpy the plain recursion has left the reorthogonalised one by O(1) after step
+    60 and shows duplicate Ritz values, so the input tells the two apart; the device run follows the reorthogonalised one to
+    1e-10 max |alpha| (two CPU orderings of the sums differ by 3e-14) and keeps V V^T = 1 and V H V^T = T to 1e-12 (|H|)."""
+    sbm, _, _ = mods
+    sb, H, _, _ = dense["cfg1"]
+    K = 120
+    assert sb.n_states == 148
+    v0 = np.random.default_rng(11).standard_normal(sb.n_states)
+    _, a, b = _lanczos_reorth(H, v0, K)
+    ap, bp = _lanczos_plain(H, v0, K)
+    ritz_plain, ritz = np.linalg.eigvalsh(_tridiag(ap, bp)), np.linalg.eigvalsh(_tridiag(a, b))
+    print("plain vs reorthogonalised: alpha differs by", np.abs(ap[60:] - a[60:]).max(), "smallest Ritz gap plain", np.diff(ritz_plain).min(), "reorthogonalised", np.diff(ritz).min())
+    assert np.abs(ap[60:] - a[60:]).max() > 0.1
+    assert np.diff(ritz_plain).min() < 1e-8 * np.abs(ritz).max() < 1e-2 * np.diff(ritz).min()      # ghosts: copies of converged Ritz values
+    plan = sbm.KronPlan(sb)
+    _invariants(plan, sb, H, v0, K)
+    plan.destroy()
+
+
+@pytest.mark.parametrize("key", ["cfg2", "cfg5"])
+def test_40_steps_other_superblocks(mods, dense, key):
+    """The same invariants on the two other superblocks; V is a view with an odd row stride into NaN-filled memory, so that rows start
+    8-byte aligned only (the 8-byte load path) and the pad columns must stay untouched."""
+    sbm, _, _ = mods
+    sb, H, _, _ = dense[key]
+    n, K = sb.n_states, 40
+    ld = n + 1 + (n % 2)                                                    # odd
+    store = torch.full((K, ld), float("nan"), dtype=torch.float64, device="cuda")
+    plan = sbm.KronPlan(sb)
+    _invariants(plan, sb, H, np.random.default_rng(11).standard_normal(n), K, V=store[:, :n])
+    plan.destroy()
+    assert torch.isnan(store[:, n:]).all()
+
+
+def test_exhausted_krylov_space_is_noticed(mods, dense):
+    """cfg1, m = 4, seed 3 (32 states), 38 steps into NaN-filled V: with the basis kept orthogonal beta_31 is rounding noise, the run
+    breaks down there: nsteps_done == 32, T_32 has the eigenvalues of H to 1e-10 |H|, and everything behind is exact zeros."""
+    sbm, _, _ = mods
+    sb, H, w, _ = dense["tiny"]
+    n, K = sb.n_states, 38
+    assert n == 32
+    v0 = torch.from_numpy(np.random.default_rng(11).standard_normal(n)).cuda()
+    V = torch.full((K, n), float("nan"), dtype=torch.float64, device="cuda")
+    plan = sbm.KronPlan(sb)
+    norm2, alpha, beta, done, V = plan.lanczos_basis(v0, K, V=V)
+    plan.destroy()
+    Vh = V.cpu().numpy()
+    print("done", done, "beta[28:34]", beta[28:34])
+    assert done == 32
+    assert np.isfinite(alpha).all() and np.isfinite(beta).all() and np.isfinite(Vh).all()
+    assert (alpha[32:] == 0.0).all() and (beta[32:] == 0.0).all() and (Vh[32:] == 0.0).all()
+    th = np.linalg.eigvalsh(_tridiag(alpha[:32], beta[:32]))
+    normH = np.abs(w).max()
+    print("eigenvalue err", np.abs(th - w).max(), "|H|", normH)
+    assert np.abs(th - w).max() <= 1e-10 * normH
+    assert np.abs(Vh[:32] @ Vh[:32].T - np.eye(32)).max() <= 1e-12
+
+
+@pytest.mark.parametrize("key", list(CASES))
+def test_planted_invariant_subspace_breaks_down_on_the_device(mods, dense, key):
+    """As for dmrgx_kron_lanczos_coeffs: v0 a combination of 5 eigenvectors, 9 steps: done == 5, poles and weights to 1e-9, the rows of V
+    and the coefficients behind are exact zeros."""
+    sbm, _, _ = mods
+    sb, H, w, v = dense[key]
+    n = sb.n_states
+    idx = np.array([0, n // 5, (2 * n) // 5, (3 * n) // 5, n - 1])
+    c = np.random.default_rng(13).uniform(0.5, 1.5, 5)
+    v0 = v[:, idx] @ c
+    plan = sbm.KronPlan(sb)
+    norm2, alpha, beta, done, V = plan.lanczos_basis(torch.from_numpy(v0).cuda(), 9)
+    plan.destroy()
+    Vh = V.cpu().numpy()
+    print(key, "done", done, "alpha", alpha, "beta", beta)
+    assert done == 5
+    assert np.isfinite(alpha).all() and np.isfinite(beta).all() and np.isfinite(Vh).all()
+    assert (alpha[5:] == 0.0).all() and (beta[5:] == 0.0).all() and (Vh[5:] == 0.0).all()
+    assert beta[4] <= 1e-7 * max(np.abs(alpha[:5]).max(), beta[:4].max())
+    th, z = np.linalg.eigh(_tridiag(alpha[:5], beta[:5]))
+    assert np.abs(th - w[idx]).max() <= 1e-9, np.abs(th - w[idx]).max()
+    assert np.abs(norm2 * z[0] ** 2 - c ** 2).max() <= 1e-9, np.abs(norm2 * z[0] ** 2 - c ** 2).max()
+
+
+def test_zero_and_nan_start_vectors_and_refusals(mods, dense):
+    sbm, _, capi = mods
+    sb = dense["cfg1"][0]
+    plan = sbm.KronPlan(sb)
+    n = sb.n_states
+    for fill in (0.0, float("nan")):
+        v0 = torch.full((n,), fill, dtype=torch.float64, device="cuda")
+        V = torch.full((6, n), float("nan"), dtype=torch.float64, device="cuda")
+        norm2, alpha, beta, done, V = plan.lanczos_basis(v0, 6, V=V)
+        assert norm2 == 0.0 and done == 0 and (alpha == 0.0).all() and (beta == 0.0).all(), (fill, norm2, done, alpha, beta)
+        assert bool((V == 0.0).all()), fill
+    ok = torch.ones(n, dtype=torch.float64, device="cuda")
+    for bad in (0, -3):
+        with pytest.raises(capi.DmrgxError) as e:
+            plan.lanczos_basis(ok, bad)
+        assert e.value.code == ERR_ARG
+    for bad_tol in (-1.0, 1.0):
+        with pytest.raises(capi.DmrgxError) as e:
+            plan.lanczos_basis(ok, 4, breakdown_tol=bad_tol)
+        assert e.value.code == ERR_ARG
+    with pytest.raises(capi.DmrgxError) as e:                               # ldv < n_states
+        plan.lanczos_basis(ok, 4, V=torch.zeros((4, n - 1), dtype=torch.float64, device="cuda"))
+    assert e.value.code == ERR_ARG and "ldv" in str(e.value)
+    store = torch.ones(5 * n, dtype=torch.float64, device="cuda")
+    for first in (0, 3 * n + n // 2, 4 * n - 1):                            # v0 inside V: its first row, across two rows, its last element
+        with pytest.raises(capi.DmrgxError) as e:
+            plan.lanczos_basis(store[first:first + n], 4, V=store[:4 * n].view(4, n))
+        assert e.value.code == ERR_ARG and "overlaps" in str(e.value)
+    norm2, _, _, done, _ = plan.lanczos_basis(store[4 * n:], 4, V=store[:4 * n].view(4, n))      # right behind V: accepted
+    assert norm2 == float(n) and done >= 1
+    plan.destroy()
+    striped = sbm.KronPlan(sb, world_size=2, rank=0)
+    full = torch.ones(striped.info.vec_len, dtype=torch.float64, device="cuda")
+    with pytest.raises(capi.DmrgxError) as e:
+        striped.lanczos_basis(full, 4)
+    assert e.value.code == ERR_ARG and "striped" in str(e.value)
+    striped.destroy()
+
+
+POISONED_NODES = [
+    "tests/test_gpu_lanczos_basis.py::test_120_steps_where_the_plain_recursion_has_lost_orthogonality",
+    "tests/test_gpu_lanczos_basis.py::test_40_steps_other_superblocks",
+    "tests/test_gpu_lanczos_basis.py::test_exhausted_krylov_space_is_noticed",
+    "tests/test_gpu_lanczos_basis.py::test_planted_invariant_subspace_breaks_down_on_the_device",
+    "tests/test_gpu_lanczos_basis.py::test_zero_and_nan_start_vectors_and_refusals",
+]
+
+
+def test_this_file_on_poisoned_workspaces():
+    """The tests above, unchanged, in one child process with every f64 pool block handed out NaN-filled (DMRGX_POOL_POISON=1, as
+    test_gpu_poison.py starts its children): nothing is read before it is written."""
+    env = dict(os.environ, DMRGX_POOL_POISON="1")
+    python = [sys.executable] + (["-s"] if sys.flags.no_user_site else [])
+    p = subprocess.run(python + ["-m", "pytest", "-q", "-x", "-p", "no:cacheprovider", *POISONED_NODES], cwd=ROOT, env=env, capture_output=True, text=True, timeout=480)
+    tail = p.stdout[-3000:] + p.stderr[-2000:]
+    assert p.returncode == 0, tail
+    assert " passed" in tail and " failed" not in tail and " skipped" not in tail, tail
