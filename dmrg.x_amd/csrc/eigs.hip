@@ -701,6 +701,9 @@ extern "C" dmrgx_status dmrgx_eigs_lowest(dmrgx_kron_plan* plan, const dmrgx_eig
     const int64_t n = I.local_len, N = I.n_states;
     int m = opts->ncv > 0 ? opts->ncv : 16;
     m = (int)std::min<int64_t>(std::min(m, MAX_NCV), N);
+    // a one-vector Krylov space cannot restart (the restart keeps one Ritz vector and needs room for the residual direction: with m == 1
+    // every cycle after the first ran no MatMult and read the first cycle's beta again, max_it times): ncv = 1 is taken as 2.  N == 1 ends at m == N.
+    m = (int)std::max<int64_t>(m, std::min<int64_t>(2, N));
     if (m < 1) DMRGX_FAIL(DMRGX_ERR_ARG, "eigs_lowest: empty problem");
     const int max_it = opts->max_it > 0 ? opts->max_it : std::max<int>(100, (int)(2 * N / m));
     const double tol = opts->tol > 0 ? opts->tol : 1e-8;

@@ -241,7 +241,8 @@ dmrgx_status dmrgx_ggemm_groups(int32_t count, const dmrgx_ggemm_group* groups, 
 
 /* ---- K2: lowest eigenpair of the planned superblock Hamiltonian -------------------------------------- */
 typedef struct {
-    int32_t ncv;        /* Krylov subspace size (SLEPc default for nev=1: 16)                            */
+    int32_t ncv;        /* Krylov subspace size (0: SLEPc's default for nev=1, 16).  Method 0 uses at most 64 vectors and at
+                           least 2 (a one-vector space cannot restart: ncv = 1 is taken as 2), never more than n_states */
     int32_t max_it;     /* maximum number of restarts                                                    */
     double  tol;        /* converged when ||r|| <= tol * |theta|  (SLEPc default criterion, default 1e-8) */
     uint64_t seed;      /* start vector: counter-based uniform(-1,1) stream of this seed, unless ...      */

@@ -197,3 +197,145 @@ def ggemm_check(got, inst, what=""):
     bound = ggemm_bound(inst.S_abs, inst.n)
     err = np.abs(np.asarray(got, dtype=np.float64) - inst.R)
     return float(np.max(np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), 0.0))) if err.size else 0.0
+
+
+# ---- Krylov kernels: odd lengths, several workgroups, planted spectra (tests/test_krylov_inputs.py, tests/test_gpu_krylov_shapes.py) ----
+# kept-sector tables {Sz: states} (left, right) that give these state counts at Ly = 2 (12 terms, 4 KronBlocks)
+KRYLOV_KEPT = {845: ({1: 3, 0: 8, -1: 2}, {1: 29, 0: 17, -1: 10}),
+               1205: ({1: 35, 0: 2, -1: 6}, {1: 34, 0: 5, -1: 7}),
+               2049: ({1: 4, 0: 4, -1: 19}, {1: 18, 0: 27, -1: 38}),          # two 2048-element workgroups of the Lanczos run, the second of one element
+               4097: ({1: 3, 0: 35, -1: 26}, {1: 27, 0: 16, -1: 4})}          # three
+TINY_GAP_EPS = 5e-3                    # scale of the terms put back on the degenerate input: (w1 - w0) / (w_max - w0) = 1.04e-3
+
+
+def krylov_superblock(wl, n_states):
+    sb = wl.synthetic_superblock("cfg2", Ly=2, seed=7, kept=KRYLOV_KEPT[n_states])
+    assert sb.n_states == n_states and len(sb.terms) == 12 and len(sb.blocks) == 4
+    return sb
+
+
+def dense_hamiltonian(wl, sb):
+    """(H, eigenvalues, eigenvectors) of a superblock, H column by column through the numpy statement of the factored apply; read-only."""
+    H = np.stack([wl.apply_factored_numpy(sb, e) for e in np.eye(sb.n_states)], axis=1)
+    w, v = np.linalg.eigh(H)
+    for a in (H, w, v):
+        a.setflags(write=False)
+    return H, w, v
+
+
+def _planted_block_hamiltonians(wl, terms_scale):
+    """The 845-state layout with H_L and H_R replaced by Q diag(lambda) Q^T per sector (Q random orthogonal): lambda in [0, 4] except the
+    lowest of the sectors of KronBlocks 1 and 2, which are -2 + -1.5 and -1.25 + -2.25: both sums are -3.5 exactly, every other sum
+    lambda_L + lambda_R of a KronBlock is >= -2.25.  The terms are dropped (terms_scale None) or scaled."""
+    sb = krylov_superblock(wl, 845)
+    rng = np.random.default_rng(23)
+    (ia, ja), (ib, jb) = sb.blocks[1], sb.blocks[2]
+    low_left, low_right = {ia: -2.0, ib: -1.25}, {ja: -1.5, jb: -2.25}
+    for op, sizes, low in ((sb.h_left, sb.left_sizes, low_left), (sb.h_right, sb.right_sizes, low_right)):
+        for c in op.cells:
+            assert c.kind == CELL_DENSE and c.r0 == 0 and c.c0 == 0 and c.nr == c.nc == sizes[c.row_sector]
+            q, _ = np.linalg.qr(rng.standard_normal((c.nr, c.nr)))
+            lam = rng.uniform(0.0, 4.0, c.nr)
+            lam[0] = low.get(c.row_sector, 0.0)
+            a = (q * lam) @ q.T
+            c.array = np.ascontiguousarray((a + a.T) * 0.5)
+    sb.terms = [] if terms_scale is None else [(terms_scale * t[0],) + tuple(t[1:]) for t in sb.terms]
+    return sb
+
+
+def planted_superblock(wl, kind):
+    """'posdef': the 845-state input with c = |w_min| + 3 added to the diagonal of every cell of H_L, which shifts the whole spectrum by c:
+    the lowest eigenvalue is +3 and the eigenvalue of largest magnitude is at the top.  'degenerate': no terms, block Hamiltonians with
+    planted spectra, a twofold ground state at -3.5 with the third eigenvalue 1.25 above.  'tinygap': the same with the terms put back,
+    scaled by TINY_GAP_EPS, which splits the pair by 1e-3 of the spectrum's width."""
+    if kind == "posdef":
+        sb = krylov_superblock(wl, 845)
+        w_min = dense_hamiltonian(wl, sb)[1][0]
+        for c in sb.h_left.cells:
+            assert c.kind == CELL_DENSE and c.nr == c.nc
+            c.array = np.ascontiguousarray(c.array + (abs(w_min) + 3.0) * np.eye(c.nr))
+        return sb
+    return _planted_block_hamiltonians(wl, {"degenerate": None, "tinygap": TINY_GAP_EPS}[kind])
+
+
+_KRYLOV_INPUTS = {}
+
+
+def krylov_input(wl, key):
+    """(superblock, dense H, eigenvalues, eigenvectors) of the dense-size inputs, built once per process and read-only: 845, 1205 (odd state
+    counts), 'cfg2' (the even 844-state superblock of the Lanczos tests) and the three planted spectra."""
+    if key not in _KRYLOV_INPUTS:
+        if key == "cfg2":
+            sb = wl.synthetic_superblock("cfg2", m=32, Ly=3, seed=3)
+        else:
+            sb = krylov_superblock(wl, key) if isinstance(key, int) else planted_superblock(wl, key)
+        _KRYLOV_INPUTS[key] = (sb,) + dense_hamiltonian(wl, sb)
+    return _KRYLOV_INPUTS[key]
+
+
+class FactoredH:
+    """The superblock Hamiltonian as an operator for the sizes at which nobody wants it dense: H @ x for a vector, H @ X for the columns of X."""
+
+    def __init__(self, wl, sb):
+        self.wl, self.sb, self.shape = wl, sb, (sb.n_states, sb.n_states)
+
+    def __matmul__(self, x):
+        x = np.asarray(x)
+        if x.ndim == 1:
+            return self.wl.apply_factored_numpy(self.sb, x)
+        return np.stack([self.wl.apply_factored_numpy(self.sb, np.ascontiguousarray(c)) for c in x.T], axis=1)
+
+
+def lanczos_reorth(H, v0, K):
+    """Lanczos with full reorthogonalisation (twice) against every earlier vector.  H: anything with H @ vector."""
+    Q = [v0 / np.linalg.norm(v0)]
+    alpha, beta = [], []
+    for j in range(K):
+        x = H @ Q[j] - (beta[j - 1] * Q[j - 1] if j else 0.0)
+        alpha.append(Q[j] @ x)
+        x = x - alpha[j] * Q[j]
+        for _ in range(2):
+            for q in Q:
+                x = x - (q @ x) * q
+        beta.append(np.linalg.norm(x))
+        Q.append(x / beta[j])
+    return v0 @ v0, np.array(alpha), np.array(beta)
+
+
+def lanczos_tridiag(alpha, beta):
+    K = len(alpha)
+    return np.diag(alpha) + np.diag(beta[:K - 1], 1) + np.diag(beta[:K - 1], -1)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint64)
+
+
+def lanczos_basis_invariants(plan, H, v0, K, V=None, ref=None):
+    """One dmrgx_kron_lanczos_basis run, twice: coefficients against numpy to 1e-10 max |alpha|, V V^T = 1 to 1e-12 and V H V^T = T to
+    1e-12 |H|, the same bits from both runs, v0 untouched.  H: the dense matrix, or a FactoredH -- then |H| is the largest |Ritz value|
+    of the numpy reference's own T, a lower bound of |H|.  ref: lanczos_reorth(H, v0, K) where the caller has it already.  The second run
+    goes into a new contiguous V, whatever the layout of the first.  Returns (norm2, alpha, beta) of the device."""
+    import torch
+    n = H.shape[0]
+    n2, a, b = ref if ref is not None else lanczos_reorth(H, v0, K)
+    normH = np.linalg.norm(H, 2) if isinstance(H, np.ndarray) else np.abs(np.linalg.eigvalsh(lanczos_tridiag(a, b))).max()
+    v0d = torch.from_numpy(v0).cuda()
+    norm2, alpha, beta, done, Vd = plan.lanczos_basis(v0d, K, V=V)
+    Vh = Vd.cpu().numpy()[:, :n].copy()
+    norm2b, alphab, betab, doneb, Vb = plan.lanczos_basis(v0d, K)
+    Vhb = Vb.cpu().numpy()
+    tol = 1e-10 * np.abs(a).max()
+    T = lanczos_tridiag(alpha, beta)
+    orth, galerkin = np.abs(Vh @ Vh.T - np.eye(K)).max(), np.abs(Vh @ (H @ Vh.T) - T).max()
+    print("n", n, "K", K, "norm2 err", abs(norm2 - n2), "alpha err", np.abs(alpha - a).max(), "beta err", np.abs(beta[:K - 1] - b[:K - 1]).max(), "tol", tol,
+          "|VV^T - 1|", orth, "|VHV^T - T|", galerkin, "|H|", normH)
+    assert done == K and np.isfinite(alpha).all() and np.isfinite(beta).all() and np.isfinite(Vh).all()
+    assert abs(norm2 - n2) <= tol
+    assert np.abs(alpha - a).max() <= tol and np.abs(beta[:K - 1] - b[:K - 1]).max() <= tol
+    assert orth <= 1e-12
+    assert galerkin <= 1e-12 * normH
+    assert norm2 == norm2b and done == doneb
+    assert np.array_equal(_bits(alpha), _bits(alphab)) and np.array_equal(_bits(beta), _bits(betab)) and np.array_equal(_bits(Vh), _bits(Vhb))
+    assert np.array_equal(_bits(v0d.cpu().numpy()), _bits(v0))
+    return norm2, alpha, beta

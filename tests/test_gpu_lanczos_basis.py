@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import lanczos_basis_invariants, lanczos_tridiag as _tridiag
 from test_gpu_lanczos_coeffs import CASES, ERR_ARG, _lanczos_reorth
 
 pytestmark = pytest.mark.gpu
@@ -54,37 +55,9 @@ def _lanczos_plain(H, v0, K):
     return np.array(alpha), np.array(beta)
 
 
-def _tridiag(alpha, beta):
-    K = len(alpha)
-    return np.diag(alpha) + np.diag(beta[:K - 1], 1) + np.diag(beta[:K - 1], -1)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
 def _invariants(plan, sb, H, v0, K, V=None):
     """One run, twice: coefficients against numpy, V V^T = 1 and V H V^T = T to 1e-12, repeatability, v0 untouched."""
-    n2, a, b = _lanczos_reorth(H, v0, K)
-    normH = np.linalg.norm(H, 2)
-    v0d = torch.from_numpy(v0).cuda()
-    norm2, alpha, beta, done, Vd = plan.lanczos_basis(v0d, K, V=V)
-    Vh = Vd.cpu().numpy()[:, :sb.n_states].copy()
-    norm2b, alphab, betab, doneb, Vb = plan.lanczos_basis(v0d, K)
-    Vhb = Vb.cpu().numpy()
-    tol = 1e-10 * np.abs(a).max()
-    T = _tridiag(alpha, beta)
-    orth, galerkin = np.abs(Vh @ Vh.T - np.eye(K)).max(), np.abs(Vh @ H @ Vh.T - T).max()
-    print("n", sb.n_states, "K", K, "norm2 err", abs(norm2 - n2), "alpha err", np.abs(alpha - a).max(), "beta err", np.abs(beta[:K - 1] - b[:K - 1]).max(), "tol", tol,
-          "|VV^T - 1|", orth, "|VHV^T - T|", galerkin, "|H|", normH)
-    assert done == K and np.isfinite(alpha).all() and np.isfinite(beta).all() and np.isfinite(Vh).all()
-    assert abs(norm2 - n2) <= tol
-    assert np.abs(alpha - a).max() <= tol and np.abs(beta[:K - 1] - b[:K - 1]).max() <= tol
-    assert orth <= 1e-12
-    assert galerkin <= 1e-12 * normH
-    assert norm2 == norm2b and done == doneb
-    assert np.array_equal(_bits(alpha), _bits(alphab)) and np.array_equal(_bits(beta), _bits(betab)) and np.array_equal(_bits(Vh), _bits(Vhb))
-    assert np.array_equal(_bits(v0d.cpu().numpy()), _bits(v0))
+    _, alpha, beta = lanczos_basis_invariants(plan, H, v0, K, V=V)
     return alpha, beta
 
 

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import lanczos_reorth as _lanczos_reorth
+
 pytestmark = pytest.mark.gpu
 ERR_ARG = 62
 CASES = {"cfg2": dict(name="cfg2", m=32, Ly=3, seed=3), "cfg1": dict(name="cfg1", m=12, Ly=1, seed=4), "cfg5": dict(name="cfg5", m=40, Ly=2, seed=5)}
@@ -31,22 +33,6 @@ def dense(mods):
             a.setflags(write=False)
         out[key] = (sb, H, w, v)
     return out
-
-
-def _lanczos_reorth(H, v0, K):
-    """Lanczos with full reorthogonalisation (twice) against every earlier vector."""
-    Q = [v0 / np.linalg.norm(v0)]
-    alpha, beta = [], []
-    for j in range(K):
-        x = H @ Q[j] - (beta[j - 1] * Q[j - 1] if j else 0.0)
-        alpha.append(Q[j] @ x)
-        x = x - alpha[j] * Q[j]
-        for _ in range(2):
-            for q in Q:
-                x = x - (q @ x) * q
-        beta.append(np.linalg.norm(x))
-        Q.append(x / beta[j])
-    return v0 @ v0, np.array(alpha), np.array(beta)
 
 
 @pytest.mark.parametrize("key", list(CASES))
