@@ -13,6 +13,7 @@
 // is enqueued without looking at the device; one copy and one synchronisation at the end bring the coefficients back.  Fixed grids and
 // fixed-order sums of block partials, no atomics: two runs give the same bits.
 // dmrgx_kron_lanczos_basis, further down, is the same run with the basis kept and fully reorthogonalised.
+// dmrgx_kron_chebyshev_moments, after it, is the Chebyshev recursion in the same idiom: moments in place of coefficients, no normalisation.
 #include "common.h"
 #include <cmath>
 
@@ -268,10 +269,189 @@ __global__ void __launch_bounds__(LZ_THREADS) lb_zero_uncounted_row_kernel(doubl
     for (int64_t e = (int64_t)blockIdx.x * LZ_THREADS + threadIdx.x; e < n; e += (int64_t)gridDim.x * LZ_THREADS) row[e] = 0.0;
 }
 
+
+// ---- Chebyshev moments (dmrgx_kron_chebyshev_moments) ---------------------------------------------------------------------------------
+// t_0 = v0, t_1 = Ht t_0, t_{n+1} = 2 Ht t_n - t_{n-1} with Ht = (H - centre) / half_width: no normalisation, no reorthogonalisation, two
+// earlier vectors.  Per step
+//   MatMult        : w = H x                                   (x = t_n and w are two fixed pool vectors)
+//   step           : t_{n+1} = s (w - centre x) - t_{n-1}, s = 2 / half_width (1 / half_width and no t_{n-1} for t_1), into ring row
+//                    (n + 1) % 32 and into x; partial sums of t_{n+1} . t_{n+1} and t_{n+1} . t_n     (reads 3 vectors, writes 2)
+//   scalars        : the partials added in block order, the guard, mu_{2n+1} and mu_{2n+2}
+// and once per 16 vectors one dmrgx_vec_gram of U against the 16 ring rows just completed.  The scalars and all moments live in one
+// device array that is copied back once at the end.
+constexpr int CB_RING = 32, CB_BLOCK = 16;
+constexpr double CB_GUARD = 1.0 + 1e-6;
+// S[CB_VALID] = number of valid vectors t_0 .. t_{valid-1} (0: v0 itself was refused); S[CB_MOM + m] = mu_diag[m], then the cross moments
+enum : int { CB_NORM2 = 0, CB_DEAD = 1, CB_VALID = 2, CB_MU1 = 3, CB_MOM = 4 };
+
+// x = row = v0, or exact zeros when v0 was refused.  (v0 is the caller's: 8-byte loads)
+__global__ void __launch_bounds__(LZ_THREADS) cb_start_kernel(const double* __restrict__ v0, double* __restrict__ row, double* __restrict__ x, int64_t n, const double* __restrict__ S)
+{
+    const bool dead = S[CB_DEAD] != 0.0;
+    for (int64_t e = (int64_t)blockIdx.x * LZ_THREADS + threadIdx.x; e < n; e += (int64_t)gridDim.x * LZ_THREADS) {
+        const double v = dead ? 0.0 : v0[e];
+        row[e] = v;
+        x[e] = v;
+    }
+}
+
+// One step of the recursion over the workgroup's LB_RANGE contiguous elements (the last range is ragged: nothing at or past n is read or
+// written).  FIRST: t_1 = (w - centre x) / half_width, the row of t_{-1} does not exist and is not read.  x, w, prev and next are 16-byte
+// aligned (pool blocks; ring rows with an even leading dimension).  partial[b] = t_{n+1} . t_{n+1}, partial[gridDim.x + b] = t_{n+1} . t_n
+// over block b.  Once the run is dead: zeros into next and x, whatever w and prev hold.
+template <bool FIRST> __global__ void __launch_bounds__(LZ_THREADS) cb_step_kernel(const double* __restrict__ w, double* __restrict__ x, const double* __restrict__ prev,
+                                                                                  double* __restrict__ next, int64_t n, double centre, double scale,
+                                                                                  const double* __restrict__ S, double* __restrict__ partial)
+{
+    const bool dead = S[CB_DEAD] != 0.0;
+    const int64_t base = (int64_t)blockIdx.x * LB_RANGE + 2 * threadIdx.x;
+    double2 t[LB_PER / 2], c[LB_PER / 2];
+#pragma unroll
+    for (int i = 0; i < LB_PER / 2; ++i) { t[i] = double2{0.0, 0.0}; c[i] = double2{0.0, 0.0}; }
+    if (!dead) {
+        double2 wr[LB_PER / 2], pr[LB_PER / 2];
+#pragma unroll
+        for (int i = 0; i < LB_PER / 2; ++i) {
+            const int64_t e = base + (int64_t)i * 2 * LZ_THREADS;
+            wr[i] = lb_load2<true>(w, e, n);
+            c[i] = lb_load2<true>(x, e, n);
+            if (!FIRST) pr[i] = lb_load2<true>(prev, e, n);
+        }
+#pragma unroll
+        for (int i = 0; i < LB_PER / 2; ++i) {
+            t[i].x = scale * (wr[i].x - centre * c[i].x);
+            t[i].y = scale * (wr[i].y - centre * c[i].y);
+            if (!FIRST) { t[i].x -= pr[i].x; t[i].y -= pr[i].y; }
+        }
+    }
+    double tt = 0.0, tc = 0.0;
+#pragma unroll
+    for (int i = 0; i < LB_PER / 2; ++i) {
+        const int64_t e = base + (int64_t)i * 2 * LZ_THREADS;
+        if (e + 1 < n) { *reinterpret_cast<double2*>(next + e) = t[i]; *reinterpret_cast<double2*>(x + e) = t[i]; }
+        else if (e < n) { next[e] = t[i].x; x[e] = t[i].x; }
+        tt += t[i].x * t[i].x; tt += t[i].y * t[i].y;            // (beyond n the registers hold zeros)
+        tc += t[i].x * c[i].x; tc += t[i].y * c[i].y;
+    }
+    tt = lz_block_sum(tt);
+    __syncthreads();                                             // lz_block_sum's LDS is used again
+    tc = lz_block_sum(tc);
+    if (threadIdx.x == 0) { partial[blockIdx.x] = tt; partial[gridDim.x + blockIdx.x] = tc; }
+}
+
+// One workgroup.  stage 0 (start): partial = the blocks' sums of v0^2; mu_0 = norm2, or the run is dead with no valid vector.
+// stage 1 (step n, which made t_{n+1}): both sums in block order; the guard -- |t_{n+1}|^2 not finite or above (1 + 1e-6) mu_0, or a
+// cross sum that is not finite -- ends the run with t_n the last valid vector; else mu_{2n+1} = 2 t_{n+1}.t_n - mu_1 (n = 0: mu_1 itself)
+// and mu_{2n+2} = 2 t_{n+1}.t_{n+1} - mu_0.  The moments of a dead run stay the zeros the array was filled with.
+__global__ void __launch_bounds__(LZ_THREADS) cb_scalar_kernel(const double* __restrict__ partial, int nblk, double* __restrict__ S, int stage, int n)
+{
+    double a = 0.0, b = 0.0;
+    for (int k = threadIdx.x; k < nblk; k += LZ_THREADS) { a += partial[k]; if (stage) b += partial[nblk + k]; }
+    a = lz_block_sum(a);
+    __syncthreads();
+    b = lz_block_sum(b);
+    if (threadIdx.x != 0) return;
+    if (stage == 0) {
+        const bool ok = a > 0.0 && a < INFINITY;
+        S[CB_NORM2] = ok ? a : 0.0;
+        S[CB_DEAD] = ok ? 0.0 : 1.0;
+        S[CB_VALID] = ok ? 1.0 : 0.0;
+        S[CB_MOM] = ok ? a : 0.0;
+        return;
+    }
+    if (S[CB_DEAD] != 0.0) return;
+    const double mu0 = S[CB_NORM2];
+    if (!(a >= 0.0 && a <= CB_GUARD * mu0) || !(fabs(b) < INFINITY)) { S[CB_DEAD] = 1.0; return; }
+    const double mu1 = n ? S[CB_MU1] : b;
+    if (n == 0) S[CB_MU1] = b;
+    S[CB_VALID] = (double)(n + 2);
+    S[CB_MOM + 2 * n + 1] = 2.0 * b - mu1;
+    S[CB_MOM + 2 * n + 2] = 2.0 * a - mu0;
+}
+
+// Before the Gram call of the ring rows that hold t_{n0} .. t_{n0 + rows - 1}: the rows of vectors that are not valid -- the one the guard
+// refused, and a refused v0 -- become exact zeros.  blockIdx.y: the row.  A run that is alive returns at once.
+__global__ void __launch_bounds__(LZ_THREADS) cb_zero_invalid_rows_kernel(double* __restrict__ rows, int64_t ldr, int64_t n, int n0, const double* __restrict__ S)
+{
+    if (S[CB_DEAD] == 0.0 || n0 + (int)blockIdx.y < (int)S[CB_VALID]) return;
+    double* __restrict__ row = rows + (int64_t)blockIdx.y * ldr;
+    for (int64_t e = (int64_t)blockIdx.x * LZ_THREADS + threadIdx.x; e < n; e += (int64_t)gridDim.x * LZ_THREADS) row[e] = 0.0;
+}
+
 }  // namespace
 }  // namespace dmrgx
 
 using namespace dmrgx;
+
+extern "C" dmrgx_status dmrgx_kron_chebyshev_moments(dmrgx_kron_plan* plan, const double* v0_dev, double centre, double half_width, int32_t nsteps,
+                                                     int32_t nu, const double* U_dev, int64_t ldu, double* norm2, double* mu_diag, double* mu_cross,
+                                                     int32_t* nsteps_done, void* stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (!plan || !v0_dev || !norm2 || !mu_diag || !nsteps_done || (nu > 0 && !mu_cross)) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_chebyshev_moments: null argument");
+    if (nsteps < 1) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_chebyshev_moments: nsteps %d, at least one step is needed", nsteps);
+    if (!(half_width > 0.0 && half_width < INFINITY) || !(fabs(centre) < INFINITY))
+        DMRGX_FAIL(DMRGX_ERR_ARG, "kron_chebyshev_moments: window centre %g, half width %g: a finite centre and a positive finite half width are needed", centre, half_width);
+    if (nu < 0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_chebyshev_moments: nu %d is negative", nu);
+    dmrgx_kron_info I;
+    DMRGX_CHK(dmrgx_kron_plan_info(plan, &I));
+    if (I.vec_len != I.n_states || I.local_len != I.n_states)
+        DMRGX_FAIL(DMRGX_ERR_ARG, "kron_chebyshev_moments: the plan is striped over ranks (world_size > 1): the recursion has no collectives");
+    const int64_t n = I.n_states;
+    if (nu > 0 && (!U_dev || ldu < n)) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_chebyshev_moments: U is null or ldu %lld is smaller than n_states %lld", (long long)ldu, (long long)n);
+    const int64_t K = nsteps, ldr = (n + 1) & ~(int64_t)1;      // ring rows 16-byte aligned
+    const int nblk = (int)std::max<int64_t>(1, (n + LB_RANGE - 1) / LB_RANGE);
+    const size_t ndiag = (size_t)(2 * K + 1), nscal = (size_t)CB_MOM + ndiag + (size_t)(K + 1) * (size_t)nu;
+
+    DevBuf dX, dW, dRing, dPartial, dS;
+    DMRGX_CHK(dX.alloc_f64((size_t)n, st));
+    DMRGX_CHK(dW.alloc_f64((size_t)n, st));
+    DMRGX_CHK(dRing.alloc_f64((size_t)CB_RING * (size_t)ldr, st));
+    DMRGX_CHK(dPartial.alloc_f64((size_t)std::max(LZ_BLOCKS, 2 * nblk), st));
+    DMRGX_CHK(dS.alloc(nscal * sizeof(double)));
+    DMRGX_HIP(zero_async(dS.p, dS.bytes, st));
+    double* S = dS.as<double>();
+    double* P = dPartial.as<double>();
+    double* x = dX.as<double>();
+    double* w = dW.as<double>();
+    double* ring = dRing.as<double>();
+    double* cross = S + CB_MOM + ndiag;                          // [nu][K + 1] on the device: a Gram call writes 16 columns of it
+
+    // the cross moments of t_{n0} .. t_{n0 + rows - 1}, which fill one block of 16 ring rows from its first row on
+    auto gram_block = [&](int64_t n0, int rows) -> dmrgx_status {
+        double* first = ring + (n0 % CB_RING) * ldr;
+        hipLaunchKernelGGL(cb_zero_invalid_rows_kernel, dim3((unsigned)std::min(nblk, LZ_BLOCKS), (unsigned)rows), dim3(LZ_THREADS), 0, st, first, ldr, n, (int)n0, (const double*)S);
+        DMRGX_HIP(hipGetLastError());
+        if (nu > 0) DMRGX_CHK(dmrgx_vec_gram(nu, rows, n, U_dev, ldu, first, ldr, cross + n0, K + 1, 0, nullptr, st));
+        return DMRGX_OK;
+    };
+
+    hipLaunchKernelGGL(lz_norm2_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, v0_dev, n, P);
+    hipLaunchKernelGGL(cb_scalar_kernel, dim3(1), dim3(LZ_THREADS), 0, st, (const double*)P, LZ_BLOCKS, S, 0, 0);
+    hipLaunchKernelGGL(cb_start_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, v0_dev, ring, x, n, (const double*)S);
+    DMRGX_HIP(hipGetLastError());
+    for (int64_t j = 0; j < K; ++j) {                            // step j: t_{j+1} from x = t_j and ring row of t_{j-1}
+        double* next = ring + ((j + 1) % CB_RING) * ldr;
+        DMRGX_CHK(dmrgx_kron_apply(plan, x, w, st));
+        if (j == 0) hipLaunchKernelGGL(cb_step_kernel<true>, dim3(nblk), dim3(LZ_THREADS), 0, st, (const double*)w, x, (const double*)nullptr, next, n, centre, 1.0 / half_width, (const double*)S, P);
+        else hipLaunchKernelGGL(cb_step_kernel<false>, dim3(nblk), dim3(LZ_THREADS), 0, st, (const double*)w, x, (const double*)(ring + ((j - 1) % CB_RING) * ldr), next, n, centre, 2.0 / half_width, (const double*)S, P);
+        hipLaunchKernelGGL(cb_scalar_kernel, dim3(1), dim3(LZ_THREADS), 0, st, (const double*)P, nblk, S, 1, (int)j);
+        DMRGX_HIP(hipGetLastError());
+        if ((j + 2) % CB_BLOCK == 0) DMRGX_CHK(gram_block(j + 2 - CB_BLOCK, CB_BLOCK));      // t_{j+1} completes a block of 16
+    }
+    if ((K + 1) % CB_BLOCK) DMRGX_CHK(gram_block((K + 1) / CB_BLOCK * CB_BLOCK, (int)((K + 1) % CB_BLOCK)));
+    std::vector<double> host(nscal);
+    DMRGX_HIP(hipMemcpyAsync(host.data(), S, nscal * sizeof(double), hipMemcpyDeviceToHost, st));
+    DMRGX_HIP(hipStreamSynchronize(st));
+    const int64_t valid = (int64_t)host[CB_VALID], D = std::max<int64_t>(valid - 1, 0);
+    *norm2 = host[CB_NORM2];
+    *nsteps_done = (int32_t)D;
+    for (int64_t m = 0; m <= 2 * K; ++m) mu_diag[m] = host[CB_MOM + m];
+    const double* hc = host.data() + CB_MOM + ndiag;
+    for (int64_t r = 0; r <= K; ++r)
+        for (int32_t i = 0; i < nu; ++i) mu_cross[r * nu + i] = hc[(int64_t)i * (K + 1) + r];
+    return DMRGX_OK;
+}
 
 extern "C" dmrgx_status dmrgx_kron_lanczos_coeffs(dmrgx_kron_plan* plan, const double* v0_dev, int32_t nsteps, double breakdown_tol,
                                                   double* norm2, double* alpha, double* beta, int32_t* nsteps_done, void* stream)

@@ -30,7 +30,9 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <memory>
 #include <mutex>
+#include <random>
 #include <thread>
 #include "DMRGKron.hpp"
 #include "CorrelatorDealing.hpp"
@@ -228,6 +230,35 @@ public:
             if (dsf_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_steps must be at least 1. Got %lld.", LLD(dsf_steps));
             ierr = PetscOptionsGetReal(NULL, NULL, "-dsf_breakdown_tol", &dsf_breakdown_tol, NULL); CHKERRQ(ierr);
             if (!(dsf_breakdown_tol >= 0.0) || dsf_breakdown_tol >= 1.0) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_breakdown_tol must lie in [0, 1). Got %g.", dsf_breakdown_tol);
+        }
+        {   /* -dsf_cheb c0,c1,...: the Chebyshev moments of G_ic(w) from every listed site c (CalculateChebyshevCorrelations) */
+            PetscBool have_sites = PETSC_FALSE;
+            PetscInt nc = 4096;
+            dsf_cheb_sites.assign((size_t)nc, 0);
+            ierr = PetscOptionsGetIntArray(NULL, NULL, "-dsf_cheb", dsf_cheb_sites.data(), &nc, &have_sites); CHKERRQ(ierr);
+            dsf_cheb_sites.resize(have_sites ? (size_t)nc : 0);
+            use_dsf_cheb = (have_sites && nc > 0) ? PETSC_TRUE : PETSC_FALSE;
+        }
+        if (use_dsf_cheb) {
+            if (mpi_size > 1) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-dsf_cheb is not available on more than one rank (got %d): the Chebyshev recursion has no collectives.", (int)mpi_size);
+            for (PetscInt c : dsf_cheb_sites) if (c < 0 || c >= num_sites) SETERRQ2(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cheb: site %lld is outside [0, %lld), the lattice sites in the numbering of To1D.", LLD(c), LLD(num_sites));
+            ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_cheb_steps", &dsf_cheb_steps, NULL); CHKERRQ(ierr);
+            if (dsf_cheb_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cheb_steps must be at least 1. Got %lld.", LLD(dsf_cheb_steps));
+            ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_cheb_bound_steps", &dsf_cheb_bound_steps, NULL); CHKERRQ(ierr);
+            if (dsf_cheb_bound_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cheb_bound_steps must be at least 1. Got %lld.", LLD(dsf_cheb_bound_steps));
+            PetscInt nw = 2;
+            ierr = PetscOptionsGetRealArray(NULL, NULL, "-dsf_cheb_window", dsf_cheb_window, &nw, &dsf_cheb_have_window); CHKERRQ(ierr);
+            if (dsf_cheb_have_window && !(nw == 2 && dsf_cheb_window[0] < dsf_cheb_window[1] && std::isfinite(dsf_cheb_window[0]) && std::isfinite(dsf_cheb_window[1])))
+                SETERRQ1(mpi_comm, PETSC_ERR_ARG_WRONG, "-dsf_cheb_window needs lo,hi: two finite energies, lo < hi. Got %lld numbers.", LLD(nw));
+            PetscInt no = 3;
+            PetscReal om[3] = {0.0, 0.0, 0.0};
+            ierr = PetscOptionsGetRealArray(NULL, NULL, "-dsf_cheb_omega", om, &no, &dsf_cheb_have_omega); CHKERRQ(ierr);
+            if (dsf_cheb_have_omega) {
+                if (!(no == 3 && std::isfinite(om[0]) && std::isfinite(om[1]) && om[0] <= om[1] && om[2] >= 1.0 && om[2] <= 1e6 && om[2] == std::floor(om[2]) && (om[2] > 1.0 || om[0] == om[1])))
+                    SETERRQ1(mpi_comm, PETSC_ERR_ARG_WRONG, "-dsf_cheb_omega needs w0,w1,nw: nw >= 1 frequencies from w0 to w1 (nw = 1: w0 = w1). Got %lld numbers.", LLD(no));
+                dsf_cheb_omega.resize((size_t)om[2]);
+                for (size_t k = 0; k < dsf_cheb_omega.size(); ++k) dsf_cheb_omega[k] = dsf_cheb_omega.size() > 1 ? om[0] + (om[1] - om[0]) * (double)k / (double)(dsf_cheb_omega.size() - 1) : om[0];
+            }
         }
         ierr = PetscOptionsGetBool(NULL, NULL, "-step_profile", &step_profile, NULL); CHKERRQ(ierr);
 
@@ -476,7 +507,7 @@ public:
         spectra_writer.Drain();
         if (fp_entanglement) { fprintf(fp_entanglement, "\n]\n"); fclose(fp_entanglement); fp_entanglement = NULL; }
         if (fp_kron) { fprintf(fp_kron, "\n]\n"); fclose(fp_kron); fp_kron = NULL; }
-        spin_file.Close(); dimer_file.Close(); dsf_file.Close(); dsf_sites_file.Close();
+        spin_file.Close(); dimer_file.Close(); dsf_file.Close(); dsf_sites_file.Close(); dsf_cheb_file.Close();
         if (fp_corr) {
             if (!corr_headers_printed) { PetscErrorCode e2 = PrintCorrelationHeaders(); CHKERRQ(e2); }
             fprintf(fp_corr, "\n  ]\n}\n"); fclose(fp_corr); fp_corr = NULL;
@@ -605,6 +636,7 @@ public:
         step.GSEnergy = gse_r;
         if (use_dsf && do_measurements) { ierr = CalculateDynamicalStructureFactor(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* needs the plan */
         if (use_dsf_sites && do_measurements) { ierr = CalculateDynamicalCorrelations(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
+        if (use_dsf_cheb && do_measurements) { ierr = CalculateChebyshevCorrelations(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
         ierr = MatDestroy_KronSumShell(&H); CHKERRQ(ierr);
         ierr = MatDestroy(&H); CHKERRQ(ierr);
         ierr = PetscTime(&tdiag); CHKERRQ(ierr);
@@ -1646,6 +1678,138 @@ public:
         return 0;
     }
 
+    /** -dsf_cheb c0,c1,... (engine extension): the Chebyshev moments of the real-space dynamical correlations of the ground state,
+            mu_n^{ic} = < Sz_i psi , T_n(Ht) Sz_c psi > / <psi|psi>,   Ht = (H - Centre) / HalfWidth,   for ALL sites i,
+        from one dmrgx_kron_chebyshev_moments run per reference site c: the three-term recursion t_{n+1} = 2 Ht t_n - t_{n-1} needs two
+        earlier vectors, no kept basis and no reorthogonalisation, so its cost is linear in the number of moments where -dsf_sites
+        grows with the square.  The images u_i = Sz_i psi of all N sites (dmrgx_kron_term_apply, in lattice order) stay on the device for
+        the whole measurement -- N x N_sb doubles, refused with PETSC_ERR_MEM if they do not fit --; row c is the start vector of run
+        c, and the library takes <u_i, t_n> of all i with one Gram call per 16 vectors.
+        The window must contain the spectrum of the superblock Hamiltonian.  Unless -dsf_cheb_window lo,hi gives it, it is found once
+        per measurement: -dsf_cheb_bound_steps Lanczos steps (dmrgx_kron_lanczos_coeffs) from a fixed pseudo-random vector give the top
+        Ritz value and its residual bound, E0 is the bottom (ChebyshevWindow, Measurements.hpp).  Should the window fail to hold, the
+        library's guard ends the run: StepsDone < Steps in the record and a warning here, not an error.
+        Moments (N x (D + 1), lattice numbering), their lattice Fourier transform MomentsQ[q][n] = sum_i cos(q . (r_i - r_c))
+        Moments[i][n] (row nx Ly + ny) and Diag[m] = mu_m^{cc}, m <= 2D (the doubling identities), D = StepsDone.  With -dsf_cheb_omega
+        w0,w1,nw also SqwGrid[q][k] = ChebyshevJackson(MomentsQ[q], D + 1, x_k) / HalfWidth at x_k = (w_k + E0 - Centre) / HalfWidth:
+        (1/N) sum_c SqwGrid is the Jackson-broadened S^zz(q, w), non-negative and free of ghosts; its resolution is about
+        pi HalfWidth / (D + 1).  The caveats of -dsf_sites (one site is an estimator; bases optimised for the ground state) apply.
+        Site s of the right block is lattice site N - 1 - s.  One rank only (refused at start-up otherwise). */
+    PetscErrorCode CalculateChebyshevCorrelations(KronBlocks_t& KronBlocks, const Vec& gsv_r, Mat& H, PetscScalar E0)
+    {
+        PetscLogDouble t0, t1;
+        PetscTime(&t0);
+        dmrgx_host::CentreFrame F;
+        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, "Chebyshev correlations"); CHKERRQ(ierr);
+        const PetscInt nls = F.nsites[0], N = F.N, Lx = Ham.Lx(), Ly = Ham.Ly(), M = Lx * Ly, K = dsf_cheb_steps;
+        dmrgx_host::SiteOperators T(F);
+        std::vector<PetscInt> site, op_of((size_t)N, -1), rx((size_t)N), ry((size_t)N);      /* site[a]: lattice site of operator a; op_of: its inverse */
+        ierr = T.AllSites(OpSz, site); CHKERRQ(ierr);
+        for (PetscInt a = 0; a < N; ++a) op_of[(size_t)site[(size_t)a]] = a;
+        for (PetscInt s = 0; s < N; ++s) {
+            if (op_of[(size_t)s] < 0) SETERRQ1(mpi_comm, 1, "Chebyshev correlations: site %lld is in neither block.", LLD(s));
+            ierr = Ham.To2D(s, rx[(size_t)s], ry[(size_t)s]); CHKERRQ(ierr);
+        }
+        auto term_of = [&](PetscInt a) { return a < nls ? dmrgx_term{1.0, (int32_t)a, -1} : dmrgx_term{1.0, -1, (int32_t)(a - nls)}; };
+        const int64_t n = gsv_r->n, ld = n + (n & 1);
+        const double* psi = gsv_r->buf->dev_ro();
+        double norm = 0.0;
+        if (dmrgx_dot(n, psi, psi, &norm, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
+        /* the images of all sites, row s = Sz_s psi, built in chunks of at most 1 GiB (the intermediates of a term_apply grow with its vectors) */
+        std::unique_ptr<dmrgx_host::DevBuffer> U;
+        try { U.reset(new dmrgx_host::DevBuffer((size_t)(N * ld), dmrgx_host::DevBuffer::device_only_t{})); }
+        catch (const std::exception& e) { SETERRQ3(mpi_comm, PETSC_ERR_MEM, "Chebyshev correlations: no memory for the images of %lld sites x %lld states (%.3f GB): %s", LLD(N), LLD(n), (double)(N * ld) * 8e-9, e.what()); }
+        const PetscInt chunk = std::max<PetscInt>(1, std::min<PetscInt>(N, (PetscInt)((((int64_t)1 << 30) / (int64_t)sizeof(double)) / ld)));
+        std::vector<dmrgx_term> terms;
+        std::vector<int32_t> vec_first;
+        for (PetscInt s0 = 0; s0 < N; s0 += chunk) {
+            const PetscInt cnt = std::min<PetscInt>(chunk, N - s0);
+            terms.clear(); vec_first.assign(1, 0);
+            for (PetscInt s = s0; s < s0 + cnt; ++s) { terms.push_back(term_of(op_of[(size_t)s])); vec_first.push_back((int32_t)terms.size()); }
+            if (dmrgx_kron_term_apply(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
+                                      (int32_t)cnt, vec_first.data(), terms.data(), U->dev_uninitialised() + s0 * ld, ld, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_apply: %s", dmrgx_last_error());
+        }
+
+        /* the window */
+        PetscInt matmults = 0, bound_steps = 0;
+        double centre, half_width, theta_max, residual = 0.0;
+        if (dsf_cheb_have_window) {
+            centre = 0.5 * (dsf_cheb_window[0] + dsf_cheb_window[1]); half_width = 0.5 * (dsf_cheb_window[1] - dsf_cheb_window[0]); theta_max = dsf_cheb_window[1];
+        } else {
+            const PetscInt B = dsf_cheb_bound_steps;
+            dmrgx_host::DevBuffer r((size_t)n);
+            {   /* uniform(-1, 1) from a fixed seed, by integer arithmetic on the generator's 64 bits: the same vector everywhere */
+                std::mt19937_64 gen(0x63686562ull);
+                double* h = r.host();
+                for (int64_t e = 0; e < n; ++e) h[e] = (double)(gen() >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+            }
+            std::vector<double> a((size_t)B, 0.0), b((size_t)B, 0.0);
+            double r2 = 0.0; int32_t done = 0;
+            if (dmrgx_kron_lanczos_coeffs(H->plan, r.dev_ro(), (int32_t)B, 0.0, &r2, a.data(), b.data(), &done, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_lanczos_coeffs: %s", dmrgx_last_error());
+            matmults += B; bound_steps = B;
+            const dmrgx_host::ChebyshevWindowResult W = dmrgx_host::ChebyshevWindow((double)E0, a, b, done);
+            if (!W.ok) SETERRQ1(mpi_comm, 1, "Chebyshev correlations: no spectral window from %d Lanczos steps.", (int)done);
+            centre = W.centre; half_width = W.half_width; theta_max = W.theta_max; residual = W.residual;
+        }
+
+        struct Run { PetscInt c = 0; double norm2 = 0.0; int32_t done = 0; std::vector<double> diag, mom, momq, grid; };
+        std::vector<Run> runs(dsf_cheb_sites.size());
+        std::vector<double> cross((size_t)((K + 1) * N)), coskr((size_t)N);
+        double t_runs = 0.0;
+        for (size_t ir = 0; ir < runs.size(); ++ir) {
+            Run& R = runs[ir];
+            R.c = dsf_cheb_sites[ir];
+            R.diag.assign((size_t)(2 * K + 1), 0.0);
+            PetscLogDouble tr0 = 0.0, tr1 = 0.0;
+            if (verbose) { if (dmrgx_stream_sync(nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error()); PetscTime(&tr0); }      /* the run alone, for the log */
+            if (dmrgx_kron_chebyshev_moments(H->plan, U->dev_ro() + R.c * ld, centre, half_width, (int32_t)K, (int32_t)N, U->dev_ro(), ld, &R.norm2, R.diag.data(), cross.data(), &R.done, nullptr))
+                SETERRQ1(mpi_comm, 1, "dmrgx_kron_chebyshev_moments: %s", dmrgx_last_error());
+            if (verbose) { PetscTime(&tr1); t_runs += tr1 - tr0; }
+            matmults += K;
+            const PetscInt D = R.done, nm = D + 1;
+            if (D < K) printf("  * WARNING: -dsf_cheb: the run from site %lld left the window [%.6f, %.6f] after %lld of %lld steps; the record holds the moments up to there.\n", LLD(R.c), centre - half_width, centre + half_width, LLD(D), LLD(K));
+            R.diag.resize((size_t)(2 * D + 1));
+            for (double& x : R.diag) x /= norm;
+            R.mom.assign((size_t)(N * nm), 0.0); R.momq.assign((size_t)(M * nm), 0.0);
+            for (PetscInt s = 0; s < N; ++s) for (PetscInt k = 0; k < nm; ++k) R.mom[(size_t)(s * nm + k)] = cross[(size_t)(k * N + s)] / norm;
+            for (PetscInt nx = 0; nx < Lx; ++nx) for (PetscInt ny = 0; ny < Ly; ++ny) {
+                double* row = R.momq.data() + (nx * Ly + ny) * nm;
+                for (PetscInt s = 0; s < N; ++s) {
+                    const double cq = std::cos(dmrgx_host::two_pi * ((double)(nx * (rx[(size_t)s] - rx[(size_t)R.c])) / (double)Lx + (double)(ny * (ry[(size_t)s] - ry[(size_t)R.c])) / (double)Ly));
+                    for (PetscInt k = 0; k < nm; ++k) row[k] += cq * R.mom[(size_t)(s * nm + k)];
+                }
+            }
+            if (dsf_cheb_have_omega) {
+                const PetscInt nw = (PetscInt)dsf_cheb_omega.size();
+                R.grid.assign((size_t)(M * nw), 0.0);
+                for (PetscInt q = 0; q < M; ++q) for (PetscInt k = 0; k < nw; ++k)
+                    R.grid[(size_t)(q * nw + k)] = dmrgx_host::ChebyshevJackson(R.momq.data() + q * nm, nm, (dsf_cheb_omega[(size_t)k] + (double)E0 - centre) / half_width) / half_width;
+            }
+        }
+        PetscTime(&t1);
+        if (verbose) printf("  * Chebyshev correlations: %lld reference sites, %lld steps per run, window [%.6f, %.6f] from %lld Lanczos steps, %lld MatMults on %lld states, tDsfCheb %.6f s, of it the Chebyshev runs %.6f s\n",
+                            LLD(runs.size()), LLD(K), centre - half_width, centre + half_width, LLD(bound_steps), LLD(matmults), LLD(n), t1 - t0, t_runs);
+        ierr = dsf_cheb_file.Begin(data_dir + "ChebyshevMoments.json"); CHKERRQ(ierr);
+        FILE* fp = dsf_cheb_file.fp;
+        fprintf(fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"E0\": %.17g, \"Norm\": %.17g, \"Steps\": %lld, \"Centre\": %.17g, \"HalfWidth\": %.17g, \"BoundSteps\": %lld, \"ThetaMax\": %.17g, \"Residual\": %.17g, \"tDsfCheb\": %.9g, \"MatMults\": %lld,\n",
+                LLD(GlobIdx), LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, norm, LLD(K), centre, half_width, LLD(bound_steps), theta_max, residual, t1 - t0, LLD(matmults));
+        if (dsf_cheb_have_omega) { fprintf(fp, "   \"Omega\": "); dsf_cheb_file.Row(dsf_cheb_omega); fprintf(fp, ",\n"); }
+        fprintf(fp, "   \"Sites\": [\n");
+        for (size_t ir = 0; ir < runs.size(); ++ir) {
+            const Run& R = runs[ir];
+            const PetscInt nm = R.done + 1;
+            const char* end = ir + 1 < runs.size() ? "},\n" : "}\n";
+            fprintf(fp, "   {\"Site\": %lld, \"r\": [%lld, %lld], \"Norm2\": %.17g, \"StepsDone\": %d,\n   \"Diag\": ", LLD(R.c), LLD(rx[(size_t)R.c]), LLD(ry[(size_t)R.c]), R.norm2, (int)R.done);
+            dsf_cheb_file.Row(R.diag); fprintf(fp, ",\n");
+            dsf_cheb_file.Table("Moments", R.mom, N, nm, ",\n");
+            dsf_cheb_file.Table("MomentsQ", R.momq, M, nm, dsf_cheb_have_omega ? ",\n" : end);
+            if (dsf_cheb_have_omega) dsf_cheb_file.Table("SqwGrid", R.grid, M, (PetscInt)dsf_cheb_omega.size(), end);
+        }
+        fprintf(fp, "   ]}");
+        fflush(fp);
+        return 0;
+    }
+
     /** -corr_dimer 1 (engine extension): the dimer-dimer table < D_b D_b' > over all pairs of nearest-neighbour bonds, D_b = S_i . S_j
         = Sz_i Sz_j + (Sp_i Sm_j + Sm_i Sp_j) / 2, its connected part and the dimer structure factors of the x and the y bonds, at every
         measurement point.  < psi | D_b^T D_b' | psi > = < D_b psi , D_b' psi >: the whole table is ONE dmrgx_kron_term_gram call over the
@@ -2096,7 +2260,7 @@ public:
             for (const Op& o : c.SysOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
             for (const Op& o : c.EnvOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
         }
-        if (use_corr_matrix || use_corr_dimer || use_dsf || use_dsf_sites) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer, -dsf, -dsf_sites: Sz and Sp of every site of both centre blocks, on every rank */
+        if (use_corr_matrix || use_corr_dimer || use_dsf || use_dsf_sites || use_dsf_cheb) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer, -dsf, -dsf_sites, -dsf_cheb: Sz and Sp of every site of both centre blocks, on every rank */
         need_built = true;
         return 0;
     }
@@ -2311,6 +2475,14 @@ private:
     PetscBool use_dsf_sites = PETSC_FALSE;      /* -dsf_sites c0,c1,...: G_ic(w) and its Fourier transform from a kept Lanczos basis, DynamicalCorrelations.json (CalculateDynamicalCorrelations) */
     std::vector<PetscInt> dsf_sites;            /* the reference sites c, lattice numbering of To1D; shares -dsf_steps and -dsf_breakdown_tol */
     dmrgx_host::JsonRecordFile dsf_sites_file{"%.17g"}; /* created at the first measurement with -dsf_sites */
+    PetscBool use_dsf_cheb = PETSC_FALSE;       /* -dsf_cheb c0,c1,...: Chebyshev moments of G_ic(w), ChebyshevMoments.json (CalculateChebyshevCorrelations) */
+    std::vector<PetscInt> dsf_cheb_sites;       /* the reference sites c, lattice numbering of To1D */
+    PetscInt dsf_cheb_steps = 200;              /* -dsf_cheb_steps: MatMults per run; moments 0 .. steps between sites, 0 .. 2 steps on the diagonal */
+    PetscInt dsf_cheb_bound_steps = 40;         /* -dsf_cheb_bound_steps: Lanczos steps of the run that finds the top of the spectrum */
+    PetscBool dsf_cheb_have_window = PETSC_FALSE, dsf_cheb_have_omega = PETSC_FALSE;
+    PetscReal dsf_cheb_window[2] = {0.0, 0.0};  /* -dsf_cheb_window lo,hi: the window given, no bound run */
+    std::vector<double> dsf_cheb_omega;         /* -dsf_cheb_omega w0,w1,nw: the grid of the Jackson-broadened SqwGrid */
+    dmrgx_host::JsonRecordFile dsf_cheb_file{"%.17g"};  /* created at the first measurement with -dsf_cheb */
     PetscBool use_corr_batch = PETSC_TRUE;      /* -corr_batch 0: every correlator through its own MatMult + dot, as the reference does */
 };
 

@@ -2,10 +2,12 @@
 #define DMRGX_HOST_MEASUREMENTS_HPP
 /** What -corr_matrix, -corr_dimer and -dsf share (DMRGBlockContainer.hpp: CalculateCorrelationMatrix, CalculateDimerCorrelations,
     CalculateDynamicalStructureFactor): the two blocks as the library sees them, the site operators of one Gram / term call, the bond
-    list, the lattice Fourier sum, the phase coefficients of -dsf, the JSON record file.  host_tool.cpp runs the pure parts without a GPU. */
+    list, the lattice Fourier sum, the phase coefficients of -dsf, the JSON record file; the spectral window and the Jackson-damped sum
+    of -dsf_cheb (CalculateChebyshevCorrelations).  host_tool.cpp runs the pure parts without a GPU. */
 #include <cmath>
 #include <deque>
 #include "DMRGKron.hpp"
+#include "TridiagQL.hpp"
 
 namespace dmrgx_host {
 
@@ -104,6 +106,44 @@ inline double DsfPhaseCoefficient(int part, PetscInt p, PetscInt M)
 {
     if (part == 0) return ((4 * p) % M == 0 && (2 * p) % M != 0) ? 0.0 : std::cos(two_pi * (double)p / (double)M);
     return (2 * p) % M == 0 ? 0.0 : std::sin(two_pi * (double)p / (double)M);
+}
+
+/** The window [E_lo, E_hi] of a Chebyshev expansion from `done` steps of a Lanczos run (alpha, beta of dmrgx_kron_lanczos_coeffs; the
+    vectors hold the steps asked for, done < alpha.size() is a breakdown) and the known lowest eigenvalue E0.  theta_max: the largest
+    eigenvalue of the Lanczos matrix of order `done`; residual = beta_{done-1} |last component of its eigenvector|, the bound
+    |lambda - theta_max| <= residual for some eigenvalue lambda of H -- 0 after a breakdown, where the Krylov space is invariant.
+    E_hi = theta_max + residual + 0.02 (theta_max - E0), E_lo = E0 - 0.01 (theta_max - E0).  ok false: done < 1 or the QL iteration failed. */
+struct ChebyshevWindowResult { double centre = 0.0, half_width = 0.0, theta_max = 0.0, residual = 0.0; bool ok = false; };
+inline ChebyshevWindowResult ChebyshevWindow(double E0, const std::vector<double>& alpha, const std::vector<double>& beta, PetscInt done)
+{
+    ChebyshevWindowResult W;
+    if (done < 1 || (size_t)done > alpha.size() || beta.size() < alpha.size()) return W;
+    std::vector<double> theta(alpha.begin(), alpha.begin() + done), e(beta.begin(), beta.begin() + done), vec;
+    if (!TridiagQLVectors(theta, e, vec)) return W;
+    PetscInt top = 0;
+    for (PetscInt k = 1; k < done; ++k) if (theta[(size_t)k] > theta[(size_t)top]) top = k;
+    W.theta_max = theta[(size_t)top];
+    W.residual = (size_t)done < alpha.size() ? 0.0 : beta[(size_t)(done - 1)] * std::fabs(vec[(size_t)(top * done + done - 1)]);
+    const double width = W.theta_max - E0, hi = W.theta_max + W.residual + 0.02 * width, lo = E0 - 0.01 * width;
+    W.centre = 0.5 * (hi + lo); W.half_width = 0.5 * (hi - lo);
+    W.ok = W.half_width > 0.0 && std::isfinite(W.half_width) && std::isfinite(W.centre);
+    return W;
+}
+
+/** The Jackson-damped Chebyshev sum of M moments mu[0..M) at x:
+        ( g_0 mu_0 + 2 sum_{n=1}^{M-1} g_n mu_n T_n(x) ) / ( pi sqrt(1 - x^2) ),
+        g_n = [ (M - n + 1) cos(pi n / (M + 1)) + sin(pi n / (M + 1)) cot(pi / (M + 1)) ] / (M + 1),
+    the moments of a positive measure give a non-negative value (the Jackson kernel is positive).  0 for |x| >= 1 or M < 1. */
+inline double ChebyshevJackson(const double* mu, PetscInt M, double x)
+{
+    if (M < 1 || !(std::fabs(x) < 1.0)) return 0.0;
+    const double pi = 0.5 * two_pi, a = pi / (double)(M + 1), cot = std::cos(a) / std::sin(a), phi = std::acos(x);
+    double sum = 0.0;
+    for (PetscInt n = M - 1; n >= 0; --n) {                      /* the small terms first */
+        const double g = ((double)(M - n + 1) * std::cos(a * (double)n) + std::sin(a * (double)n) * cot) / (double)(M + 1);
+        sum += (n ? 2.0 : 1.0) * g * mu[n] * std::cos((double)n * phi);
+    }
+    return sum / (pi * std::sqrt(1.0 - x * x));
 }
 
 /** A nearest-neighbour bond of the lattice: sites i < j, the site (ix, jy) from which NearestNeighbors generates it, 'x' if the two

@@ -193,6 +193,21 @@ int main()
             printf("fourier");
             for (double v : dmrgx_host::LatticeFourier(Lx, Ly, x.data(), y.data(), T.data(), n, (double)n)) printf(" %.17g", v);
             printf("\n");
+        } else if (cmd == "chebwindow") {        /* chebwindow E0 nsteps done alpha_0 .. alpha_{nsteps-1} beta_0 .. beta_{nsteps-1}  ->  ok centre half_width theta_max residual */
+            double E0; size_t nsteps; PetscInt done; is >> E0 >> nsteps >> done;
+            std::vector<double> a(nsteps), b(nsteps);
+            for (double& x : a) is >> x;
+            for (double& x : b) is >> x;
+            const dmrgx_host::ChebyshevWindowResult W = dmrgx_host::ChebyshevWindow(E0, a, b, done);
+            printf("chebwindow %d %.17g %.17g %.17g %.17g\n", (int)W.ok, W.centre, W.half_width, W.theta_max, W.residual);
+        } else if (cmd == "chebjackson") {       /* chebjackson M nx mu_0 .. mu_{M-1} x_0 .. x_{nx-1}  ->  the damped sum at every x */
+            PetscInt M, nx; is >> M >> nx;
+            std::vector<double> mu((size_t)M), xs((size_t)nx);
+            for (double& v : mu) is >> v;
+            for (double& v : xs) is >> v;
+            printf("chebjackson");
+            for (double x : xs) printf(" %.17g", dmrgx_host::ChebyshevJackson(mu.data(), M, x));
+            printf("\n");
         } else if (cmd == "jsonrec") {           /* jsonrec path format nrec: nrec records {"K": k, "R": row of 3, "T": 2 x 3 table} of thirds, then Close() */
             std::string path, fmt; PetscInt nrec; is >> path >> fmt >> nrec;
             dmrgx_host::JsonRecordFile J(fmt.c_str());

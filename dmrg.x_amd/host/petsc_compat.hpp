@@ -91,7 +91,12 @@ public:
     }
     const std::map<std::string, std::string>& All() const { return kv; }
 private:
-    static bool IsNumber(const std::string& s) { char* e = nullptr; strtod(s.c_str(), &e); return e && *e == '\0' && !s.empty(); }
+    /* a number, or numbers between commas (-dsf_cheb_window -11.5,3): a value, not an option name */
+    static bool IsNumber(const std::string& s) {
+        if (s.empty()) return false;
+        const char* p = s.c_str();
+        while (true) { char* e = nullptr; strtod(p, &e); if (e == p) return false; if (*e == '\0') return true; if (*e != ',') return false; p = e + 1; }
+    }
     std::map<std::string, std::string> kv;
 };
 
@@ -205,6 +210,23 @@ inline PetscErrorCode PetscOptionsGetIntArray(void*, void*, const char* name, Pe
             size_t c = s.find(',', pos);
             std::string tok = s.substr(pos, c == std::string::npos ? std::string::npos : c - pos);
             if (!tok.empty()) arr[cnt++] = (PetscInt)strtoll(tok.c_str(), nullptr, 10);
+            if (c == std::string::npos) break;
+            pos = c + 1;
+        }
+    }
+    *n = cnt;
+    if (set) *set = f ? PETSC_TRUE : PETSC_FALSE;
+    return 0;
+}
+inline PetscErrorCode PetscOptionsGetRealArray(void*, void*, const char* name, PetscReal* arr, PetscInt* n, PetscBool* set) {
+    std::string s; const bool f = dmrgx_host::Options::Global().Find(name, s);
+    PetscInt cnt = 0;
+    if (f) {
+        size_t pos = 0;
+        while (pos <= s.size() && cnt < *n) {
+            size_t c = s.find(',', pos);
+            std::string tok = s.substr(pos, c == std::string::npos ? std::string::npos : c - pos);
+            if (!tok.empty()) arr[cnt++] = strtod(tok.c_str(), nullptr);
             if (c == std::string::npos) break;
             pos = c + 1;
         }

@@ -171,6 +171,24 @@ class KronPlan:
                                                          self._stream_ptr(stream)))
         return norm2.value, np.array(alpha[:n]), np.array(beta[:n]), done.value, V
 
+    def chebyshev_moments(self, v0, centre, half_width, nsteps, U=None, stream=None):
+        """Chebyshev moments of Ht = (H - centre) / half_width from the start vector v0 (dmrgx_kron_chebyshev_moments): t_0 = v0,
+        t_1 = Ht t_0, t_{n+1} = 2 Ht t_n - t_{n-1}, device-resident, guarded on the device.  v0: f64 device tensor of n_states, only read.
+        U: None, or a 2-D f64 device tensor of nu rows with unit stride along the vector (its row stride is the library's ldu), only read.
+        Returns (norm2, mu_diag[2 nsteps + 1], mu_cross[nsteps + 1, nu], nsteps_done): mu_diag[m] = <v0, T_m(Ht) v0>,
+        mu_cross[n, i] = <U[i], t_n>; beyond 2 nsteps_done and beyond row nsteps_done everything is zero."""
+        assert v0.dtype == torch.float64 and v0.is_contiguous() and v0.numel() >= self.info.n_states
+        K = max(int(nsteps), 0)
+        nu, u_ptr, ldu = 0, C.c_void_p(), 0
+        if U is not None:
+            assert U.dtype == torch.float64 and U.dim() == 2 and U.shape[1] >= self.info.n_states and (U.shape[1] <= 1 or U.stride(1) == 1)
+            nu, u_ptr, ldu = U.shape[0], C.c_void_p(U.data_ptr()), U.stride(0) if U.shape[0] > 1 else max(U.stride(0), U.shape[1])
+        norm2, done = C.c_double(0.0), C.c_int32(0)
+        diag, cross = (C.c_double * (2 * K + 1))(), (C.c_double * max((K + 1) * nu, 1))()
+        _capi.check(_capi.lib().dmrgx_kron_chebyshev_moments(self._handle, C.c_void_p(v0.data_ptr()), float(centre), float(half_width), int(nsteps), int(nu), u_ptr,
+                                                             int(ldu), C.byref(norm2), diag, cross, C.byref(done), self._stream_ptr(stream)))
+        return norm2.value, np.array(diag[:2 * K + 1]), np.array(cross[:(K + 1) * nu]).reshape(K + 1, nu), done.value
+
     def timing(self, enable):
         _capi.check(_capi.lib().dmrgx_kron_plan_timing(self._handle, 1 if enable else 0))
 

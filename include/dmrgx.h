@@ -29,6 +29,7 @@
  *   dmrgx_kron_lanczos_coeffs   themselves (the Gram calls only hand back their inner products) and the Lanczos coefficients of the planned
  *                               superblock Hamiltonian from such a vector: the continued fraction behind a dynamical structure factor
  *   dmrgx_kron_lanczos_basis    (-dsf); the same run with the basis kept and reorthogonalised, for overlaps with it (-dsf_sites)
+ *   dmrgx_kron_chebyshev_moments  the Chebyshev recursion on the planned Hamiltonian and its moments with a family of vectors (-dsf_cheb)
  *   dmrgx_comm_*             <- the communicator of the reference's MPI path: VecScatter-to-all of x inside every MatMult
  *                               (src/DMRGKron.cpp:1833-1834) and the MPI_Allreduce behind SLEPc's VecDot / VecNorm
  *
@@ -501,6 +502,35 @@ dmrgx_status dmrgx_kron_lanczos_coeffs(dmrgx_kron_plan* plan, const double* v0_d
 dmrgx_status dmrgx_kron_lanczos_basis(dmrgx_kron_plan* plan, const double* v0_dev, int32_t nsteps, double breakdown_tol,
                                       double* V_dev, int64_t ldv, double* norm2, double* alpha /* [nsteps] */, double* beta /* [nsteps] */,
                                       int32_t* nsteps_done, void* stream);
+
+/* ---- Chebyshev moments from a given start vector (kernel polynomial method: broadened spectra at linear cost) ---------- */
+/* With Ht = (H - centre) / half_width on the planned Hamiltonian (world_size == 1; a striped plan is refused with DMRGX_ERR_ARG):
+ * t_0 = v0 (not normalised), t_1 = Ht t_0, t_{n+1} = 2 Ht t_n - t_{n-1}; nsteps = K >= 1 MatMults give t_0 .. t_K.  Nothing is
+ * normalised or reorthogonalised and no basis is kept: the recursion is stable as long as the spectrum of H lies inside
+ * [centre - half_width, centre + half_width].  Host outputs:
+ *   *norm2         = mu_0 = <v0, v0>;
+ *   mu_diag[m]     = <v0, T_m(Ht) v0>, m = 0 .. 2K, by the doubling identities mu_{2n} = 2 <t_n, t_n> - mu_0 and
+ *                    mu_{2n+1} = 2 <t_{n+1}, t_n> - mu_1;
+ *   mu_cross[n*nu + i] = <u_i, t_n>, n = 0 .. K, u_i = row i of U (U_dev[i*ldu + e], e < n_states; ldu >= n_states, any 8-byte
+ *                    alignment, only read).  nu == 0: no cross moments, U_dev and mu_cross may be NULL.
+ * The whole run is enqueued without looking at the device and ends with one copy and one synchronisation.  Per step one fused kernel
+ * reads w = H t_n, t_n and t_{n-1}, writes t_{n+1} and leaves the workgroups' partial sums of <t_{n+1}, t_{n+1}> and <t_{n+1}, t_n>; a
+ * one-workgroup kernel adds them in block order.  The vectors go through a ring of 32 rows; whenever 16 consecutive t_n are complete (and
+ * for the last, partial block) one dmrgx_vec_gram of U against those rows writes their cross moments on the device, so U is read once
+ * per 16 steps.
+ * The guard, decided on the device: inside the window |t_n|^2 <= mu_0.  At the first n where <t_{n+1}, t_{n+1}> is not a finite number
+ * or exceeds (1 + 1e-6) mu_0 the run is dead: *nsteps_done = D = n, the index of the last valid vector; every later vector is exact
+ * zeros, mu_diag[m] = 0 for m > 2D and every row n > D of mu_cross is 0.  Without a trip D = K.  A v0 whose squared norm is not a
+ * positive finite number gives *norm2 = 0, D = 0 and all moments 0.  With a finite U no output is ever NaN or infinite.
+ * Refused (DMRGX_ERR_ARG): a null argument (mu_cross only when nu > 0), K < 1, a half_width that is not a positive finite number, a
+ * centre that is not finite, nu < 0, nu > 0 with U_dev NULL or ldu < n_states.
+ * Memory from the pool: 2 + 32 vectors of n_states doubles, 2 ceil(n_states / 2048) partial sums, (K + 1) nu + 2K + 1 moments.  Fixed
+ * grids, fixed-order sums, no atomics: two runs give the same bits. */
+dmrgx_status dmrgx_kron_chebyshev_moments(dmrgx_kron_plan* plan, const double* v0_dev, double centre, double half_width, int32_t nsteps,
+                                          int32_t nu, const double* U_dev, int64_t ldu,
+                                          double* norm2, double* mu_diag /* host [2 nsteps + 1] */,
+                                          double* mu_cross /* host [(nsteps + 1) * nu], row n; may be NULL when nu == 0 */,
+                                          int32_t* nsteps_done, void* stream);
 
 #ifdef __cplusplus
 }
