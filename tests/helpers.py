@@ -339,3 +339,179 @@ def lanczos_basis_invariants(plan, H, v0, K, V=None, ref=None):
     assert np.array_equal(_bits(alpha), _bits(alphab)) and np.array_equal(_bits(beta), _bits(betab)) and np.array_equal(_bits(Vh), _bits(Vhb))
     assert np.array_equal(_bits(v0d.cpu().numpy()), _bits(v0))
     return norm2, alpha, beta
+
+
+# ---- density-matrix eigensolver: planted tridiagonals, clusters, edges (tests/test_rdm_inputs.py, tests/test_gpu_rdm_spectra.py) ----
+# The constants of csrc/symeig.hip / symeig.h the inputs and the order lists were built around; test_rdm_inputs.py parses the sources and
+# fails when one of them is retuned.
+RDM_CONSTANTS = {"DMRGX_DC_LEAF": 16, "DC_FUSE_NL": 384, "DMRGX_WY_NB": 64, "TRID_MAXM": 32, "TRID_PF": 8, "SYMEIG_MAX_N": 3072}
+RDM_LEAF = RDM_CONSTANTS["DMRGX_DC_LEAF"]
+# orders above 40 at the edges of the solver: the tree's halving (63 .. 66, 127 .. 131, 511 .. 514, 1024, 1025), the fused / split Loewner
+# kernels (a top merge of DC_FUSE_NL = 384 +- 1; 768 and 769: level-1 merges of 384 and 385), the last partial WY block (n - 2 = 64 q + r with
+# r = 0, 1, 63) and the 512-column prefetch chunk of the launch-per-column kernel (TRID_PF chunks of 64)
+RDM_EDGE_ORDERS = [63, 64, 65, 66, 127, 128, 129, 130, 131, 383, 384, 385, 511, 512, 513, 514, 768, 769, 1024, 1025]
+RDM_EDGE_CALLS = [[63, 64, 65, 66, 127, 128, 129, 130, 131, 383, 384, 385], [511, 512, 513, 514], [768, 769], [1024, 1025]]
+
+
+def rdm_tree_bounds(n, leaf=RDM_LEAF):
+    """(depth, node boundaries at that depth) of the divide-and-conquer tree: repeated halving until every leaf is at most `leaf`."""
+    depth = 0
+    while -(-n // (1 << depth)) > leaf:
+        depth += 1
+    b = [0, n]
+    for _ in range(depth):
+        b = [x for lo, hi in zip(b[:-1], b[1:]) for x in (lo, (lo + hi) // 2)] + [n]
+    return depth, b
+
+
+def rdm_bidiag(a, b):
+    """The state (flat, row-major) of a layout of one n x n KronBlock whose Psi is lower bidiagonal with diagonal a and subdiagonal b:
+    rho_L = Psi Psi^T is tridiagonal with d_i = a_i^2 + b_{i-1}^2, e_i = a_i b_i and structural zeros elsewhere (rho_R = Psi^T Psi: d_i =
+    a_i^2 + b_i^2, e_i = a_{i+1} b_i).  With dyadic a, b every entry is exact on any hardware.  Not normalised: the library does not need
+    Tr rho = 1."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    assert b.shape == (len(a) - 1,)
+    psi = (np.diag(a) + np.diag(b, -1)).ravel()
+    psi.setflags(write=False)
+    return psi
+
+
+def _split_coupled(n, a_low):
+    """Couplings only at the tree's split points s: a[s-1] = a_low, a[s] = 0.75, b[s-1] = 1, every other a = 1 and b = 0.  With a_low = 1.25,
+    d[s-1] = d[s] = 1.5625 exactly: after Cuppen's rank-one tear both boundary entries are 0.3125, z is non-zero on these two equal poles only,
+    one rotation merges them and ONE pole survives (k = 1).  With a_low = 1.5 the two differ (2.25, 1.5625) and two survive."""
+    a, b = np.ones(n), np.zeros(n - 1)
+    for s in rdm_tree_bounds(n)[1][1:-1]:
+        a[s - 1], a[s], b[s - 1] = a_low, 0.75, 1.0
+    return a, b
+
+
+def _tridiag_cholesky(d, e):
+    """Lower-bidiagonal Cholesky factor (diagonal, subdiagonal) of the SPD tridiagonal (d, e)."""
+    n = len(d)
+    a, b = np.zeros(n), np.zeros(n - 1)
+    for i in range(n):
+        t = d[i] - (b[i - 1] ** 2 if i else 0.0)
+        assert t > 0.0
+        a[i] = np.sqrt(t)
+        if i < n - 1:
+            b[i] = e[i] / a[i]
+    return a, b
+
+
+def glued_wilkinson(m, copies, glue, shift=1.5):
+    """Psi = the Cholesky factor of `copies` Wilkinson matrices W_{2m+1} (diagonal |-m .. m|, off-diagonal 1) glued by `glue` and shifted by
+    `shift` (W21's lowest eigenvalue is -1.125: positive definite): every eigenvalue of W comes `copies` times, split by ~glue, and the large
+    ones in pairs that agree to 1e-14 already."""
+    w = np.abs(np.arange(-m, m + 1)).astype(np.float64) + shift
+    d = np.tile(w, copies)
+    e = np.ones(len(d) - 1)
+    e[2 * m::2 * m + 1] = glue
+    return rdm_bidiag(*_tridiag_cholesky(d, e))
+
+
+def _orth(rng, n):
+    return np.linalg.qr(rng.standard_normal((n, n)))[0]
+
+
+def _rdm_named(name):
+    rng = np.random.default_rng(1729)
+    if name in ("k1_20", "k1_40", "k2_20"):
+        return rdm_bidiag(*_split_coupled(int(name[3:]), 1.25 if name[1] == "1" else 1.5))
+    if name == "toeplitz121_100":
+        return rdm_bidiag(np.ones(100), np.ones(99))
+    if name == "zero_coupling_50":                       # split points of n = 50: 12, 25, 37; e = 0 behind rows 5 and 30
+        i = np.arange(50)
+        a, b = 1.0 + (i % 4) / 4.0, 0.5 + (i[:49] % 3) / 8.0
+        b[5] = b[30] = 0.0
+        return rdm_bidiag(a, b)
+    if name == "diagonal_100":                           # 3 x 10 repeated values, 20 exact zeros, a tail of 50 down to 2^-50, shuffled
+        a = np.concatenate([np.full(10, 1.0), np.full(10, 0.5), np.full(10, 0.25), np.zeros(20), 2.0 ** -np.arange(1.0, 51.0)])
+        return rdm_bidiag(a[rng.permutation(100)], np.zeros(99))
+    if name == "blockdiag_64":                           # dense blocks; no block edge (7, 23, 40, 41) is a split point of n = 64 (16, 32, 48)
+        Psi, o = np.zeros((64, 64)), 0
+        for p in (7, 16, 17, 1, 23):
+            Psi[o:o + p, o:o + p] = np.round(rng.standard_normal((p, p)) * 64.0) / 256.0      # dyadic: the zero blocks of rho stay exact
+            o += p
+        return Psi.ravel()
+    if name.startswith("glued_"):
+        copies, glue = {"glued_6_1e-8": (6, 1e-8), "glued_6_1e-14": (6, 1e-14), "glued_12_1e-8": (12, 1e-8)}[name]
+        return glued_wilkinson(10, copies, glue)
+    if name == "clusters_200":                           # eight clusters of 25 eigenvalues of rho at 2^-c (1 + spread u), u in [0, 1)
+        spreads = [0.0, 1e-16, 1e-14, 1e-12, 1e-10, 1e-8, 1e-6, 1e-4]
+        lam = np.concatenate([2.0 ** -c * (1.0 + sp * np.arange(25) / 25.0) for c, sp in enumerate(spreads)])
+        return ((_orth(rng, 200) * np.sqrt(lam)) @ _orth(rng, 200).T).ravel()
+    if name == "graded_pairs_300":                       # s = exp(-0.5 i) in exactly equal pairs, rank 260: s down to 1e-56, s^2 to 1e-112
+        s = np.exp(-0.5 * np.arange(300.0))
+        s[1::2] = s[0::2]
+        s[260:] = 0.0
+        return ((_orth(rng, 300) * s) @ _orth(rng, 300).T).ravel()
+    if name == "gaussian_100x60":                        # the control: what almost every other RDM test uses
+        return rng.standard_normal(100 * 60)
+    raise KeyError(name)
+
+
+RDM_TRIDIAGONALS = ["k1_20", "k1_40", "k2_20", "toeplitz121_100", "zero_coupling_50", "diagonal_100", "glued_6_1e-8", "glued_6_1e-14", "glued_12_1e-8"]
+RDM_NAMED = RDM_TRIDIAGONALS + ["blockdiag_64", "clusters_200", "graded_pairs_300"]
+_RDM_INPUTS, _RDM_STATS = {}, {}
+
+
+def rdm_input(name):
+    """(rows, columns, Psi as a read-only matrix) of a named input; built once per process."""
+    if name not in _RDM_INPUTS:
+        psi = np.ascontiguousarray(_rdm_named(name), dtype=np.float64)
+        rows = 100 if name == "gaussian_100x60" else int(round(np.sqrt(psi.size)))
+        Psi = psi.reshape(rows, -1)
+        Psi.setflags(write=False)
+        _RDM_INPUTS[name] = (rows, Psi.shape[1], Psi)
+    return _RDM_INPUTS[name]
+
+
+def rdm_model_stats(rho, leaf=RDM_LEAF):
+    """What the project's numpy model of the solver (tools/proto_trid_dc.py) does with rho: {"merges": [(n, k, rotations, longest rotation chain,
+    all deflated), ...] (leaves' level first, the root last), "tau_zero": reflectors with tau == 0 (of n), "e_zero": couplings that are exactly 0
+    (of n - 1), "w": the model's eigenvalues (ascending), "X": its eigenvectors (columns)}.  A merge with rotations >= 1 is one that the device
+    sends through the sequential scan of dc_deflate_kernel and dc_rot_kernel."""
+    import importlib.util
+    import os
+    import sys
+    if "proto_trid_dc" not in sys.modules:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "proto_trid_dc.py")
+        spec = importlib.util.spec_from_file_location("proto_trid_dc", path)
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules["proto_trid_dc"] = mod
+        spec.loader.exec_module(mod)
+    proto = sys.modules["proto_trid_dc"]
+    d, e, VT, tau = proto.trid_pipeline(np.array(rho, dtype=np.float64))
+    merges = []
+    w, Z, _ = proto.stedc(d, e, leaf=leaf, detail=merges)
+    return {"merges": merges, "tau_zero": int(np.sum(tau == 0.0)), "e_zero": int(np.sum(e == 0.0)), "n": len(d),
+            "w": w, "X": proto.backtransform(VT, tau, Z, nb=RDM_CONSTANTS["DMRGX_WY_NB"])}
+
+
+def rdm_named_stats(name):
+    """rdm_model_stats of rho_L of a named input, once per process."""
+    if name not in _RDM_STATS:
+        Psi = rdm_input(name)[2]
+        _RDM_STATS[name] = rdm_model_stats(Psi @ Psi.T)
+    return _RDM_STATS[name]
+
+
+def rdm_bounds(rho, w_ref):
+    """(eigenvalue bound, residual bound) of a density matrix: the project's backward-stability constant c n eps with c n eps = 3e-15 n, on
+    max |w| for the eigenvalues and on |rho|_2 (= max |w|, rho is symmetric) for rho U^T - U^T diag(w)."""
+    n = rho.shape[0]
+    return 3e-15 * n * np.abs(w_ref).max() + 1e-17, 3e-15 * n * np.abs(w_ref).max() + 1e-16
+
+
+RDM_ORTH_TOL = 1e-13          # rows of the eigenvector matrix, orders up to 1100
+
+
+def rdm_ratios(rho, w, U, w_ref=None):
+    """(eigenvalue error / its bound, residual / its bound, orthogonality error) of eigenvalues w (descending) and eigenvectors U (rows)
+    against numpy's eigvalsh of rho."""
+    if w_ref is None:
+        w_ref = np.linalg.eigvalsh(rho)[::-1]
+    be, br = rdm_bounds(rho, w_ref)
+    c = U.shape[0]
+    return (np.abs(w - w_ref).max() / be, np.abs(rho @ U.T - U.T * w[:c]).max() / br, np.abs(U @ U.T - np.eye(c)).max())

@@ -408,8 +408,9 @@ def _rdm_check(sbm, ls, rs, blocks, psi, tol_orth=1e-13):
 
 def test_rdm_direct_solver_degenerate_and_boundary_cases(mods):
     """The tridiagonalisation + divide-and-conquer solver (csrc/symeig.hip) where its special paths run: exactly degenerate Schmidt
-    values (type-2 deflation: Givens chains applied to the rows of the merge matrices), orders around the leaf size and the tree's
-    split points (1, 2, 3, 31 .. 34, 63 .. 66), rank one, and a multiple of the identity."""
+    values (type-2 deflation: Givens chains applied to the rows of the merge matrices), orders around the tree's split points (1, 2, 3,
+    31 .. 34, 63 .. 66: with the leaf of 16 these are the orders at which a second and a third level of merges begin; the orders around
+    one leaf, 15 .. 17, are in tests/test_gpu_rdm_spectra.py), rank one, and a multiple of the identity."""
     sbm, _, _ = mods
     rng = np.random.default_rng(11)
     # degenerate pairs and a triple, graded over 12 decades

@@ -9,7 +9,7 @@ checked on the CPU before they are debugged on a GPU box:
                   poles, rotation chains applied to rows of U_full, Q_new = blockdiag(Q1, Q2) . U_full
   backtransform   X = H_0 .. H_{n-3} Z in blocks of 32 reflectors with S = striu(V^T V) + diag(1/tau)
 
-Developer tool (not imported by the product or the tests).  Run: python tools/proto_trid_dc.py
+Developer tool (not imported by the product; tests/helpers.py imports it for rdm_model_stats).  Run: python tools/proto_trid_dc.py
 """
 import numpy as np
 
@@ -127,7 +127,8 @@ def merge(D, Qbd, n1, beta):
     ds = D[order].copy(); zs = z[order].copy()
     tol = 8.0 * EPS * max(np.abs(ds).max(), np.abs(zs).max())
     nondef = []; deflated = []; rots = []                       # rots: (col_pj, col_jj, c, s)
-    if rho * np.abs(zs).max() <= tol:
+    all_defl = bool(rho * np.abs(zs).max() <= tol)
+    if all_defl:
         deflated = list(range(n))
     else:
         pj = -1
@@ -171,9 +172,11 @@ def merge(D, Qbd, n1, beta):
         Ufull[order[sp], frank[k + t]] = 1.0; pcol[order[sp]] = frank[k + t]
     # rotation chains on the rows of Ufull, in reverse order
     t = len(rots) - 1
+    longest = 0
     while t >= 0:
         b = t; a = t
         while a > 0 and rots[a - 1][1] == rots[a][0]: a -= 1
+        longest = max(longest, b - a + 1)
         R = Ufull[rots[b][1], :].copy()
         for u in range(b, a - 1, -1):
             cp, cj, c_, s_ = rots[u]
@@ -186,10 +189,11 @@ def merge(D, Qbd, n1, beta):
     Qn = np.zeros_like(Qbd)
     Qn[:n1, :] = Qbd[:n1, :n1] @ Ufull[:n1, :]
     Qn[n1:, :] = Qbd[n1:, n1:] @ Ufull[n1:, :]
-    return Dn, Qn, k
+    return Dn, Qn, k, (n, k, len(rots), longest, all_defl)
 
 
-def stedc(d, e, leaf=32):
+def stedc(d, e, leaf=32, detail=None):
+    """detail: an optional list that receives one (n, k, rotations, longest rotation chain, all deflated) per merge, leaves' level first."""
     n = len(d)
     scale = max(np.abs(d).max(), np.abs(e).max() if n > 1 else 0.0)
     if scale == 0.0: return np.zeros(n), np.eye(n), []
@@ -222,8 +226,9 @@ def stedc(d, e, leaf=32):
             n1 = len(D1)
             Qbd = np.zeros((n1 + len(D2),) * 2); Qbd[:n1, :n1] = Q1; Qbd[n1:, n1:] = Q2
             s = bb[i] + n1
-            Dn, Qn, k = merge(np.concatenate([D1, D2]), Qbd, n1, e[s - 1])
+            Dn, Qn, k, info = merge(np.concatenate([D1, D2]), Qbd, n1, e[s - 1])
             nD.append(Dn); nQ.append(Qn); stats.append((len(Dn), k))
+            if detail is not None: detail.append(info)
         Ds, Qs = nD, nQ
     return Ds[0] * scale, Qs[0], stats
 
