@@ -119,6 +119,11 @@ class EigsStats(C.Structure):
                 ("residual", C.c_double), ("seconds", C.c_double)]
 
 
+class CvStats(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("n_matvec", C.c_int32), ("dead", C.c_int32),
+                ("residual", C.c_double), ("true_residual", C.c_double)]
+
+
 # name -> (restype, argtypes): every symbol include/dmrgx.h declares
 SIGNATURES = {
     "dmrgx_abi_version": (C.c_int32, []),
@@ -179,6 +184,9 @@ SIGNATURES = {
                                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p]),
     "dmrgx_kron_chebyshev_moments": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p]),
+    "dmrgx_kron_correction_vector": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                 C.POINTER(CvStats), C.c_void_p]),
     "dmrgx_eigs_comm_timing": (C.c_int32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),
     "dmrgx_eigs_lowest": (C.c_int32, [C.c_void_p, C.POINTER(EigsOpts), C.POINTER(C.c_double), C.c_void_p,
                                       C.POINTER(EigsStats), C.c_void_p]),

@@ -260,6 +260,33 @@ public:
                 for (size_t k = 0; k < dsf_cheb_omega.size(); ++k) dsf_cheb_omega[k] = dsf_cheb_omega.size() > 1 ? om[0] + (om[1] - om[0]) * (double)k / (double)(dsf_cheb_omega.size() - 1) : om[0];
             }
         }
+        {   /* -dsf_cv c0,c1,...: the correction vectors of G_ic(w + i eta) from every listed site c (CalculateCorrectionVectors) */
+            PetscBool have_sites = PETSC_FALSE;
+            PetscInt nc = 4096;
+            dsf_cv_sites.assign((size_t)nc, 0);
+            ierr = PetscOptionsGetIntArray(NULL, NULL, "-dsf_cv", dsf_cv_sites.data(), &nc, &have_sites); CHKERRQ(ierr);
+            dsf_cv_sites.resize(have_sites ? (size_t)nc : 0);
+            use_dsf_cv = (have_sites && nc > 0) ? PETSC_TRUE : PETSC_FALSE;
+        }
+        if (use_dsf_cv) {
+            if (mpi_size > 1) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-dsf_cv is not available on more than one rank (got %d): the conjugate-gradient run has no collectives.", (int)mpi_size);
+            for (PetscInt c : dsf_cv_sites) if (c < 0 || c >= num_sites) SETERRQ2(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cv: site %lld is outside [0, %lld), the lattice sites in the numbering of To1D.", LLD(c), LLD(num_sites));
+            PetscInt no = 3;
+            PetscReal om[3] = {0.0, 0.0, 0.0};
+            PetscBool have_omega = PETSC_FALSE;
+            ierr = PetscOptionsGetRealArray(NULL, NULL, "-dsf_cv_omega", om, &no, &have_omega); CHKERRQ(ierr);
+            if (!have_omega) SETERRQ(mpi_comm, PETSC_ERR_ARG_WRONG, "-dsf_cv needs -dsf_cv_omega w0,w1,nw: the frequencies at which the correction vectors are solved.");
+            if (!(no == 3 && std::isfinite(om[0]) && std::isfinite(om[1]) && om[0] <= om[1] && om[2] >= 1.0 && om[2] <= 1e6 && om[2] == std::floor(om[2]) && (om[2] > 1.0 || om[0] == om[1])))
+                SETERRQ1(mpi_comm, PETSC_ERR_ARG_WRONG, "-dsf_cv_omega needs w0,w1,nw: nw >= 1 frequencies from w0 to w1 (nw = 1: w0 = w1). Got %lld numbers.", LLD(no));
+            dsf_cv_omega.resize((size_t)om[2]);
+            for (size_t k = 0; k < dsf_cv_omega.size(); ++k) dsf_cv_omega[k] = dsf_cv_omega.size() > 1 ? om[0] + (om[1] - om[0]) * (double)k / (double)(dsf_cv_omega.size() - 1) : om[0];
+            ierr = PetscOptionsGetReal(NULL, NULL, "-dsf_cv_eta", &dsf_cv_eta, NULL); CHKERRQ(ierr);
+            if (!(dsf_cv_eta > 0.0) || !std::isfinite(dsf_cv_eta)) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cv_eta must be positive and finite. Got %g.", dsf_cv_eta);
+            ierr = PetscOptionsGetReal(NULL, NULL, "-dsf_cv_tol", &dsf_cv_tol, NULL); CHKERRQ(ierr);
+            if (!(dsf_cv_tol > 0.0) || dsf_cv_tol >= 1.0) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cv_tol must lie in (0, 1). Got %g.", dsf_cv_tol);
+            ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_cv_maxit", &dsf_cv_maxit, NULL); CHKERRQ(ierr);
+            if (dsf_cv_maxit < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cv_maxit must be at least 1. Got %lld.", LLD(dsf_cv_maxit));
+        }
         ierr = PetscOptionsGetBool(NULL, NULL, "-step_profile", &step_profile, NULL); CHKERRQ(ierr);
 
         PetscBool opt = PETSC_FALSE;
@@ -507,7 +534,7 @@ public:
         spectra_writer.Drain();
         if (fp_entanglement) { fprintf(fp_entanglement, "\n]\n"); fclose(fp_entanglement); fp_entanglement = NULL; }
         if (fp_kron) { fprintf(fp_kron, "\n]\n"); fclose(fp_kron); fp_kron = NULL; }
-        spin_file.Close(); dimer_file.Close(); dsf_file.Close(); dsf_sites_file.Close(); dsf_cheb_file.Close();
+        spin_file.Close(); dimer_file.Close(); dsf_file.Close(); dsf_sites_file.Close(); dsf_cheb_file.Close(); dsf_cv_file.Close();
         if (fp_corr) {
             if (!corr_headers_printed) { PetscErrorCode e2 = PrintCorrelationHeaders(); CHKERRQ(e2); }
             fprintf(fp_corr, "\n  ]\n}\n"); fclose(fp_corr); fp_corr = NULL;
@@ -637,6 +664,7 @@ public:
         if (use_dsf && do_measurements) { ierr = CalculateDynamicalStructureFactor(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* needs the plan */
         if (use_dsf_sites && do_measurements) { ierr = CalculateDynamicalCorrelations(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
         if (use_dsf_cheb && do_measurements) { ierr = CalculateChebyshevCorrelations(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
+        if (use_dsf_cv && do_measurements) { ierr = CalculateCorrectionVectors(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
         ierr = MatDestroy_KronSumShell(&H); CHKERRQ(ierr);
         ierr = MatDestroy(&H); CHKERRQ(ierr);
         ierr = PetscTime(&tdiag); CHKERRQ(ierr);
@@ -1810,6 +1838,115 @@ public:
         return 0;
     }
 
+    /** -dsf_cv c0,c1,... (engine extension): the real-space dynamical correlations of the ground state at given complex frequencies,
+            G_ic(w_k + i eta) = < Sz_i psi , 1 / (E0 + w_k + i eta - H) Sz_c psi > / <psi|psi>,   for ALL sites i,
+        by the correction-vector method: one dmrgx_kron_correction_vector call per reference site c and frequency w_k of -dsf_cv_omega
+        solves [(H - sigma)^2 + eta^2] Y = -eta Sz_c psi, sigma = E0 + w_k, by conjugate gradients on the device to the relative residual
+        -dsf_cv_tol (at most -dsf_cv_maxit iterations, two MatMults each), forms X = (H - sigma) Y / eta and takes the overlaps of both with
+        the images of all sites.  Unlike -dsf, -dsf_sites and -dsf_cheb the error at each frequency is controlled -- |ImG - exact| <=
+        |u| |v| Residual / eta -- and the broadening is a true Lorentzian of half width eta.  No warm start between frequencies.
+        The images u_i = Sz_i psi of all N sites (dmrgx_kron_term_apply, lattice order) stay on the device for the whole measurement, as
+        for -dsf_cheb; beside them Y, X and the four pool vectors of the solver: N + 6 vectors of N_sb doubles.
+        The record: ImG[i][k], ReG[i][k] (the overlaps over <psi|psi>), Aw[i][k] = -ImG / pi, SqwGrid[q][k] = sum_i cos(q . (r_i - r_c))
+        Aw[i][k] (row nx Ly + ny; (1/N) sum_c SqwGrid is the Lorentzian-broadened S^zz(q, w)), Iterations[k], Converged[k] and Residual[k],
+        the true residual |b - A Y| / |b| of the returned Y.  A frequency that did not converge within -dsf_cv_maxit is written as it is,
+        with a warning here.  The caveats of -dsf_sites apply: the block bases are optimised for the ground state alone -- no correction
+        vector is targeted in the density matrix.  Site s of the right block is lattice site N - 1 - s.  One rank only (refused at
+        start-up otherwise). */
+    PetscErrorCode CalculateCorrectionVectors(KronBlocks_t& KronBlocks, const Vec& gsv_r, Mat& H, PetscScalar E0)
+    {
+        PetscLogDouble t0, t1;
+        PetscTime(&t0);
+        dmrgx_host::CentreFrame F;
+        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, "Correction vectors"); CHKERRQ(ierr);
+        const PetscInt nls = F.nsites[0], N = F.N, Lx = Ham.Lx(), Ly = Ham.Ly(), M = Lx * Ly, nw = (PetscInt)dsf_cv_omega.size();
+        dmrgx_host::SiteOperators T(F);
+        std::vector<PetscInt> site, op_of((size_t)N, -1), rx((size_t)N), ry((size_t)N);      /* site[a]: lattice site of operator a; op_of: its inverse */
+        ierr = T.AllSites(OpSz, site); CHKERRQ(ierr);
+        for (PetscInt a = 0; a < N; ++a) op_of[(size_t)site[(size_t)a]] = a;
+        for (PetscInt s = 0; s < N; ++s) {
+            if (op_of[(size_t)s] < 0) SETERRQ1(mpi_comm, 1, "Correction vectors: site %lld is in neither block.", LLD(s));
+            ierr = Ham.To2D(s, rx[(size_t)s], ry[(size_t)s]); CHKERRQ(ierr);
+        }
+        auto term_of = [&](PetscInt a) { return a < nls ? dmrgx_term{1.0, (int32_t)a, -1} : dmrgx_term{1.0, -1, (int32_t)(a - nls)}; };
+        const int64_t n = gsv_r->n, ld = n + (n & 1);
+        const double* psi = gsv_r->buf->dev_ro();
+        double norm = 0.0;
+        if (dmrgx_dot(n, psi, psi, &norm, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
+        /* the images of all sites, row s = Sz_s psi, built in chunks of at most 1 GiB, and the two vectors of a solve */
+        std::unique_ptr<dmrgx_host::DevBuffer> U, YX;
+        try {
+            U.reset(new dmrgx_host::DevBuffer((size_t)(N * ld), dmrgx_host::DevBuffer::device_only_t{}));
+            YX.reset(new dmrgx_host::DevBuffer((size_t)(2 * ld), dmrgx_host::DevBuffer::device_only_t{}));
+        }
+        catch (const std::exception& e) { SETERRQ3(mpi_comm, PETSC_ERR_MEM, "Correction vectors: no memory for the images of %lld sites and two vectors of %lld states (%.3f GB): %s", LLD(N), LLD(n), (double)((N + 2) * ld) * 8e-9, e.what()); }
+        const PetscInt chunk = std::max<PetscInt>(1, std::min<PetscInt>(N, (PetscInt)((((int64_t)1 << 30) / (int64_t)sizeof(double)) / ld)));
+        std::vector<dmrgx_term> terms;
+        std::vector<int32_t> vec_first;
+        for (PetscInt s0 = 0; s0 < N; s0 += chunk) {
+            const PetscInt cnt = std::min<PetscInt>(chunk, N - s0);
+            terms.clear(); vec_first.assign(1, 0);
+            for (PetscInt s = s0; s < s0 + cnt; ++s) { terms.push_back(term_of(op_of[(size_t)s])); vec_first.push_back((int32_t)terms.size()); }
+            if (dmrgx_kron_term_apply(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
+                                      (int32_t)cnt, vec_first.data(), terms.data(), U->dev_uninitialised() + s0 * ld, ld, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_apply: %s", dmrgx_last_error());
+        }
+
+        struct Run { PetscInt c = 0; double norm2 = 0.0; std::vector<double> iterations, converged, residual, im, re, aw, grid; };
+        std::vector<Run> runs(dsf_cv_sites.size());
+        std::vector<double> im((size_t)N), re((size_t)N), column((size_t)(N * N));
+        double* Yd = YX->dev_uninitialised();
+        double* Xd = Yd + ld;
+        PetscInt matmults = 0, iterations = 0;
+        for (size_t ir = 0; ir < runs.size(); ++ir) {
+            Run& R = runs[ir];
+            R.c = dsf_cv_sites[ir];
+            R.iterations.assign((size_t)nw, 0.0); R.converged.assign((size_t)nw, 0.0); R.residual.assign((size_t)nw, 0.0);
+            R.im.assign((size_t)(N * nw), 0.0); R.re.assign((size_t)(N * nw), 0.0); R.aw.assign((size_t)(N * nw), 0.0); R.grid.assign((size_t)(M * nw), 0.0);
+            for (PetscInt k = 0; k < nw; ++k) {
+                dmrgx_cv_stats cs;
+                if (dmrgx_kron_correction_vector(H->plan, U->dev_ro() + R.c * ld, (double)E0 + dsf_cv_omega[(size_t)k], dsf_cv_eta, dsf_cv_tol, (int32_t)dsf_cv_maxit, 0, Yd, Xd,
+                                                 (int32_t)N, U->dev_ro(), ld, &R.norm2, im.data(), re.data(), &cs, nullptr))
+                    SETERRQ1(mpi_comm, 1, "dmrgx_kron_correction_vector: %s", dmrgx_last_error());
+                matmults += cs.n_matvec; iterations += cs.iterations;
+                if (!cs.converged) printf("  * WARNING: -dsf_cv: site %lld, w = %.6f: not converged after %d iterations (residual %.3e, tol %.3e%s); the record holds the last iterate.\n",
+                                          LLD(R.c), dsf_cv_omega[(size_t)k], (int)cs.iterations, cs.true_residual, dsf_cv_tol, cs.dead ? ", the iteration broke down" : "");
+                R.iterations[(size_t)k] = (double)cs.iterations; R.converged[(size_t)k] = (double)cs.converged; R.residual[(size_t)k] = cs.true_residual;
+                /* the lattice Fourier sum of column c alone: T[i][c] = Aw[i][k], every other entry zero */
+                std::fill(column.begin(), column.end(), 0.0);
+                for (PetscInt s = 0; s < N; ++s) {
+                    const size_t at = (size_t)(s * nw + k);
+                    R.im[at] = im[(size_t)s] / norm; R.re[at] = re[(size_t)s] / norm; R.aw[at] = -R.im[at] / (0.5 * dmrgx_host::two_pi);
+                    column[(size_t)(s * N + R.c)] = R.aw[at];
+                }
+                const std::vector<double> Sq = dmrgx_host::LatticeFourier(Lx, Ly, rx.data(), ry.data(), column.data(), N, 1.0);
+                for (PetscInt q = 0; q < M; ++q) R.grid[(size_t)(q * nw + k)] = Sq[(size_t)q];
+            }
+        }
+        PetscTime(&t1);
+        if (verbose) printf("  * Correction vectors: %lld reference sites x %lld frequencies, eta %.6f, %lld iterations, %lld MatMults on %lld states, tDsfCv %.6f s\n",
+                            LLD(runs.size()), LLD(nw), dsf_cv_eta, LLD(iterations), LLD(matmults), LLD(n), t1 - t0);
+        ierr = dsf_cv_file.Begin(data_dir + "CorrectionVectors.json"); CHKERRQ(ierr);
+        FILE* fp = dsf_cv_file.fp;
+        fprintf(fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"E0\": %.17g, \"Norm\": %.17g, \"Eta\": %.17g, \"Tol\": %.17g, \"MaxIt\": %lld, \"tDsfCv\": %.9g, \"MatMults\": %lld,\n   \"Omega\": ",
+                LLD(GlobIdx), LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, norm, dsf_cv_eta, dsf_cv_tol, LLD(dsf_cv_maxit), t1 - t0, LLD(matmults));
+        dsf_cv_file.Row(dsf_cv_omega);
+        fprintf(fp, ",\n   \"Sites\": [\n");
+        for (size_t ir = 0; ir < runs.size(); ++ir) {
+            const Run& R = runs[ir];
+            fprintf(fp, "   {\"Site\": %lld, \"r\": [%lld, %lld], \"Norm2\": %.17g,\n   \"Iterations\": ", LLD(R.c), LLD(rx[(size_t)R.c]), LLD(ry[(size_t)R.c]), R.norm2);
+            dsf_cv_file.Row(R.iterations); fprintf(fp, ",\n   \"Converged\": ");
+            dsf_cv_file.Row(R.converged); fprintf(fp, ",\n   \"Residual\": ");
+            dsf_cv_file.Row(R.residual); fprintf(fp, ",\n");
+            dsf_cv_file.Table("ImG", R.im, N, nw, ",\n");
+            dsf_cv_file.Table("ReG", R.re, N, nw, ",\n");
+            dsf_cv_file.Table("Aw", R.aw, N, nw, ",\n");
+            dsf_cv_file.Table("SqwGrid", R.grid, M, nw, ir + 1 < runs.size() ? "},\n" : "}\n");
+        }
+        fprintf(fp, "   ]}");
+        fflush(fp);
+        return 0;
+    }
+
     /** -corr_dimer 1 (engine extension): the dimer-dimer table < D_b D_b' > over all pairs of nearest-neighbour bonds, D_b = S_i . S_j
         = Sz_i Sz_j + (Sp_i Sm_j + Sm_i Sp_j) / 2, its connected part and the dimer structure factors of the x and the y bonds, at every
         measurement point.  < psi | D_b^T D_b' | psi > = < D_b psi , D_b' psi >: the whole table is ONE dmrgx_kron_term_gram call over the
@@ -2260,7 +2397,7 @@ public:
             for (const Op& o : c.SysOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
             for (const Op& o : c.EnvOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
         }
-        if (use_corr_matrix || use_corr_dimer || use_dsf || use_dsf_sites || use_dsf_cheb) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer, -dsf, -dsf_sites, -dsf_cheb: Sz and Sp of every site of both centre blocks, on every rank */
+        if (use_corr_matrix || use_corr_dimer || use_dsf || use_dsf_sites || use_dsf_cheb || use_dsf_cv) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer, -dsf, -dsf_sites, -dsf_cheb, -dsf_cv: Sz and Sp of every site of both centre blocks, on every rank */
         need_built = true;
         return 0;
     }
@@ -2483,6 +2620,13 @@ private:
     PetscReal dsf_cheb_window[2] = {0.0, 0.0};  /* -dsf_cheb_window lo,hi: the window given, no bound run */
     std::vector<double> dsf_cheb_omega;         /* -dsf_cheb_omega w0,w1,nw: the grid of the Jackson-broadened SqwGrid */
     dmrgx_host::JsonRecordFile dsf_cheb_file{"%.17g"};  /* created at the first measurement with -dsf_cheb */
+    PetscBool use_dsf_cv = PETSC_FALSE;         /* -dsf_cv c0,c1,...: correction vectors of G_ic(w + i eta), CorrectionVectors.json (CalculateCorrectionVectors) */
+    std::vector<PetscInt> dsf_cv_sites;         /* the reference sites c, lattice numbering of To1D */
+    std::vector<double> dsf_cv_omega;           /* -dsf_cv_omega w0,w1,nw: the frequencies, one solve per site and frequency */
+    PetscReal dsf_cv_eta = 0.1;                 /* -dsf_cv_eta: half width at half maximum of the Lorentzian */
+    PetscReal dsf_cv_tol = 1e-8;                /* -dsf_cv_tol: |r| <= tol |b| ends a solve */
+    PetscInt dsf_cv_maxit = 2000;               /* -dsf_cv_maxit: iterations per solve at most */
+    dmrgx_host::JsonRecordFile dsf_cv_file{"%.17g"};    /* created at the first measurement with -dsf_cv */
     PetscBool use_corr_batch = PETSC_TRUE;      /* -corr_batch 0: every correlator through its own MatMult + dot, as the reference does */
 };
 

@@ -189,6 +189,30 @@ class KronPlan:
                                                              int(ldu), C.byref(norm2), diag, cross, C.byref(done), self._stream_ptr(stream)))
         return norm2.value, np.array(diag[:2 * K + 1]), np.array(cross[:(K + 1) * nu]).reshape(K + 1, nu), done.value
 
+    def correction_vector(self, v0, sigma, eta, tol=0.0, max_it=1000, check_every=0, U=None, want_real=True, stream=None):
+        """The correction vector 1 / (sigma + i eta - H) v0 = X + i Y (dmrgx_kron_correction_vector): conjugate gradients on
+        (H - sigma)^2 + eta^2, device-resident, convergence |r| <= tol |b| decided on the device (tol 0: 1e-8), iterations enqueued in blocks
+        of check_every (0: 8).  v0: f64 device tensor of n_states, only read.  U: None, or a 2-D f64 device tensor of nu rows with unit
+        stride along the vector (its row stride is the library's ldu), only read.  want_real False: X is not formed.  Returns a dict: Y, X
+        (device tensors; X None when not wanted), norm2 = |v0|^2, im[nu] = <U[i], Y>, re[nu] = <U[i], X> (None without X), and the fields of
+        dmrgx_cv_stats: iterations, converged, n_matvec, dead, residual, true_residual.  Not converging within max_it is no error."""
+        assert v0.dtype == torch.float64 and v0.is_contiguous() and v0.numel() >= self.info.n_states
+        n = self.info.n_states
+        nu, u_ptr, ldu = 0, C.c_void_p(), 0
+        if U is not None:
+            assert U.dtype == torch.float64 and U.dim() == 2 and U.shape[1] >= n and (U.shape[1] <= 1 or U.stride(1) == 1)
+            nu, u_ptr, ldu = U.shape[0], C.c_void_p(U.data_ptr()), U.stride(0) if U.shape[0] > 1 else max(U.stride(0), U.shape[1])
+        Y = torch.empty(n, dtype=torch.float64, device=v0.device)
+        X = torch.empty(n, dtype=torch.float64, device=v0.device) if want_real else None
+        norm2, stats = C.c_double(0.0), _capi.CvStats()
+        im, re = (C.c_double * max(nu, 1))(), (C.c_double * max(nu, 1))()
+        _capi.check(_capi.lib().dmrgx_kron_correction_vector(self._handle, C.c_void_p(v0.data_ptr()), float(sigma), float(eta), float(tol), int(max_it), int(check_every),
+                                                             C.c_void_p(Y.data_ptr()), C.c_void_p(X.data_ptr()) if want_real else C.c_void_p(), int(nu), u_ptr, int(ldu),
+                                                             C.byref(norm2), im, re if want_real else None, C.byref(stats), self._stream_ptr(stream)))
+        out = dict(Y=Y, X=X, norm2=norm2.value, im=np.array(im[:nu]), re=np.array(re[:nu]) if want_real else None)
+        out.update({k: getattr(stats, k) for k, _ in _capi.CvStats._fields_})
+        return out
+
     def timing(self, enable):
         _capi.check(_capi.lib().dmrgx_kron_plan_timing(self._handle, 1 if enable else 0))
 

@@ -30,6 +30,8 @@
  *                               superblock Hamiltonian from such a vector: the continued fraction behind a dynamical structure factor
  *   dmrgx_kron_lanczos_basis    (-dsf); the same run with the basis kept and reorthogonalised, for overlaps with it (-dsf_sites)
  *   dmrgx_kron_chebyshev_moments  the Chebyshev recursion on the planned Hamiltonian and its moments with a family of vectors (-dsf_cheb)
+ *   dmrgx_kron_correction_vector  the correction vector 1 / (sigma + i eta - H) v0 by a device-resident conjugate-gradient run, and its
+ *                               overlaps with a family of vectors: G_ic(w + i eta) under a true Lorentzian (-dsf_cv)
  *   dmrgx_comm_*             <- the communicator of the reference's MPI path: VecScatter-to-all of x inside every MatMult
  *                               (src/DMRGKron.cpp:1833-1834) and the MPI_Allreduce behind SLEPc's VecDot / VecNorm
  *
@@ -531,6 +533,47 @@ dmrgx_status dmrgx_kron_chebyshev_moments(dmrgx_kron_plan* plan, const double* v
                                           double* norm2, double* mu_diag /* host [2 nsteps + 1] */,
                                           double* mu_cross /* host [(nsteps + 1) * nu], row n; may be NULL when nu == 0 */,
                                           int32_t* nsteps_done, void* stream);
+
+/* ---- Correction vector at one complex frequency (Lorentzian-broadened spectra to a stated residual) -------------------- */
+/* 1 / (sigma + i eta - H) v0 = X + i Y on the planned Hamiltonian (world_size == 1; a striped plan is refused with DMRGX_ERR_ARG):
+ *   Y = -eta [(H - sigma)^2 + eta^2]^-1 v0,   X = (H - sigma) Y / eta,
+ * so that for any u  -(1/pi) <u, Y> = (1/pi) sum_n <u|n><n|v0> eta / ((sigma - E_n)^2 + eta^2): the spectral function under a Lorentzian of
+ * half width at half maximum eta, and <u, X> its real counterpart.  Y is found by conjugate gradients on the positive definite
+ * A = (H - sigma)^2 + eta^2 with b = -eta v0 and y_0 = 0.  Per iteration two MatMults (t = H p, u = H s with s = t - sigma p), p.A p as the sum
+ * of squares s.s + eta^2 p.p, three fused vector kernels and two one-workgroup scalar kernels; alpha, beta, r.r, the count and the flags
+ * live in a small device array.  Convergence is decided on the device: r.r <= tol^2 b.b (tol == 0: 1e-8; outside [0, 1): DMRGX_ERR_ARG).
+ * Iterations are enqueued in blocks of check_every (0: 8); after each block one small copy brings the count and the flags back -- the only
+ * place where the host looks at the device.  Once the run has converged, died or counted max_it iterations, the kernels that remain in
+ * the block leave every vector alone and count nothing (their MatMults still run): Y, X, im, re, iterations and both residuals do not
+ * depend on check_every, bit for bit; only n_matvec = 2 blocks check_every + 2 does.  After the loop two more MatMults give X (written when
+ * X_dev is not NULL) and the true residual |b - A Y| / |b| of the returned Y.
+ * v0 (reference layout, n_states doubles) is only read.  Y_dev and X_dev are the caller's buffers of n_states doubles, any 8-byte alignment;
+ * every element is written.  U, ldu, nu as in dmrgx_kron_chebyshev_moments (only read; columns beyond n_states neither read nor touched);
+ * the overlaps im[i] = <u_i, Y> and re[i] = <u_i, X> are two dmrgx_vec_gram calls after the loop.  The MatMult runs between pool vectors
+ * only, two fixed (x, y) pairs; it never sees Y, X or U.
+ * Not reaching tol within max_it is no error: DMRGX_OK with converged = 0 and the last iterate.  A v0 whose squared norm is not a positive
+ * finite number gives *norm2 = 0, Y = X = exact zeros, zero overlaps, iterations = 0, converged = 0, dead = 1.  A partial sum that is not
+ * finite, or a p.A p that is not positive and finite, sets dead before that iteration reaches Y: with a finite H and U no output is ever
+ * NaN.  (An H that is not finite shows in the closing MatMults: dead = 1 and true_residual = infinity.)
+ * Refused (DMRGX_ERR_ARG): a null plan, v0, Y, norm2 or stats; nu > 0 with im NULL, or with X_dev given and re NULL; eta not positive and
+ * finite; sigma not finite; max_it < 1; check_every < 0; nu < 0; nu > 0 with U_dev NULL or ldu < n_states; Y or X overlapping v0, U or
+ * each other.  Memory from the pool: four vectors of n_states doubles, 2 ceil(n_states / 2048) partial sums, 12 + 2 nu scalars.  Fixed
+ * grids, fixed-order sums, no atomics: two runs give the same bits. */
+typedef struct {
+    int32_t iterations;      /* CG iterations that counted                                              */
+    int32_t converged;       /* 1: the recurrence residual reached tol                                  */
+    int32_t n_matvec;        /* dmrgx_kron_apply calls enqueued (frozen iterations of the last block included) */
+    int32_t dead;            /* 1: a sum turned non-finite or p.A p was not positive: stopped before that update */
+    double  residual;        /* |r| / |b| of the recurrence at the last counted iteration               */
+    double  true_residual;   /* |b - A Y| / |b| recomputed from the returned Y                          */
+} dmrgx_cv_stats;
+dmrgx_status dmrgx_kron_correction_vector(dmrgx_kron_plan* plan, const double* v0_dev, double sigma, double eta,
+                                          double tol, int32_t max_it, int32_t check_every,
+                                          double* Y_dev, double* X_dev /* may be NULL */,
+                                          int32_t nu, const double* U_dev, int64_t ldu,
+                                          double* norm2, double* im /* host [nu]: <u_i, Y> */,
+                                          double* re /* host [nu]: <u_i, X>; NULL iff X_dev NULL or nu == 0 */,
+                                          dmrgx_cv_stats* stats, void* stream);
 
 #ifdef __cplusplus
 }
