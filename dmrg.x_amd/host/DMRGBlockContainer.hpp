@@ -210,38 +210,13 @@ public:
             ierr = PetscOptionsGetIntArray(NULL, NULL, "-dsf_q", dsf_q.data(), &nq, &have_q); CHKERRQ(ierr);
             dsf_q.resize((size_t)nq);
             if (!have_q || nq < 2 || nq % 2) SETERRQ1(mpi_comm, PETSC_ERR_ARG_WRONG, "-dsf 1 needs -dsf_q nx0,ny0,nx1,ny1,...: pairs of integers, q = (2 pi nx / Lx, 2 pi ny / Ly). Got %lld numbers.", LLD(nq));
-            ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_steps", &dsf_steps, NULL); CHKERRQ(ierr);
-            if (dsf_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_steps must be at least 1. Got %lld.", LLD(dsf_steps));
-            ierr = PetscOptionsGetReal(NULL, NULL, "-dsf_breakdown_tol", &dsf_breakdown_tol, NULL); CHKERRQ(ierr);
-            if (!(dsf_breakdown_tol >= 0.0) || dsf_breakdown_tol >= 1.0) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_breakdown_tol must lie in [0, 1). Got %g.", dsf_breakdown_tol);
+            ierr = ReadLanczosStepOptions(); CHKERRQ(ierr);
         }
-        {   /* -dsf_sites c0,c1,...: the real-space dynamical correlations G_ic(w) from every listed site c (CalculateDynamicalCorrelations) */
-            PetscBool have_sites = PETSC_FALSE;
-            PetscInt nc = 4096;
-            dsf_sites.assign((size_t)nc, 0);
-            ierr = PetscOptionsGetIntArray(NULL, NULL, "-dsf_sites", dsf_sites.data(), &nc, &have_sites); CHKERRQ(ierr);
-            dsf_sites.resize(have_sites ? (size_t)nc : 0);
-            use_dsf_sites = (have_sites && nc > 0) ? PETSC_TRUE : PETSC_FALSE;
-        }
-        if (use_dsf_sites) {
-            if (mpi_size > 1) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-dsf_sites is not available on more than one rank (got %d): the Lanczos run behind G_ic(w) has no collectives.", (int)mpi_size);
-            for (PetscInt c : dsf_sites) if (c < 0 || c >= num_sites) SETERRQ2(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_sites: site %lld is outside [0, %lld), the lattice sites in the numbering of To1D.", LLD(c), LLD(num_sites));
-            ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_steps", &dsf_steps, NULL); CHKERRQ(ierr);
-            if (dsf_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_steps must be at least 1. Got %lld.", LLD(dsf_steps));
-            ierr = PetscOptionsGetReal(NULL, NULL, "-dsf_breakdown_tol", &dsf_breakdown_tol, NULL); CHKERRQ(ierr);
-            if (!(dsf_breakdown_tol >= 0.0) || dsf_breakdown_tol >= 1.0) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_breakdown_tol must lie in [0, 1). Got %g.", dsf_breakdown_tol);
-        }
-        {   /* -dsf_cheb c0,c1,...: the Chebyshev moments of G_ic(w) from every listed site c (CalculateChebyshevCorrelations) */
-            PetscBool have_sites = PETSC_FALSE;
-            PetscInt nc = 4096;
-            dsf_cheb_sites.assign((size_t)nc, 0);
-            ierr = PetscOptionsGetIntArray(NULL, NULL, "-dsf_cheb", dsf_cheb_sites.data(), &nc, &have_sites); CHKERRQ(ierr);
-            dsf_cheb_sites.resize(have_sites ? (size_t)nc : 0);
-            use_dsf_cheb = (have_sites && nc > 0) ? PETSC_TRUE : PETSC_FALSE;
-        }
-        if (use_dsf_cheb) {
-            if (mpi_size > 1) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-dsf_cheb is not available on more than one rank (got %d): the Chebyshev recursion has no collectives.", (int)mpi_size);
-            for (PetscInt c : dsf_cheb_sites) if (c < 0 || c >= num_sites) SETERRQ2(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cheb: site %lld is outside [0, %lld), the lattice sites in the numbering of To1D.", LLD(c), LLD(num_sites));
+        /* -dsf_sites c0,c1,...: the real-space dynamical correlations G_ic(w) from every listed site c (CalculateDynamicalCorrelations) */
+        ierr = ReadSiteListOption("-dsf_sites", "the Lanczos run behind G_ic(w)", dsf_sites, use_dsf_sites); CHKERRQ(ierr);
+        if (use_dsf_sites && !use_dsf) { ierr = ReadLanczosStepOptions(); CHKERRQ(ierr); }      /* (-dsf has read them above) */
+        ierr = ReadSiteListOption("-dsf_cheb", "the Chebyshev recursion", dsf_cheb_sites, use_dsf_cheb); CHKERRQ(ierr);
+        if (use_dsf_cheb) {   /* -dsf_cheb c0,c1,...: the Chebyshev moments of G_ic(w) from every listed site c (CalculateChebyshevCorrelations) */
             ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_cheb_steps", &dsf_cheb_steps, NULL); CHKERRQ(ierr);
             if (dsf_cheb_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cheb_steps must be at least 1. Got %lld.", LLD(dsf_cheb_steps));
             ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_cheb_bound_steps", &dsf_cheb_bound_steps, NULL); CHKERRQ(ierr);
@@ -250,36 +225,13 @@ public:
             ierr = PetscOptionsGetRealArray(NULL, NULL, "-dsf_cheb_window", dsf_cheb_window, &nw, &dsf_cheb_have_window); CHKERRQ(ierr);
             if (dsf_cheb_have_window && !(nw == 2 && dsf_cheb_window[0] < dsf_cheb_window[1] && std::isfinite(dsf_cheb_window[0]) && std::isfinite(dsf_cheb_window[1])))
                 SETERRQ1(mpi_comm, PETSC_ERR_ARG_WRONG, "-dsf_cheb_window needs lo,hi: two finite energies, lo < hi. Got %lld numbers.", LLD(nw));
-            PetscInt no = 3;
-            PetscReal om[3] = {0.0, 0.0, 0.0};
-            ierr = PetscOptionsGetRealArray(NULL, NULL, "-dsf_cheb_omega", om, &no, &dsf_cheb_have_omega); CHKERRQ(ierr);
-            if (dsf_cheb_have_omega) {
-                if (!(no == 3 && std::isfinite(om[0]) && std::isfinite(om[1]) && om[0] <= om[1] && om[2] >= 1.0 && om[2] <= 1e6 && om[2] == std::floor(om[2]) && (om[2] > 1.0 || om[0] == om[1])))
-                    SETERRQ1(mpi_comm, PETSC_ERR_ARG_WRONG, "-dsf_cheb_omega needs w0,w1,nw: nw >= 1 frequencies from w0 to w1 (nw = 1: w0 = w1). Got %lld numbers.", LLD(no));
-                dsf_cheb_omega.resize((size_t)om[2]);
-                for (size_t k = 0; k < dsf_cheb_omega.size(); ++k) dsf_cheb_omega[k] = dsf_cheb_omega.size() > 1 ? om[0] + (om[1] - om[0]) * (double)k / (double)(dsf_cheb_omega.size() - 1) : om[0];
-            }
+            ierr = ReadOmegaGridOption("-dsf_cheb_omega", dsf_cheb_omega, dsf_cheb_have_omega); CHKERRQ(ierr);
         }
-        {   /* -dsf_cv c0,c1,...: the correction vectors of G_ic(w + i eta) from every listed site c (CalculateCorrectionVectors) */
-            PetscBool have_sites = PETSC_FALSE;
-            PetscInt nc = 4096;
-            dsf_cv_sites.assign((size_t)nc, 0);
-            ierr = PetscOptionsGetIntArray(NULL, NULL, "-dsf_cv", dsf_cv_sites.data(), &nc, &have_sites); CHKERRQ(ierr);
-            dsf_cv_sites.resize(have_sites ? (size_t)nc : 0);
-            use_dsf_cv = (have_sites && nc > 0) ? PETSC_TRUE : PETSC_FALSE;
-        }
-        if (use_dsf_cv) {
-            if (mpi_size > 1) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-dsf_cv is not available on more than one rank (got %d): the conjugate-gradient run has no collectives.", (int)mpi_size);
-            for (PetscInt c : dsf_cv_sites) if (c < 0 || c >= num_sites) SETERRQ2(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cv: site %lld is outside [0, %lld), the lattice sites in the numbering of To1D.", LLD(c), LLD(num_sites));
-            PetscInt no = 3;
-            PetscReal om[3] = {0.0, 0.0, 0.0};
+        ierr = ReadSiteListOption("-dsf_cv", "the conjugate-gradient run", dsf_cv_sites, use_dsf_cv); CHKERRQ(ierr);
+        if (use_dsf_cv) {   /* -dsf_cv c0,c1,...: the correction vectors of G_ic(w + i eta) from every listed site c (CalculateCorrectionVectors) */
             PetscBool have_omega = PETSC_FALSE;
-            ierr = PetscOptionsGetRealArray(NULL, NULL, "-dsf_cv_omega", om, &no, &have_omega); CHKERRQ(ierr);
+            ierr = ReadOmegaGridOption("-dsf_cv_omega", dsf_cv_omega, have_omega); CHKERRQ(ierr);
             if (!have_omega) SETERRQ(mpi_comm, PETSC_ERR_ARG_WRONG, "-dsf_cv needs -dsf_cv_omega w0,w1,nw: the frequencies at which the correction vectors are solved.");
-            if (!(no == 3 && std::isfinite(om[0]) && std::isfinite(om[1]) && om[0] <= om[1] && om[2] >= 1.0 && om[2] <= 1e6 && om[2] == std::floor(om[2]) && (om[2] > 1.0 || om[0] == om[1])))
-                SETERRQ1(mpi_comm, PETSC_ERR_ARG_WRONG, "-dsf_cv_omega needs w0,w1,nw: nw >= 1 frequencies from w0 to w1 (nw = 1: w0 = w1). Got %lld numbers.", LLD(no));
-            dsf_cv_omega.resize((size_t)om[2]);
-            for (size_t k = 0; k < dsf_cv_omega.size(); ++k) dsf_cv_omega[k] = dsf_cv_omega.size() > 1 ? om[0] + (om[1] - om[0]) * (double)k / (double)(dsf_cv_omega.size() - 1) : om[0];
             ierr = PetscOptionsGetReal(NULL, NULL, "-dsf_cv_eta", &dsf_cv_eta, NULL); CHKERRQ(ierr);
             if (!(dsf_cv_eta > 0.0) || !std::isfinite(dsf_cv_eta)) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cv_eta must be positive and finite. Got %g.", dsf_cv_eta);
             ierr = PetscOptionsGetReal(NULL, NULL, "-dsf_cv_tol", &dsf_cv_tol, NULL); CHKERRQ(ierr);
@@ -1501,25 +1453,17 @@ public:
         cos and sin are taken of the exact fraction 2 pi p / (Lx Ly) with their exact zeros, so that a part that vanishes by symmetry
         vanishes in the coefficients too; a part whose |v|^2 <= 1e-20 <psi|psi> (rounding of Sz_tot psi at q = 0, for instance) holds no
         weight a double could resolve next to the others and is recorded without a run: StepsDone 0.
-        Site s of the right block is lattice site N - 1 - s, as in SetUpCorrelation.  One rank only (refused at start-up otherwise). */
+        Set-up (operators, site maps, psi): SzFrame, Measurements.hpp.  One rank only (refused at start-up otherwise). */
     PetscErrorCode CalculateDynamicalStructureFactor(KronBlocks_t& KronBlocks, const Vec& gsv_r, Mat& H, PetscScalar E0)
     {
         PetscLogDouble t0, t1;
         PetscTime(&t0);
-        dmrgx_host::CentreFrame F;
-        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, "Dynamical structure factor"); CHKERRQ(ierr);
-        const PetscInt nls = F.nsites[0], N = F.N, Lx = Ham.Lx(), Ly = Ham.Ly(), M = Lx * Ly;
-        /* Sz of every site of both blocks, and where the site sits on the lattice */
-        dmrgx_host::SiteOperators T(F);
-        std::vector<PetscInt> site, rx((size_t)N), ry((size_t)N);
-        ierr = T.AllSites(OpSz, site); CHKERRQ(ierr);
-        for (PetscInt i = 0; i < N; ++i) { ierr = Ham.To2D(site[(size_t)i], rx[(size_t)i], ry[(size_t)i]); CHKERRQ(ierr); }
+        dmrgx_host::SzFrame S;
+        PetscErrorCode ierr = S.Init(KronBlocks, num_sites, Ham, gsv_r, "Dynamical structure factor"); CHKERRQ(ierr);
+        const PetscInt N = S.F.N, Lx = S.Lx, Ly = S.Ly, M = S.M;
+        const int64_t n = S.n;
         std::vector<dmrgx_term> terms;
         terms.reserve((size_t)N);
-        const int64_t n = gsv_r->n;
-        const double* psi = gsv_r->buf->dev_ro();
-        double norm = 0.0;
-        if (dmrgx_dot(n, psi, psi, &norm, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
         dmrgx_host::DevBuffer v((size_t)n, dmrgx_host::DevBuffer::device_only_t{});
 
         struct Part { double norm2 = 0.0; int32_t done = 0; std::vector<double> alpha, beta, theta, z; };
@@ -1533,19 +1477,19 @@ public:
                 Part& A = P.part[part];
                 terms.clear();
                 for (PetscInt i = 0; i < N; ++i) {
-                    const PetscInt p = (((P.nx * rx[(size_t)i] * Ly + P.ny * ry[(size_t)i] * Lx) % M) + M) % M;      /* q . r = 2 pi p / M exactly */
+                    const PetscInt s = S.site[(size_t)i];                /* operator i of the frame is Sz of lattice site s */
+                    const PetscInt p = (((P.nx * S.rx[(size_t)s] * Ly + P.ny * S.ry[(size_t)s] * Lx) % M) + M) % M;      /* q . r = 2 pi p / M exactly */
                     const double c = dmrgx_host::DsfPhaseCoefficient(part, p, M);
                     /* a site whose coefficient is exactly zero takes no part: its Sz cells are neither copied nor multiplied */
                     if (c == 0.0) continue;
-                    terms.push_back(i < nls ? dmrgx_term{c / std::sqrt((double)N), (int32_t)i, -1} : dmrgx_term{c / std::sqrt((double)N), -1, (int32_t)(i - nls)});
+                    terms.push_back(S.term(i, c / std::sqrt((double)N)));
                 }
                 if (terms.empty()) continue;                            /* the part vanishes on the lattice: Norm2 0, no run */
                 const int32_t vec_first[2] = {0, (int32_t)terms.size()};
-                if (dmrgx_kron_term_apply(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
-                                          1, vec_first, terms.data(), v.dev_uninitialised(), n, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_apply: %s", dmrgx_last_error());
+                ierr = S.Apply(1, vec_first, terms.data(), v.dev_uninitialised(), n); CHKERRQ(ierr);
                 if (dmrgx_dot(n, v.dev_ro(), v.dev_ro(), &A.norm2, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
                 if (A.norm2 != A.norm2) SETERRQ3(mpi_comm, 1, "Dynamical structure factor: the %s part of q = (%lld,%lld) is not a number.", part == 0 ? "cosine" : "sine", LLD(P.nx), LLD(P.ny));
-                if (!(A.norm2 > dsf_no_weight * norm)) continue;        /* no weight: no run */
+                if (!(A.norm2 > dsf_no_weight * S.norm)) continue;        /* no weight: no run */
                 A.alpha.assign((size_t)dsf_steps, 0.0); A.beta.assign((size_t)dsf_steps, 0.0);
                 if (dmrgx_kron_lanczos_coeffs(H->plan, v.dev_ro(), (int32_t)dsf_steps, dsf_breakdown_tol, &A.norm2, A.alpha.data(), A.beta.data(), &A.done, nullptr))
                     SETERRQ1(mpi_comm, 1, "dmrgx_kron_lanczos_coeffs: %s", dmrgx_last_error());
@@ -1556,16 +1500,15 @@ public:
             }
             /* the poles of both parts, ascending */
             std::vector<std::pair<double, double>> pw;
-            for (const Part& A : P.part) for (size_t k = 0; k < A.theta.size(); ++k) pw.push_back({A.theta[k] - E0, A.norm2 * A.z[k] * A.z[k] / norm});
+            for (const Part& A : P.part) for (size_t k = 0; k < A.theta.size(); ++k) pw.push_back({A.theta[k] - E0, A.norm2 * A.z[k] * A.z[k] / S.norm});
             std::sort(pw.begin(), pw.end());
             for (const auto& x : pw) { P.poles.push_back(x.first); P.weights.push_back(x.second); P.total += x.second; }
         }
         PetscTime(&t1);
         if (verbose) printf("  * Dynamical structure factor: %lld q points, %lld Lanczos steps per run, %lld MatMults on %lld states, tDsf %.6f s\n", LLD(points.size()), LLD(dsf_steps), LLD(matmults), LLD(n), t1 - t0);
-        ierr = dsf_file.Begin(data_dir + "DynamicalStructureFactor.json"); CHKERRQ(ierr);
+        ierr = dsf_file.BeginDynamical(data_dir + "DynamicalStructureFactor.json", GlobIdx, LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, S.norm); CHKERRQ(ierr);
         FILE* fp_dsf = dsf_file.fp;
-        fprintf(fp_dsf, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"E0\": %.17g, \"Norm\": %.17g, \"Steps\": %lld, \"tDsf\": %.9g, \"MatMults\": %lld,\n   \"Points\": [\n", LLD(GlobIdx),
-                LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, norm, LLD(dsf_steps), t1 - t0, LLD(matmults));
+        fprintf(fp_dsf, ", \"Steps\": %lld, \"tDsf\": %.9g, \"MatMults\": %lld,\n   \"Points\": [\n", LLD(dsf_steps), t1 - t0, LLD(matmults));
         for (size_t iq = 0; iq < points.size(); ++iq) {
             const Point& P = points[iq];
             fprintf(fp_dsf, "     {\"q\": [%lld, %lld],\n", LLD(P.nx), LLD(P.ny));
@@ -1584,38 +1527,30 @@ public:
 
     /** -dsf_sites c0,c1,... (engine extension): the real-space dynamical correlations of the ground state from every listed site c,
             G_ic(w) = sum_n <0|Sz_i|n> <n|Sz_c|0> delta(w - E_n + E_0)   for ALL sites i,
-        from ONE Lanczos run per c, where -dsf needs two runs per wave vector.  v = Sz_c psi is one dmrgx_kron_term_apply;
-        dmrgx_kron_lanczos_basis runs the recursion from v with the basis V kept and fully reorthogonalised, so that T = V H V^T and
-        V V^T = 1 hold to rounding; the images u_i = Sz_i psi of all N sites are formed by dmrgx_kron_term_apply in chunks of at most 1 GiB
-        and their overlaps M[i][k] = <u_i, q_k> are one dmrgx_vec_gram(chunk, V) each.  With T = S Theta S^T (TridiagQL.hpp, all
-        eigenvectors) the Galerkin approximation of G in the Krylov space of v is
+        from ONE Lanczos run per c, where -dsf needs two runs per wave vector.  dmrgx_kron_lanczos_basis runs the recursion from
+        v = Sz_c psi with the basis V kept and fully reorthogonalised, so that T = V H V^T and V V^T = 1 hold to rounding; the overlaps
+        M[i][k] = <u_i, q_k> with the images u_i = Sz_i psi (SzFrame::Images, a chunk at a time) are one dmrgx_vec_gram(chunk, V) each.
+        With T = S Theta S^T (TridiagQL.hpp, all eigenvectors) the Galerkin approximation of G in the Krylov space of v is
             Poles[n] = theta_n - E0,   Amplitudes[i][n] = (M S)[i][n] |v| S[0][n] / <psi|psi>,
-        and Sqw[q][n] = sum_i cos(q . (r_i - r_c)) Amplitudes[i][n] at all Lx Ly wave vectors q = (2 pi nx / Lx, 2 pi ny / Ly), row
-        nx Ly + ny: (1/N) sum_c Sqw is S^zz(q, w).  Static[i] = sum_n Amplitudes[i][n] = <Sz_i Sz_c> exactly (S is orthogonal), and the
-        moments sum_n Amplitudes[i][n] Poles[n]^p equal <u_i, (H - E0)^p v> for p < steps done.
+        and Sqw[q][n] = sum_i cos(q . (r_i - r_c)) Amplitudes[i][n] (SiteCosineSum) at all Lx Ly wave vectors q = (2 pi nx / Lx,
+        2 pi ny / Ly), row nx Ly + ny: (1/N) sum_c Sqw is S^zz(q, w).  Static[i] = sum_n Amplitudes[i][n] = <Sz_i Sz_c> exactly (S is
+        orthogonal), and the moments sum_n Amplitudes[i][n] Poles[n]^p equal <u_i, (H - E0)^p v> for p < steps done.
         The psi component of v is left in: it shows as a pole at w = 0 whose amplitude at i is <Sz_i> <Sz_c>.  Amplitudes[c] are the
         weights |v|^2 S[0][n]^2 >= 0 of the continued fraction of v; for i != c they carry either sign, and Sqw of ONE site is an
         estimator that need not be positive where the lattice is not translation invariant (an open cylinder) -- only the average over c
         is S^zz(q, w).  The block bases were optimised for the ground state alone: the caveat of -dsf applies unchanged.
         Memory: the basis, steps x N_sb doubles on the device for the whole measurement (2.6 GB at 20 x 8, m = 2048, 100 steps), beside
-        one chunk of images.  Site s of the right block is lattice site N - 1 - s.  One rank only (refused at start-up otherwise). */
+        one chunk of images.  One rank only (refused at start-up otherwise). */
     PetscErrorCode CalculateDynamicalCorrelations(KronBlocks_t& KronBlocks, const Vec& gsv_r, Mat& H, PetscScalar E0)
     {
         PetscLogDouble t0, t1;
         PetscTime(&t0);
-        dmrgx_host::CentreFrame F;
-        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, "Dynamical correlations"); CHKERRQ(ierr);
-        const PetscInt nls = F.nsites[0], N = F.N, Lx = Ham.Lx(), Ly = Ham.Ly(), M = Lx * Ly, K = dsf_steps;
-        dmrgx_host::SiteOperators T(F);
-        std::vector<PetscInt> site, rx((size_t)N), ry((size_t)N);      /* site[a]: lattice site of operator a of the table; (rx, ry)[s]: where lattice site s sits */
-        ierr = T.AllSites(OpSz, site); CHKERRQ(ierr);
-        for (PetscInt s = 0; s < N; ++s) { ierr = Ham.To2D(s, rx[(size_t)s], ry[(size_t)s]); CHKERRQ(ierr); }
-        auto term_of = [&](PetscInt a) { return a < nls ? dmrgx_term{1.0, (int32_t)a, -1} : dmrgx_term{1.0, -1, (int32_t)(a - nls)}; };
-        const int64_t n = gsv_r->n, ld = n + (n & 1);                 /* even rows: the library streams them in 16-byte loads */
-        const double* psi = gsv_r->buf->dev_ro();
-        double norm = 0.0;
-        if (dmrgx_dot(n, psi, psi, &norm, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
-        const PetscInt chunk = std::max<PetscInt>(1, std::min<PetscInt>(N, (PetscInt)((((int64_t)1 << 30) / (int64_t)sizeof(double)) / ld)));
+        dmrgx_host::SzFrame S;
+        PetscErrorCode ierr = S.Init(KronBlocks, num_sites, Ham, gsv_r, "Dynamical correlations"); CHKERRQ(ierr);
+        const PetscInt N = S.F.N, M = S.M, K = dsf_steps, chunk = S.chunk();
+        const int64_t n = S.n, ld = S.ld;
+        std::vector<PetscInt> ops((size_t)N);                        /* the images are taken in the order of the operators */
+        for (PetscInt a = 0; a < N; ++a) ops[(size_t)a] = a;
         std::unique_ptr<dmrgx_host::DevBuffer> v, V, U, Mdev;
         try {
             v.reset(new dmrgx_host::DevBuffer((size_t)n, dmrgx_host::DevBuffer::device_only_t{}));
@@ -1626,22 +1561,14 @@ public:
 
         struct Run { PetscInt c = 0; double norm2 = 0.0; int32_t done = 0; std::vector<double> alpha, beta, poles, amp, stat, sqw; };
         std::vector<Run> runs(dsf_sites.size());
-        std::vector<double> Mh((size_t)(N * K)), Mchunk((size_t)(chunk * K)), theta, vec, coskr((size_t)(M * N));
-        std::vector<dmrgx_term> terms;
-        std::vector<int32_t> vec_first;
+        std::vector<double> Mh((size_t)(N * K)), Mchunk((size_t)(chunk * K)), theta, vec;
         PetscInt matmults = 0;
         double t_runs = 0.0;
         for (size_t ir = 0; ir < runs.size(); ++ir) {
             Run& R = runs[ir];
             R.c = dsf_sites[ir];
-            PetscInt ac = -1;
-            for (PetscInt a = 0; a < N; ++a) if (site[(size_t)a] == R.c) ac = a;
-            if (ac < 0) SETERRQ1(mpi_comm, 1, "Dynamical correlations: site %lld is in neither block.", LLD(R.c));
             /* v = Sz_c psi, then the run from it */
-            const dmrgx_term tc = term_of(ac);
-            const int32_t one_vec[2] = {0, 1};
-            if (dmrgx_kron_term_apply(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
-                                      1, one_vec, &tc, v->dev_uninitialised(), n, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_apply: %s", dmrgx_last_error());
+            ierr = S.Images(&S.op_of[(size_t)R.c], 1, v->dev_uninitialised(), n); CHKERRQ(ierr);
             R.alpha.assign((size_t)K, 0.0); R.beta.assign((size_t)K, 0.0);
             PetscLogDouble tr0 = 0.0, tr1 = 0.0;
             if (verbose) { if (dmrgx_stream_sync(nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error()); PetscTime(&tr0); }      /* the run alone, for the log */
@@ -1652,13 +1579,10 @@ public:
             /* M[s][k] = < Sz_s psi , q_k > for every lattice site s */
             for (PetscInt a0 = 0; a0 < N; a0 += chunk) {
                 const PetscInt cnt = std::min<PetscInt>(chunk, N - a0);
-                terms.clear(); vec_first.assign(1, 0);
-                for (PetscInt a = a0; a < a0 + cnt; ++a) { terms.push_back(term_of(a)); vec_first.push_back((int32_t)terms.size()); }
-                if (dmrgx_kron_term_apply(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
-                                          (int32_t)cnt, vec_first.data(), terms.data(), U->dev_uninitialised(), ld, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_apply: %s", dmrgx_last_error());
+                ierr = S.Images(ops.data() + a0, cnt, U->dev_uninitialised(), ld); CHKERRQ(ierr);
                 if (dmrgx_vec_gram((int32_t)cnt, (int32_t)K, n, U->dev_ro(), ld, V->dev_ro(), ld, Mdev->dev_uninitialised(), K, 0, nullptr, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_vec_gram: %s", dmrgx_last_error());
                 if (dmrgx_memcpy_d2h(Mchunk.data(), Mdev->dev_ro(), (size_t)(cnt * K) * sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
-                for (PetscInt a = a0; a < a0 + cnt; ++a) std::copy(Mchunk.begin() + (a - a0) * K, Mchunk.begin() + (a - a0 + 1) * K, Mh.begin() + site[(size_t)a] * K);
+                for (PetscInt a = a0; a < a0 + cnt; ++a) std::copy(Mchunk.begin() + (a - a0) * K, Mchunk.begin() + (a - a0 + 1) * K, Mh.begin() + S.site[(size_t)a] * K);
             }
             /* T = S Theta S^T on the host, the poles ascending */
             const PetscInt D = R.done;
@@ -1669,34 +1593,29 @@ public:
             for (PetscInt k = 0; k < D; ++k) order[(size_t)k] = k;
             std::sort(order.begin(), order.end(), [&](PetscInt a, PetscInt b) { return theta[(size_t)a] < theta[(size_t)b]; });
             const double vnorm = std::sqrt(R.norm2);
-            R.poles.resize((size_t)D); R.amp.assign((size_t)(N * D), 0.0); R.stat.assign((size_t)N, 0.0); R.sqw.assign((size_t)(M * D), 0.0);
+            R.poles.resize((size_t)D); R.amp.assign((size_t)(N * D), 0.0); R.stat.assign((size_t)N, 0.0);
             for (PetscInt p = 0; p < D; ++p) {
                 const double* z = vec.data() + order[(size_t)p] * D;            /* eigenvector of pole p: z[k] = S[k][n] */
                 R.poles[(size_t)p] = theta[(size_t)order[(size_t)p]] - (double)E0;
                 for (PetscInt s = 0; s < N; ++s) {
                     double acc = 0.0;
                     for (PetscInt k = 0; k < D; ++k) acc += Mh[(size_t)(s * K + k)] * z[k];
-                    R.amp[(size_t)(s * D + p)] = acc * vnorm * z[0] / norm;
+                    R.amp[(size_t)(s * D + p)] = acc * vnorm * z[0] / S.norm;
                 }
             }
             for (PetscInt s = 0; s < N; ++s) for (PetscInt p = 0; p < D; ++p) R.stat[(size_t)s] += R.amp[(size_t)(s * D + p)];
-            for (PetscInt nx = 0; nx < Lx; ++nx) for (PetscInt ny = 0; ny < Ly; ++ny) for (PetscInt s = 0; s < N; ++s)
-                coskr[(size_t)((nx * Ly + ny) * N + s)] = std::cos(dmrgx_host::two_pi * ((double)(nx * (rx[(size_t)s] - rx[(size_t)R.c])) / (double)Lx + (double)(ny * (ry[(size_t)s] - ry[(size_t)R.c])) / (double)Ly));
-            for (PetscInt q = 0; q < M; ++q) for (PetscInt s = 0; s < N; ++s) {
-                const double cq = coskr[(size_t)(q * N + s)];
-                for (PetscInt p = 0; p < D; ++p) R.sqw[(size_t)(q * D + p)] += cq * R.amp[(size_t)(s * D + p)];
-            }
+            R.sqw = dmrgx_host::SiteCosineSum(S.Lx, S.Ly, S.rx.data(), S.ry.data(), R.c, R.amp.data(), N, D);
         }
         PetscTime(&t1);
         if (verbose) printf("  * Dynamical correlations: %lld reference sites, %lld Lanczos steps per run with the basis kept, %lld MatMults on %lld states, images in chunks of %lld, tDsfSites %.6f s, of it the Lanczos runs %.6f s\n", LLD(runs.size()), LLD(K), LLD(matmults), LLD(n), LLD(chunk), t1 - t0, t_runs);
-        ierr = dsf_sites_file.Begin(data_dir + "DynamicalCorrelations.json"); CHKERRQ(ierr);
+        ierr = dsf_sites_file.BeginDynamical(data_dir + "DynamicalCorrelations.json", GlobIdx, LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, S.norm); CHKERRQ(ierr);
         FILE* fp = dsf_sites_file.fp;
-        fprintf(fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"E0\": %.17g, \"Norm\": %.17g, \"Steps\": %lld, \"tDsfSites\": %.9g, \"MatMults\": %lld,\n   \"Sites\": [\n", LLD(GlobIdx),
-                LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, norm, LLD(K), t1 - t0, LLD(matmults));
+        fprintf(fp, ", \"Steps\": %lld, \"tDsfSites\": %.9g, \"MatMults\": %lld,\n   \"Sites\": [\n", LLD(K), t1 - t0, LLD(matmults));
         for (size_t ir = 0; ir < runs.size(); ++ir) {
             const Run& R = runs[ir];
             const PetscInt D = R.done;
-            fprintf(fp, "   {\"Site\": %lld, \"r\": [%lld, %lld], \"Norm2\": %.17g, \"StepsDone\": %d,\n   \"Alpha\": ", LLD(R.c), LLD(rx[(size_t)R.c]), LLD(ry[(size_t)R.c]), R.norm2, (int)R.done);
+            dsf_sites_file.OpenSite(R.c, S.rx[(size_t)R.c], S.ry[(size_t)R.c], R.norm2);
+            fprintf(fp, ", \"StepsDone\": %d,\n   \"Alpha\": ", (int)R.done);
             dsf_sites_file.Row(R.alpha); fprintf(fp, ",\n   \"Beta\": "); dsf_sites_file.Row(R.beta); fprintf(fp, ",\n   \"Poles\": "); dsf_sites_file.Row(R.poles);
             fprintf(fp, ",\n   \"Static\": "); dsf_sites_file.Row(R.stat); fprintf(fp, ",\n");
             dsf_sites_file.Table("Amplitudes", R.amp, N, D, ",\n"); dsf_sites_file.Table("Sqw", R.sqw, M, D, ir + 1 < runs.size() ? "},\n" : "}\n");
@@ -1710,7 +1629,7 @@ public:
             mu_n^{ic} = < Sz_i psi , T_n(Ht) Sz_c psi > / <psi|psi>,   Ht = (H - Centre) / HalfWidth,   for ALL sites i,
         from one dmrgx_kron_chebyshev_moments run per reference site c: the three-term recursion t_{n+1} = 2 Ht t_n - t_{n-1} needs two
         earlier vectors, no kept basis and no reorthogonalisation, so its cost is linear in the number of moments where -dsf_sites
-        grows with the square.  The images u_i = Sz_i psi of all N sites (dmrgx_kron_term_apply, in lattice order) stay on the device for
+        grows with the square.  The images u_i = Sz_i psi of all N sites (SzFrame::Images, lattice order) stay on the device for
         the whole measurement -- N x N_sb doubles, refused with PETSC_ERR_MEM if they do not fit --; row c is the start vector of run
         c, and the library takes <u_i, t_n> of all i with one Gram call per 16 vectors.
         The window must contain the spectrum of the superblock Hamiltonian.  Unless -dsf_cheb_window lo,hi gives it, it is found once
@@ -1722,41 +1641,20 @@ public:
         w0,w1,nw also SqwGrid[q][k] = ChebyshevJackson(MomentsQ[q], D + 1, x_k) / HalfWidth at x_k = (w_k + E0 - Centre) / HalfWidth:
         (1/N) sum_c SqwGrid is the Jackson-broadened S^zz(q, w), non-negative and free of ghosts; its resolution is about
         pi HalfWidth / (D + 1).  The caveats of -dsf_sites (one site is an estimator; bases optimised for the ground state) apply.
-        Site s of the right block is lattice site N - 1 - s.  One rank only (refused at start-up otherwise). */
+        One rank only (refused at start-up otherwise). */
     PetscErrorCode CalculateChebyshevCorrelations(KronBlocks_t& KronBlocks, const Vec& gsv_r, Mat& H, PetscScalar E0)
     {
         PetscLogDouble t0, t1;
         PetscTime(&t0);
-        dmrgx_host::CentreFrame F;
-        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, "Chebyshev correlations"); CHKERRQ(ierr);
-        const PetscInt nls = F.nsites[0], N = F.N, Lx = Ham.Lx(), Ly = Ham.Ly(), M = Lx * Ly, K = dsf_cheb_steps;
-        dmrgx_host::SiteOperators T(F);
-        std::vector<PetscInt> site, op_of((size_t)N, -1), rx((size_t)N), ry((size_t)N);      /* site[a]: lattice site of operator a; op_of: its inverse */
-        ierr = T.AllSites(OpSz, site); CHKERRQ(ierr);
-        for (PetscInt a = 0; a < N; ++a) op_of[(size_t)site[(size_t)a]] = a;
-        for (PetscInt s = 0; s < N; ++s) {
-            if (op_of[(size_t)s] < 0) SETERRQ1(mpi_comm, 1, "Chebyshev correlations: site %lld is in neither block.", LLD(s));
-            ierr = Ham.To2D(s, rx[(size_t)s], ry[(size_t)s]); CHKERRQ(ierr);
-        }
-        auto term_of = [&](PetscInt a) { return a < nls ? dmrgx_term{1.0, (int32_t)a, -1} : dmrgx_term{1.0, -1, (int32_t)(a - nls)}; };
-        const int64_t n = gsv_r->n, ld = n + (n & 1);
-        const double* psi = gsv_r->buf->dev_ro();
-        double norm = 0.0;
-        if (dmrgx_dot(n, psi, psi, &norm, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
-        /* the images of all sites, row s = Sz_s psi, built in chunks of at most 1 GiB (the intermediates of a term_apply grow with its vectors) */
+        dmrgx_host::SzFrame S;
+        PetscErrorCode ierr = S.Init(KronBlocks, num_sites, Ham, gsv_r, "Chebyshev correlations"); CHKERRQ(ierr);
+        const PetscInt N = S.F.N, M = S.M, K = dsf_cheb_steps;
+        const int64_t n = S.n, ld = S.ld;
+        /* the images of all sites, row s = Sz_s psi */
         std::unique_ptr<dmrgx_host::DevBuffer> U;
         try { U.reset(new dmrgx_host::DevBuffer((size_t)(N * ld), dmrgx_host::DevBuffer::device_only_t{})); }
         catch (const std::exception& e) { SETERRQ3(mpi_comm, PETSC_ERR_MEM, "Chebyshev correlations: no memory for the images of %lld sites x %lld states (%.3f GB): %s", LLD(N), LLD(n), (double)(N * ld) * 8e-9, e.what()); }
-        const PetscInt chunk = std::max<PetscInt>(1, std::min<PetscInt>(N, (PetscInt)((((int64_t)1 << 30) / (int64_t)sizeof(double)) / ld)));
-        std::vector<dmrgx_term> terms;
-        std::vector<int32_t> vec_first;
-        for (PetscInt s0 = 0; s0 < N; s0 += chunk) {
-            const PetscInt cnt = std::min<PetscInt>(chunk, N - s0);
-            terms.clear(); vec_first.assign(1, 0);
-            for (PetscInt s = s0; s < s0 + cnt; ++s) { terms.push_back(term_of(op_of[(size_t)s])); vec_first.push_back((int32_t)terms.size()); }
-            if (dmrgx_kron_term_apply(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
-                                      (int32_t)cnt, vec_first.data(), terms.data(), U->dev_uninitialised() + s0 * ld, ld, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_apply: %s", dmrgx_last_error());
-        }
+        ierr = S.Images(S.op_of.data(), N, U->dev_uninitialised(), ld); CHKERRQ(ierr);
 
         /* the window */
         PetscInt matmults = 0, bound_steps = 0;
@@ -1782,7 +1680,7 @@ public:
 
         struct Run { PetscInt c = 0; double norm2 = 0.0; int32_t done = 0; std::vector<double> diag, mom, momq, grid; };
         std::vector<Run> runs(dsf_cheb_sites.size());
-        std::vector<double> cross((size_t)((K + 1) * N)), coskr((size_t)N);
+        std::vector<double> cross((size_t)((K + 1) * N));
         double t_runs = 0.0;
         for (size_t ir = 0; ir < runs.size(); ++ir) {
             Run& R = runs[ir];
@@ -1797,16 +1695,10 @@ public:
             const PetscInt D = R.done, nm = D + 1;
             if (D < K) printf("  * WARNING: -dsf_cheb: the run from site %lld left the window [%.6f, %.6f] after %lld of %lld steps; the record holds the moments up to there.\n", LLD(R.c), centre - half_width, centre + half_width, LLD(D), LLD(K));
             R.diag.resize((size_t)(2 * D + 1));
-            for (double& x : R.diag) x /= norm;
-            R.mom.assign((size_t)(N * nm), 0.0); R.momq.assign((size_t)(M * nm), 0.0);
-            for (PetscInt s = 0; s < N; ++s) for (PetscInt k = 0; k < nm; ++k) R.mom[(size_t)(s * nm + k)] = cross[(size_t)(k * N + s)] / norm;
-            for (PetscInt nx = 0; nx < Lx; ++nx) for (PetscInt ny = 0; ny < Ly; ++ny) {
-                double* row = R.momq.data() + (nx * Ly + ny) * nm;
-                for (PetscInt s = 0; s < N; ++s) {
-                    const double cq = std::cos(dmrgx_host::two_pi * ((double)(nx * (rx[(size_t)s] - rx[(size_t)R.c])) / (double)Lx + (double)(ny * (ry[(size_t)s] - ry[(size_t)R.c])) / (double)Ly));
-                    for (PetscInt k = 0; k < nm; ++k) row[k] += cq * R.mom[(size_t)(s * nm + k)];
-                }
-            }
+            for (double& x : R.diag) x /= S.norm;
+            R.mom.assign((size_t)(N * nm), 0.0);
+            for (PetscInt s = 0; s < N; ++s) for (PetscInt k = 0; k < nm; ++k) R.mom[(size_t)(s * nm + k)] = cross[(size_t)(k * N + s)] / S.norm;
+            R.momq = dmrgx_host::SiteCosineSum(S.Lx, S.Ly, S.rx.data(), S.ry.data(), R.c, R.mom.data(), N, nm);
             if (dsf_cheb_have_omega) {
                 const PetscInt nw = (PetscInt)dsf_cheb_omega.size();
                 R.grid.assign((size_t)(M * nw), 0.0);
@@ -1817,17 +1709,18 @@ public:
         PetscTime(&t1);
         if (verbose) printf("  * Chebyshev correlations: %lld reference sites, %lld steps per run, window [%.6f, %.6f] from %lld Lanczos steps, %lld MatMults on %lld states, tDsfCheb %.6f s, of it the Chebyshev runs %.6f s\n",
                             LLD(runs.size()), LLD(K), centre - half_width, centre + half_width, LLD(bound_steps), LLD(matmults), LLD(n), t1 - t0, t_runs);
-        ierr = dsf_cheb_file.Begin(data_dir + "ChebyshevMoments.json"); CHKERRQ(ierr);
+        ierr = dsf_cheb_file.BeginDynamical(data_dir + "ChebyshevMoments.json", GlobIdx, LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, S.norm); CHKERRQ(ierr);
         FILE* fp = dsf_cheb_file.fp;
-        fprintf(fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"E0\": %.17g, \"Norm\": %.17g, \"Steps\": %lld, \"Centre\": %.17g, \"HalfWidth\": %.17g, \"BoundSteps\": %lld, \"ThetaMax\": %.17g, \"Residual\": %.17g, \"tDsfCheb\": %.9g, \"MatMults\": %lld,\n",
-                LLD(GlobIdx), LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, norm, LLD(K), centre, half_width, LLD(bound_steps), theta_max, residual, t1 - t0, LLD(matmults));
+        fprintf(fp, ", \"Steps\": %lld, \"Centre\": %.17g, \"HalfWidth\": %.17g, \"BoundSteps\": %lld, \"ThetaMax\": %.17g, \"Residual\": %.17g, \"tDsfCheb\": %.9g, \"MatMults\": %lld,\n",
+                LLD(K), centre, half_width, LLD(bound_steps), theta_max, residual, t1 - t0, LLD(matmults));
         if (dsf_cheb_have_omega) { fprintf(fp, "   \"Omega\": "); dsf_cheb_file.Row(dsf_cheb_omega); fprintf(fp, ",\n"); }
         fprintf(fp, "   \"Sites\": [\n");
         for (size_t ir = 0; ir < runs.size(); ++ir) {
             const Run& R = runs[ir];
             const PetscInt nm = R.done + 1;
             const char* end = ir + 1 < runs.size() ? "},\n" : "}\n";
-            fprintf(fp, "   {\"Site\": %lld, \"r\": [%lld, %lld], \"Norm2\": %.17g, \"StepsDone\": %d,\n   \"Diag\": ", LLD(R.c), LLD(rx[(size_t)R.c]), LLD(ry[(size_t)R.c]), R.norm2, (int)R.done);
+            dsf_cheb_file.OpenSite(R.c, S.rx[(size_t)R.c], S.ry[(size_t)R.c], R.norm2);
+            fprintf(fp, ", \"StepsDone\": %d,\n   \"Diag\": ", (int)R.done);
             dsf_cheb_file.Row(R.diag); fprintf(fp, ",\n");
             dsf_cheb_file.Table("Moments", R.mom, N, nm, ",\n");
             dsf_cheb_file.Table("MomentsQ", R.momq, M, nm, dsf_cheb_have_omega ? ",\n" : end);
@@ -1845,55 +1738,33 @@ public:
         -dsf_cv_tol (at most -dsf_cv_maxit iterations, two MatMults each), forms X = (H - sigma) Y / eta and takes the overlaps of both with
         the images of all sites.  Unlike -dsf, -dsf_sites and -dsf_cheb the error at each frequency is controlled -- |ImG - exact| <=
         |u| |v| Residual / eta -- and the broadening is a true Lorentzian of half width eta.  No warm start between frequencies.
-        The images u_i = Sz_i psi of all N sites (dmrgx_kron_term_apply, lattice order) stay on the device for the whole measurement, as
+        The images u_i = Sz_i psi of all N sites (SzFrame::Images, lattice order) stay on the device for the whole measurement, as
         for -dsf_cheb; beside them Y, X and the four pool vectors of the solver: N + 6 vectors of N_sb doubles.
         The record: ImG[i][k], ReG[i][k] (the overlaps over <psi|psi>), Aw[i][k] = -ImG / pi, SqwGrid[q][k] = sum_i cos(q . (r_i - r_c))
-        Aw[i][k] (row nx Ly + ny; (1/N) sum_c SqwGrid is the Lorentzian-broadened S^zz(q, w)), Iterations[k], Converged[k] and Residual[k],
-        the true residual |b - A Y| / |b| of the returned Y.  A frequency that did not converge within -dsf_cv_maxit is written as it is,
-        with a warning here.  The caveats of -dsf_sites apply: the block bases are optimised for the ground state alone -- no correction
-        vector is targeted in the density matrix.  Site s of the right block is lattice site N - 1 - s.  One rank only (refused at
-        start-up otherwise). */
+        Aw[i][k] (SiteCosineSum, row nx Ly + ny; (1/N) sum_c SqwGrid is the Lorentzian-broadened S^zz(q, w)), Iterations[k], Converged[k]
+        and Residual[k], the true residual |b - A Y| / |b| of the returned Y.  A frequency that did not converge within -dsf_cv_maxit is
+        written as it is, with a warning here.  The caveats of -dsf_sites apply: the block bases are optimised for the ground state alone
+        -- no correction vector is targeted in the density matrix.  One rank only (refused at start-up otherwise). */
     PetscErrorCode CalculateCorrectionVectors(KronBlocks_t& KronBlocks, const Vec& gsv_r, Mat& H, PetscScalar E0)
     {
         PetscLogDouble t0, t1;
         PetscTime(&t0);
-        dmrgx_host::CentreFrame F;
-        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, "Correction vectors"); CHKERRQ(ierr);
-        const PetscInt nls = F.nsites[0], N = F.N, Lx = Ham.Lx(), Ly = Ham.Ly(), M = Lx * Ly, nw = (PetscInt)dsf_cv_omega.size();
-        dmrgx_host::SiteOperators T(F);
-        std::vector<PetscInt> site, op_of((size_t)N, -1), rx((size_t)N), ry((size_t)N);      /* site[a]: lattice site of operator a; op_of: its inverse */
-        ierr = T.AllSites(OpSz, site); CHKERRQ(ierr);
-        for (PetscInt a = 0; a < N; ++a) op_of[(size_t)site[(size_t)a]] = a;
-        for (PetscInt s = 0; s < N; ++s) {
-            if (op_of[(size_t)s] < 0) SETERRQ1(mpi_comm, 1, "Correction vectors: site %lld is in neither block.", LLD(s));
-            ierr = Ham.To2D(s, rx[(size_t)s], ry[(size_t)s]); CHKERRQ(ierr);
-        }
-        auto term_of = [&](PetscInt a) { return a < nls ? dmrgx_term{1.0, (int32_t)a, -1} : dmrgx_term{1.0, -1, (int32_t)(a - nls)}; };
-        const int64_t n = gsv_r->n, ld = n + (n & 1);
-        const double* psi = gsv_r->buf->dev_ro();
-        double norm = 0.0;
-        if (dmrgx_dot(n, psi, psi, &norm, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
-        /* the images of all sites, row s = Sz_s psi, built in chunks of at most 1 GiB, and the two vectors of a solve */
+        dmrgx_host::SzFrame S;
+        PetscErrorCode ierr = S.Init(KronBlocks, num_sites, Ham, gsv_r, "Correction vectors"); CHKERRQ(ierr);
+        const PetscInt N = S.F.N, M = S.M, nw = (PetscInt)dsf_cv_omega.size();
+        const int64_t n = S.n, ld = S.ld;
+        /* the images of all sites, row s = Sz_s psi, and the two vectors of a solve */
         std::unique_ptr<dmrgx_host::DevBuffer> U, YX;
         try {
             U.reset(new dmrgx_host::DevBuffer((size_t)(N * ld), dmrgx_host::DevBuffer::device_only_t{}));
             YX.reset(new dmrgx_host::DevBuffer((size_t)(2 * ld), dmrgx_host::DevBuffer::device_only_t{}));
         }
         catch (const std::exception& e) { SETERRQ3(mpi_comm, PETSC_ERR_MEM, "Correction vectors: no memory for the images of %lld sites and two vectors of %lld states (%.3f GB): %s", LLD(N), LLD(n), (double)((N + 2) * ld) * 8e-9, e.what()); }
-        const PetscInt chunk = std::max<PetscInt>(1, std::min<PetscInt>(N, (PetscInt)((((int64_t)1 << 30) / (int64_t)sizeof(double)) / ld)));
-        std::vector<dmrgx_term> terms;
-        std::vector<int32_t> vec_first;
-        for (PetscInt s0 = 0; s0 < N; s0 += chunk) {
-            const PetscInt cnt = std::min<PetscInt>(chunk, N - s0);
-            terms.clear(); vec_first.assign(1, 0);
-            for (PetscInt s = s0; s < s0 + cnt; ++s) { terms.push_back(term_of(op_of[(size_t)s])); vec_first.push_back((int32_t)terms.size()); }
-            if (dmrgx_kron_term_apply(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
-                                      (int32_t)cnt, vec_first.data(), terms.data(), U->dev_uninitialised() + s0 * ld, ld, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_apply: %s", dmrgx_last_error());
-        }
+        ierr = S.Images(S.op_of.data(), N, U->dev_uninitialised(), ld); CHKERRQ(ierr);
 
         struct Run { PetscInt c = 0; double norm2 = 0.0; std::vector<double> iterations, converged, residual, im, re, aw, grid; };
         std::vector<Run> runs(dsf_cv_sites.size());
-        std::vector<double> im((size_t)N), re((size_t)N), column((size_t)(N * N));
+        std::vector<double> im((size_t)N), re((size_t)N);
         double* Yd = YX->dev_uninitialised();
         double* Xd = Yd + ld;
         PetscInt matmults = 0, iterations = 0;
@@ -1901,7 +1772,7 @@ public:
             Run& R = runs[ir];
             R.c = dsf_cv_sites[ir];
             R.iterations.assign((size_t)nw, 0.0); R.converged.assign((size_t)nw, 0.0); R.residual.assign((size_t)nw, 0.0);
-            R.im.assign((size_t)(N * nw), 0.0); R.re.assign((size_t)(N * nw), 0.0); R.aw.assign((size_t)(N * nw), 0.0); R.grid.assign((size_t)(M * nw), 0.0);
+            R.im.assign((size_t)(N * nw), 0.0); R.re.assign((size_t)(N * nw), 0.0); R.aw.assign((size_t)(N * nw), 0.0);
             for (PetscInt k = 0; k < nw; ++k) {
                 dmrgx_cv_stats cs;
                 if (dmrgx_kron_correction_vector(H->plan, U->dev_ro() + R.c * ld, (double)E0 + dsf_cv_omega[(size_t)k], dsf_cv_eta, dsf_cv_tol, (int32_t)dsf_cv_maxit, 0, Yd, Xd,
@@ -1911,29 +1782,25 @@ public:
                 if (!cs.converged) printf("  * WARNING: -dsf_cv: site %lld, w = %.6f: not converged after %d iterations (residual %.3e, tol %.3e%s); the record holds the last iterate.\n",
                                           LLD(R.c), dsf_cv_omega[(size_t)k], (int)cs.iterations, cs.true_residual, dsf_cv_tol, cs.dead ? ", the iteration broke down" : "");
                 R.iterations[(size_t)k] = (double)cs.iterations; R.converged[(size_t)k] = (double)cs.converged; R.residual[(size_t)k] = cs.true_residual;
-                /* the lattice Fourier sum of column c alone: T[i][c] = Aw[i][k], every other entry zero */
-                std::fill(column.begin(), column.end(), 0.0);
                 for (PetscInt s = 0; s < N; ++s) {
                     const size_t at = (size_t)(s * nw + k);
-                    R.im[at] = im[(size_t)s] / norm; R.re[at] = re[(size_t)s] / norm; R.aw[at] = -R.im[at] / (0.5 * dmrgx_host::two_pi);
-                    column[(size_t)(s * N + R.c)] = R.aw[at];
+                    R.im[at] = im[(size_t)s] / S.norm; R.re[at] = re[(size_t)s] / S.norm; R.aw[at] = -R.im[at] / (0.5 * dmrgx_host::two_pi);
                 }
-                const std::vector<double> Sq = dmrgx_host::LatticeFourier(Lx, Ly, rx.data(), ry.data(), column.data(), N, 1.0);
-                for (PetscInt q = 0; q < M; ++q) R.grid[(size_t)(q * nw + k)] = Sq[(size_t)q];
             }
+            R.grid = dmrgx_host::SiteCosineSum(S.Lx, S.Ly, S.rx.data(), S.ry.data(), R.c, R.aw.data(), N, nw);
         }
         PetscTime(&t1);
         if (verbose) printf("  * Correction vectors: %lld reference sites x %lld frequencies, eta %.6f, %lld iterations, %lld MatMults on %lld states, tDsfCv %.6f s\n",
                             LLD(runs.size()), LLD(nw), dsf_cv_eta, LLD(iterations), LLD(matmults), LLD(n), t1 - t0);
-        ierr = dsf_cv_file.Begin(data_dir + "CorrectionVectors.json"); CHKERRQ(ierr);
+        ierr = dsf_cv_file.BeginDynamical(data_dir + "CorrectionVectors.json", GlobIdx, LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, S.norm); CHKERRQ(ierr);
         FILE* fp = dsf_cv_file.fp;
-        fprintf(fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"E0\": %.17g, \"Norm\": %.17g, \"Eta\": %.17g, \"Tol\": %.17g, \"MaxIt\": %lld, \"tDsfCv\": %.9g, \"MatMults\": %lld,\n   \"Omega\": ",
-                LLD(GlobIdx), LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, norm, dsf_cv_eta, dsf_cv_tol, LLD(dsf_cv_maxit), t1 - t0, LLD(matmults));
+        fprintf(fp, ", \"Eta\": %.17g, \"Tol\": %.17g, \"MaxIt\": %lld, \"tDsfCv\": %.9g, \"MatMults\": %lld,\n   \"Omega\": ", dsf_cv_eta, dsf_cv_tol, LLD(dsf_cv_maxit), t1 - t0, LLD(matmults));
         dsf_cv_file.Row(dsf_cv_omega);
         fprintf(fp, ",\n   \"Sites\": [\n");
         for (size_t ir = 0; ir < runs.size(); ++ir) {
             const Run& R = runs[ir];
-            fprintf(fp, "   {\"Site\": %lld, \"r\": [%lld, %lld], \"Norm2\": %.17g,\n   \"Iterations\": ", LLD(R.c), LLD(rx[(size_t)R.c]), LLD(ry[(size_t)R.c]), R.norm2);
+            dsf_cv_file.OpenSite(R.c, S.rx[(size_t)R.c], S.ry[(size_t)R.c], R.norm2);
+            fprintf(fp, ",\n   \"Iterations\": ");
             dsf_cv_file.Row(R.iterations); fprintf(fp, ",\n   \"Converged\": ");
             dsf_cv_file.Row(R.converged); fprintf(fp, ",\n   \"Residual\": ");
             dsf_cv_file.Row(R.residual); fprintf(fp, ",\n");
@@ -2465,6 +2332,42 @@ private:
     Block& AddSite() { return SingleSite; }
 
     void PrintBlocks(const PetscInt& nsys, const PetscInt& nenv) const { printf("  [%lld]-* *-[%lld]\n", LLD(nsys), LLD(nenv)); }
+
+    /** A site-list option (-dsf_sites, -dsf_cheb, -dsf_cv c0,c1,...): on when present and not empty; then refused on more than one rank
+        (`what` has no collectives), and every site must be a lattice site. */
+    PetscErrorCode ReadSiteListOption(const char* option, const char* what, std::vector<PetscInt>& sites, PetscBool& use)
+    {
+        PetscBool have_sites = PETSC_FALSE;
+        PetscInt nc = 4096;
+        sites.assign((size_t)nc, 0);
+        PetscErrorCode ierr = PetscOptionsGetIntArray(NULL, NULL, option, sites.data(), &nc, &have_sites); CHKERRQ(ierr);
+        sites.resize(have_sites ? (size_t)nc : 0);
+        use = (have_sites && nc > 0) ? PETSC_TRUE : PETSC_FALSE;
+        if (!use) return 0;
+        if (mpi_size > 1) SETERRQ3(mpi_comm, PETSC_ERR_SUP, "%s is not available on more than one rank (got %d): %s has no collectives.", option, (int)mpi_size, what);
+        for (PetscInt c : sites) if (c < 0 || c >= num_sites) SETERRQ3(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "%s: site %lld is outside [0, %lld), the lattice sites in the numbering of To1D.", option, LLD(c), LLD(num_sites));
+        return 0;
+    }
+
+    /** A frequency grid w0,w1,nw (-dsf_cheb_omega, -dsf_cv_omega): `have` if the option is there, then `grid` or the refusal. */
+    PetscErrorCode ReadOmegaGridOption(const char* option, std::vector<double>& grid, PetscBool& have)
+    {
+        PetscInt no = 3;
+        PetscReal om[3] = {0.0, 0.0, 0.0};
+        PetscErrorCode ierr = PetscOptionsGetRealArray(NULL, NULL, option, om, &no, &have); CHKERRQ(ierr);
+        if (have && !dmrgx_host::OmegaGrid(om, no, grid)) SETERRQ2(mpi_comm, PETSC_ERR_ARG_WRONG, "%s needs w0,w1,nw: nw >= 1 frequencies from w0 to w1 (nw = 1: w0 = w1). Got %lld numbers.", option, LLD(no));
+        return 0;
+    }
+
+    /** -dsf_steps and -dsf_breakdown_tol, which -dsf and -dsf_sites share. */
+    PetscErrorCode ReadLanczosStepOptions()
+    {
+        PetscErrorCode ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_steps", &dsf_steps, NULL); CHKERRQ(ierr);
+        if (dsf_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_steps must be at least 1. Got %lld.", LLD(dsf_steps));
+        ierr = PetscOptionsGetReal(NULL, NULL, "-dsf_breakdown_tol", &dsf_breakdown_tol, NULL); CHKERRQ(ierr);
+        if (!(dsf_breakdown_tol >= 0.0) || dsf_breakdown_tol >= 1.0) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_breakdown_tol must lie in [0, 1). Got %g.", dsf_breakdown_tol);
+        return 0;
+    }
 
     PetscErrorCode SaveStepHeaders()
     {

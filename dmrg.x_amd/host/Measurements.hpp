@@ -1,9 +1,10 @@
 #ifndef DMRGX_HOST_MEASUREMENTS_HPP
 #define DMRGX_HOST_MEASUREMENTS_HPP
-/** What -corr_matrix, -corr_dimer and -dsf share (DMRGBlockContainer.hpp: CalculateCorrelationMatrix, CalculateDimerCorrelations,
-    CalculateDynamicalStructureFactor): the two blocks as the library sees them, the site operators of one Gram / term call, the bond
-    list, the lattice Fourier sum, the phase coefficients of -dsf, the JSON record file; the spectral window and the Jackson-damped sum
-    of -dsf_cheb (CalculateChebyshevCorrelations).  host_tool.cpp runs the pure parts without a GPU. */
+/** What the measurements of DMRGBlockContainer.hpp share.  All of them: the two blocks as the library sees them, the site operators of
+    one Gram / term call, the JSON record file; -corr_matrix and -corr_dimer: the bond list and the lattice Fourier sum.  The four
+    dynamical ones, -dsf, -dsf_sites, -dsf_cheb and -dsf_cv (CalculateDynamicalStructureFactor, CalculateDynamicalCorrelations,
+    CalculateChebyshevCorrelations, CalculateCorrectionVectors): SzFrame, SiteCosineSum, the w0,w1,nw grid, the openings of their records;
+    the phase coefficients of -dsf, the window and the Jackson-damped sum of -dsf_cheb.  host_tool.cpp runs the pure parts without a GPU. */
 #include <cmath>
 #include <deque>
 #include "DMRGKron.hpp"
@@ -86,6 +87,57 @@ private:
     std::map<std::tuple<int, int, PetscInt>, int32_t> index;    /* (side, Sz / Sp / Sm, block site) -> index in ops[side] */
 };
 
+/** Sz of every site of the centre superblock and the ground state it acts on: the set-up of -dsf, -dsf_sites, -dsf_cheb and -dsf_cv.
+    Operator a of the table T is Sz of lattice site site[a], op_of is the inverse; (rx, ry)[s] is where LATTICE site s sits on the
+    Lx x Ly lattice of M = Lx Ly sites.  psi: the n states on the device, norm = <psi|psi>; ld = n rounded up to even, the row length
+    of a family of vectors (the library streams rows in 16-byte loads). */
+struct SzFrame {
+    CentreFrame F;
+    SiteOperators T{F};
+    std::vector<PetscInt> site, op_of, rx, ry;
+    PetscInt Lx = 0, Ly = 0, M = 0;
+    int64_t n = 0, ld = 0;
+    const double* psi = nullptr; double norm = 0.0;
+    template<class Hamiltonian> PetscErrorCode Init(KronBlocks_t& KronBlocks, PetscInt num_sites, const Hamiltonian& Ham, const Vec& gsv_r, const char* display_name)
+    {
+        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, display_name); CHKERRQ(ierr);
+        ierr = T.AllSites(OpSz, site); CHKERRQ(ierr);
+        op_of.assign((size_t)F.N, -1); rx.resize((size_t)F.N); ry.resize((size_t)F.N);
+        for (PetscInt a = 0; a < F.N; ++a) op_of[(size_t)site[(size_t)a]] = a;
+        for (PetscInt s = 0; s < F.N; ++s) {
+            if (op_of[(size_t)s] < 0) SETERRQ2(PETSC_COMM_SELF, 1, "%s: site %lld is in neither block.", F.name, LLD(s));
+            ierr = Ham.To2D(s, rx[(size_t)s], ry[(size_t)s]); CHKERRQ(ierr);
+        }
+        Lx = Ham.Lx(); Ly = Ham.Ly(); M = Lx * Ly;
+        n = gsv_r->n; ld = n + (n & 1); psi = gsv_r->buf->dev_ro();
+        if (dmrgx_dot(n, psi, psi, &norm, nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "dmrgx_dot: %s", dmrgx_last_error());
+        return 0;
+    }
+    /** coeff Sz of operator a, as a term of one vector. */
+    dmrgx_term term(PetscInt a, double coeff = 1.0) const { return a < F.nsites[0] ? dmrgx_term{coeff, (int32_t)a, -1} : dmrgx_term{coeff, -1, (int32_t)(a - F.nsites[0])}; }
+    /** dmrgx_kron_term_apply on psi: vector j = the sum of terms[vec_first[j] .. vec_first[j + 1]), written to dst + j ld_dst. */
+    PetscErrorCode Apply(PetscInt nvec, const int32_t* vec_first, const dmrgx_term* terms, double* dst, int64_t ld_dst) const
+    {
+        if (dmrgx_kron_term_apply(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
+                                  (int32_t)nvec, vec_first, terms, dst, ld_dst, nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "dmrgx_kron_term_apply: %s", dmrgx_last_error());
+        return 0;
+    }
+    /** Images of at most 1 GiB per term_apply (its intermediates grow with its vectors). */
+    PetscInt chunk() const { return std::max<PetscInt>(1, std::min<PetscInt>(F.N, (PetscInt)((((int64_t)1 << 30) / (int64_t)sizeof(double)) / ld))); }
+    /** dst + j ld_dst = Sz of operator ops[j] on psi, j < count, in chunks. */
+    PetscErrorCode Images(const PetscInt* ops, PetscInt count, double* dst, int64_t ld_dst) const
+    {
+        std::vector<dmrgx_term> terms; std::vector<int32_t> vec_first;
+        for (PetscInt j0 = 0; j0 < count; j0 += chunk()) {
+            const PetscInt cnt = std::min<PetscInt>(chunk(), count - j0);
+            terms.clear(); vec_first.assign(1, 0);
+            for (PetscInt j = j0; j < j0 + cnt; ++j) { terms.push_back(term(ops[j])); vec_first.push_back((int32_t)terms.size()); }
+            PetscErrorCode ierr = Apply(cnt, vec_first.data(), terms.data(), dst + j0 * ld_dst, ld_dst); CHKERRQ(ierr);
+        }
+        return 0;
+    }
+};
+
 /** S[nx][ny] = (1 / norm) sum_ab cos(q . (r_a - r_b)) T[a][b] over n points r_a = (x[a], y[a]) of the Lx x Ly lattice,
     q = (2 pi nx / Lx, 2 pi ny / Ly); T is n x n, the result Lx x Ly, both row-major. */
 inline std::vector<double> LatticeFourier(PetscInt Lx, PetscInt Ly, const PetscInt* x, const PetscInt* y, const double* T, PetscInt n, double norm)
@@ -98,6 +150,29 @@ inline std::vector<double> LatticeFourier(PetscInt Lx, PetscInt Ly, const PetscI
         S[(size_t)(nx * Ly + ny)] = acc / norm;
     }
     return S;
+}
+
+/** The lattice Fourier sum of one column, from the reference site c:  out[nx Ly + ny][k] = sum_s cos(q . (r_s - r_c)) T[s][k] over
+    the N sites r_s = (rx[s], ry[s]); T is N x ncol, the result (Lx Ly) x ncol, both row-major.  Every element is summed over s
+    ascending from 0.0: LatticeFourier of the N x N matrix that holds T[:, k] in column c gives the same bits with norm = 1. */
+inline std::vector<double> SiteCosineSum(PetscInt Lx, PetscInt Ly, const PetscInt* rx, const PetscInt* ry, PetscInt c, const double* T, PetscInt N, PetscInt ncol)
+{
+    std::vector<double> out((size_t)(Lx * Ly * ncol), 0.0);
+    for (PetscInt nx = 0; nx < Lx; ++nx) for (PetscInt ny = 0; ny < Ly; ++ny) for (PetscInt s = 0; s < N; ++s) {
+        const double cq = std::cos(two_pi * ((double)(nx * (rx[s] - rx[c])) / (double)Lx + (double)(ny * (ry[s] - ry[c])) / (double)Ly));
+        for (PetscInt k = 0; k < ncol; ++k) out[(size_t)((nx * Ly + ny) * ncol + k)] += cq * T[s * ncol + k];
+    }
+    return out;
+}
+
+/** The frequencies of a w0,w1,nw option: nw >= 1 equidistant points from w0 to w1 (nw = 1: w0 = w1).  false, and no grid, unless
+    om[0..count) is three such numbers. */
+inline bool OmegaGrid(const double* om, PetscInt count, std::vector<double>& grid)
+{
+    if (!(count == 3 && std::isfinite(om[0]) && std::isfinite(om[1]) && om[0] <= om[1] && om[2] >= 1.0 && om[2] <= 1e6 && om[2] == std::floor(om[2]) && (om[2] > 1.0 || om[0] == om[1]))) return false;
+    grid.resize((size_t)om[2]);
+    for (size_t k = 0; k < grid.size(); ++k) grid[k] = grid.size() > 1 ? om[0] + (om[1] - om[0]) * (double)k / (double)(grid.size() - 1) : om[0];
+    return true;
 }
 
 /** cos (part 0) or sin (part 1) of the exact fraction 2 pi p / M, 0 <= p < M, with the exact zeros taken from p, not from a rounded
@@ -191,6 +266,14 @@ struct JsonRecordFile {
         for (PetscInt i = 0; i < nr; ++i) { fprintf(fp, "     "); Row(T.data() + i * nc, nc); fprintf(fp, "%s\n", i + 1 < nr ? "," : ""); }
         fprintf(fp, "   ]%s", end);
     }
+    /** Begin() and how the record of a dynamical measurement opens; in it, how the entry of a reference site opens.  The caller goes on with ", ...". */
+    PetscErrorCode BeginDynamical(const std::string& path, PetscInt glob_idx, const char* loop_type, double E0, double norm)
+    {
+        const PetscErrorCode ierr = Begin(path);
+        if (!ierr) fprintf(fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"E0\": %.17g, \"Norm\": %.17g", LLD(glob_idx), loop_type, E0, norm);
+        return ierr;
+    }
+    void OpenSite(PetscInt c, PetscInt x, PetscInt y, double norm2) const { fprintf(fp, "   {\"Site\": %lld, \"r\": [%lld, %lld], \"Norm2\": %.17g", LLD(c), LLD(x), LLD(y), norm2); }
     void Close() { if (fp) { fprintf(fp, "\n]\n"); fclose(fp); fp = NULL; } }
 };
 

@@ -183,15 +183,27 @@ int main()
             printf("bonds");
             for (const dmrgx_host::DimerBond& b : dmrgx_host::DimerBonds(ham)) printf(" %lld,%lld,%c,%lld,%lld", LLD(b.i), LLD(b.j), b.orient, LLD(b.ix), LLD(b.jy));
             printf("\n");
-        } else if (cmd == "fourier") {           /* fourier Lx Ly n x_0 .. x_{n-1} y_0 .. y_{n-1} T_00 .. T_{n-1,n-1}  ->  the Lx x Ly table, norm n */
-            PetscInt Lx, Ly, n; is >> Lx >> Ly >> n;
+        } else if (cmd == "fourier" || cmd == "cossum") {
+            /* fourier Lx Ly n x_0 .. x_{n-1} y_0 .. y_{n-1} T_00 .. T_{n-1,n-1} [norm]  ->  the Lx x Ly table of LatticeFourier, norm n unless given
+               cossum Lx Ly n c ncol x_0 .. x_{n-1} y_0 .. y_{n-1} T_00 .. T_{n-1,ncol-1}  ->  the (Lx Ly) x ncol table of SiteCosineSum, row by row */
+            PetscInt Lx, Ly, n, c = -1, ncol; is >> Lx >> Ly >> n;
+            if (cmd == "cossum") is >> c >> ncol; else ncol = n;
             std::vector<PetscInt> x((size_t)n), y((size_t)n);
-            std::vector<double> T((size_t)(n * n));
+            std::vector<double> T((size_t)(n * ncol));
             for (PetscInt& v : x) is >> v;
             for (PetscInt& v : y) is >> v;
             for (double& v : T) is >> v;
-            printf("fourier");
-            for (double v : dmrgx_host::LatticeFourier(Lx, Ly, x.data(), y.data(), T.data(), n, (double)n)) printf(" %.17g", v);
+            double norm;
+            if (!(is >> norm)) norm = (double)n;
+            printf("%s", cmd.c_str());
+            for (double v : c < 0 ? dmrgx_host::LatticeFourier(Lx, Ly, x.data(), y.data(), T.data(), n, norm) : dmrgx_host::SiteCosineSum(Lx, Ly, x.data(), y.data(), c, T.data(), n, ncol)) printf(" %.17g", v);
+            printf("\n");
+        } else if (cmd == "omegagrid") {         /* omegagrid w0 w1 nw  ->  1 and the grid, or 0 */
+            std::vector<double> om, grid;
+            for (double v; is >> v;) om.push_back(v);
+            const bool ok = dmrgx_host::OmegaGrid(om.data(), (PetscInt)om.size(), grid);
+            printf("omegagrid %d", (int)ok);
+            for (double v : grid) printf(" %.17g", v);
             printf("\n");
         } else if (cmd == "chebwindow") {        /* chebwindow E0 nsteps done alpha_0 .. alpha_{nsteps-1} beta_0 .. beta_{nsteps-1}  ->  ok centre half_width theta_max residual */
             double E0; size_t nsteps; PetscInt done; is >> E0 >> nsteps >> done;

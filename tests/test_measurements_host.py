@@ -1,5 +1,6 @@
-"""host/Measurements.hpp (no GPU): what -corr_matrix, -corr_dimer and -dsf share on the host -- the exact-zero phase coefficients of
--dsf, the bond list, the lattice Fourier sum and the JSON record file -- through the host tool."""
+"""host/Measurements.hpp (no GPU): what the measurements share on the host -- the exact-zero phase coefficients of -dsf, the bond list,
+the lattice Fourier sum, the one-column cosine sum and the frequency grid of the site-based dynamical measurements and the JSON record
+file -- through the host tool."""
 import json
 import os
 import subprocess
@@ -105,6 +106,89 @@ def test_lattice_fourier_against_numpy(Lx, Ly, n):
     want = np.array([[(np.cos(2 * np.pi * (nx * dx / Lx + ny * dy / Ly)) * T).sum() / n for ny in range(Ly)] for nx in range(Lx)])
     assert abs(got[0, 0] - T.sum() / n) <= 1e-13 * np.abs(T).sum() / n
     assert np.abs(got - want).max() <= 1e-13 * np.abs(T).sum() / n, np.abs(got - want).max()
+
+
+def _lattice(Lx, Ly):
+    ham = J1J2XXZModel_SquareLattice(Lx=Lx, Ly=Ly, heisenberg=1.0)
+    xy = np.array([ham.To2D(s) for s in range(Lx * Ly)])
+    return xy[:, 0], xy[:, 1]
+
+
+def _numbers(*arrays):
+    return " ".join(repr(v) for a in arrays for v in np.asarray(a).ravel().tolist())
+
+
+def _cossum(Lx, Ly, c, T):
+    """SiteCosineSum of the n x ncol table T over all sites of the Lx x Ly lattice, reference site c: the (Lx Ly) x ncol table."""
+    x, y = _lattice(Lx, Ly)
+    n, ncol = T.shape
+    out, _ = _tool([f"cossum {Lx} {Ly} {n} {c} {ncol} " + _numbers(x, y, T)])
+    tok = out[0].split()
+    assert tok[0] == "cossum" and len(tok) == 1 + Lx * Ly * ncol
+    return np.array([float(v) for v in tok[1:]]).reshape(Lx * Ly, ncol)
+
+
+def _cossum_numpy(Lx, Ly, c, T):
+    """The same sum with the cosine argument formed by the same expression, 2 pi (nx dx / Lx + ny dy / Ly) from integer nx dx, ny dy."""
+    x, y = _lattice(Lx, Ly)
+    return np.array([(np.cos(2 * np.pi * ((nx * (x - x[c])) / Lx + (ny * (y - y[c])) / Ly))[:, None] * T).sum(axis=0) for nx in range(Lx) for ny in range(Ly)])
+
+
+@pytest.fixture(scope="module")
+def table_6x2():
+    """12 x 3, entries in [-1, 1]: as many rows as the 6 x 2 lattice has sites."""
+    return np.random.default_rng(20261019).uniform(-1.0, 1.0, (12, 3))
+
+
+@pytest.mark.parametrize("c", [0, 7])
+def test_cosine_sum_is_lattice_fourier_of_one_column(table_6x2, c):
+    """The path -dsf_cv took before SiteCosineSum: LatticeFourier with norm 1 of the 12 x 12 matrix that is zero except for column c.
+    The zeros add nothing and the other terms come in the same order, so every double is the same.  The tool's fourier command
+    divides by n unless a norm follows the matrix: it is given 1.0 here, so that nothing is scaled back."""
+    x, y = _lattice(6, 2)
+    got = _cossum(6, 2, c, table_6x2)
+    for k in range(3):
+        Z = np.zeros((12, 12))
+        Z[:, c] = table_6x2[:, k]
+        out, _ = _tool(["fourier 6 2 12 " + _numbers(x, y, Z) + " 1.0"])
+        tok = out[0].split()
+        assert tok[0] == "fourier" and len(tok) == 1 + 12
+        assert (got[:, k] == np.array([float(v) for v in tok[1:]])).all(), (c, k)
+
+
+@pytest.mark.parametrize("c", [0, 7])
+def test_cosine_sum_against_numpy(table_6x2, c):
+    """1e-13, the bound tests/test_gpu_dsf_cv.py puts on SqwGrid at N = 12 and |T| <= 1."""
+    err = np.abs(_cossum(6, 2, c, table_6x2) - _cossum_numpy(6, 2, c, table_6x2)).max()
+    assert err <= 1e-13, err
+
+
+def test_cosine_sum_on_4x4():
+    """q = (0, 0): every cosine is cos(0) = 1, so row 0 is the plain sum of the column over s ascending -- the same doubles.  The other
+    rows against numpy to 1e-13: 16 terms with |T| <= 1, each a few eps off through the angle (below 4 pi) and the product."""
+    T = np.random.default_rng(44).uniform(-1.0, 1.0, (16, 1))
+    got = _cossum(4, 4, 5, T)
+    acc = 0.0
+    for v in T[:, 0].tolist():
+        acc += v
+    assert got.shape == (16, 1) and got[0, 0] == acc
+    assert np.abs(got - _cossum_numpy(4, 4, 5, T)).max() <= 1e-13
+
+
+@pytest.mark.parametrize("w0,w1,nw", [(0.0, 4.0, 9), (0.3, 0.3, 1), (-1.0, 2.0, 4)])
+def test_omega_grid(w0, w1, nw):
+    """w0 + (w1 - w0) k / (nw - 1) in this order of operations, w0 alone for nw = 1: the same doubles as Python's."""
+    out, _ = _tool([f"omegagrid {w0!r} {w1!r} {nw}"])
+    tok = out[0].split()
+    assert tok[:2] == ["omegagrid", "1"]
+    assert [float(v) for v in tok[2:]] == ([w0 + (w1 - w0) * k / (nw - 1) for k in range(nw)] if nw > 1 else [w0])
+
+
+@pytest.mark.parametrize("line", ["0 4 0", "0 4", "4 0 3", "0 4 2.5", "0 4 1"])
+def test_omega_grid_refuses_malformed_input(line):
+    """nw = 0, two numbers, w0 > w1, a fractional nw, nw = 1 with w0 != w1: a failure and no grid."""
+    out, _ = _tool(["omegagrid " + line])
+    assert out == ["omegagrid 0"]
 
 
 # two records of the tool's jsonrec command, number format %.15g: record k holds the row R = T[1:4] and the 2 x 3 table T of the six
