@@ -17,75 +17,31 @@
 // After the loop: p = y, t = H p, s = t - sigma y = eta X, X = s / eta, u = H s, true residual |b - (u - sigma s + eta^2 y)| / |b|.
 // The MatMult sees the pairs (p, t) and (s, t) only.  Iterations are enqueued in blocks of check_every; one small copy per block brings
 // the scalars back.  Fixed grids, partials added in block order by one workgroup, no atomics: the same bits whatever check_every is.
-#include "common.h"
+#include "krylov.h"
 #include <cmath>
 #include <limits>
 
 namespace dmrgx {
 namespace {
 
-// a workgroup owns CV_RANGE contiguous elements, CV_PER per thread in 16-byte pairs (the layout of the Chebyshev step kernel)
-constexpr int CV_THREADS = 256, CV_PER = 8, CV_RANGE = CV_THREADS * CV_PER;
 // the device scalars; the overlaps <u_i, Y>, <u_i, X> follow from CV_NS on
 enum : int { CV_NORM2 = 0, CV_BB = 1, CV_RR = 2, CV_ALPHA = 3, CV_BETA = 4, CV_ITER = 5, CV_CONV = 6, CV_DEAD = 7, CV_STOP = 8, CV_APPLY = 9, CV_TRUE2 = 10, CV_NS = 12 };
 
-__device__ __forceinline__ double cv_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// the workgroup's sum of `v`, valid in thread 0 (wave sums added in wave order); ends with the LDS free for the next call
-__device__ __forceinline__ double cv_block_sum(double v) {
-    __shared__ double red[CV_THREADS / 64];
-    v = cv_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0) for (int k = 0; k < CV_THREADS / 64; ++k) t += red[k];
-    __syncthreads();
-    return t;
-}
-
-// elements e, e + 1 of p (e even); beyond n: zeros.  VEC: p + e is 16-byte aligned
-template <bool VEC> __device__ __forceinline__ double2 cv_load2(const double* __restrict__ p, int64_t e, int64_t n)
-{
-    if (VEC && e + 1 < n) return *reinterpret_cast<const double2*>(p + e);
-    double2 r;
-    r.x = e < n ? p[e] : 0.0;
-    r.y = e + 1 < n ? p[e + 1] : 0.0;
-    return r;
-}
-
-// one past the last element of this workgroup's range
-__device__ __forceinline__ int64_t cv_range_end(int64_t n)
-{
-    const int64_t end = (int64_t)(blockIdx.x + 1) * CV_RANGE;
-    return end < n ? end : n;
-}
-
-template <bool VEC> __device__ __forceinline__ void cv_store2(double* __restrict__ p, int64_t e, int64_t n, double2 v)
-{
-    if (VEC && e + 1 < n) { *reinterpret_cast<double2*>(p + e) = v; return; }
-    if (e < n) p[e] = v.x;
-    if (e + 1 < n) p[e + 1] = v.y;
-}
-
-// partial[b] = sum over block b's elements of x[e]^2  (x is the caller's: 8-byte loads)
-__global__ void __launch_bounds__(CV_THREADS) cv_norm2_kernel(const double* __restrict__ x, int64_t n, double* __restrict__ partial)
+// partial[b] = sum of x[e]^2 over block b's range (lanczos.hip strides the whole grid: other bits).  (x is the caller's: 8-byte loads)
+__global__ void __launch_bounds__(RANGE_THREADS) cv_norm2_kernel(const double* __restrict__ x, int64_t n, double* __restrict__ partial)
 {
     double acc = 0.0;
-    for (int64_t e = (int64_t)blockIdx.x * CV_RANGE + threadIdx.x; e < cv_range_end(n); e += CV_THREADS) acc += x[e] * x[e];
-    acc = cv_block_sum(acc);
+    for (int64_t e = range_first(); e < range_end(n); e += RANGE_THREADS) acc += x[e] * x[e];
+    acc = block_sum<RANGE_THREADS>(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
 // r = p = -eta v0, y = 0; a refused v0: exact zeros everywhere, whatever v0 holds
-__global__ void __launch_bounds__(CV_THREADS) cv_start_kernel(const double* __restrict__ v0, double* __restrict__ r, double* __restrict__ p, double* __restrict__ y, int64_t n,
-                                                             double eta, const double* __restrict__ S)
+__global__ void __launch_bounds__(RANGE_THREADS) cv_start_kernel(const double* __restrict__ v0, double* __restrict__ r, double* __restrict__ p, double* __restrict__ y, int64_t n,
+                                                                double eta, const double* __restrict__ S)
 {
     const bool dead = S[CV_DEAD] != 0.0;
-    for (int64_t e = (int64_t)blockIdx.x * CV_RANGE + threadIdx.x; e < cv_range_end(n); e += CV_THREADS) {
+    for (int64_t e = range_first(); e < range_end(n); e += RANGE_THREADS) {
         const double b = dead ? 0.0 : -eta * v0[e];
         r[e] = b;
         p[e] = b;
@@ -94,101 +50,98 @@ __global__ void __launch_bounds__(CV_THREADS) cv_start_kernel(const double* __re
 }
 
 // s = t - sigma p; partial[b] = s . s, partial[gridDim.x + b] = p . p over block b.  (t, p, s: pool blocks, 16-byte pairs)
-__global__ void __launch_bounds__(CV_THREADS) cv_s_kernel(const double* __restrict__ t, const double* __restrict__ p, double* __restrict__ s, int64_t n, double sigma,
-                                                         const double* __restrict__ S, double* __restrict__ partial)
+__global__ void __launch_bounds__(RANGE_THREADS) cv_s_kernel(const double* __restrict__ t, const double* __restrict__ p, double* __restrict__ s, int64_t n, double sigma,
+                                                            const double* __restrict__ S, double* __restrict__ partial)
 {
     if (S[CV_STOP] != 0.0) return;
-    const int64_t base = (int64_t)blockIdx.x * CV_RANGE + 2 * threadIdx.x;
-    double2 tr[CV_PER / 2], pr[CV_PER / 2];
+    double2 tr[RANGE_PAIRS], pr[RANGE_PAIRS];
 #pragma unroll
-    for (int i = 0; i < CV_PER / 2; ++i) {
-        const int64_t e = base + (int64_t)i * 2 * CV_THREADS;
-        tr[i] = cv_load2<true>(t, e, n);
-        pr[i] = cv_load2<true>(p, e, n);
+    for (int i = 0; i < RANGE_PAIRS; ++i) {
+        const int64_t e = range_pair(i);
+        tr[i] = load2<true>(t, e, n);
+        pr[i] = load2<true>(p, e, n);
     }
     double ss = 0.0, pp = 0.0;
 #pragma unroll
-    for (int i = 0; i < CV_PER / 2; ++i) {
-        const int64_t e = base + (int64_t)i * 2 * CV_THREADS;
+    for (int i = 0; i < RANGE_PAIRS; ++i) {
+        const int64_t e = range_pair(i);
         double2 x;
         x.x = tr[i].x - sigma * pr[i].x;
         x.y = tr[i].y - sigma * pr[i].y;
-        cv_store2<true>(s, e, n, x);
+        store2<true>(s, e, n, x);
         ss += x.x * x.x; ss += x.y * x.y;                        // (beyond n the registers hold zeros)
         pp += pr[i].x * pr[i].x; pp += pr[i].y * pr[i].y;
     }
-    ss = cv_block_sum(ss);
-    pp = cv_block_sum(pp);
+    ss = block_sum<RANGE_THREADS>(ss);
+    pp = block_sum<RANGE_THREADS>(pp);
     if (threadIdx.x == 0) { partial[blockIdx.x] = ss; partial[gridDim.x + blockIdx.x] = pp; }
 }
 
 // r -= alpha (u - sigma s + eta^2 p); partial[b] = r . r over block b
-__global__ void __launch_bounds__(CV_THREADS) cv_residual_kernel(const double* __restrict__ u, const double* __restrict__ s, const double* __restrict__ p, double* __restrict__ r,
-                                                                int64_t n, double sigma, double eta2, const double* __restrict__ S, double* __restrict__ partial)
+__global__ void __launch_bounds__(RANGE_THREADS) cv_residual_kernel(const double* __restrict__ u, const double* __restrict__ s, const double* __restrict__ p, double* __restrict__ r,
+                                                                   int64_t n, double sigma, double eta2, const double* __restrict__ S, double* __restrict__ partial)
 {
     if (S[CV_STOP] != 0.0) return;
     const double alpha = S[CV_ALPHA];
-    const int64_t base = (int64_t)blockIdx.x * CV_RANGE + 2 * threadIdx.x;
-    double2 ur[CV_PER / 2], sr[CV_PER / 2], pr[CV_PER / 2], rr[CV_PER / 2];
+    double2 ur[RANGE_PAIRS], sr[RANGE_PAIRS], pr[RANGE_PAIRS], rr[RANGE_PAIRS];
 #pragma unroll
-    for (int i = 0; i < CV_PER / 2; ++i) {
-        const int64_t e = base + (int64_t)i * 2 * CV_THREADS;
-        ur[i] = cv_load2<true>(u, e, n);
-        sr[i] = cv_load2<true>(s, e, n);
-        pr[i] = cv_load2<true>(p, e, n);
-        rr[i] = cv_load2<true>(r, e, n);
+    for (int i = 0; i < RANGE_PAIRS; ++i) {
+        const int64_t e = range_pair(i);
+        ur[i] = load2<true>(u, e, n);
+        sr[i] = load2<true>(s, e, n);
+        pr[i] = load2<true>(p, e, n);
+        rr[i] = load2<true>(r, e, n);
     }
     double acc = 0.0;
 #pragma unroll
-    for (int i = 0; i < CV_PER / 2; ++i) {
-        const int64_t e = base + (int64_t)i * 2 * CV_THREADS;
+    for (int i = 0; i < RANGE_PAIRS; ++i) {
+        const int64_t e = range_pair(i);
         double2 x;
         x.x = rr[i].x - alpha * (ur[i].x - sigma * sr[i].x + eta2 * pr[i].x);
         x.y = rr[i].y - alpha * (ur[i].y - sigma * sr[i].y + eta2 * pr[i].y);
-        cv_store2<true>(r, e, n, x);
+        store2<true>(r, e, n, x);
         acc += x.x * x.x; acc += x.y * x.y;
     }
-    acc = cv_block_sum(acc);
+    acc = block_sum<RANGE_THREADS>(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
 // the iteration counted: y += alpha p, and p = r + beta p unless that iteration converged.  YVEC: the caller's y is 16-byte aligned
-template <bool YVEC> __global__ void __launch_bounds__(CV_THREADS) cv_direction_kernel(const double* __restrict__ r, double* __restrict__ p, double* __restrict__ y, int64_t n,
-                                                                                      const double* __restrict__ S)
+template <bool YVEC> __global__ void __launch_bounds__(RANGE_THREADS) cv_direction_kernel(const double* __restrict__ r, double* __restrict__ p, double* __restrict__ y, int64_t n,
+                                                                                         const double* __restrict__ S)
 {
     if (S[CV_APPLY] == 0.0) return;
     const double alpha = S[CV_ALPHA], beta = S[CV_BETA];
     const bool turn = S[CV_CONV] == 0.0;
-    const int64_t base = (int64_t)blockIdx.x * CV_RANGE + 2 * threadIdx.x;
-    double2 rr[CV_PER / 2], pr[CV_PER / 2], yr[CV_PER / 2];
+    double2 rr[RANGE_PAIRS], pr[RANGE_PAIRS], yr[RANGE_PAIRS];
 #pragma unroll
-    for (int i = 0; i < CV_PER / 2; ++i) {
-        const int64_t e = base + (int64_t)i * 2 * CV_THREADS;
-        if (turn) rr[i] = cv_load2<true>(r, e, n);
-        pr[i] = cv_load2<true>(p, e, n);
-        yr[i] = cv_load2<YVEC>(y, e, n);
+    for (int i = 0; i < RANGE_PAIRS; ++i) {
+        const int64_t e = range_pair(i);
+        if (turn) rr[i] = load2<true>(r, e, n);
+        pr[i] = load2<true>(p, e, n);
+        yr[i] = load2<YVEC>(y, e, n);
     }
 #pragma unroll
-    for (int i = 0; i < CV_PER / 2; ++i) {
-        const int64_t e = base + (int64_t)i * 2 * CV_THREADS;
+    for (int i = 0; i < RANGE_PAIRS; ++i) {
+        const int64_t e = range_pair(i);
         double2 x;
         x.x = yr[i].x + alpha * pr[i].x;
         x.y = yr[i].y + alpha * pr[i].y;
-        cv_store2<YVEC>(y, e, n, x);
+        store2<YVEC>(y, e, n, x);
         if (turn) {
             x.x = rr[i].x + beta * pr[i].x;
             x.y = rr[i].y + beta * pr[i].y;
-            cv_store2<true>(p, e, n, x);
+            store2<true>(p, e, n, x);
         }
     }
 }
 
 // closing 1: s = t - sigma y = eta X (t = H y), X = s / eta when X is wanted; a refused v0: exact zeros.  (y, X: the caller's, 8-byte accesses)
-__global__ void __launch_bounds__(CV_THREADS) cv_x_kernel(const double* __restrict__ t, const double* __restrict__ y, double* __restrict__ s, double* __restrict__ X, int64_t n,
-                                                         double sigma, double eta, const double* __restrict__ S)
+__global__ void __launch_bounds__(RANGE_THREADS) cv_x_kernel(const double* __restrict__ t, const double* __restrict__ y, double* __restrict__ s, double* __restrict__ X, int64_t n,
+                                                            double sigma, double eta, const double* __restrict__ S)
 {
     const bool none = S[CV_NORM2] == 0.0;
-    for (int64_t e = (int64_t)blockIdx.x * CV_RANGE + threadIdx.x; e < cv_range_end(n); e += CV_THREADS) {
+    for (int64_t e = range_first(); e < range_end(n); e += RANGE_THREADS) {
         const double x = none ? 0.0 : t[e] - sigma * y[e];
         s[e] = x;
         if (X) X[e] = none ? 0.0 : x / eta;
@@ -196,16 +149,16 @@ __global__ void __launch_bounds__(CV_THREADS) cv_x_kernel(const double* __restri
 }
 
 // closing 2: partial[b] = sum over block b of (b - A y)^2, b = -eta v0, A y = u - sigma s + eta^2 y (u = H s)
-__global__ void __launch_bounds__(CV_THREADS) cv_true_residual_kernel(const double* __restrict__ v0, const double* __restrict__ u, const double* __restrict__ s, const double* __restrict__ y,
-                                                                     int64_t n, double sigma, double eta, const double* __restrict__ S, double* __restrict__ partial)
+__global__ void __launch_bounds__(RANGE_THREADS) cv_true_residual_kernel(const double* __restrict__ v0, const double* __restrict__ u, const double* __restrict__ s, const double* __restrict__ y,
+                                                                        int64_t n, double sigma, double eta, const double* __restrict__ S, double* __restrict__ partial)
 {
     const bool none = S[CV_NORM2] == 0.0;
     double acc = 0.0;
-    for (int64_t e = (int64_t)blockIdx.x * CV_RANGE + threadIdx.x; e < cv_range_end(n); e += CV_THREADS) {
+    for (int64_t e = range_first(); e < range_end(n); e += RANGE_THREADS) {
         const double d = none ? 0.0 : -eta * v0[e] - (u[e] - sigma * s[e] + eta * eta * y[e]);
         acc += d * d;
     }
-    acc = cv_block_sum(acc);
+    acc = block_sum<RANGE_THREADS>(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
@@ -216,12 +169,9 @@ __global__ void __launch_bounds__(CV_THREADS) cv_true_residual_kernel(const doub
 //                      the convergence and max_it decisions.  CV_APPLY tells the direction kernel of THIS iteration whether it counted
 //   stage 3 (closing): the squared true residual; not finite (an H that is not) -> dead, reported as infinity
 // A stopped run passes stages 1 and 2 unchanged.
-__global__ void __launch_bounds__(CV_THREADS) cv_scalar_kernel(const double* __restrict__ partial, int nblk, double* __restrict__ S, int stage, double eta2, double tol2, int max_it)
+__global__ void __launch_bounds__(RANGE_THREADS) cv_scalar_kernel(const double* __restrict__ partial, int nblk, double* __restrict__ S, int stage, double eta2, double tol2, int max_it)
 {
-    double a = 0.0, b = 0.0;
-    for (int k = threadIdx.x; k < nblk; k += CV_THREADS) { a += partial[k]; if (stage == 1) b += partial[nblk + k]; }
-    a = cv_block_sum(a);
-    b = cv_block_sum(b);
+    const double a = sum_partials<RANGE_THREADS>(partial, nblk), b = stage == 1 ? sum_partials<RANGE_THREADS>(partial + nblk, nblk) : 0.0;
     if (threadIdx.x != 0) return;
     if (stage == 0) {
         const double bb = eta2 * a;
@@ -259,12 +209,6 @@ __global__ void __launch_bounds__(CV_THREADS) cv_scalar_kernel(const double* __r
     else if (it >= (double)max_it) S[CV_STOP] = 1.0;
 }
 
-bool cv_overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na * sizeof(double), b0 = (uintptr_t)b, b1 = b0 + nb * sizeof(double);
-    return a && b && na && nb && a0 < b1 && b0 < a1;
-}
-
 }  // namespace
 }  // namespace dmrgx
 
@@ -282,43 +226,40 @@ extern "C" dmrgx_status dmrgx_kron_correction_vector(dmrgx_kron_plan* plan, cons
     if (max_it < 1) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_correction_vector: max_it %d, at least one iteration is needed", max_it);
     if (check_every < 0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_correction_vector: check_every %d is negative", check_every);
     if (nu < 0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_correction_vector: nu %d is negative", nu);
-    dmrgx_kron_info I;
-    DMRGX_CHK(dmrgx_kron_plan_info(plan, &I));
-    if (I.vec_len != I.n_states || I.local_len != I.n_states)
-        DMRGX_FAIL(DMRGX_ERR_ARG, "kron_correction_vector: the plan is striped over ranks (world_size > 1): the iteration has no collectives");
-    const int64_t n = I.n_states;
+    int64_t n = 0;
+    DMRGX_CHK(whole_plan_states(plan, "kron_correction_vector", "iteration", &n));
     if (nu > 0 && (!U_dev || ldu < n)) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_correction_vector: U is null or ldu %lld is smaller than n_states %lld", (long long)ldu, (long long)n);
     const size_t nn = (size_t)n, u_span = nu > 0 ? (size_t)(nu - 1) * (size_t)ldu + nn : 0;
-    if (cv_overlap(Y_dev, nn, v0_dev, nn) || cv_overlap(X_dev, nn, v0_dev, nn) || cv_overlap(Y_dev, nn, X_dev, nn) || cv_overlap(Y_dev, nn, U_dev, u_span) ||
-        cv_overlap(X_dev, nn, U_dev, u_span))
+    if (spans_overlap(Y_dev, nn, v0_dev, nn) || spans_overlap(X_dev, nn, v0_dev, nn) || spans_overlap(Y_dev, nn, X_dev, nn) || spans_overlap(Y_dev, nn, U_dev, u_span) ||
+        spans_overlap(X_dev, nn, U_dev, u_span))
         DMRGX_FAIL(DMRGX_ERR_ARG, "kron_correction_vector: Y or X overlaps v0, U or the other one");
     const double tol_ = tol > 0.0 ? tol : 1e-8, tol2 = tol_ * tol_, eta2 = eta * eta;
     const int64_t ce = check_every > 0 ? check_every : 8;
-    const int nblk = (int)std::max<int64_t>(1, (n + CV_RANGE - 1) / CV_RANGE);
+    const int nblk = range_blocks(n);
     const size_t nscal = (size_t)CV_NS + 2 * (size_t)nu;
     const bool yvec = ((uintptr_t)Y_dev & 15) == 0;
 
-    DevBuf dR, dP, dSv, dT, dPartial, dS;
+    DevBuf dR, dP, dSv, dT, dPartial;
+    DevScalars dS;
     DMRGX_CHK(dR.alloc_f64(nn, st));
     DMRGX_CHK(dP.alloc_f64(nn, st));
     DMRGX_CHK(dSv.alloc_f64(nn, st));
     DMRGX_CHK(dT.alloc_f64(nn, st));
     DMRGX_CHK(dPartial.alloc_f64((size_t)2 * nblk, st));
-    DMRGX_CHK(dS.alloc(nscal * sizeof(double)));
-    DMRGX_HIP(zero_async(dS.p, dS.bytes, st));
-    double* S = dS.as<double>();
+    DMRGX_CHK(dS.alloc_zeroed(nscal, st));
+    double* S = dS.dev();
     double* P = dPartial.as<double>();
     double* r = dR.as<double>();
     double* p = dP.as<double>();
     double* s = dSv.as<double>();
     double* t = dT.as<double>();
-    const dim3 grid((unsigned)nblk), block(CV_THREADS), one(1);
+    const dim3 grid((unsigned)nblk), block(RANGE_THREADS), one(1);
 
     hipLaunchKernelGGL(cv_norm2_kernel, grid, block, 0, st, v0_dev, n, P);
     hipLaunchKernelGGL(cv_scalar_kernel, one, block, 0, st, (const double*)P, nblk, S, 0, eta2, tol2, (int)max_it);
     hipLaunchKernelGGL(cv_start_kernel, grid, block, 0, st, v0_dev, r, p, Y_dev, n, eta, (const double*)S);
     DMRGX_HIP(hipGetLastError());
-    double head[CV_NS];
+    std::vector<double> head(CV_NS), host(nscal);
     int64_t blocks = 0;
     for (;;) {
         for (int64_t k = 0; k < ce; ++k) {
@@ -333,8 +274,7 @@ extern "C" dmrgx_status dmrgx_kron_correction_vector(dmrgx_kron_plan* plan, cons
             DMRGX_HIP(hipGetLastError());
         }
         ++blocks;
-        DMRGX_HIP(hipMemcpyAsync(head, S, sizeof(head), hipMemcpyDeviceToHost, st));      // the one place where the host looks at the device
-        DMRGX_HIP(hipStreamSynchronize(st));
+        DMRGX_CHK(dS.read(head, st));                                // the one place where the host looks at the device
         if (head[CV_STOP] != 0.0) break;
     }
     // closing: X and the true residual of the returned Y, through the same two (x, y) pairs
@@ -349,9 +289,7 @@ extern "C" dmrgx_status dmrgx_kron_correction_vector(dmrgx_kron_plan* plan, cons
         DMRGX_CHK(dmrgx_vec_gram(nu, 1, n, U_dev, ldu, Y_dev, n, S + CV_NS, 1, 0, nullptr, st));
         if (X_dev) DMRGX_CHK(dmrgx_vec_gram(nu, 1, n, U_dev, ldu, X_dev, n, S + CV_NS + nu, 1, 0, nullptr, st));
     }
-    std::vector<double> host(nscal);
-    DMRGX_HIP(hipMemcpyAsync(host.data(), S, nscal * sizeof(double), hipMemcpyDeviceToHost, st));
-    DMRGX_HIP(hipStreamSynchronize(st));
+    DMRGX_CHK(dS.read(host, st));
     const double bb = host[CV_BB];
     *norm2 = host[CV_NORM2];
     stats->iterations = (int32_t)host[CV_ITER];

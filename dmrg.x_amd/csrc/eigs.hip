@@ -12,7 +12,7 @@
 // from device memory, and the host fetches the projected matrix once per cycle (ncv/2 MatMults).
 // world_size > 1: vectors are this rank's stripe segment; per Lanczos step there are exactly two fused all-reduces (of
 // j+2 doubles each) and one all-gather of the Krylov vector before the MatMult.
-#include "common.h"
+#include "krylov.h"
 #include <mutex>
 #include <algorithm>
 #include <chrono>
@@ -24,12 +24,6 @@ namespace dmrgx {
 namespace {
 
 constexpr int DOT_BLOCKS = 1024, DOT_THREADS = 256, DOT_CHUNK = 8, MAX_NCV = 64, FUSE_NV = 24, GD_NV = 8;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
 
 // partial[(chunk*DOT_CHUNK + i) * DOT_BLOCKS + block] = sum_e V[(v0+i)*ldv + e] * w[e]   (i < DOT_CHUNK)
 // the last chunk's slot `nv` holds w.w
@@ -82,15 +76,10 @@ multi_dot_kernel(const double* __restrict__ V, int64_t ldv, int nv, const double
 __global__ void __launch_bounds__(DOT_THREADS)
 reduce_partials_kernel(const double* __restrict__ partial, double* __restrict__ out, int count, int nblk)
 {
-    __shared__ double red[DOT_THREADS / 64];
     const int i = blockIdx.x;
     if (i >= count) return;
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += DOT_THREADS) s += partial[(int64_t)i * nblk + b];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { double t = 0.0; for (int k = 0; k < DOT_THREADS / 64; ++k) t += red[k]; out[i] = t; }
+    const double s = sum_partials<DOT_THREADS>(partial + (int64_t)i * nblk, nblk);
+    if (threadIdx.x == 0) out[i] = s;
 }
 
 // w -= sum_i c[i] V[i] ; partial[b] = sum_e w[e]^2 ; hacc[i] += c[i] (accumulated projection coefficients)
@@ -99,7 +88,6 @@ multi_axpy_kernel(const double* __restrict__ V, int64_t ldv, int nv, const doubl
                   double* __restrict__ partial, double* __restrict__ hacc)
 {
     __shared__ double cs[MAX_NCV + 1];
-    __shared__ double red[DOT_THREADS / 64];
     if (threadIdx.x < nv) cs[threadIdx.x] = c[threadIdx.x];
     __syncthreads();
     if (blockIdx.x == 0 && threadIdx.x < nv && hacc) hacc[threadIdx.x] += cs[threadIdx.x];
@@ -110,10 +98,8 @@ multi_axpy_kernel(const double* __restrict__ V, int64_t ldv, int nv, const doubl
         w[e] = x;
         nrm += x * x;
     }
-    nrm = wave_sum(nrm);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = nrm;
-    __syncthreads();
-    if (threadIdx.x == 0) { double t = 0.0; for (int k = 0; k < DOT_THREADS / 64; ++k) t += red[k]; partial[blockIdx.x] = t; }
+    nrm = block_sum<DOT_THREADS>(nrm);
+    if (threadIdx.x == 0) partial[blockIdx.x] = nrm;
 }
 
 // First Gram-Schmidt pass fused with the dots of the second: w' = w - V c is formed per element and immediately
@@ -549,17 +535,12 @@ __global__ void __launch_bounds__(DOT_THREADS)
 gd_reduce_look_kernel(const double* __restrict__ partial, double* __restrict__ out, int count, int nblk, int look_idx, int look_only,
                       const GdState* __restrict__ S, double* __restrict__ look)
 {
-    __shared__ double red[DOT_THREADS / 64];
     const int i = blockIdx.x;
     if (i >= count) return;
     double t = 0.0;
-    if (!look_only) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < nblk; b += DOT_THREADS) s += partial[(int64_t)i * nblk + b];
-        s = wave_sum(s);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) { for (int k = 0; k < DOT_THREADS / 64; ++k) t += red[k]; out[i] = t; }
+    if (!look_only) {                                                          // (a kernel argument: the barriers of the sum stay uniform)
+        t = sum_partials<DOT_THREADS>(partial + (int64_t)i * nblk, nblk);
+        if (threadIdx.x == 0) out[i] = t;
     } else if (threadIdx.x == 0) t = out[i];
     if (threadIdx.x == 0 && i == look_idx) { look[0] = t; look[1] = S->theta; look[2] = S->hv0_2; }
 }

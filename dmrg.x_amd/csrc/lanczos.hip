@@ -14,7 +14,7 @@
 // fixed-order sums of block partials, no atomics: two runs give the same bits.
 // dmrgx_kron_lanczos_basis, further down, is the same run with the basis kept and fully reorthogonalised.
 // dmrgx_kron_chebyshev_moments, after it, is the Chebyshev recursion in the same idiom: moments in place of coefficients, no normalisation.
-#include "common.h"
+#include "krylov.h"
 #include <cmath>
 
 namespace dmrgx {
@@ -24,29 +24,12 @@ constexpr int LZ_BLOCKS = 1024, LZ_THREADS = 256;
 // the device scalars: S[LZ_COEF + j] = alpha_j, S[LZ_COEF + nsteps + j] = beta_j
 enum : int { LZ_NORM2 = 0, LZ_DEAD = 1, LZ_SCALE = 2, LZ_DONE = 3, LZ_INV = 4, LZ_BETA_PREV = 5, LZ_ALPHA = 6, LZ_COEF = 8 };
 
-__device__ __forceinline__ double lz_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// the workgroup's sum of `v`, valid in thread 0 (wave sums added in wave order)
-__device__ __forceinline__ double lz_block_sum(double v) {
-    __shared__ double red[LZ_THREADS / 64];
-    v = lz_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0) for (int k = 0; k < LZ_THREADS / 64; ++k) t += red[k];
-    return t;
-}
-
-// partial[b] = sum over block b's elements of x[e]^2
+// partial[b] = sum of x[e]^2 over e = b LZ_THREADS + thread, strided by the whole grid (corrvec.hip sums contiguous ranges: other bits)
 __global__ void __launch_bounds__(LZ_THREADS) lz_norm2_kernel(const double* __restrict__ x, int64_t n, double* __restrict__ partial)
 {
     double acc = 0.0;
     for (int64_t e = (int64_t)blockIdx.x * LZ_THREADS + threadIdx.x; e < n; e += (int64_t)gridDim.x * LZ_THREADS) acc += x[e] * x[e];
-    acc = lz_block_sum(acc);
+    acc = block_sum<LZ_THREADS>(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
@@ -61,7 +44,7 @@ __global__ void __launch_bounds__(LZ_THREADS) lz_pass1_kernel(double* __restrict
         w[e] = x;
         acc += qcur[e] * x;
     }
-    acc = lz_block_sum(acc);
+    acc = block_sum<LZ_THREADS>(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
@@ -76,15 +59,31 @@ __global__ void __launch_bounds__(LZ_THREADS) lz_pass2_kernel(double* __restrict
         w[e] = x;
         acc += x * x;
     }
-    acc = lz_block_sum(acc);
+    acc = block_sum<LZ_THREADS>(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
-// dst = src / beta, or exact zeros when there is no next vector (whatever src holds)
-__global__ void __launch_bounds__(LZ_THREADS) lz_scale_kernel(const double* src, double* dst, int64_t n, const double* __restrict__ S)
+// dst = src / beta, and dst2 too unless it is null; exact zeros when there is no next vector (whatever src holds).  src may be dst
+// (the three-term run scales in place): neither is __restrict__.  dst2 is never src or dst.
+__global__ void __launch_bounds__(LZ_THREADS) lz_scale_kernel(const double* src, double* dst, double* __restrict__ dst2, int64_t n, const double* __restrict__ S)
 {
     const double inv = S[LZ_INV];
-    for (int64_t e = (int64_t)blockIdx.x * LZ_THREADS + threadIdx.x; e < n; e += (int64_t)gridDim.x * LZ_THREADS) dst[e] = inv != 0.0 ? src[e] * inv : 0.0;
+    for (int64_t e = (int64_t)blockIdx.x * LZ_THREADS + threadIdx.x; e < n; e += (int64_t)gridDim.x * LZ_THREADS) {
+        const double q = inv != 0.0 ? src[e] * inv : 0.0;
+        dst[e] = q;
+        if (dst2) dst2[e] = q;
+    }
+}
+
+// Thread 0 of a scalar kernel, step j alive with finite sums: beta_j = sqrt(s) and the breakdown decision against
+// max(|alpha_i|, i <= j; beta_i, i < j), a = alpha_j.  The step counts; *inv = 1 / beta_j when there is a next vector, else the run is dead.
+__device__ __forceinline__ double lz_decide_beta(double* __restrict__ S, double s, double a, int j, double tol, double* inv)
+{
+    const double scale = fmax(S[LZ_SCALE], fabs(a)), beta = sqrt(s);
+    S[LZ_DONE] = (double)(j + 1);
+    if (beta > tol * scale) { *inv = 1.0 / beta; S[LZ_SCALE] = fmax(scale, beta); S[LZ_BETA_PREV] = beta; }
+    else { S[LZ_DEAD] = 1.0; S[LZ_BETA_PREV] = 0.0; }
+    return beta;
 }
 
 // One workgroup: the partials added in block order, then the scalar logic of the stage.
@@ -94,9 +93,7 @@ __global__ void __launch_bounds__(LZ_THREADS) lz_scale_kernel(const double* src,
 //                    the beta of the breaking step is kept as measured, every later coefficient is 0 and no 1/beta is ever formed of it
 __global__ void __launch_bounds__(LZ_THREADS) lz_reduce_kernel(const double* __restrict__ partial, int nblk, double* __restrict__ S, int stage, int j, int nsteps, double tol)
 {
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += LZ_THREADS) s += partial[b];
-    s = lz_block_sum(s);
+    const double s = sum_partials<LZ_THREADS>(partial, nblk);
     if (threadIdx.x != 0) return;
     const bool dead = S[LZ_DEAD] != 0.0;
     if (stage == 0) {
@@ -114,13 +111,7 @@ __global__ void __launch_bounds__(LZ_THREADS) lz_reduce_kernel(const double* __r
     } else {
         double beta = 0.0, inv = 0.0;
         if (!dead && !(s >= 0.0 && s < INFINITY)) { S[LZ_DEAD] = 1.0; S[LZ_BETA_PREV] = 0.0; S[LZ_ALPHA] = 0.0; S[LZ_COEF + j] = 0.0; }      // likewise: step j does not count
-        else if (!dead) {
-            const double scale = fmax(S[LZ_SCALE], fabs(S[LZ_ALPHA]));
-            beta = sqrt(s);
-            S[LZ_DONE] = (double)(j + 1);
-            if (beta > tol * scale) { inv = 1.0 / beta; S[LZ_SCALE] = fmax(scale, beta); S[LZ_BETA_PREV] = beta; }
-            else { S[LZ_DEAD] = 1.0; S[LZ_BETA_PREV] = 0.0; if (!(beta >= 0.0)) beta = 0.0; }
-        }
+        else if (!dead) beta = lz_decide_beta(S, s, S[LZ_ALPHA], j, tol, &inv);
         S[LZ_INV] = inv;
         S[LZ_COEF + nsteps + j] = beta;
     }
@@ -131,48 +122,37 @@ __global__ void __launch_bounds__(LZ_THREADS) lz_reduce_kernel(const double* __r
 // Row j of V is q_j.  After the three-term step above (pass 1, alpha, pass 2 -- the same kernels), w is orthogonalised against all of
 // q_0..q_j twice by classical Gram-Schmidt:  h = V_{0..j} w  (multi-dot, then one reduction per k),  w -= V_{0..j}^T h  (multi-axpy).
 // alpha_j is everything removed along q_j (the three-term alpha plus h_j of both passes), beta_j = |w| after the second pass.
-// Both kernels are streaming reads of V_{0..j}: a workgroup owns LB_RANGE contiguous elements of the vector, keeps its piece of w in
-// registers (LB_PER doubles per thread) and lets the rows go past in 16-byte loads -- V_{0..j} and w are read once per kernel.
-constexpr int LB_PER = 8, LB_RANGE = LZ_THREADS * LB_PER, LB_KC = 64;
-
-// elements e, e + 1 of p (e even); beyond n: zeros.  VEC: p + e is 16-byte aligned
-template <bool VEC> __device__ __forceinline__ double2 lb_load2(const double* __restrict__ p, int64_t e, int64_t n)
-{
-    if (VEC && e + 1 < n) return *reinterpret_cast<const double2*>(p + e);
-    double2 r;
-    r.x = e < n ? p[e] : 0.0;
-    r.y = e + 1 < n ? p[e + 1] : 0.0;
-    return r;
-}
+// Both kernels are streaming reads of V_{0..j} in the range layout of krylov.h: a workgroup keeps its piece of w in registers (8 doubles
+// per thread) and lets the rows go past in 16-byte loads -- V_{0..j} and w are read once per kernel.
+constexpr int LB_KC = 64;
 
 // partial[k * gridDim.x + b] = sum over block b's range of V[k * ldv + e] * w[e],  k < nk.  Wave sums go to LDS per k and are added in
 // wave order once per LB_KC rows, so that there is no barrier per row.
-template <bool VEC> __global__ void __launch_bounds__(LZ_THREADS) lb_multidot_kernel(const double* __restrict__ w, const double* __restrict__ V, int64_t ldv, int nk, int64_t n,
-                                                                                     double* __restrict__ partial)
+template <bool VEC> __global__ void __launch_bounds__(RANGE_THREADS) lb_multidot_kernel(const double* __restrict__ w, const double* __restrict__ V, int64_t ldv, int nk, int64_t n,
+                                                                                        double* __restrict__ partial)
 {
-    __shared__ double red[LB_KC][LZ_THREADS / 64];
-    const int64_t base = (int64_t)blockIdx.x * LB_RANGE + 2 * threadIdx.x;
-    double2 wr[LB_PER / 2];
+    __shared__ double red[LB_KC][RANGE_THREADS / 64];
+    double2 wr[RANGE_PAIRS];
 #pragma unroll
-    for (int t = 0; t < LB_PER / 2; ++t) wr[t] = lb_load2<true>(w, base + (int64_t)t * 2 * LZ_THREADS, n);      // (w: a pool block, 256-byte aligned)
+    for (int t = 0; t < RANGE_PAIRS; ++t) wr[t] = load2<true>(w, range_pair(t), n);      // (w: a pool block, 256-byte aligned)
     for (int k0 = 0; k0 < nk; k0 += LB_KC) {
         const int kc = min(LB_KC, nk - k0);
         for (int kk = 0; kk < kc; ++kk) {
             const double* __restrict__ row = V + (int64_t)(k0 + kk) * ldv;
-            double2 v[LB_PER / 2];
+            double2 v[RANGE_PAIRS];
 #pragma unroll
-            for (int t = 0; t < LB_PER / 2; ++t) v[t] = lb_load2<VEC>(row, base + (int64_t)t * 2 * LZ_THREADS, n);
+            for (int t = 0; t < RANGE_PAIRS; ++t) v[t] = load2<VEC>(row, range_pair(t), n);
             double acc = 0.0;
 #pragma unroll
-            for (int t = 0; t < LB_PER / 2; ++t) { acc += v[t].x * wr[t].x; acc += v[t].y * wr[t].y; }
-            acc = lz_wave_sum(acc);
+            for (int t = 0; t < RANGE_PAIRS; ++t) { acc += v[t].x * wr[t].x; acc += v[t].y * wr[t].y; }
+            acc = wave_sum(acc);
             if ((threadIdx.x & 63) == 0) red[kk][threadIdx.x >> 6] = acc;
         }
         __syncthreads();
         if ((int)threadIdx.x < kc) {
             double s = 0.0;
 #pragma unroll
-            for (int i = 0; i < LZ_THREADS / 64; ++i) s += red[threadIdx.x][i];
+            for (int i = 0; i < RANGE_THREADS / 64; ++i) s += red[threadIdx.x][i];
             partial[(int64_t)(k0 + threadIdx.x) * gridDim.x + blockIdx.x] = s;
         }
         __syncthreads();
@@ -182,40 +162,34 @@ template <bool VEC> __global__ void __launch_bounds__(LZ_THREADS) lb_multidot_ke
 // block k: h[k] = the partials of row k added in block order
 __global__ void __launch_bounds__(LZ_THREADS) lb_hreduce_kernel(const double* __restrict__ partial, int nblk, double* __restrict__ h)
 {
-    const double* __restrict__ p = partial + (int64_t)blockIdx.x * nblk;
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += LZ_THREADS) s += p[b];
-    s = lz_block_sum(s);
+    const double s = sum_partials<LZ_THREADS>(partial + (int64_t)blockIdx.x * nblk, nblk);
     if (threadIdx.x == 0) h[blockIdx.x] = s;
 }
 
 // w -= sum_{k < nk} h[k] V[k];  NORM: partial[b] = w . w over block b's range afterwards
-template <bool VEC, bool NORM> __global__ void __launch_bounds__(LZ_THREADS) lb_multiaxpy_kernel(double* __restrict__ w, const double* __restrict__ V, int64_t ldv, int nk, int64_t n,
-                                                                                                 const double* __restrict__ h, double* __restrict__ partial)
+template <bool VEC, bool NORM> __global__ void __launch_bounds__(RANGE_THREADS) lb_multiaxpy_kernel(double* __restrict__ w, const double* __restrict__ V, int64_t ldv, int nk, int64_t n,
+                                                                                                    const double* __restrict__ h, double* __restrict__ partial)
 {
-    const int64_t base = (int64_t)blockIdx.x * LB_RANGE + 2 * threadIdx.x;
-    double2 wr[LB_PER / 2];
+    double2 wr[RANGE_PAIRS];
 #pragma unroll
-    for (int t = 0; t < LB_PER / 2; ++t) wr[t] = lb_load2<true>(w, base + (int64_t)t * 2 * LZ_THREADS, n);
+    for (int t = 0; t < RANGE_PAIRS; ++t) wr[t] = load2<true>(w, range_pair(t), n);
     for (int k = 0; k < nk; ++k) {
         const double* __restrict__ row = V + (int64_t)k * ldv;
         const double hk = h[k];
-        double2 v[LB_PER / 2];
+        double2 v[RANGE_PAIRS];
 #pragma unroll
-        for (int t = 0; t < LB_PER / 2; ++t) v[t] = lb_load2<VEC>(row, base + (int64_t)t * 2 * LZ_THREADS, n);
+        for (int t = 0; t < RANGE_PAIRS; ++t) v[t] = load2<VEC>(row, range_pair(t), n);
 #pragma unroll
-        for (int t = 0; t < LB_PER / 2; ++t) { wr[t].x -= hk * v[t].x; wr[t].y -= hk * v[t].y; }
+        for (int t = 0; t < RANGE_PAIRS; ++t) { wr[t].x -= hk * v[t].x; wr[t].y -= hk * v[t].y; }
     }
     double acc = 0.0;
 #pragma unroll
-    for (int t = 0; t < LB_PER / 2; ++t) {
-        const int64_t e = base + (int64_t)t * 2 * LZ_THREADS;
-        if (e + 1 < n) *reinterpret_cast<double2*>(w + e) = wr[t];
-        else if (e < n) w[e] = wr[t].x;
+    for (int t = 0; t < RANGE_PAIRS; ++t) {
+        store2<true>(w, range_pair(t), n, wr[t]);
         if (NORM) { acc += wr[t].x * wr[t].x; acc += wr[t].y * wr[t].y; }      // (beyond n the registers hold zeros)
     }
     if (NORM) {
-        acc = lz_block_sum(acc);
+        acc = block_sum<RANGE_THREADS>(acc);
         if (threadIdx.x == 0) partial[blockIdx.x] = acc;
     }
 }
@@ -225,38 +199,18 @@ template <bool VEC, bool NORM> __global__ void __launch_bounds__(LZ_THREADS) lb_
 __global__ void __launch_bounds__(LZ_THREADS) lb_beta_kernel(const double* __restrict__ partial, int nblk, double* __restrict__ S, const double* __restrict__ h1,
                                                              const double* __restrict__ h2, int j, int nsteps, double tol)
 {
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += LZ_THREADS) s += partial[b];
-    s = lz_block_sum(s);
+    const double s = sum_partials<LZ_THREADS>(partial, nblk);
     if (threadIdx.x != 0) return;
-    const bool dead = S[LZ_DEAD] != 0.0;
     double beta = 0.0, inv = 0.0, a = 0.0;
-    if (!dead) {
+    if (S[LZ_DEAD] == 0.0) {
         a = S[LZ_ALPHA] + h1[j] + h2[j];
         if (!(fabs(a) < INFINITY) || !(s >= 0.0 && s < INFINITY)) { S[LZ_DEAD] = 1.0; S[LZ_BETA_PREV] = 0.0; a = 0.0; }      // step j does not count
-        else {
-            const double scale = fmax(S[LZ_SCALE], fabs(a));
-            beta = sqrt(s);
-            S[LZ_DONE] = (double)(j + 1);
-            if (beta > tol * scale) { inv = 1.0 / beta; S[LZ_SCALE] = fmax(scale, beta); S[LZ_BETA_PREV] = beta; }
-            else { S[LZ_DEAD] = 1.0; S[LZ_BETA_PREV] = 0.0; }
-        }
+        else beta = lz_decide_beta(S, s, a, j, tol, &inv);
     }
     S[LZ_ALPHA] = a;
     S[LZ_COEF + j] = a;
     S[LZ_INV] = inv;
     S[LZ_COEF + nsteps + j] = beta;
-}
-
-// row = x = src / beta, or exact zeros when there is no next vector (whatever src holds)
-__global__ void __launch_bounds__(LZ_THREADS) lb_scale2_kernel(const double* __restrict__ src, double* __restrict__ row, double* __restrict__ x, int64_t n, const double* __restrict__ S)
-{
-    const double inv = S[LZ_INV];
-    for (int64_t e = (int64_t)blockIdx.x * LZ_THREADS + threadIdx.x; e < n; e += (int64_t)gridDim.x * LZ_THREADS) {
-        const double q = inv != 0.0 ? src[e] * inv : 0.0;
-        row[e] = q;
-        x[e] = q;
-    }
 }
 
 // A run that a non-finite sum ended inside step j leaves q_j in row j although step j does not count: rows >= steps done are zeros.
@@ -295,7 +249,7 @@ __global__ void __launch_bounds__(LZ_THREADS) cb_start_kernel(const double* __re
     }
 }
 
-// One step of the recursion over the workgroup's LB_RANGE contiguous elements (the last range is ragged: nothing at or past n is read or
+// One step of the recursion over the workgroup's RANGE_LEN contiguous elements (the last range is ragged: nothing at or past n is read or
 // written).  FIRST: t_1 = (w - centre x) / half_width, the row of t_{-1} does not exist and is not read.  x, w, prev and next are 16-byte
 // aligned (pool blocks; ring rows with an even leading dimension).  partial[b] = t_{n+1} . t_{n+1}, partial[gridDim.x + b] = t_{n+1} . t_n
 // over block b.  Once the run is dead: zeros into next and x, whatever w and prev hold.
@@ -304,21 +258,20 @@ template <bool FIRST> __global__ void __launch_bounds__(LZ_THREADS) cb_step_kern
                                                                                   const double* __restrict__ S, double* __restrict__ partial)
 {
     const bool dead = S[CB_DEAD] != 0.0;
-    const int64_t base = (int64_t)blockIdx.x * LB_RANGE + 2 * threadIdx.x;
-    double2 t[LB_PER / 2], c[LB_PER / 2];
+    double2 t[RANGE_PAIRS], c[RANGE_PAIRS];
 #pragma unroll
-    for (int i = 0; i < LB_PER / 2; ++i) { t[i] = double2{0.0, 0.0}; c[i] = double2{0.0, 0.0}; }
+    for (int i = 0; i < RANGE_PAIRS; ++i) { t[i] = double2{0.0, 0.0}; c[i] = double2{0.0, 0.0}; }
     if (!dead) {
-        double2 wr[LB_PER / 2], pr[LB_PER / 2];
+        double2 wr[RANGE_PAIRS], pr[RANGE_PAIRS];
 #pragma unroll
-        for (int i = 0; i < LB_PER / 2; ++i) {
-            const int64_t e = base + (int64_t)i * 2 * LZ_THREADS;
-            wr[i] = lb_load2<true>(w, e, n);
-            c[i] = lb_load2<true>(x, e, n);
-            if (!FIRST) pr[i] = lb_load2<true>(prev, e, n);
+        for (int i = 0; i < RANGE_PAIRS; ++i) {
+            const int64_t e = range_pair(i);
+            wr[i] = load2<true>(w, e, n);
+            c[i] = load2<true>(x, e, n);
+            if (!FIRST) pr[i] = load2<true>(prev, e, n);
         }
 #pragma unroll
-        for (int i = 0; i < LB_PER / 2; ++i) {
+        for (int i = 0; i < RANGE_PAIRS; ++i) {
             t[i].x = scale * (wr[i].x - centre * c[i].x);
             t[i].y = scale * (wr[i].y - centre * c[i].y);
             if (!FIRST) { t[i].x -= pr[i].x; t[i].y -= pr[i].y; }
@@ -326,16 +279,14 @@ template <bool FIRST> __global__ void __launch_bounds__(LZ_THREADS) cb_step_kern
     }
     double tt = 0.0, tc = 0.0;
 #pragma unroll
-    for (int i = 0; i < LB_PER / 2; ++i) {
-        const int64_t e = base + (int64_t)i * 2 * LZ_THREADS;
-        if (e + 1 < n) { *reinterpret_cast<double2*>(next + e) = t[i]; *reinterpret_cast<double2*>(x + e) = t[i]; }
-        else if (e < n) { next[e] = t[i].x; x[e] = t[i].x; }
+    for (int i = 0; i < RANGE_PAIRS; ++i) {
+        store2<true>(next, range_pair(i), n, t[i]);
+        store2<true>(x, range_pair(i), n, t[i]);
         tt += t[i].x * t[i].x; tt += t[i].y * t[i].y;            // (beyond n the registers hold zeros)
         tc += t[i].x * c[i].x; tc += t[i].y * c[i].y;
     }
-    tt = lz_block_sum(tt);
-    __syncthreads();                                             // lz_block_sum's LDS is used again
-    tc = lz_block_sum(tc);
+    tt = block_sum<RANGE_THREADS>(tt);
+    tc = block_sum<RANGE_THREADS>(tc);
     if (threadIdx.x == 0) { partial[blockIdx.x] = tt; partial[gridDim.x + blockIdx.x] = tc; }
 }
 
@@ -345,11 +296,7 @@ template <bool FIRST> __global__ void __launch_bounds__(LZ_THREADS) cb_step_kern
 // and mu_{2n+2} = 2 t_{n+1}.t_{n+1} - mu_0.  The moments of a dead run stay the zeros the array was filled with.
 __global__ void __launch_bounds__(LZ_THREADS) cb_scalar_kernel(const double* __restrict__ partial, int nblk, double* __restrict__ S, int stage, int n)
 {
-    double a = 0.0, b = 0.0;
-    for (int k = threadIdx.x; k < nblk; k += LZ_THREADS) { a += partial[k]; if (stage) b += partial[nblk + k]; }
-    a = lz_block_sum(a);
-    __syncthreads();
-    b = lz_block_sum(b);
+    const double a = sum_partials<LZ_THREADS>(partial, nblk), b = stage ? sum_partials<LZ_THREADS>(partial + nblk, nblk) : 0.0;
     if (threadIdx.x != 0) return;
     if (stage == 0) {
         const bool ok = a > 0.0 && a < INFINITY;
@@ -378,6 +325,31 @@ __global__ void __launch_bounds__(LZ_THREADS) cb_zero_invalid_rows_kernel(double
     for (int64_t e = (int64_t)blockIdx.x * LZ_THREADS + threadIdx.x; e < n; e += (int64_t)gridDim.x * LZ_THREADS) row[e] = 0.0;
 }
 
+// ---- host side ----------------------------------------------------------------------------------------------------------------------
+// vec: every row of V is 16-byte aligned
+void lb_multidot(bool vec, int nblk, hipStream_t st, const double* w, const double* V, int64_t ldv, int nk, int64_t n, double* partial)
+{
+    const auto kernel = vec ? lb_multidot_kernel<true> : lb_multidot_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(nblk), dim3(RANGE_THREADS), 0, st, w, V, ldv, nk, n, partial);
+}
+
+void lb_multiaxpy(bool vec, bool norm, int nblk, hipStream_t st, double* w, const double* V, int64_t ldv, int nk, int64_t n, const double* h, double* partial)
+{
+    const auto kernel = vec ? (norm ? lb_multiaxpy_kernel<true, true> : lb_multiaxpy_kernel<true, false>) : (norm ? lb_multiaxpy_kernel<false, true> : lb_multiaxpy_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(nblk), dim3(RANGE_THREADS), 0, st, w, V, ldv, nk, n, h, partial);
+}
+
+// the end of both Lanczos calls: the one copy and synchronisation, then norm2, the steps done and the coefficients
+dmrgx_status lz_read_out(const DevScalars& S, int32_t nsteps, double* norm2, double* alpha, double* beta, int32_t* nsteps_done, hipStream_t st)
+{
+    std::vector<double> host((size_t)LZ_COEF + 2 * (size_t)nsteps);
+    DMRGX_CHK(S.read(host, st));
+    *norm2 = host[LZ_NORM2];
+    *nsteps_done = (int32_t)host[LZ_DONE];
+    for (int32_t j = 0; j < nsteps; ++j) { alpha[j] = host[LZ_COEF + j]; beta[j] = host[LZ_COEF + nsteps + j]; }
+    return DMRGX_OK;
+}
+
 }  // namespace
 }  // namespace dmrgx
 
@@ -393,24 +365,21 @@ extern "C" dmrgx_status dmrgx_kron_chebyshev_moments(dmrgx_kron_plan* plan, cons
     if (!(half_width > 0.0 && half_width < INFINITY) || !(fabs(centre) < INFINITY))
         DMRGX_FAIL(DMRGX_ERR_ARG, "kron_chebyshev_moments: window centre %g, half width %g: a finite centre and a positive finite half width are needed", centre, half_width);
     if (nu < 0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_chebyshev_moments: nu %d is negative", nu);
-    dmrgx_kron_info I;
-    DMRGX_CHK(dmrgx_kron_plan_info(plan, &I));
-    if (I.vec_len != I.n_states || I.local_len != I.n_states)
-        DMRGX_FAIL(DMRGX_ERR_ARG, "kron_chebyshev_moments: the plan is striped over ranks (world_size > 1): the recursion has no collectives");
-    const int64_t n = I.n_states;
+    int64_t n = 0;
+    DMRGX_CHK(whole_plan_states(plan, "kron_chebyshev_moments", "recursion", &n));
     if (nu > 0 && (!U_dev || ldu < n)) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_chebyshev_moments: U is null or ldu %lld is smaller than n_states %lld", (long long)ldu, (long long)n);
     const int64_t K = nsteps, ldr = (n + 1) & ~(int64_t)1;      // ring rows 16-byte aligned
-    const int nblk = (int)std::max<int64_t>(1, (n + LB_RANGE - 1) / LB_RANGE);
+    const int nblk = range_blocks(n);
     const size_t ndiag = (size_t)(2 * K + 1), nscal = (size_t)CB_MOM + ndiag + (size_t)(K + 1) * (size_t)nu;
 
-    DevBuf dX, dW, dRing, dPartial, dS;
+    DevBuf dX, dW, dRing, dPartial;
+    DevScalars dS;
     DMRGX_CHK(dX.alloc_f64((size_t)n, st));
     DMRGX_CHK(dW.alloc_f64((size_t)n, st));
     DMRGX_CHK(dRing.alloc_f64((size_t)CB_RING * (size_t)ldr, st));
     DMRGX_CHK(dPartial.alloc_f64((size_t)std::max(LZ_BLOCKS, 2 * nblk), st));
-    DMRGX_CHK(dS.alloc(nscal * sizeof(double)));
-    DMRGX_HIP(zero_async(dS.p, dS.bytes, st));
-    double* S = dS.as<double>();
+    DMRGX_CHK(dS.alloc_zeroed(nscal, st));
+    double* S = dS.dev();
     double* P = dPartial.as<double>();
     double* x = dX.as<double>();
     double* w = dW.as<double>();
@@ -433,16 +402,15 @@ extern "C" dmrgx_status dmrgx_kron_chebyshev_moments(dmrgx_kron_plan* plan, cons
     for (int64_t j = 0; j < K; ++j) {                            // step j: t_{j+1} from x = t_j and ring row of t_{j-1}
         double* next = ring + ((j + 1) % CB_RING) * ldr;
         DMRGX_CHK(dmrgx_kron_apply(plan, x, w, st));
-        if (j == 0) hipLaunchKernelGGL(cb_step_kernel<true>, dim3(nblk), dim3(LZ_THREADS), 0, st, (const double*)w, x, (const double*)nullptr, next, n, centre, 1.0 / half_width, (const double*)S, P);
-        else hipLaunchKernelGGL(cb_step_kernel<false>, dim3(nblk), dim3(LZ_THREADS), 0, st, (const double*)w, x, (const double*)(ring + ((j - 1) % CB_RING) * ldr), next, n, centre, 2.0 / half_width, (const double*)S, P);
+        if (j == 0) hipLaunchKernelGGL(cb_step_kernel<true>, dim3(nblk), dim3(RANGE_THREADS), 0, st, (const double*)w, x, (const double*)nullptr, next, n, centre, 1.0 / half_width, (const double*)S, P);
+        else hipLaunchKernelGGL(cb_step_kernel<false>, dim3(nblk), dim3(RANGE_THREADS), 0, st, (const double*)w, x, (const double*)(ring + ((j - 1) % CB_RING) * ldr), next, n, centre, 2.0 / half_width, (const double*)S, P);
         hipLaunchKernelGGL(cb_scalar_kernel, dim3(1), dim3(LZ_THREADS), 0, st, (const double*)P, nblk, S, 1, (int)j);
         DMRGX_HIP(hipGetLastError());
         if ((j + 2) % CB_BLOCK == 0) DMRGX_CHK(gram_block(j + 2 - CB_BLOCK, CB_BLOCK));      // t_{j+1} completes a block of 16
     }
     if ((K + 1) % CB_BLOCK) DMRGX_CHK(gram_block((K + 1) / CB_BLOCK * CB_BLOCK, (int)((K + 1) % CB_BLOCK)));
     std::vector<double> host(nscal);
-    DMRGX_HIP(hipMemcpyAsync(host.data(), S, nscal * sizeof(double), hipMemcpyDeviceToHost, st));
-    DMRGX_HIP(hipStreamSynchronize(st));
+    DMRGX_CHK(dS.read(host, st));
     const int64_t valid = (int64_t)host[CB_VALID], D = std::max<int64_t>(valid - 1, 0);
     *norm2 = host[CB_NORM2];
     *nsteps_done = (int32_t)D;
@@ -460,20 +428,16 @@ extern "C" dmrgx_status dmrgx_kron_lanczos_coeffs(dmrgx_kron_plan* plan, const d
     if (!plan || !v0_dev || !norm2 || !alpha || !beta || !nsteps_done) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_coeffs: null argument");
     if (nsteps < 1) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_coeffs: nsteps %d, at least one step is needed", nsteps);
     if (!(breakdown_tol >= 0.0) || breakdown_tol >= 1.0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_coeffs: breakdown_tol %g outside [0, 1)", breakdown_tol);
-    dmrgx_kron_info I;
-    DMRGX_CHK(dmrgx_kron_plan_info(plan, &I));
-    if (I.vec_len != I.n_states || I.local_len != I.n_states)
-        DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_coeffs: the plan is striped over ranks (world_size > 1): the recursion has no collectives");
+    int64_t n = 0;
+    DMRGX_CHK(whole_plan_states(plan, "kron_lanczos_coeffs", "recursion", &n));
     const double tol = breakdown_tol > 0.0 ? breakdown_tol : 1e-7;
-    const int64_t n = I.n_states;
-    const size_t nscal = (size_t)LZ_COEF + 2 * (size_t)nsteps;
 
-    DevBuf dQ, dPartial, dS;
+    DevBuf dQ, dPartial;
+    DevScalars dS;
     DMRGX_CHK(dQ.alloc_f64((size_t)3 * n, st));
     DMRGX_CHK(dPartial.alloc_f64((size_t)LZ_BLOCKS, st));
-    DMRGX_CHK(dS.alloc(nscal * sizeof(double)));
-    DMRGX_HIP(zero_async(dS.p, dS.bytes, st));
-    double* S = dS.as<double>();
+    DMRGX_CHK(dS.alloc_zeroed((size_t)LZ_COEF + 2 * (size_t)nsteps, st));
+    double* S = dS.dev();
     double* P = dPartial.as<double>();
     double* qprev = dQ.as<double>();
     double* qcur = qprev + n;
@@ -482,7 +446,7 @@ extern "C" dmrgx_status dmrgx_kron_lanczos_coeffs(dmrgx_kron_plan* plan, const d
 
     hipLaunchKernelGGL(lz_norm2_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, v0_dev, n, P);
     hipLaunchKernelGGL(lz_reduce_kernel, dim3(1), dim3(LZ_THREADS), 0, st, (const double*)P, LZ_BLOCKS, S, 0, 0, nsteps, tol);
-    hipLaunchKernelGGL(lz_scale_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, v0_dev, qcur, n, (const double*)S);
+    hipLaunchKernelGGL(lz_scale_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, v0_dev, qcur, (double*)nullptr, n, (const double*)S);
     DMRGX_HIP(hipGetLastError());
     for (int32_t j = 0; j < nsteps; ++j) {
         DMRGX_CHK(dmrgx_kron_apply(plan, qcur, w, st));
@@ -490,17 +454,11 @@ extern "C" dmrgx_status dmrgx_kron_lanczos_coeffs(dmrgx_kron_plan* plan, const d
         hipLaunchKernelGGL(lz_reduce_kernel, dim3(1), dim3(LZ_THREADS), 0, st, (const double*)P, LZ_BLOCKS, S, 1, j, nsteps, tol);
         hipLaunchKernelGGL(lz_pass2_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, w, (const double*)qcur, n, (const double*)S, P);
         hipLaunchKernelGGL(lz_reduce_kernel, dim3(1), dim3(LZ_THREADS), 0, st, (const double*)P, LZ_BLOCKS, S, 2, j, nsteps, tol);
-        hipLaunchKernelGGL(lz_scale_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, (const double*)w, w, n, (const double*)S);
+        hipLaunchKernelGGL(lz_scale_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, (const double*)w, w, (double*)nullptr, n, (const double*)S);
         DMRGX_HIP(hipGetLastError());
         double* t = qprev; qprev = qcur; qcur = w; w = t;               // three buffers, three (x, y) pairs: the plan patches its tables once each
     }
-    std::vector<double> host(nscal);
-    DMRGX_HIP(hipMemcpyAsync(host.data(), S, nscal * sizeof(double), hipMemcpyDeviceToHost, st));
-    DMRGX_HIP(hipStreamSynchronize(st));
-    *norm2 = host[LZ_NORM2];
-    *nsteps_done = (int32_t)host[LZ_DONE];
-    for (int32_t j = 0; j < nsteps; ++j) { alpha[j] = host[LZ_COEF + j]; beta[j] = host[LZ_COEF + nsteps + j]; }
-    return DMRGX_OK;
+    return lz_read_out(dS, nsteps, norm2, alpha, beta, nsteps_done, st);
 }
 
 extern "C" dmrgx_status dmrgx_kron_lanczos_basis(dmrgx_kron_plan* plan, const double* v0_dev, int32_t nsteps, double breakdown_tol, double* V_dev, int64_t ldv,
@@ -510,32 +468,24 @@ extern "C" dmrgx_status dmrgx_kron_lanczos_basis(dmrgx_kron_plan* plan, const do
     if (!plan || !v0_dev || !V_dev || !norm2 || !alpha || !beta || !nsteps_done) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_basis: null argument");
     if (nsteps < 1) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_basis: nsteps %d, at least one step is needed", nsteps);
     if (!(breakdown_tol >= 0.0) || breakdown_tol >= 1.0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_basis: breakdown_tol %g outside [0, 1)", breakdown_tol);
-    dmrgx_kron_info I;
-    DMRGX_CHK(dmrgx_kron_plan_info(plan, &I));
-    if (I.vec_len != I.n_states || I.local_len != I.n_states)
-        DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_basis: the plan is striped over ranks (world_size > 1): the recursion has no collectives");
-    const int64_t n = I.n_states;
+    int64_t n = 0;
+    DMRGX_CHK(whole_plan_states(plan, "kron_lanczos_basis", "recursion", &n));
     if (ldv < n) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_basis: ldv %lld is smaller than n_states %lld", (long long)ldv, (long long)n);
-    {
-        const uintptr_t v_lo = (uintptr_t)V_dev, v_hi = v_lo + ((size_t)(nsteps - 1) * (size_t)ldv + (size_t)n) * sizeof(double);
-        const uintptr_t s_lo = (uintptr_t)v0_dev, s_hi = s_lo + (size_t)n * sizeof(double);
-        if (v_lo < s_hi && s_lo < v_hi) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_basis: V overlaps v0");
-    }
+    if (spans_overlap(V_dev, (size_t)(nsteps - 1) * (size_t)ldv + (size_t)n, v0_dev, (size_t)n)) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_lanczos_basis: V overlaps v0");
     const double tol = breakdown_tol > 0.0 ? breakdown_tol : 1e-7;
-    const size_t nscal = (size_t)LZ_COEF + 2 * (size_t)nsteps;
-    const int nblk = (int)std::max<int64_t>(1, (n + LB_RANGE - 1) / LB_RANGE);
+    const int nblk = range_blocks(n);
     const bool vec = ((uintptr_t)V_dev & 15) == 0 && (ldv & 1) == 0;      // every row 16-byte aligned
 
     // x = q_j and w = H q_j are fixed buffers: the plan sees one (x, y) pair for the whole run, and never a row of V
-    DevBuf dX, dW, dPartial, dRowPartial, dH, dS;
+    DevBuf dX, dW, dPartial, dRowPartial, dH;
+    DevScalars dS;
     DMRGX_CHK(dX.alloc_f64((size_t)n, st));
     DMRGX_CHK(dW.alloc_f64((size_t)n, st));
     DMRGX_CHK(dPartial.alloc_f64((size_t)std::max(LZ_BLOCKS, nblk), st));
     DMRGX_CHK(dRowPartial.alloc_f64((size_t)nsteps * (size_t)nblk, st));
     DMRGX_CHK(dH.alloc_f64((size_t)2 * (size_t)nsteps, st));
-    DMRGX_CHK(dS.alloc(nscal * sizeof(double)));
-    DMRGX_HIP(zero_async(dS.p, dS.bytes, st));
-    double* S = dS.as<double>();
+    DMRGX_CHK(dS.alloc_zeroed((size_t)LZ_COEF + 2 * (size_t)nsteps, st));
+    double* S = dS.dev();
     double* P = dPartial.as<double>();
     double* RP = dRowPartial.as<double>();
     double* h1 = dH.as<double>();
@@ -545,7 +495,7 @@ extern "C" dmrgx_status dmrgx_kron_lanczos_basis(dmrgx_kron_plan* plan, const do
 
     hipLaunchKernelGGL(lz_norm2_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, v0_dev, n, P);
     hipLaunchKernelGGL(lz_reduce_kernel, dim3(1), dim3(LZ_THREADS), 0, st, (const double*)P, LZ_BLOCKS, S, 0, 0, nsteps, tol);
-    hipLaunchKernelGGL(lb_scale2_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, v0_dev, V_dev, x, n, (const double*)S);
+    hipLaunchKernelGGL(lz_scale_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, v0_dev, V_dev, x, n, (const double*)S);
     DMRGX_HIP(hipGetLastError());
     for (int32_t j = 0; j < nsteps; ++j) {
         const double* qcur = V_dev + (int64_t)j * ldv;
@@ -557,28 +507,15 @@ extern "C" dmrgx_status dmrgx_kron_lanczos_basis(dmrgx_kron_plan* plan, const do
         hipLaunchKernelGGL(lz_pass2_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, w, qcur, n, (const double*)S, P);
         for (int pass = 0; pass < 2; ++pass) {
             double* h = pass ? h2 : h1;                                       // entries [0, j] are rewritten every step; entry j is what the beta kernel reads
-            if (vec) hipLaunchKernelGGL(lb_multidot_kernel<true>, dim3(nblk), dim3(LZ_THREADS), 0, st, (const double*)w, (const double*)V_dev, ldv, nk, n, RP);
-            else hipLaunchKernelGGL(lb_multidot_kernel<false>, dim3(nblk), dim3(LZ_THREADS), 0, st, (const double*)w, (const double*)V_dev, ldv, nk, n, RP);
+            lb_multidot(vec, nblk, st, w, V_dev, ldv, nk, n, RP);
             hipLaunchKernelGGL(lb_hreduce_kernel, dim3(nk), dim3(LZ_THREADS), 0, st, (const double*)RP, nblk, h);
-            if (pass == 0) {
-                if (vec) hipLaunchKernelGGL((lb_multiaxpy_kernel<true, false>), dim3(nblk), dim3(LZ_THREADS), 0, st, w, (const double*)V_dev, ldv, nk, n, (const double*)h, P);
-                else hipLaunchKernelGGL((lb_multiaxpy_kernel<false, false>), dim3(nblk), dim3(LZ_THREADS), 0, st, w, (const double*)V_dev, ldv, nk, n, (const double*)h, P);
-            } else {
-                if (vec) hipLaunchKernelGGL((lb_multiaxpy_kernel<true, true>), dim3(nblk), dim3(LZ_THREADS), 0, st, w, (const double*)V_dev, ldv, nk, n, (const double*)h, P);
-                else hipLaunchKernelGGL((lb_multiaxpy_kernel<false, true>), dim3(nblk), dim3(LZ_THREADS), 0, st, w, (const double*)V_dev, ldv, nk, n, (const double*)h, P);
-            }
+            lb_multiaxpy(vec, pass == 1, nblk, st, w, V_dev, ldv, nk, n, h, P);      // the second pass leaves the partials of w . w
         }
         hipLaunchKernelGGL(lb_beta_kernel, dim3(1), dim3(LZ_THREADS), 0, st, (const double*)P, nblk, S, (const double*)h1, (const double*)h2, j, nsteps, tol);
-        if (j + 1 < nsteps) hipLaunchKernelGGL(lb_scale2_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, (const double*)w, V_dev + (int64_t)(j + 1) * ldv, x, n, (const double*)S);
+        if (j + 1 < nsteps) hipLaunchKernelGGL(lz_scale_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, (const double*)w, V_dev + (int64_t)(j + 1) * ldv, x, n, (const double*)S);
         DMRGX_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(lb_zero_uncounted_row_kernel, dim3(LZ_BLOCKS), dim3(LZ_THREADS), 0, st, V_dev, ldv, n, nsteps, (const double*)S);
     DMRGX_HIP(hipGetLastError());
-    std::vector<double> host(nscal);
-    DMRGX_HIP(hipMemcpyAsync(host.data(), S, nscal * sizeof(double), hipMemcpyDeviceToHost, st));
-    DMRGX_HIP(hipStreamSynchronize(st));
-    *norm2 = host[LZ_NORM2];
-    *nsteps_done = (int32_t)host[LZ_DONE];
-    for (int32_t j = 0; j < nsteps; ++j) { alpha[j] = host[LZ_COEF + j]; beta[j] = host[LZ_COEF + nsteps + j]; }
-    return DMRGX_OK;
+    return lz_read_out(dS, nsteps, norm2, alpha, beta, nsteps_done, st);
 }

@@ -1,5 +1,6 @@
 // libdmrgx_hip.so: library-level entry points (error reporting, device probe, plain GEMM wrapper).
 #include "ggemm.h"
+#include "krylov.h"
 #include <algorithm>
 
 namespace dmrgx {
@@ -184,13 +185,10 @@ namespace {
 constexpr int VDOT_BLOCKS = 512, VDOT_THREADS = 256;
 __global__ void __launch_bounds__(VDOT_THREADS) vdot_partial_kernel(const double* __restrict__ x, const double* __restrict__ y, int64_t n, double* __restrict__ partial)
 {
-    __shared__ double red[VDOT_THREADS / 64];
     double s = 0.0;
     for (int64_t e = (int64_t)blockIdx.x * VDOT_THREADS + threadIdx.x; e < n; e += (int64_t)VDOT_BLOCKS * VDOT_THREADS) s += x[e] * y[e];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { double t = 0.0; for (int k = 0; k < VDOT_THREADS / 64; ++k) t += red[k]; partial[blockIdx.x] = t; }
+    s = block_sum<VDOT_THREADS>(s);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 }  // namespace
 }  // namespace dmrgx

@@ -1,7 +1,7 @@
 """Child process of tests/test_gpu_poison.py: runs fixed-input kernels and writes their outputs to an .npz file, so that runs in
 separate processes -- clean or with DMRGX_POOL_POISON=1 -- can be compared bit for bit.
 
-    python tests/bitwise_worker.py OUT.npz apply,solvers,striped
+    python tests/bitwise_worker.py OUT.npz apply,solvers,striped,krylov
 """
 import hashlib
 import os
@@ -81,6 +81,53 @@ def striped(out):
             p.destroy()
 
 
+def krylov(out):
+    """The device-resident Krylov calls and dmrgx_dot on helpers.krylov_superblock at 845 states (odd, inside one 2048-element range) and
+    4097 (odd, across two range borders), every input from a fixed seed; every returned array and scalar is kept.  lanczos_basis runs
+    into a fresh V (ldv = n, odd: 8-byte loads) and into a view of a wider tensor with an even row stride (16-byte loads); the Chebyshev
+    run of 17 steps crosses one Gram block of 16 rows; the correction vector runs with check_every 0 and 3 and into a Y 8 bytes off a
+    16-byte boundary (eta and sigma as in test_gpu_corrvec.CASES[0]: 0.5 and the spectrum's lower end, -33.53 and -93.84 to four digits;
+    a numpy restatement converges to 1e-10 in 270 and 324 iterations)."""
+    import ctypes as C
+    from dmrgx_amd import _capi
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from helpers import krylov_superblock
+    for n, sigma in ((845, -33.5), (4097, -93.8)):
+        plan = sbm.KronPlan(krylov_superblock(wl, n))
+        rng = np.random.default_rng(300 + n)
+        v0 = torch.from_numpy(rng.standard_normal(n)).cuda()
+        U = torch.from_numpy(rng.standard_normal((13, n))).cuda()
+
+        def keep(tag, names, values):
+            for name, value in zip(names, values):
+                out["krylov_%d_%s_%s" % (n, tag, name)] = value.cpu().numpy() if torch.is_tensor(value) else np.array(value)
+
+        keep("coeffs", ("norm2", "alpha", "beta", "done"), plan.lanczos_coeffs(v0, 12))
+        keep("basis_odd", ("norm2", "alpha", "beta", "done", "V"), plan.lanczos_basis(v0, 12))
+        wide = torch.full((12, n + 3), float("nan"), dtype=torch.float64, device="cuda")
+        assert wide.data_ptr() % 16 == 0 and wide.stride(0) % 2 == 0
+        keep("basis_even", ("norm2", "alpha", "beta", "done", "V"), plan.lanczos_basis(v0, 12, V=wide[:, :n]))
+        for nu in (0, 13):
+            # (both spectra lie inside [-102, 102])
+            keep("cheb_nu%d" % nu, ("norm2", "diag", "cross", "done"), plan.chebyshev_moments(v0, 0.0, 128.0, 17, U=U[:nu] if nu else None))
+        eta = 0.5
+        for ce in (0, 3):
+            cv = plan.correction_vector(v0, sigma, eta, tol=1e-10, max_it=600, check_every=ce, U=U)
+            keep("cv_ce%d" % ce, sorted(cv), [cv[k] for k in sorted(cv)])
+        ys = torch.full((n + 2,), float("nan"), dtype=torch.float64, device="cuda")
+        assert ys[1:].data_ptr() % 16 == 8
+        norm2, stats, im = C.c_double(0.0), _capi.CvStats(), (C.c_double * 13)()
+        _capi.check(_capi.lib().dmrgx_kron_correction_vector(plan._handle, C.c_void_p(v0.data_ptr()), sigma, eta, 1e-10, 600, 0, C.c_void_p(ys[1:].data_ptr()), C.c_void_p(),
+                                                             13, C.c_void_p(U.data_ptr()), n, C.byref(norm2), im, None, C.byref(stats), plan._stream_ptr(None)))
+        assert torch.isnan(ys[[0, n + 1]]).all()
+        keep("cv_offset", ("Y", "norm2", "im"), (ys[1:n + 1], norm2.value, np.array(im[:])))
+        keep("cv_offset", [k for k, _ in _capi.CvStats._fields_], [getattr(stats, k) for k, _ in _capi.CvStats._fields_])
+        dot = C.c_double(0.0)
+        _capi.check(_capi.lib().dmrgx_dot(n, C.c_void_p(v0.data_ptr()), C.c_void_p(U[1].data_ptr()), C.byref(dot), None))
+        keep("dot", ("v0_u1",), (dot.value,))
+        plan.destroy()
+
+
 if __name__ == "__main__":
     path, what = sys.argv[1], sys.argv[2].split(",")
     res = {}
@@ -90,5 +137,7 @@ if __name__ == "__main__":
         solvers(res)
     if "striped" in what:
         striped(res)
+    if "krylov" in what:
+        krylov(res)
     np.savez(path, **res)
     print("bitwise worker ok", sorted(res))
