@@ -216,16 +216,27 @@ public:
         ierr = ReadSiteListOption("-dsf_sites", "the Lanczos run behind G_ic(w)", dsf_sites, use_dsf_sites); CHKERRQ(ierr);
         if (use_dsf_sites && !use_dsf) { ierr = ReadLanczosStepOptions(); CHKERRQ(ierr); }      /* (-dsf has read them above) */
         ierr = ReadSiteListOption("-dsf_cheb", "the Chebyshev recursion", dsf_cheb_sites, use_dsf_cheb); CHKERRQ(ierr);
+        /* -dsf_dimer b0,b1,...: the Chebyshev moments of the dimer correlations D_bc(w) from every listed bond c, numbered as the Bonds of
+           DimerCorrelations.json (CalculateDimerDynamics).  On the device: the images of all bonds and the 34 vectors of a moment run. */
+        ierr = ReadSiteListOption("-dsf_dimer", "the Chebyshev recursion", dsf_dimer_bonds, use_dsf_dimer, (PetscInt)dmrgx_host::DimerBonds(Ham).size(), "bond",
+                                  "the nearest-neighbour bonds in the order of Bonds in DimerCorrelations.json"); CHKERRQ(ierr);
+        if (use_dsf_dimer) {
+            ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_dimer_steps", &dsf_dimer_steps, NULL); CHKERRQ(ierr);
+            if (dsf_dimer_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_dimer_steps must be at least 1. Got %lld.", LLD(dsf_dimer_steps));
+            ierr = ReadOmegaGridOption("-dsf_dimer_omega", dsf_dimer_omega, dsf_dimer_have_omega); CHKERRQ(ierr);
+        }
         if (use_dsf_cheb) {   /* -dsf_cheb c0,c1,...: the Chebyshev moments of G_ic(w) from every listed site c (CalculateChebyshevCorrelations) */
             ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_cheb_steps", &dsf_cheb_steps, NULL); CHKERRQ(ierr);
             if (dsf_cheb_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cheb_steps must be at least 1. Got %lld.", LLD(dsf_cheb_steps));
+            ierr = ReadOmegaGridOption("-dsf_cheb_omega", dsf_cheb_omega, dsf_cheb_have_omega); CHKERRQ(ierr);
+        }
+        if (use_dsf_cheb || use_dsf_dimer) {   /* the window of the Chebyshev expansion, which the two share */
             ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_cheb_bound_steps", &dsf_cheb_bound_steps, NULL); CHKERRQ(ierr);
             if (dsf_cheb_bound_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cheb_bound_steps must be at least 1. Got %lld.", LLD(dsf_cheb_bound_steps));
             PetscInt nw = 2;
             ierr = PetscOptionsGetRealArray(NULL, NULL, "-dsf_cheb_window", dsf_cheb_window, &nw, &dsf_cheb_have_window); CHKERRQ(ierr);
             if (dsf_cheb_have_window && !(nw == 2 && dsf_cheb_window[0] < dsf_cheb_window[1] && std::isfinite(dsf_cheb_window[0]) && std::isfinite(dsf_cheb_window[1])))
                 SETERRQ1(mpi_comm, PETSC_ERR_ARG_WRONG, "-dsf_cheb_window needs lo,hi: two finite energies, lo < hi. Got %lld numbers.", LLD(nw));
-            ierr = ReadOmegaGridOption("-dsf_cheb_omega", dsf_cheb_omega, dsf_cheb_have_omega); CHKERRQ(ierr);
         }
         ierr = ReadSiteListOption("-dsf_cv", "the conjugate-gradient run", dsf_cv_sites, use_dsf_cv); CHKERRQ(ierr);
         if (use_dsf_cv) {   /* -dsf_cv c0,c1,...: the correction vectors of G_ic(w + i eta) from every listed site c (CalculateCorrectionVectors) */
@@ -486,7 +497,7 @@ public:
         spectra_writer.Drain();
         if (fp_entanglement) { fprintf(fp_entanglement, "\n]\n"); fclose(fp_entanglement); fp_entanglement = NULL; }
         if (fp_kron) { fprintf(fp_kron, "\n]\n"); fclose(fp_kron); fp_kron = NULL; }
-        spin_file.Close(); dimer_file.Close(); dsf_file.Close(); dsf_sites_file.Close(); dsf_cheb_file.Close(); dsf_cv_file.Close();
+        spin_file.Close(); dimer_file.Close(); dsf_file.Close(); dsf_sites_file.Close(); dsf_cheb_file.Close(); dsf_cv_file.Close(); dsf_dimer_file.Close();
         if (fp_corr) {
             if (!corr_headers_printed) { PetscErrorCode e2 = PrintCorrelationHeaders(); CHKERRQ(e2); }
             fprintf(fp_corr, "\n  ]\n}\n"); fclose(fp_corr); fp_corr = NULL;
@@ -616,6 +627,7 @@ public:
         if (use_dsf && do_measurements) { ierr = CalculateDynamicalStructureFactor(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* needs the plan */
         if (use_dsf_sites && do_measurements) { ierr = CalculateDynamicalCorrelations(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
         if (use_dsf_cheb && do_measurements) { ierr = CalculateChebyshevCorrelations(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
+        if (use_dsf_dimer && do_measurements) { ierr = CalculateDimerDynamics(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
         if (use_dsf_cv && do_measurements) { ierr = CalculateCorrectionVectors(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
         ierr = MatDestroy_KronSumShell(&H); CHKERRQ(ierr);
         ierr = MatDestroy(&H); CHKERRQ(ierr);
@@ -1657,26 +1669,10 @@ public:
         ierr = S.Images(S.op_of.data(), N, U->dev_uninitialised(), ld); CHKERRQ(ierr);
 
         /* the window */
-        PetscInt matmults = 0, bound_steps = 0;
+        PetscInt bound_steps = 0;
         double centre, half_width, theta_max, residual = 0.0;
-        if (dsf_cheb_have_window) {
-            centre = 0.5 * (dsf_cheb_window[0] + dsf_cheb_window[1]); half_width = 0.5 * (dsf_cheb_window[1] - dsf_cheb_window[0]); theta_max = dsf_cheb_window[1];
-        } else {
-            const PetscInt B = dsf_cheb_bound_steps;
-            dmrgx_host::DevBuffer r((size_t)n);
-            {   /* uniform(-1, 1) from a fixed seed, by integer arithmetic on the generator's 64 bits: the same vector everywhere */
-                std::mt19937_64 gen(0x63686562ull);
-                double* h = r.host();
-                for (int64_t e = 0; e < n; ++e) h[e] = (double)(gen() >> 11) * (2.0 / 9007199254740992.0) - 1.0;
-            }
-            std::vector<double> a((size_t)B, 0.0), b((size_t)B, 0.0);
-            double r2 = 0.0; int32_t done = 0;
-            if (dmrgx_kron_lanczos_coeffs(H->plan, r.dev_ro(), (int32_t)B, 0.0, &r2, a.data(), b.data(), &done, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_lanczos_coeffs: %s", dmrgx_last_error());
-            matmults += B; bound_steps = B;
-            const dmrgx_host::ChebyshevWindowResult W = dmrgx_host::ChebyshevWindow((double)E0, a, b, done);
-            if (!W.ok) SETERRQ1(mpi_comm, 1, "Chebyshev correlations: no spectral window from %d Lanczos steps.", (int)done);
-            centre = W.centre; half_width = W.half_width; theta_max = W.theta_max; residual = W.residual;
-        }
+        ierr = FindChebyshevWindow(H, n, (double)E0, "Chebyshev correlations", centre, half_width, theta_max, residual, bound_steps); CHKERRQ(ierr);
+        PetscInt matmults = bound_steps;
 
         struct Run { PetscInt c = 0; double norm2 = 0.0; int32_t done = 0; std::vector<double> diag, mom, momq, grid; };
         std::vector<Run> runs(dsf_cheb_sites.size());
@@ -1725,6 +1721,146 @@ public:
             dsf_cheb_file.Table("Moments", R.mom, N, nm, ",\n");
             dsf_cheb_file.Table("MomentsQ", R.momq, M, nm, dsf_cheb_have_omega ? ",\n" : end);
             if (dsf_cheb_have_omega) dsf_cheb_file.Table("SqwGrid", R.grid, M, (PetscInt)dsf_cheb_omega.size(), end);
+        }
+        fprintf(fp, "   ]}");
+        fflush(fp);
+        return 0;
+    }
+
+    /** The window [centre - half_width, centre + half_width] of a Chebyshev expansion on the planned Hamiltonian of n states, for -dsf_cheb and
+        -dsf_dimer: -dsf_cheb_window lo,hi as given (bound_steps 0, theta_max = hi), else from -dsf_cheb_bound_steps Lanczos steps
+        (dmrgx_kron_lanczos_coeffs) from a fixed pseudo-random vector and the known bottom E0 (ChebyshevWindow, Measurements.hpp). */
+    PetscErrorCode FindChebyshevWindow(Mat& H, int64_t n, double E0, const char* name, double& centre, double& half_width, double& theta_max, double& residual, PetscInt& bound_steps)
+    {
+        residual = 0.0; bound_steps = 0;
+        if (dsf_cheb_have_window) {
+            centre = 0.5 * (dsf_cheb_window[0] + dsf_cheb_window[1]); half_width = 0.5 * (dsf_cheb_window[1] - dsf_cheb_window[0]); theta_max = dsf_cheb_window[1];
+            return 0;
+        }
+        const PetscInt B = dsf_cheb_bound_steps;
+        dmrgx_host::DevBuffer r((size_t)n);
+        {   /* uniform(-1, 1) from a fixed seed, by integer arithmetic on the generator's 64 bits: the same vector everywhere */
+            std::mt19937_64 gen(0x63686562ull);
+            double* h = r.host();
+            for (int64_t e = 0; e < n; ++e) h[e] = (double)(gen() >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+        }
+        std::vector<double> a((size_t)B, 0.0), b((size_t)B, 0.0);
+        double r2 = 0.0; int32_t done = 0;
+        if (dmrgx_kron_lanczos_coeffs(H->plan, r.dev_ro(), (int32_t)B, 0.0, &r2, a.data(), b.data(), &done, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_lanczos_coeffs: %s", dmrgx_last_error());
+        bound_steps = B;
+        const dmrgx_host::ChebyshevWindowResult W = dmrgx_host::ChebyshevWindow(E0, a, b, done);
+        if (!W.ok) SETERRQ2(mpi_comm, 1, "%s: no spectral window from %d Lanczos steps.", name, (int)done);
+        centre = W.centre; half_width = W.half_width; theta_max = W.theta_max; residual = W.residual;
+        return 0;
+    }
+
+    /** -dsf_dimer b0,b1,... (engine extension): the Chebyshev moments of the dynamical dimer correlations of the ground state,
+            mu_n^{bc} = < dD_b psi , T_n(Ht) dD_c psi > / <psi|psi>,   dD_b = D_b - <D_b>,   D_b = S_i . S_j,   Ht = (H - Centre) / HalfWidth,
+        for ALL nearest-neighbour bonds b, from one dmrgx_kron_chebyshev_moments run per reference bond c (its index in Bonds, the order of
+        DimerBonds(Ham) and of DimerCorrelations.json): the singlet channel -- valence-bond order against a spin liquid, what Raman
+        scattering sees -- where -dsf_cheb measures the spin channel.  The images D_b psi of all nb bonds (DimerFrame::Images: the bond
+        operators and terms of -corr_dimer) are written into one device family, and ONE dmrgx_vec_project_out call removes psi from all
+        of them: <D_b> is about -0.3 where <Sz_i> vanishes, and its delta peak at w = 0, far heavier than the inelastic part, would be
+        smeared by the Jackson kernel over the window where the singlet gap is.  The coefficients of that call are D[b] = <D_b> =
+        <psi|D_b|psi> / <psi|psi>.  Row c of the family is the start vector of run c, the whole family its U.  The window is found as for
+        -dsf_cheb (FindChebyshevWindow: -dsf_cheb_window, or -dsf_cheb_bound_steps Lanczos steps); a run that leaves it ends with
+        StepsDone < Steps and a warning.
+        Per reference bond: Norm2 = <dD_c psi, dD_c psi>; Elastic = <psi, dD_c psi> / sqrt(Norm Norm2), what is left of the elastic line
+        (rounding); Diag[m] = mu_m^{cc}, m <= 2 StepsDone; Moments (nb x (StepsDone + 1), Moments[:, 0] = Connected[:, c] of -corr_dimer);
+        MomentsQ[q][n] = sum over the bonds b of c's orientation of cos(q . (r_b - r_c)) Moments[b][n] at their Positions (row nx Ly + ny);
+        with -dsf_dimer_omega w0,w1,nw SqwGrid[q][k] = ChebyshevJackson(MomentsQ[q], StepsDone + 1, x_k) / HalfWidth at
+        x_k = (w_k + E0 - Centre) / HalfWidth: averaged over the reference bonds of one orientation the Jackson-broadened dimer structure
+        factor S_a(q, w), non-negative.  MatMults = BoundSteps + refs * Steps.
+        Memory on the device: the nb images (nb x N_sb doubles, refused with PETSC_ERR_MEM if they do not fit) plus the 34 vectors of the
+        moment run.  The block bases are ground-state bases (the caveat of -dsf_sites).  One rank only (refused at start-up otherwise). */
+    PetscErrorCode CalculateDimerDynamics(KronBlocks_t& KronBlocks, const Vec& gsv_r, Mat& H, PetscScalar E0)
+    {
+        PetscLogDouble t0, t1;
+        PetscTime(&t0);
+        dmrgx_host::DimerFrame B;
+        PetscErrorCode ierr = B.Init(KronBlocks, num_sites, Ham, gsv_r, "Dimer dynamics"); CHKERRQ(ierr);
+        const PetscInt nb = B.nb, K = dsf_dimer_steps, Lx = Ham.Lx(), Ly = Ham.Ly(), M = Lx * Ly;
+        const int64_t n = B.n, ld = n + (n & 1);
+        /* the images of all bonds, row b = D_b psi, then (D_b - <D_b>) psi */
+        std::unique_ptr<dmrgx_host::DevBuffer> U;
+        try { U.reset(new dmrgx_host::DevBuffer((size_t)(nb * ld), dmrgx_host::DevBuffer::device_only_t{})); }
+        catch (const std::exception& e) { SETERRQ4(mpi_comm, PETSC_ERR_MEM, "Dimer dynamics: no memory for the images of %lld bonds x %lld states (%.3f GB): %s", LLD(nb), LLD(n), (double)(nb * ld) * 8e-9, e.what()); }
+        ierr = B.Images(U->dev_uninitialised(), ld); CHKERRQ(ierr);
+        std::vector<double> D((size_t)nb, 0.0);
+        double norm = 0.0;
+        if (dmrgx_vec_project_out((int32_t)nb, n, U->dev_uninitialised(), ld, B.psi, D.data(), &norm, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_vec_project_out: %s", dmrgx_last_error());
+        if (!(norm > 0.0)) SETERRQ(mpi_comm, 1, "Dimer dynamics: the ground state has no norm.");
+
+        PetscInt bound_steps = 0;
+        double centre, half_width, theta_max, residual = 0.0;
+        ierr = FindChebyshevWindow(H, n, (double)E0, "Dimer dynamics", centre, half_width, theta_max, residual, bound_steps); CHKERRQ(ierr);
+        PetscInt matmults = bound_steps;
+
+        const dmrgx_host::OrientedBonds oriented[2] = {dmrgx_host::BondsOfOrientation(B.bonds, 'x'), dmrgx_host::BondsOfOrientation(B.bonds, 'y')};
+        struct Run { PetscInt c = 0; double norm2 = 0.0, elastic = 0.0; int32_t done = 0; std::vector<double> diag, mom, momq, grid; };
+        std::vector<Run> runs(dsf_dimer_bonds.size());
+        std::vector<double> cross((size_t)((K + 1) * nb));
+        double t_runs = 0.0;
+        for (size_t ir = 0; ir < runs.size(); ++ir) {
+            Run& R = runs[ir];
+            R.c = dsf_dimer_bonds[ir];
+            R.diag.assign((size_t)(2 * K + 1), 0.0);
+            const double* v0 = U->dev_ro() + R.c * ld;
+            PetscLogDouble tr0 = 0.0, tr1 = 0.0;
+            if (verbose) { if (dmrgx_stream_sync(nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error()); PetscTime(&tr0); }      /* the run alone, for the log */
+            if (dmrgx_kron_chebyshev_moments(H->plan, v0, centre, half_width, (int32_t)K, (int32_t)nb, U->dev_ro(), ld, &R.norm2, R.diag.data(), cross.data(), &R.done, nullptr))
+                SETERRQ1(mpi_comm, 1, "dmrgx_kron_chebyshev_moments: %s", dmrgx_last_error());
+            if (verbose) { PetscTime(&tr1); t_runs += tr1 - tr0; }
+            matmults += K;
+            double overlap = 0.0;
+            if (dmrgx_dot(n, B.psi, v0, &overlap, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
+            R.elastic = R.norm2 > 0.0 ? overlap / std::sqrt(norm * R.norm2) : 0.0;
+            const PetscInt Dn = R.done, nm = Dn + 1;
+            if (Dn < K) printf("  * WARNING: -dsf_dimer: the run from bond %lld left the window [%.6f, %.6f] after %lld of %lld steps; the record holds the moments up to there.\n", LLD(R.c), centre - half_width, centre + half_width, LLD(Dn), LLD(K));
+            R.diag.resize((size_t)(2 * Dn + 1));
+            for (double& x : R.diag) x /= norm;
+            R.mom.assign((size_t)(nb * nm), 0.0);
+            for (PetscInt b = 0; b < nb; ++b) for (PetscInt k = 0; k < nm; ++k) R.mom[(size_t)(b * nm + k)] = cross[(size_t)(k * nb + b)] / norm;
+            /* the cosine sum over the bonds of c's orientation, from c */
+            const dmrgx_host::OrientedBonds& O = oriented[B.bonds[(size_t)R.c].orient == 'x' ? 0 : 1];
+            const PetscInt no = (PetscInt)O.of.size(), c_in = (PetscInt)(std::find(O.of.begin(), O.of.end(), R.c) - O.of.begin());
+            std::vector<double> sel((size_t)(no * nm));
+            for (PetscInt k = 0; k < no; ++k) std::copy(R.mom.begin() + O.of[(size_t)k] * nm, R.mom.begin() + (O.of[(size_t)k] + 1) * nm, sel.begin() + k * nm);
+            R.momq = dmrgx_host::SiteCosineSum(Lx, Ly, O.x.data(), O.y.data(), c_in, sel.data(), no, nm);
+            if (dsf_dimer_have_omega) {
+                const PetscInt nw = (PetscInt)dsf_dimer_omega.size();
+                R.grid.assign((size_t)(M * nw), 0.0);
+                for (PetscInt q = 0; q < M; ++q) for (PetscInt k = 0; k < nw; ++k)
+                    R.grid[(size_t)(q * nw + k)] = dmrgx_host::ChebyshevJackson(R.momq.data() + q * nm, nm, (dsf_dimer_omega[(size_t)k] + (double)E0 - centre) / half_width) / half_width;
+            }
+        }
+        PetscTime(&t1);
+        if (verbose) printf("  * Dimer dynamics: %lld reference bonds of %lld, %lld steps per run, window [%.6f, %.6f] from %lld Lanczos steps, %lld MatMults on %lld states, tDimerDyn %.6f s, of it the Chebyshev runs %.6f s\n",
+                            LLD(runs.size()), LLD(nb), LLD(K), centre - half_width, centre + half_width, LLD(bound_steps), LLD(matmults), LLD(n), t1 - t0, t_runs);
+        ierr = dsf_dimer_file.BeginDynamical(data_dir + "DimerDynamics.json", GlobIdx, LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, norm); CHKERRQ(ierr);
+        FILE* fp = dsf_dimer_file.fp;
+        fprintf(fp, ", \"Steps\": %lld, \"Centre\": %.17g, \"HalfWidth\": %.17g, \"BoundSteps\": %lld, \"ThetaMax\": %.17g, \"Residual\": %.17g, \"tDimerDyn\": %.9g, \"MatMults\": %lld,\n   \"Bonds\": [",
+                LLD(K), centre, half_width, LLD(bound_steps), theta_max, residual, t1 - t0, LLD(matmults));
+        for (PetscInt b = 0; b < nb; ++b) fprintf(fp, "%s[%lld, %lld]", b ? ", " : "", LLD(B.bonds[(size_t)b].i), LLD(B.bonds[(size_t)b].j));
+        fprintf(fp, "],\n   \"Orientation\": [");
+        for (PetscInt b = 0; b < nb; ++b) fprintf(fp, "%s\"%c\"", b ? ", " : "", B.bonds[(size_t)b].orient);
+        fprintf(fp, "],\n   \"Position\": [");
+        for (PetscInt b = 0; b < nb; ++b) fprintf(fp, "%s[%lld, %lld]", b ? ", " : "", LLD(B.bonds[(size_t)b].ix), LLD(B.bonds[(size_t)b].jy));
+        fprintf(fp, "],\n   \"D\": ");
+        dsf_dimer_file.Row(D); fprintf(fp, ",\n");
+        if (dsf_dimer_have_omega) { fprintf(fp, "   \"Omega\": "); dsf_dimer_file.Row(dsf_dimer_omega); fprintf(fp, ",\n"); }
+        fprintf(fp, "   \"RefBonds\": [\n");
+        for (size_t ir = 0; ir < runs.size(); ++ir) {
+            const Run& R = runs[ir];
+            const dmrgx_host::DimerBond& bc = B.bonds[(size_t)R.c];
+            const PetscInt nm = R.done + 1;
+            const char* end = ir + 1 < runs.size() ? "},\n" : "}\n";
+            fprintf(fp, "   {\"Bond\": %lld, \"Sites\": [%lld, %lld], \"Orientation\": \"%c\", \"Norm2\": %.17g, \"Elastic\": %.17g, \"StepsDone\": %d,\n   \"Diag\": ",
+                    LLD(R.c), LLD(bc.i), LLD(bc.j), bc.orient, R.norm2, R.elastic, (int)R.done);
+            dsf_dimer_file.Row(R.diag); fprintf(fp, ",\n");
+            dsf_dimer_file.Table("Moments", R.mom, nb, nm, ",\n");
+            dsf_dimer_file.Table("MomentsQ", R.momq, M, nm, dsf_dimer_have_omega ? ",\n" : end);
+            if (dsf_dimer_have_omega) dsf_dimer_file.Table("SqwGrid", R.grid, M, (PetscInt)dsf_dimer_omega.size(), end);
         }
         fprintf(fp, "   ]}");
         fflush(fp);
@@ -1818,11 +1954,8 @@ public:
         = Sz_i Sz_j + (Sp_i Sm_j + Sm_i Sp_j) / 2, its connected part and the dimer structure factors of the x and the y bonds, at every
         measurement point.  < psi | D_b^T D_b' | psi > = < D_b psi , D_b' psi >: the whole table is ONE dmrgx_kron_term_gram call over the
         bond images D_b psi -- vector 0 is psi itself (norm and < D_b >), vector 1 + b the image of bond b -- instead of a plan, a MatMult
-        and a dot product per pair of bonds.  D_b is built from the stored, truncated block operators, the operator of site i first:
-        a bond inside the left block is A_b (x) 1 with A_b formed on the device in dense per-sector form (one grouped GEMM per chunk of
-        bonds: every sector block of every bond is one group of three products; the site operators are densified once per measurement
-        and released when the bond operators exist), a bond inside the right block is 1 (x) B_b, a bond across the cut is three
-        two-sided terms.  Sm is Sp read transposed.  Site s of the right block is lattice site N - 1 - s.
+        and a dot product per pair of bonds.  The bond operators and the term list of every bond are DimerFrame's (Measurements.hpp),
+        which -dsf_dimer shares.  Site s of the right block is lattice site N - 1 - s.
         DD[b][b'] is < psi | D_b^T D_b' | psi >: it equals < D_b D_b' > when nothing was truncated or the two bonds sit in different
         blocks -- truncated operators of one block do not commute, the caveat of the SpSm table.  On several ranks every rank
         computes the same table from the replicated psi (no collective); rank 0 writes one record per measurement to
@@ -1831,126 +1964,14 @@ public:
     {
         PetscLogDouble t0, t1;
         PetscTime(&t0);
-        dmrgx_host::CentreFrame F;
-        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, "Dimer correlations"); CHKERRQ(ierr);
-        const std::vector<dmrgx_host::DimerBond> bonds = dmrgx_host::DimerBonds(Ham);
-        const PetscInt nb = (PetscInt)bonds.size();
-        auto side_of = [&](const dmrgx_host::DimerBond& b) { return b.j < F.nsites[0] ? 0 : (b.i >= F.nsites[0] ? 1 : 2); };      /* 2: across the cut */
-
-        /* ---- bond operators inside a block, dense per sector: C[q] = Sz_i[q] Sz_j[q] + (Sp_i / 2)[q -> q+1] Sm_j[q+1 -> q] + (Sm_i / 2)[q -> q-1] Sp_j[q-1 -> q] */
-        std::vector<Mat> bond_op((size_t)nb);
-        int64_t bond_doubles = 0;
-        for (int side = 0; side < 2; ++side) {
-            const std::vector<int32_t>& sz = F.sizes[side];
-            const int32_t ns = (int32_t)sz.size();
-            enum { DSz = 0, DSp = 1, DSm = 2, DHalfSp = 3, DHalfSm = 4 };
-            std::map<std::pair<int, PetscInt>, Mat> dense;          /* (kind, block site) -> dense form, for this measurement */
-            auto densify = [&](int kind, PetscInt s, Mat& d) -> PetscErrorCode {
-                auto it = dense.find({kind, s});
-                if (it != dense.end()) { d = it->second; return 0; }
-                Mat m;
-                PetscErrorCode e = F.resident(side, kind == DSz ? OpSz : OpSp, s, m); CHKERRQ(e);
-                if (kind == DSm || kind == DHalfSm) {               /* Sm(s) = Sp(s) read transposed */
-                    auto v = std::make_shared<dmrgx_host::SectorMat>();
-                    v->transpose_of = m; v->shift = OpSm; v->sizes = m->sizes;
-                    m = v;
-                }
-                if (dmrgx_host::SectorMatDensify(m, d, kind >= DHalfSp ? 0.5 : 1.0)) SETERRQ1(mpi_comm, 1, "Dimer correlations: densifying a site operator: %s", dmrgx_last_error());
-                dense[{kind, s}] = d;
-                return 0;
-            };
-            auto cell_at = [](const Mat& M, int32_t q) -> const dmrgx_host::MatCell* { for (const dmrgx_host::MatCell& c : M->cells) if (c.q == q) return &c; return nullptr; };
-            std::vector<dmrgx_ggemm_group> groups;
-            std::vector<dmrgx_ggemm_prod> prods;
-            std::vector<size_t> first_prod;
-            int64_t chunk_elems = 0, total = 0;
-            for (int32_t q = 0; q < ns; ++q) total += (int64_t)sz[(size_t)q] * sz[(size_t)q];
-            const int64_t chunk_limit = (int64_t)1 << 28;           /* 2 GiB of bond operators per grouped launch */
-            auto flush = [&]() -> PetscErrorCode {
-                for (size_t g = 0; g < groups.size(); ++g) groups[g].prods = prods.data() + first_prod[g];
-                if (!groups.empty() && dmrgx_ggemm_groups((int32_t)groups.size(), groups.data(), 0, nullptr, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_ggemm_groups: %s", dmrgx_last_error());
-                groups.clear(); prods.clear(); first_prod.clear(); chunk_elems = 0;
-                return 0;
-            };
-            for (PetscInt b = 0; b < nb; ++b) {
-                if (side_of(bonds[(size_t)b]) != side) continue;
-                const PetscInt si = F.block_site(side, bonds[(size_t)b].i), sj = F.block_site(side, bonds[(size_t)b].j);
-                Mat zi, zj, hpi, hmi, pj, mj;
-                ierr = densify(DSz, si, zi); CHKERRQ(ierr); ierr = densify(DSz, sj, zj); CHKERRQ(ierr);
-                ierr = densify(DHalfSp, si, hpi); CHKERRQ(ierr); ierr = densify(DSm, sj, mj); CHKERRQ(ierr);
-                ierr = densify(DHalfSm, si, hmi); CHKERRQ(ierr); ierr = densify(DSp, sj, pj); CHKERRQ(ierr);
-                if (chunk_elems + total > chunk_limit) { ierr = flush(); CHKERRQ(ierr); }
-                Mat C = std::make_shared<dmrgx_host::SectorMat>();
-                C->shift = 0; C->sizes = sz;
-                auto arena = std::make_shared<dmrgx_host::DevBuffer>((size_t)std::max<int64_t>(total, 1), dmrgx_host::DevBuffer::device_only_t{});
-                int64_t cursor = 0;
-                for (int32_t q = 0; q < ns; ++q) {
-                    const int32_t n = sz[(size_t)q];
-                    dmrgx_host::MatCell c;
-                    c.q = q; c.nr = c.nc = n; c.ld = n; c.buf = arena; c.off = cursor;
-                    C->cells.push_back(c);
-                    first_prod.push_back(prods.size());
-                    int32_t np = 0;
-                    auto product = [&](const Mat& A, const Mat& B, int32_t qmid) {        /* A[q -> qmid] B[qmid -> q] */
-                        if (qmid < 0 || qmid >= ns) return;
-                        const dmrgx_host::MatCell* a = cell_at(A, q);
-                        const dmrgx_host::MatCell* bb = cell_at(B, qmid);
-                        if (!a || !bb) return;
-                        prods.push_back(dmrgx_ggemm_prod{0, sz[(size_t)qmid], a->buf->dev_ro() + a->off, a->ld, bb->buf->dev_ro() + bb->off, bb->ld, 1.0});
-                        ++np;
-                    };
-                    product(zi, zj, q); product(hpi, mj, q + 1); product(hmi, pj, q - 1);
-                    groups.push_back(dmrgx_ggemm_group{arena->dev_uninitialised() + cursor, n, n, n, 0, np, nullptr});
-                    cursor += (int64_t)n * n;
-                }
-                chunk_elems += total;
-                bond_doubles += total;
-                bond_op[(size_t)b] = C;
-            }
-            ierr = flush(); CHKERRQ(ierr);
-        }                                                           /* (the dense site operators go back to the pool here: stream-ordered) */
-
+        dmrgx_host::DimerFrame B;
+        PetscErrorCode ierr = B.Init(KronBlocks, num_sites, Ham, gsv_r, "Dimer correlations"); CHKERRQ(ierr);
+        const std::vector<dmrgx_host::DimerBond>& bonds = B.bonds;
+        const PetscInt nb = B.nb, nv = nb + 1;
+        const int64_t bond_doubles = B.bond_doubles;
         /* ---- the vectors: psi, then the image of every bond */
-        dmrgx_host::SiteOperators T(F);
-        std::vector<int32_t> vec_first{0};
-        std::vector<dmrgx_term> terms;
-        terms.push_back(dmrgx_term{1.0, -1, -1});
-        vec_first.push_back((int32_t)terms.size());
-        for (PetscInt b = 0; b < nb; ++b) {
-            const int side = side_of(bonds[(size_t)b]);
-            if (side < 2) {
-                const int32_t idx = T.Add(side, bond_op[(size_t)b]);
-                terms.push_back(side == 0 ? dmrgx_term{1.0, idx, -1} : dmrgx_term{1.0, -1, idx});
-            } else {
-                const PetscInt si = bonds[(size_t)b].i, sj = F.block_site(1, bonds[(size_t)b].j);
-                const Op_t left_type[3] = {OpSz, OpSp, OpSm}, right_type[3] = {OpSz, OpSm, OpSp};
-                const double coeff[3] = {1.0, 0.5, 0.5};
-                for (int t = 0; t < 3; ++t) {
-                    int32_t il, ir;
-                    ierr = T.Site(0, left_type[t], si, il); CHKERRQ(ierr);
-                    ierr = T.Site(1, right_type[t], sj, ir); CHKERRQ(ierr);
-                    terms.push_back(dmrgx_term{coeff[t], il, ir});
-                }
-            }
-            vec_first.push_back((int32_t)terms.size());
-        }
-        const PetscInt nv = nb + 1;
-        /* the workspace holds at least the largest image block of every vector: the blocks (IL, IR), (IL - 1, IR + 1), (IL + 1, IR - 1) */
-        int64_t largest = 1;
-        for (size_t k = 0; k < F.bil.size(); ++k)
-            for (int32_t d = -1; d <= 1; ++d) {
-                const int32_t a = F.bil[k] - d, c = F.bir[k] + d;
-                if (a >= 0 && a < (int32_t)F.sizes[0].size() && c >= 0 && c < (int32_t)F.sizes[1].size()) largest = std::max<int64_t>(largest, (int64_t)F.sizes[0][(size_t)a] * F.sizes[1][(size_t)c]);
-            }
-        const size_t workspace = std::max<size_t>((size_t)1 << 30, (size_t)largest * (size_t)nv * sizeof(double));
-        std::vector<double> G((size_t)(nv * nv), 0.0);
-        {
-            dmrgx_host::DevBuffer g((size_t)(nv * nv), dmrgx_host::DevBuffer::device_only_t{});
-            if (dmrgx_kron_term_gram(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), gsv_r->buf->dev_ro(), (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
-                                     (int32_t)nv, vec_first.data(), terms.data(), workspace, g.dev_uninitialised(), nv, nullptr, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_gram: %s", dmrgx_last_error());
-            if (dmrgx_memcpy_d2h(G.data(), g.dev_ro(), G.size() * sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
-        }
-        bond_op.clear();
+        std::vector<double> G;
+        ierr = B.Gram(G); CHKERRQ(ierr);
         const double norm = G[0];
         std::vector<double> D((size_t)nb, 0.0), DD((size_t)(nb * nb), 0.0), Conn((size_t)(nb * nb), 0.0);
         for (PetscInt b = 0; b < nb; ++b) {
@@ -1962,12 +1983,11 @@ public:
         const PetscInt Lx = Ham.Lx(), Ly = Ham.Ly();
         std::vector<double> Sq[2] = {std::vector<double>((size_t)(Lx * Ly), 0.0), std::vector<double>((size_t)(Lx * Ly), 0.0)};
         for (int o = 0; o < 2; ++o) {
-            std::vector<PetscInt> of, x, y;
-            for (PetscInt b = 0; b < nb; ++b) if (bonds[(size_t)b].orient == (o == 0 ? 'x' : 'y')) { of.push_back(b); x.push_back(bonds[(size_t)b].ix); y.push_back(bonds[(size_t)b].jy); }
-            if (of.empty()) continue;
+            const dmrgx_host::OrientedBonds O = dmrgx_host::BondsOfOrientation(bonds, o == 0 ? 'x' : 'y');
+            if (O.of.empty()) continue;
             std::vector<double> C;                                  /* Connected among the bonds of this orientation */
-            for (PetscInt b : of) for (PetscInt c : of) C.push_back(Conn[(size_t)(b * nb + c)]);
-            Sq[o] = dmrgx_host::LatticeFourier(Lx, Ly, x.data(), y.data(), C.data(), (PetscInt)of.size(), (double)of.size());
+            for (PetscInt b : O.of) for (PetscInt c : O.of) C.push_back(Conn[(size_t)(b * nb + c)]);
+            Sq[o] = dmrgx_host::LatticeFourier(Lx, Ly, O.x.data(), O.y.data(), C.data(), (PetscInt)O.of.size(), (double)O.of.size());
         }
         PetscTime(&t1);
         if (!mpi_rank && verbose)
@@ -2264,7 +2284,7 @@ public:
             for (const Op& o : c.SysOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
             for (const Op& o : c.EnvOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
         }
-        if (use_corr_matrix || use_corr_dimer || use_dsf || use_dsf_sites || use_dsf_cheb || use_dsf_cv) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer, -dsf, -dsf_sites, -dsf_cheb, -dsf_cv: Sz and Sp of every site of both centre blocks, on every rank */
+        if (use_corr_matrix || use_corr_dimer || use_dsf || use_dsf_sites || use_dsf_cheb || use_dsf_cv || use_dsf_dimer) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer, -dsf, -dsf_sites, -dsf_cheb, -dsf_cv, -dsf_dimer: Sz and Sp of every site of both centre blocks, on every rank */
         need_built = true;
         return 0;
     }
@@ -2334,9 +2354,11 @@ private:
     void PrintBlocks(const PetscInt& nsys, const PetscInt& nenv) const { printf("  [%lld]-* *-[%lld]\n", LLD(nsys), LLD(nenv)); }
 
     /** A site-list option (-dsf_sites, -dsf_cheb, -dsf_cv c0,c1,...): on when present and not empty; then refused on more than one rank
-        (`what` has no collectives), and every site must be a lattice site. */
-    PetscErrorCode ReadSiteListOption(const char* option, const char* what, std::vector<PetscInt>& sites, PetscBool& use)
+        (`what` has no collectives), and every site must be a lattice site.  With `count` (-dsf_dimer): a list of `noun`s out of [0, count). */
+    PetscErrorCode ReadSiteListOption(const char* option, const char* what, std::vector<PetscInt>& sites, PetscBool& use,
+                                      PetscInt count = -1, const char* noun = "site", const char* range = "the lattice sites in the numbering of To1D")
     {
+        if (count < 0) count = num_sites;
         PetscBool have_sites = PETSC_FALSE;
         PetscInt nc = 4096;
         sites.assign((size_t)nc, 0);
@@ -2345,7 +2367,7 @@ private:
         use = (have_sites && nc > 0) ? PETSC_TRUE : PETSC_FALSE;
         if (!use) return 0;
         if (mpi_size > 1) SETERRQ3(mpi_comm, PETSC_ERR_SUP, "%s is not available on more than one rank (got %d): %s has no collectives.", option, (int)mpi_size, what);
-        for (PetscInt c : sites) if (c < 0 || c >= num_sites) SETERRQ3(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "%s: site %lld is outside [0, %lld), the lattice sites in the numbering of To1D.", option, LLD(c), LLD(num_sites));
+        for (PetscInt c : sites) if (c < 0 || c >= count) SETERRQ5(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "%s: %s %lld is outside [0, %lld), %s.", option, noun, LLD(c), LLD(count), range);
         return 0;
     }
 
@@ -2523,6 +2545,12 @@ private:
     PetscReal dsf_cheb_window[2] = {0.0, 0.0};  /* -dsf_cheb_window lo,hi: the window given, no bound run */
     std::vector<double> dsf_cheb_omega;         /* -dsf_cheb_omega w0,w1,nw: the grid of the Jackson-broadened SqwGrid */
     dmrgx_host::JsonRecordFile dsf_cheb_file{"%.17g"};  /* created at the first measurement with -dsf_cheb */
+    PetscBool use_dsf_dimer = PETSC_FALSE;      /* -dsf_dimer b0,b1,...: Chebyshev moments of the dimer correlations D_bc(w), DimerDynamics.json (CalculateDimerDynamics); shares -dsf_cheb_window and -dsf_cheb_bound_steps */
+    std::vector<PetscInt> dsf_dimer_bonds;      /* the reference bonds c: their index in DimerBonds(Ham), the Bonds of DimerCorrelations.json */
+    PetscInt dsf_dimer_steps = 200;             /* -dsf_dimer_steps: MatMults per run */
+    PetscBool dsf_dimer_have_omega = PETSC_FALSE;
+    std::vector<double> dsf_dimer_omega;        /* -dsf_dimer_omega w0,w1,nw: the grid of the Jackson-broadened SqwGrid */
+    dmrgx_host::JsonRecordFile dsf_dimer_file{"%.17g"}; /* created at the first measurement with -dsf_dimer */
     PetscBool use_dsf_cv = PETSC_FALSE;         /* -dsf_cv c0,c1,...: correction vectors of G_ic(w + i eta), CorrectionVectors.json (CalculateCorrectionVectors) */
     std::vector<PetscInt> dsf_cv_sites;         /* the reference sites c, lattice numbering of To1D */
     std::vector<double> dsf_cv_omega;           /* -dsf_cv_omega w0,w1,nw: the frequencies, one solve per site and frequency */

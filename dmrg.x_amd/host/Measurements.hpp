@@ -1,7 +1,8 @@
 #ifndef DMRGX_HOST_MEASUREMENTS_HPP
 #define DMRGX_HOST_MEASUREMENTS_HPP
 /** What the measurements of DMRGBlockContainer.hpp share.  All of them: the two blocks as the library sees them, the site operators of
-    one Gram / term call, the JSON record file; -corr_matrix and -corr_dimer: the bond list and the lattice Fourier sum.  The four
+    one Gram / term call, the JSON record file; -corr_matrix and -corr_dimer: the bond list and the lattice Fourier sum; -corr_dimer and
+    -dsf_dimer (CalculateDimerCorrelations, CalculateDimerDynamics): DimerFrame, the bond operators as terms, and BondsOfOrientation.  The four
     dynamical ones, -dsf, -dsf_sites, -dsf_cheb and -dsf_cv (CalculateDynamicalStructureFactor, CalculateDynamicalCorrelations,
     CalculateChebyshevCorrelations, CalculateCorrectionVectors): SzFrame, SiteCosineSum, the w0,w1,nw grid, the openings of their records;
     the phase coefficients of -dsf, the window and the Jackson-damped sum of -dsf_cheb.  host_tool.cpp runs the pure parts without a GPU. */
@@ -241,6 +242,181 @@ template<class Hamiltonian> std::vector<DimerBond> DimerBonds(const Hamiltonian&
     }
     return bonds;
 }
+
+/** The bonds of one orientation ('x' or 'y'): of[k] = their index in `bonds`, (x[k], y[k]) = their position (ix, jy), in the order of `bonds`. */
+struct OrientedBonds { std::vector<PetscInt> of, x, y; };
+inline OrientedBonds BondsOfOrientation(const std::vector<DimerBond>& bonds, char orient)
+{
+    OrientedBonds O;
+    for (size_t b = 0; b < bonds.size(); ++b) if (bonds[b].orient == orient) { O.of.push_back((PetscInt)b); O.x.push_back(bonds[b].ix); O.y.push_back(bonds[b].jy); }
+    return O;
+}
+
+/** D_b = S_i . S_j = Sz_i Sz_j + (Sp_i Sm_j + Sm_i Sp_j) / 2 of every nearest-neighbour bond of the centre superblock, as terms on the
+    ground state: the set-up of -corr_dimer and -dsf_dimer.  side_of[b]: 0 / 1 a bond inside the left / right block, 2 across the cut.
+    D_b is built from the stored, truncated block operators, the operator of site i first: a bond inside the left block is A_b (x) 1 with
+    A_b formed on the device in dense per-sector form (one grouped GEMM per chunk of bonds: every sector block of every bond is one group
+    of three products; the site operators are densified once and released when the bond operators exist), a bond inside the right block
+    is 1 (x) B_b -- one one-sided term each --, a bond across the cut is three two-sided terms.  Sm is Sp read transposed.  Bond b is
+    terms[vec_first[b] .. vec_first[b + 1]) over the operators of T.  The bond operators (bond_doubles doubles) live as long as the frame. */
+struct DimerFrame {
+    CentreFrame F;
+    SiteOperators T{F};
+    std::vector<DimerBond> bonds;
+    std::vector<int> side_of;
+    std::vector<Mat> bond_op;
+    std::vector<int32_t> vec_first;
+    std::vector<dmrgx_term> terms;
+    PetscInt nb = 0;
+    int64_t n = 0, bond_doubles = 0;
+    const double* psi = nullptr;
+    template<class Hamiltonian> PetscErrorCode Init(KronBlocks_t& KronBlocks, PetscInt num_sites, const Hamiltonian& Ham, const Vec& gsv_r, const char* display_name)
+    {
+        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, display_name); CHKERRQ(ierr);
+        bonds = DimerBonds(Ham);
+        nb = (PetscInt)bonds.size();
+        n = gsv_r->n; psi = gsv_r->buf->dev_ro();
+        for (const DimerBond& b : bonds) side_of.push_back(b.j < F.nsites[0] ? 0 : (b.i >= F.nsites[0] ? 1 : 2));
+        ierr = BuildBondOperators(); CHKERRQ(ierr);
+        vec_first.assign(1, 0);
+        for (PetscInt b = 0; b < nb; ++b) {
+            const int side = side_of[(size_t)b];
+            if (side < 2) {
+                const int32_t idx = T.Add(side, bond_op[(size_t)b]);
+                terms.push_back(side == 0 ? dmrgx_term{1.0, idx, -1} : dmrgx_term{1.0, -1, idx});
+            } else {
+                const PetscInt si = bonds[(size_t)b].i, sj = F.block_site(1, bonds[(size_t)b].j);
+                const Op_t left_type[3] = {OpSz, OpSp, OpSm}, right_type[3] = {OpSz, OpSm, OpSp};
+                const double coeff[3] = {1.0, 0.5, 0.5};
+                for (int t = 0; t < 3; ++t) {
+                    int32_t il, ir;
+                    ierr = T.Site(0, left_type[t], si, il); CHKERRQ(ierr);
+                    ierr = T.Site(1, right_type[t], sj, ir); CHKERRQ(ierr);
+                    terms.push_back(dmrgx_term{coeff[t], il, ir});
+                }
+            }
+            vec_first.push_back((int32_t)terms.size());
+        }
+        return 0;
+    }
+    /** G ((nb + 1) x (nb + 1), row-major, host): the Gram matrix of psi (vector 0) and the images D_b psi (vector 1 + b), ONE dmrgx_kron_term_gram call. */
+    PetscErrorCode Gram(std::vector<double>& G) const
+    {
+        const PetscInt nv = nb + 1;
+        std::vector<int32_t> first{0};
+        std::vector<dmrgx_term> all;
+        all.push_back(dmrgx_term{1.0, -1, -1});
+        all.insert(all.end(), terms.begin(), terms.end());
+        for (int32_t f : vec_first) first.push_back(f + 1);
+        /* the workspace holds at least the largest image block of every vector: the blocks (IL, IR), (IL - 1, IR + 1), (IL + 1, IR - 1) */
+        int64_t largest = 1;
+        for (size_t k = 0; k < F.bil.size(); ++k)
+            for (int32_t d = -1; d <= 1; ++d) {
+                const int32_t a = F.bil[k] - d, c = F.bir[k] + d;
+                if (a >= 0 && a < (int32_t)F.sizes[0].size() && c >= 0 && c < (int32_t)F.sizes[1].size()) largest = std::max<int64_t>(largest, (int64_t)F.sizes[0][(size_t)a] * F.sizes[1][(size_t)c]);
+            }
+        const size_t workspace = std::max<size_t>((size_t)1 << 30, (size_t)largest * (size_t)nv * sizeof(double));
+        G.assign((size_t)(nv * nv), 0.0);
+        DevBuffer g((size_t)(nv * nv), DevBuffer::device_only_t{});
+        if (dmrgx_kron_term_gram(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
+                                 (int32_t)nv, first.data(), all.data(), workspace, g.dev_uninitialised(), nv, nullptr, nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "dmrgx_kron_term_gram: %s", dmrgx_last_error());
+        if (dmrgx_memcpy_d2h(G.data(), g.dev_ro(), G.size() * sizeof(double), nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "%s", dmrgx_last_error());
+        return 0;
+    }
+    /** dst + b ld = D_b psi for all nb bonds, through dmrgx_kron_term_apply in chunks of at most 1 GiB of images (as SzFrame::Images). */
+    PetscErrorCode Images(double* dst, int64_t ld) const
+    {
+        const PetscInt chunk = std::max<PetscInt>(1, std::min<PetscInt>(nb, (PetscInt)((((int64_t)1 << 30) / (int64_t)sizeof(double)) / std::max<int64_t>(ld, 1))));
+        std::vector<int32_t> first;
+        for (PetscInt b0 = 0; b0 < nb; b0 += chunk) {
+            const PetscInt cnt = std::min<PetscInt>(chunk, nb - b0);
+            const int32_t t0 = vec_first[(size_t)b0];
+            first.clear();
+            for (PetscInt b = b0; b <= b0 + cnt; ++b) first.push_back(vec_first[(size_t)b] - t0);
+            if (dmrgx_kron_term_apply(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
+                                      (int32_t)cnt, first.data(), terms.data() + t0, dst + b0 * ld, ld, nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "dmrgx_kron_term_apply: %s", dmrgx_last_error());
+        }
+        return 0;
+    }
+private:
+    /** bond_op[b] of every bond inside a block, dense per sector:
+        C[q] = Sz_i[q] Sz_j[q] + (Sp_i / 2)[q -> q+1] Sm_j[q+1 -> q] + (Sm_i / 2)[q -> q-1] Sp_j[q-1 -> q] */
+    PetscErrorCode BuildBondOperators()
+    {
+        PetscErrorCode ierr;
+        bond_op.assign((size_t)nb, Mat());
+        for (int side = 0; side < 2; ++side) {
+            const std::vector<int32_t>& sz = F.sizes[side];
+            const int32_t ns = (int32_t)sz.size();
+            enum { DSz = 0, DSp = 1, DSm = 2, DHalfSp = 3, DHalfSm = 4 };
+            std::map<std::pair<int, PetscInt>, Mat> dense;          /* (kind, block site) -> dense form, for this measurement */
+            auto densify = [&](int kind, PetscInt s, Mat& d) -> PetscErrorCode {
+                auto it = dense.find({kind, s});
+                if (it != dense.end()) { d = it->second; return 0; }
+                Mat m;
+                PetscErrorCode e = F.resident(side, kind == DSz ? OpSz : OpSp, s, m); CHKERRQ(e);
+                if (kind == DSm || kind == DHalfSm) {               /* Sm(s) = Sp(s) read transposed */
+                    auto v = std::make_shared<SectorMat>();
+                    v->transpose_of = m; v->shift = OpSm; v->sizes = m->sizes;
+                    m = v;
+                }
+                if (SectorMatDensify(m, d, kind >= DHalfSp ? 0.5 : 1.0)) SETERRQ2(PETSC_COMM_SELF, 1, "%s: densifying a site operator: %s", F.name, dmrgx_last_error());
+                dense[{kind, s}] = d;
+                return 0;
+            };
+            auto cell_at = [](const Mat& M, int32_t q) -> const MatCell* { for (const MatCell& c : M->cells) if (c.q == q) return &c; return nullptr; };
+            std::vector<dmrgx_ggemm_group> groups;
+            std::vector<dmrgx_ggemm_prod> prods;
+            std::vector<size_t> first_prod;
+            int64_t chunk_elems = 0, total = 0;
+            for (int32_t q = 0; q < ns; ++q) total += (int64_t)sz[(size_t)q] * sz[(size_t)q];
+            const int64_t chunk_limit = (int64_t)1 << 28;           /* 2 GiB of bond operators per grouped launch */
+            auto flush = [&]() -> PetscErrorCode {
+                for (size_t g = 0; g < groups.size(); ++g) groups[g].prods = prods.data() + first_prod[g];
+                if (!groups.empty() && dmrgx_ggemm_groups((int32_t)groups.size(), groups.data(), 0, nullptr, nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "dmrgx_ggemm_groups: %s", dmrgx_last_error());
+                groups.clear(); prods.clear(); first_prod.clear(); chunk_elems = 0;
+                return 0;
+            };
+            for (PetscInt b = 0; b < nb; ++b) {
+                if (side_of[(size_t)b] != side) continue;
+                const PetscInt si = F.block_site(side, bonds[(size_t)b].i), sj = F.block_site(side, bonds[(size_t)b].j);
+                Mat zi, zj, hpi, hmi, pj, mj;
+                ierr = densify(DSz, si, zi); CHKERRQ(ierr); ierr = densify(DSz, sj, zj); CHKERRQ(ierr);
+                ierr = densify(DHalfSp, si, hpi); CHKERRQ(ierr); ierr = densify(DSm, sj, mj); CHKERRQ(ierr);
+                ierr = densify(DHalfSm, si, hmi); CHKERRQ(ierr); ierr = densify(DSp, sj, pj); CHKERRQ(ierr);
+                if (chunk_elems + total > chunk_limit) { ierr = flush(); CHKERRQ(ierr); }
+                Mat C = std::make_shared<SectorMat>();
+                C->shift = 0; C->sizes = sz;
+                auto arena = std::make_shared<DevBuffer>((size_t)std::max<int64_t>(total, 1), DevBuffer::device_only_t{});
+                int64_t cursor = 0;
+                for (int32_t q = 0; q < ns; ++q) {
+                    const int32_t nq = sz[(size_t)q];
+                    MatCell c;
+                    c.q = q; c.nr = c.nc = nq; c.ld = nq; c.buf = arena; c.off = cursor;
+                    C->cells.push_back(c);
+                    first_prod.push_back(prods.size());
+                    int32_t np = 0;
+                    auto product = [&](const Mat& A, const Mat& B, int32_t qmid) {        /* A[q -> qmid] B[qmid -> q] */
+                        if (qmid < 0 || qmid >= ns) return;
+                        const MatCell* a = cell_at(A, q);
+                        const MatCell* bb = cell_at(B, qmid);
+                        if (!a || !bb) return;
+                        prods.push_back(dmrgx_ggemm_prod{0, sz[(size_t)qmid], a->buf->dev_ro() + a->off, a->ld, bb->buf->dev_ro() + bb->off, bb->ld, 1.0});
+                        ++np;
+                    };
+                    product(zi, zj, q); product(hpi, mj, q + 1); product(hmi, pj, q - 1);
+                    groups.push_back(dmrgx_ggemm_group{arena->dev_uninitialised() + cursor, nq, nq, nq, 0, np, nullptr});
+                    cursor += (int64_t)nq * nq;
+                }
+                chunk_elems += total;
+                bond_doubles += total;
+                bond_op[(size_t)b] = C;
+            }
+            ierr = flush(); CHKERRQ(ierr);
+        }                                                           /* (the dense site operators go back to the pool here: stream-ordered) */
+        return 0;
+    }
+};
 
 /** A JSON file that holds one list of records, one per measurement: created by the first Begin(), finished by Close().  The caller
     writes the record itself to fp; numbers of Row() and Table() go through `number`, a printf format for one double. */

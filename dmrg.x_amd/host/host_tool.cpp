@@ -183,6 +183,12 @@ int main()
             printf("bonds");
             for (const dmrgx_host::DimerBond& b : dmrgx_host::DimerBonds(ham)) printf(" %lld,%lld,%c,%lld,%lld", LLD(b.i), LLD(b.j), b.orient, LLD(b.ix), LLD(b.jy));
             printf("\n");
+        } else if (cmd == "bondsof") {           /* bondsof x|y: the bonds of ham of that orientation: index,ix,jy */
+            std::string o; is >> o;
+            const dmrgx_host::OrientedBonds O = dmrgx_host::BondsOfOrientation(dmrgx_host::DimerBonds(ham), o.empty() ? '?' : o[0]);
+            printf("bondsof %zu", O.of.size());
+            for (size_t k = 0; k < O.of.size(); ++k) printf(" %lld,%lld,%lld", LLD(O.of[k]), LLD(O.x[k]), LLD(O.y[k]));
+            printf("\n");
         } else if (cmd == "fourier" || cmd == "cossum") {
             /* fourier Lx Ly n x_0 .. x_{n-1} y_0 .. y_{n-1} T_00 .. T_{n-1,n-1} [norm]  ->  the Lx x Ly table of LatticeFourier, norm n unless given
                cossum Lx Ly n c ncol x_0 .. x_{n-1} y_0 .. y_{n-1} T_00 .. T_{n-1,ncol-1}  ->  the (Lx Ly) x ncol table of SiteCosineSum, row by row */

@@ -267,6 +267,21 @@ def vec_gram(U, V, accumulate=False, out=None):
     return out, report
 
 
+def vec_project_out(V, p):
+    """V[a, :] -= coef[a] p with coef[a] = <V[a, :], p> / <p, p>, in place (dmrgx_vec_project_out).  V: a 2-D f64 device tensor with unit
+    stride along the vector (row stride >= length; views of larger buffers are fine, the columns beyond the length are left alone);
+    p: a contiguous 1-D f64 device tensor of that length, only read, not overlapping V.  Returns (coef[nv] as a numpy array, <p, p>);
+    a p whose squared norm is not a positive finite number leaves V alone and returns zeros."""
+    assert V.dtype == torch.float64 and p.dtype == torch.float64 and V.dim() == 2 and p.dim() == 1 and V.shape[1] == p.shape[0]
+    nv, n = V.shape
+    assert n <= 1 or (V.stride(1) == 1 and p.stride(0) == 1)
+    ldv = V.stride(0) if nv > 1 else max(V.stride(0), n)
+    coef, norm2 = (C.c_double * max(nv, 1))(), C.c_double(0.0)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _capi.check(_capi.lib().dmrgx_vec_project_out(nv, n, C.c_void_p(V.data_ptr()), ldv, C.c_void_p(p.data_ptr()), coef, C.byref(norm2), st))
+    return np.array(coef[:nv]), norm2.value
+
+
 def _gram_arguments(sb_or_layout, psi, left_ops, right_ops):
     """The arguments dmrgx_kron_op_gram and dmrgx_kron_term_gram share, as ctypes values: (sectors, sectors, nblocks, il, ir, psi pointer, n_left,
     left operators, n_right, right operators), psi as a device tensor, and the list that keeps every buffer behind them alive."""

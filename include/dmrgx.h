@@ -32,6 +32,7 @@
  *   dmrgx_kron_chebyshev_moments  the Chebyshev recursion on the planned Hamiltonian and its moments with a family of vectors (-dsf_cheb)
  *   dmrgx_kron_correction_vector  the correction vector 1 / (sigma + i eta - H) v0 by a device-resident conjugate-gradient run, and its
  *                               overlaps with a family of vectors: G_ic(w + i eta) under a true Lorentzian (-dsf_cv)
+ *   dmrgx_vec_project_out       one vector removed from a family of vectors, coefficients returned: (D_b - <D_b>) psi for all bonds (-dsf_dimer)
  *   dmrgx_comm_*             <- the communicator of the reference's MPI path: VecScatter-to-all of x inside every MatMult
  *                               (src/DMRGKron.cpp:1833-1834) and the MPI_Allreduce behind SLEPc's VecDot / VecNorm
  *
@@ -574,6 +575,26 @@ dmrgx_status dmrgx_kron_correction_vector(dmrgx_kron_plan* plan, const double* v
                                           double* norm2, double* im /* host [nu]: <u_i, Y> */,
                                           double* re /* host [nu]: <u_i, X>; NULL iff X_dev NULL or nu == 0 */,
                                           dmrgx_cv_stats* stats, void* stream);
+
+/* ---- One vector projected out of a family of vectors (operators with an expectation value: no elastic line) ------------ */
+/* For every row a < nv of V (V_dev[a*ldv + e], e < len):  coef[a] = <v_a, p> / <p, p>,  then  v_a -= coef[a] p;  *p_norm2 = <p, p>.
+ * With p = psi and v_b = D_b psi the rows become (D_b - <D_b>) psi and coef the expectation values: the start vectors and images of a
+ * dynamical measurement without the delta peak at w = 0 (-dsf_dimer).  Needs no plan: any vectors of one length on the device.
+ * Three launches over ranges of 2048 elements: (1) workgroup b keeps its range of p in registers, walks the nv rows and leaves the
+ * partial sums of <v_a, p> and of <p, p>; (2) one workgroup adds the partials in block order, divides and writes the nv coefficients
+ * to a device array; (3) the same ranges, p again in registers, v_a[e] -= coef[a] p[e].  p is read twice, V is read twice and written
+ * once.  The sums are carried as unevaluated pairs of doubles (exact products by fma, TwoSum) through the division: coef[a] is the
+ * quotient of the exact sums to a rounding or two whatever len is -- a row stored as 3 p comes back with coef 3.0 and with nothing but
+ * the rounding of its own elements left.  The call ends with one copy and one synchronisation.
+ * Rows go through 16-byte accesses when V_dev and p_dev are 16-byte aligned and ldv is even, through 8-byte accesses otherwise; the
+ * columns from len to ldv are neither read nor written.  p is only read.
+ * If <p, p> is not a positive finite number (p = 0, a NaN, overflow) V is left untouched, every coef is 0 and *p_norm2 = 0.  A row
+ * whose dot with p is not finite is left untouched with coef 0 while the other rows are done; so is a row whose coef is exactly 0.
+ * len == 0: DMRGX_OK, zeros, nothing touched.  Refused (DMRGX_ERR_ARG): a null pointer, nv < 1, len < 0, ldv < len, p overlapping V.
+ * Memory from the pool: 2 (nv + 1) ceil(len / 2048) doubles of partial sums, nv + 2 scalars.  Fixed grids, fixed-order sums, no
+ * atomics: two calls give the same bits in coef and V. */
+dmrgx_status dmrgx_vec_project_out(int32_t nv, int64_t len, double* V_dev, int64_t ldv, const double* p_dev,
+                                   double* coef /* host [nv] */, double* p_norm2 /* host */, void* stream);
 
 #ifdef __cplusplus
 }
