@@ -8,8 +8,9 @@
 // Per Lanczos step the vector work is three fused HBM-bound passes over the basis instead of BLAS-1 calls (CGS2):
 //   multi_dot       : c = V^T w                                  (reads j+2 vectors)
 //   axpy_dot        : w' = w - V c ; c2 = V^T w' , w'.w'         (reads j+2 vectors, writes w')
-//   axpy_normalise  : v_{j+1} = (w' - V c2) / sqrt(w'.w' - |c2|^2)   (reads j+2 vectors, writes v_{j+1})  Nothing is copied to the host inside a restart cycle: the normalisation reads beta^2
-// from device memory, and the host fetches the projected matrix once per cycle (ncv/2 MatMults).
+//   axpy_normalise  : v_{j+1} = (w' - V c2) / sqrt(w'.w' - |c2|^2)   (reads j+2 vectors, writes v_{j+1})
+// The host waits for nothing inside a restart cycle: the normalisation reads beta^2 from device memory, the coefficients of a step reach
+// the host's look one step behind the queue, and the host fetches the projected matrix once per cycle (ncv/2 MatMults).
 // world_size > 1: vectors are this rank's stripe segment; per Lanczos step there are exactly two fused all-reduces (of
 // j+2 doubles each) and one all-gather of the Krylov vector before the MatMult.
 #include "krylov.h"
@@ -603,8 +604,6 @@ void jacobi_eigh(int n, std::vector<double>& A, std::vector<double>& w, std::vec
 
 using namespace dmrgx;
 
-static dmrgx_status eigs_davidson(dmrgx_kron_plan* plan, const dmrgx_eigs_opts* opts, double* e0, double* psi_full, dmrgx_eigs_stats* stats, hipStream_t st);
-
 namespace {
 // Where a distributed MatMult spends its time, for the N > 1 bench line: three events per MatMult on the solver's
 // stream, read when the timer goes out of scope (the solve has synchronised by then), summed into process-wide totals.
@@ -645,102 +644,97 @@ extern "C" dmrgx_status dmrgx_eigs_comm_timing(double* allgather_ms, double* app
     return DMRGX_OK;
 }
 
-// Pinned doubles per host thread for what travels to the host behind the solver's own synchronisations: [0, 8) scalars ([2]: squared
-// norm of a caller-supplied start vector), [8, 8 + MAX_NCV + 2) the newest column of the projected matrix of the Davidson iteration
-// (a read-back into pageable memory is staged and blocks the host for ~20 us; one per MatMult).
-static double* pinned_scalars()
+namespace {
+
+// developer aid (DMRGX_EIGS_TRACE set): the Ritz pair per look and, on the Davidson path, the wall time of the set-up stages (synchronising)
+bool eigs_trace()
 {
-    static thread_local double* p = nullptr;
-    if (!p && hipHostMalloc((void**)&p, (8 + MAX_NCV + 2) * sizeof(double), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
-    return p;
-}
-// A start vector is not trusted when its norm is zero / NaN (seen from the first coefficients) or below what the caller asked for.
-static bool start_too_light(const dmrgx_eigs_opts* opts, const double* pin)
-{
-    return opts->min_initial_norm2 > 0.0 && pin && !(pin[2] >= opts->min_initial_norm2);
+    static const bool on = getenv("DMRGX_EIGS_TRACE") != nullptr;
+    return on;
 }
 
-extern "C" dmrgx_status dmrgx_eigs_lowest(dmrgx_kron_plan* plan, const dmrgx_eigs_opts* opts, double* e0,
-                                          double* psi_full, dmrgx_eigs_stats* stats, void* stream)
+// What the host looks at behind an event or one of the solver's own synchronisations, per host thread (callers on different threads /
+// devices do not share it) and pinned (a read-back into pageable memory is staged and blocks the host for ~20 us): the squared norm of a
+// caller-supplied start vector, the Davidson look (|r|^2, theta, |H v_0|^2) and the two slots of the Lanczos look-behind, each the
+// coefficient rows of a cycle.
+constexpr size_t LOOK_STRIDE = (size_t)(MAX_NCV + 1) * (MAX_NCV + 2);
+struct HostLooks {
+    double* pin = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};              // [0], [1]: the Lanczos slots; [2]: the Davidson look
+    double* start_norm2() const { return pin; }
+    double* gd_look() const { return pin + 1; }
+    double* lanczos_look(int slot) const { return pin + 4 + (size_t)slot * LOOK_STRIDE; }
+};
+dmrgx_status host_looks(HostLooks** out)
 {
-    hipStream_t st = (hipStream_t)stream;
-    if (!plan || !opts || !e0 || !psi_full) DMRGX_FAIL(DMRGX_ERR_ARG, "eigs_lowest: null argument");
-    // the diagonally preconditioned iteration pays off from a start vector close to the answer (the engine's transformed ground
-    // state: 16-19 MatMults where Lanczos needs 21-27); from a random vector it is twice as slow as Lanczos (measured 140 vs 72),
-    // so without a supplied start vector the request falls through to the Lanczos path
+    static thread_local HostLooks h;
+    if (!h.pin) {
+        for (hipEvent_t& e : h.ev) if (!e) DMRGX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        DMRGX_HIP(hipHostMalloc((void**)&h.pin, (4 + 2 * LOOK_STRIDE) * sizeof(double), hipHostMallocDefault));
+    }
+    *out = &h;
+    return DMRGX_OK;
+}
+
+// One call of dmrgx_eigs_lowest: what the Lanczos and the Davidson path share.  Vectors are this rank's stripe segment, n of the N states.
+// Every device buffer of either path is a member, so that solve_again() drops the whole work space of the attempt it abandons.
+struct EigsRun {
+    dmrgx_kron_plan* const plan;
+    const dmrgx_eigs_opts* const opts;
+    double* const e0;
+    double* const psi_full;
+    dmrgx_eigs_stats* const stats;
+    const hipStream_t st;
     dmrgx_kron_info I;
-    DMRGX_CHK(dmrgx_kron_plan_info(plan, &I));
-    // (a search space of fewer than two vectors -- a one-state superblock sector, ncv = 1 -- has nothing to precondition: Lanczos path)
-    const bool gd_space = std::min<int64_t>(opts->ncv > 0 ? opts->ncv : 16, I.n_states) >= 2;
-    if (opts->method == 1 && opts->use_initial && opts->max_matvec <= 0 && gd_space) return eigs_davidson(plan, opts, e0, psi_full, stats, st);
-    const bool dist = I.vec_len != I.n_states;
-    const bool hooks = opts->allgather && opts->allreduce_sum;
-    if (dist && !hooks && !opts->comm) DMRGX_FAIL(DMRGX_ERR_ARG, "eigs_lowest: a striped plan needs a communicator (opts->comm) or the allgather/allreduce hooks");
-    auto gather_full = [&](double* full) -> dmrgx_status {      // in-place all-gather of the rank segments of a full vector
-        return hooks ? opts->allgather(opts->user, full, I.seg_stride, st) : dmrgx_comm_allgather(opts->comm, full, I.seg_stride, st);
-    };
-    const int64_t n = I.local_len, N = I.n_states;
-    int m = opts->ncv > 0 ? opts->ncv : 16;
-    m = (int)std::min<int64_t>(std::min(m, MAX_NCV), N);
-    // a one-vector Krylov space cannot restart (the restart keeps one Ritz vector and needs room for the residual direction: with m == 1
-    // every cycle after the first ran no MatMult and read the first cycle's beta again, max_it times): ncv = 1 is taken as 2.  N == 1 ends at m == N.
-    m = (int)std::max<int64_t>(m, std::min<int64_t>(2, N));
-    if (m < 1) DMRGX_FAIL(DMRGX_ERR_ARG, "eigs_lowest: empty problem");
-    const int max_it = opts->max_it > 0 ? opts->max_it : std::max<int>(100, (int)(2 * N / m));
-    const double tol = opts->tol > 0 ? opts->tol : 1e-8;
-    const auto t_begin = std::chrono::steady_clock::now();
+    int64_t n = 0, N = 0;
+    bool dist = false, hooks = false;
+    std::chrono::steady_clock::time_point t_begin;
+    HostLooks* host = nullptr;
+    CommTimer ctimer;       // (distributed only) HIP events round the all-gather and the apply of every MatMult: dmrgx_eigs_comm_timing
+    DevBuf dX, dPartial, dV, dW, dTmp, dScal;                    // both paths
+    DevBuf dQ;                                                   // Lanczos
+    DevBuf dT, dD, dState, dLook;                                // Davidson
+    // set by the path: the row stride == length of every work vector, the basis (dV) and the scalar scratch in dScal (layout)
+    int64_t ld = 0;
+    double* V = nullptr;
+    double *c1 = nullptr, *c2 = nullptr, *nrm = nullptr;         // [nv+1]: V^T w, w.w; [nv+1]: the same of the second pass; [1]
 
-    DevBuf dV, dW, dX, dTmp, dPartial, dScal, dQ;
-    DMRGX_CHK(dV.alloc_f64((size_t)(m + 1) * n, st));
-    DMRGX_CHK(dW.alloc_f64((size_t)n, st));
-    DMRGX_CHK(dTmp.alloc_f64((size_t)(m / 2 + 2) * n, st));
-    if (dist) DMRGX_CHK(dX.alloc_f64((size_t)I.vec_len, st));
-    DMRGX_CHK(dPartial.alloc_f64((size_t)(MAX_NCV + DOT_CHUNK + 1) * DOT_BLOCKS, st));
-    // scalars: per step j a row of (m+2) doubles: h_j[0..m] accumulated coefficients, slot m+1: beta_j^2 ; + scratch c[]
-    const int row = m + 2;
-    DMRGX_CHK(dScal.alloc_f64((size_t)((m + 1) * row + 3 * (MAX_NCV + 2)), st));
-    DMRGX_CHK(dQ.alloc_f64((size_t)MAX_NCV * MAX_NCV, st));
-    double* V = dV.as<double>();
-    double* w = dW.as<double>();
-    double* c1 = dScal.as<double>() + (size_t)(m + 1) * row;      // [nv+1]: V^T w, w.w
-    double* c2 = c1 + (MAX_NCV + 2);                              // [nv+1]: V^T w', w'.w' (second pass)
-    double* nrm = c2 + (MAX_NCV + 2);                             // [1]
-    auto Hrow = [&](int j) { return dScal.as<double>() + (size_t)j * row; };
-    auto vec = [&](int j) { return V + (size_t)j * n; };
-    DMRGX_HIP(zero_async(dV.p, dV.bytes, st));        // (the Ritz-vector rotations read all m rows of V against zero-padded coefficients)
-    DMRGX_HIP(zero_async(dW.p, dW.bytes, st));
-    if (dist) DMRGX_HIP(zero_async(dX.p, dX.bytes, st));
+    EigsRun(dmrgx_kron_plan* p, const dmrgx_eigs_opts* o, double* e, double* psi, dmrgx_eigs_stats* s, hipStream_t stream)
+        : plan(p), opts(o), e0(e), psi_full(psi), stats(s), st(stream), ctimer(stream) {}
 
-    const bool vec2 = (n % 2 == 0);                     // all vectors are whole allocations (256-byte aligned) of stride n
-    const int nblk = DOT_BLOCKS;      // (scaling the grid down with n was measured slower even at n = 1.6e5: these passes are latency-bound)
-    auto allreduce = [&](double* buf, int64_t count) -> dmrgx_status {
+    dmrgx_status init()
+    {
+        DMRGX_CHK(dmrgx_kron_plan_info(plan, &I));
+        dist = I.vec_len != I.n_states;
+        hooks = opts->allgather && opts->allreduce_sum;
+        if (dist && !hooks && !opts->comm) DMRGX_FAIL(DMRGX_ERR_ARG, "eigs_lowest: a striped plan needs a communicator (opts->comm) or the allgather/allreduce hooks");
+        n = I.local_len; N = I.n_states;
+        t_begin = std::chrono::steady_clock::now();
+        return host_looks(&host);
+    }
+    double seconds() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); }
+    double* psi_local() const { return dist ? psi_full + I.local_offset : psi_full; }
+
+    // dX and the per-block partial sums (the larger of the two paths' needs); both paths allocate them between dTmp and dScal
+    dmrgx_status alloc_shared()
+    {
+        if (dist) DMRGX_CHK(dX.alloc_f64((size_t)I.vec_len, st));
+        return dPartial.alloc_f64((size_t)(MAX_NCV + DOT_CHUNK + 2) * DOT_BLOCKS, st);
+    }
+    void layout(double* scratch) { V = dV.as<double>(); c1 = scratch; c2 = c1 + (MAX_NCV + 2); nrm = c2 + (MAX_NCV + 2); }
+    void release_work() { for (DevBuf* b : {&dX, &dPartial, &dV, &dW, &dTmp, &dScal, &dQ, &dT, &dD, &dState, &dLook}) b->release(); }
+
+    dmrgx_status allreduce(double* buf, int64_t count)
+    {
         if (!dist) return DMRGX_OK;
         return hooks ? opts->allreduce_sum(opts->user, buf, count, st) : dmrgx_comm_allreduce_sum(opts->comm, buf, count, st);
-    };
-    // dots of w against V[0..nv) plus w.w  -> c1[0..nv]
-    auto multi_dot = [&](int nv) -> dmrgx_status {
-        const int chunks = (nv + 1 + DOT_CHUNK - 1) / DOT_CHUNK;
-        if (vec2) hipLaunchKernelGGL(multi_dot_kernel<true>, dim3(nblk, chunks), dim3(DOT_THREADS), 0, st, V, n, nv, w, n, dPartial.as<double>());
-        else hipLaunchKernelGGL(multi_dot_kernel<false>, dim3(nblk, chunks), dim3(DOT_THREADS), 0, st, V, n, nv, w, n, dPartial.as<double>());
-        DMRGX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3(nv + 1), dim3(DOT_THREADS), 0, st, dPartial.as<double>(), c1, nv + 1, nblk);
-        DMRGX_HIP(hipGetLastError());
-        return allreduce(c1, nv + 1);
-    };
-    // final == false: only subtract.  final == true: also set nrm = ||w_new||^2 from the dots just reduced.
-    auto multi_axpy = [&](int nv, double* hacc, bool final) -> dmrgx_status {
-        if (final) { hipLaunchKernelGGL(norm_after_projection_kernel, dim3(1), dim3(64), 0, st, c1, nv, nrm); DMRGX_HIP(hipGetLastError()); }
-        hipLaunchKernelGGL(multi_axpy_kernel, dim3(nblk), dim3(DOT_THREADS), 0, st, V, n, nv, c1, w, n, dPartial.as<double>(), hacc);
-        DMRGX_HIP(hipGetLastError());
-        return DMRGX_OK;
-    };
-    auto normalise_into = [&](double* dst) -> dmrgx_status {
-        hipLaunchKernelGGL(scale_copy_kernel, dim3(1024), dim3(256), 0, st, w, dst, n, nrm);
-        DMRGX_HIP(hipGetLastError());
-        return DMRGX_OK;
-    };
-    CommTimer ctimer(st);       // (distributed only) HIP events round the all-gather and the apply of every MatMult: dmrgx_eigs_comm_timing
-    auto matvec = [&](const double* v_local, double* y_local) -> dmrgx_status {
+    }
+    dmrgx_status gather_full(double* full)                       // in-place all-gather of the rank segments of a full vector
+    {
+        return hooks ? opts->allgather(opts->user, full, I.seg_stride, st) : dmrgx_comm_allgather(opts->comm, full, I.seg_stride, st);
+    }
+    dmrgx_status matvec(const double* v_local, double* y_local)
+    {
         if (!dist) return dmrgx_kron_apply(plan, v_local, y_local, st);
         DMRGX_HIP(hipMemcpyAsync(dX.as<double>() + I.local_offset, v_local, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
         ctimer.mark();
@@ -749,65 +743,177 @@ extern "C" dmrgx_status dmrgx_eigs_lowest(dmrgx_kron_plan* plan, const dmrgx_eig
         const dmrgx_status rc = dmrgx_kron_apply(plan, dX.as<double>(), y_local, st);
         ctimer.mark();
         return rc;
-    };
+    }
+    // dst <- the caller's start vector, or uniform random values
+    dmrgx_status start_vector(double* dst)
+    {
+        if (opts->use_initial) { DMRGX_HIP(hipMemcpyAsync(dst, psi_full + I.local_offset, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st)); return DMRGX_OK; }
+        if (!dist) { hipLaunchKernelGGL(random_fill_kernel, dim3(1024), dim3(256), 0, st, dst, n, opts->seed, (int64_t)0); DMRGX_HIP(hipGetLastError()); return DMRGX_OK; }
+        // only real entries get random values: padding of a striped segment must stay zero, so fill through the plan's layout conversion
+        DevBuf ref;
+        DMRGX_CHK(ref.alloc((size_t)N * sizeof(double)));
+        hipLaunchKernelGGL(random_fill_kernel, dim3(1024), dim3(256), 0, st, ref.as<double>(), N, opts->seed, (int64_t)0);
+        DMRGX_HIP(hipGetLastError());
+        DMRGX_CHK(dmrgx_kron_vec_to_striped(plan, ref.as<double>(), dX.as<double>(), st));
+        DMRGX_HIP(hipMemcpyAsync(dst, dX.as<double>() + I.local_offset, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+        DMRGX_HIP(hipStreamSynchronize(st));                     // ref goes out of scope
+        return DMRGX_OK;
+    }
+    // |start vector|^2 (at `dev`) of a caller-supplied start vector travels to the host behind the stream: read after the next synchronisation
+    dmrgx_status fetch_start_norm2(const double* dev)
+    {
+        if (!opts->use_initial) return DMRGX_OK;
+        *host->start_norm2() = 0.0;
+        DMRGX_HIP(hipMemcpyAsync(host->start_norm2(), dev, sizeof(double), hipMemcpyDeviceToHost, st));
+        return DMRGX_OK;
+    }
+    // A start vector is not trusted when its norm is zero / NaN (seen from the first coefficients) or below what the caller asked for.
+    bool start_too_light() const { return opts->use_initial && opts->min_initial_norm2 > 0.0 && !(*host->start_norm2() >= opts->min_initial_norm2); }
+
+    // per-block partial sums of V[0..nv)^T x and x.x (dPartial); reduce == true: also out[0..nv] = the sums (all-reduced)
+    // (DOT_BLOCKS workgroups whatever n is: scaling the grid down with n was measured slower even at n = 1.6e5, these passes are latency-bound)
+    dmrgx_status multi_dot(int nv, const double* x, double* out, bool reduce)
+    {
+        const int chunks = (nv + 1 + DOT_CHUNK - 1) / DOT_CHUNK;
+        // two doubles per lane when the rows are 16-byte aligned: all vectors are whole allocations (256-byte aligned) of stride ld
+        if (ld % 2 == 0) hipLaunchKernelGGL(multi_dot_kernel<true>, dim3(DOT_BLOCKS, chunks), dim3(DOT_THREADS), 0, st, V, ld, nv, x, ld, dPartial.as<double>());
+        else hipLaunchKernelGGL(multi_dot_kernel<false>, dim3(DOT_BLOCKS, chunks), dim3(DOT_THREADS), 0, st, V, ld, nv, x, ld, dPartial.as<double>());
+        DMRGX_HIP(hipGetLastError());
+        if (!reduce) return DMRGX_OK;
+        hipLaunchKernelGGL(reduce_partials_kernel, dim3(nv + 1), dim3(DOT_THREADS), 0, st, dPartial.as<double>(), out, nv + 1, DOT_BLOCKS);
+        DMRGX_HIP(hipGetLastError());
+        return allreduce(out, nv + 1);
+    }
+    // CGS2 on x after its first dots c1 = V^T x: x <- x - V c1 fused with the second pass's dots c2 = V^T x, x.x (one fused all-reduce) ...
+    // NV >= nv: the registers the kernel holds the basis in.  hacc: where the Lanczos path accumulates the step's coefficients (or null)
+    template <int NV> dmrgx_status project_and_dot(int nv, double* x, double* hacc)
+    {
+        hipLaunchKernelGGL(axpy_dot_kernel<NV>, dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, st, V, ld, nv, c1, x, ld, dPartial.as<double>(), hacc);
+        DMRGX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(reduce_partials_kernel, dim3(nv + 1), dim3(DOT_THREADS), 0, st, dPartial.as<double>(), c2, nv + 1, DOT_BLOCKS);
+        DMRGX_HIP(hipGetLastError());
+        return allreduce(c2, nv + 1);
+    }
+    // ... then dst = (x - V c2) / beta, beta^2 = x.x - |c2|^2 (recorded at beta2 unless null)
+    dmrgx_status project_and_normalise(int nv, const double* x, double* dst, double* beta2, double* hacc)
+    {
+        if (ld % 2 == 0) hipLaunchKernelGGL(axpy_normalise_kernel<true>, dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, st, V, ld, nv, c2, x, dst, ld, beta2, hacc);
+        else hipLaunchKernelGGL(axpy_normalise_kernel<false>, dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, st, V, ld, nv, c2, x, dst, ld, beta2, hacc);
+        DMRGX_HIP(hipGetLastError());
+        return DMRGX_OK;
+    }
+    // psi = src / |src|, gathered; returns once it is there
+    dmrgx_status finish_vector(const double* src)
+    {
+        DMRGX_CHK(multi_dot(0, src, c1, true));
+        DMRGX_HIP(hipMemcpyAsync(nrm, c1, sizeof(double), hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(scale_copy_kernel, dim3(1024), dim3(256), 0, st, src, psi_local(), n, (const double*)nrm);
+        DMRGX_HIP(hipGetLastError());
+        if (dist) DMRGX_CHK(gather_full(psi_full));
+        DMRGX_HIP(hipStreamSynchronize(st));
+        return DMRGX_OK;
+    }
+    void finish(double lambda, double resid, int n_matvec, int restarts, int converged)
+    {
+        *e0 = lambda;
+        if (!stats) return;
+        stats->n_matvec = n_matvec; stats->n_restart = restarts; stats->converged = converged; stats->start_rejected = 0; stats->residual = resid;
+        stats->seconds = seconds();
+    }
+    // Give this attempt up and solve with the options `o2` instead.  Called right after a synchronisation: nothing is queued on the work
+    // space, which is released first (the repeated solve allocates its own -- ADVICE round 4); the attempt's MatMults and seconds stay
+    // in the returned totals, `restarts` of its restarts too.  rejected: the caller's start vector was dropped.
+    dmrgx_status solve_again(const dmrgx_eigs_opts& o2, int n_matvec, int restarts, bool rejected)
+    {
+        release_work();
+        dmrgx_eigs_stats s2;
+        memset(&s2, 0, sizeof(s2));
+        const dmrgx_status rc = dmrgx_eigs_lowest(plan, &o2, e0, psi_full, &s2, (void*)st);
+        if (stats) {
+            *stats = s2; stats->n_matvec += n_matvec; stats->n_restart += restarts; stats->seconds = seconds();
+            if (rejected) stats->start_rejected = 1;
+        }
+        return rc;
+    }
+    dmrgx_status eigs_lanczos();
+    dmrgx_status eigs_davidson();
+};
+
+// Rayleigh-Ritz on the leading mm columns of a cycle's projected matrix.  The cycle began with kept.size() Ritz vectors, whose block is
+// diag(kept); the later columns come from the coefficient rows the device recorded (hbuf: `row` doubles per step, slot m + 1 beta^2).
+struct Ritz {
+    std::vector<double> th, Q;      // ascending Ritz values, their vectors in the columns (row-major mm x mm)
+    double resid;                   // residual estimate of the lowest pair: |beta_mm Q[mm - 1][0]|
+};
+Ritz ritz_of_leading(int mm, int m, int row, const std::vector<double>& hbuf, const std::vector<double>& kept)
+{
+    const int k = (int)kept.size();
+    std::vector<double> A((size_t)mm * mm, 0.0);
+    for (int j = 0; j < mm; ++j) for (int i = 0; i <= j; ++i) {
+        const double v = j >= k ? hbuf[(size_t)j * row + i] : (i == j ? kept[j] : 0.0);
+        A[(size_t)i * mm + j] = v; A[(size_t)j * mm + i] = v;
+    }
+    Ritz r;
+    jacobi_eigh(mm, A, r.th, r.Q);
+    r.resid = std::fabs(std::sqrt(std::max(0.0, hbuf[(size_t)(mm - 1) * row + m + 1])) * r.Q[(size_t)(mm - 1) * mm + 0]);
+    return r;
+}
+
+// ---- thick-restart Lanczos (opts->method == 0, and whatever the Davidson path does not take) ------------------------------------
+dmrgx_status EigsRun::eigs_lanczos()
+{
+    int m = opts->ncv > 0 ? opts->ncv : 16;
+    m = (int)std::min<int64_t>(std::min(m, MAX_NCV), N);
+    // a one-vector Krylov space cannot restart (the restart keeps one Ritz vector and needs room for the residual direction: with m == 1
+    // every cycle after the first ran no MatMult and read the first cycle's beta again, max_it times): ncv = 1 is taken as 2.  N == 1 ends at m == N.
+    m = (int)std::max<int64_t>(m, std::min<int64_t>(2, N));
+    if (m < 1) DMRGX_FAIL(DMRGX_ERR_ARG, "eigs_lowest: empty problem");
+    const int max_it = opts->max_it > 0 ? opts->max_it : std::max<int>(100, (int)(2 * N / m));
+    const double tol = opts->tol > 0 ? opts->tol : 1e-8;
+
+    ld = n;
+    DMRGX_CHK(dV.alloc_f64((size_t)(m + 1) * n, st));
+    DMRGX_CHK(dW.alloc_f64((size_t)n, st));
+    DMRGX_CHK(dTmp.alloc_f64((size_t)(m / 2 + 2) * n, st));
+    DMRGX_CHK(alloc_shared());
+    // scalars: per step j a row of (m+2) doubles: h_j[0..m] accumulated coefficients, slot m+1: beta_j^2 ; + scratch c[]
+    const int row = m + 2;
+    DMRGX_CHK(dScal.alloc_f64((size_t)((m + 1) * row + 3 * (MAX_NCV + 2)), st));
+    DMRGX_CHK(dQ.alloc_f64((size_t)MAX_NCV * MAX_NCV, st));
+    layout(dScal.as<double>() + (size_t)(m + 1) * row);
+    double* const w = dW.as<double>();
+    auto Hrow = [&](int j) { return dScal.as<double>() + (size_t)j * row; };
+    auto vec = [&](int j) { return V + (size_t)j * n; };
+    DMRGX_HIP(zero_async(dV.p, dV.bytes, st));        // (the Ritz-vector rotations read all m rows of V against zero-padded coefficients)
+    DMRGX_HIP(zero_async(dW.p, dW.bytes, st));
+    if (dist) DMRGX_HIP(zero_async(dX.p, dX.bytes, st));
 
     // ---- start vector: w <- v0 ; V[0] = w/||w|| ------------------------------------------------------------
-    if (opts->use_initial) DMRGX_HIP(hipMemcpyAsync(w, psi_full + I.local_offset, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    else {
-        // only real entries get random values: padding of a striped segment must stay zero, so fill through the
-        // plan's layout conversion when striped
-        if (!dist) { hipLaunchKernelGGL(random_fill_kernel, dim3(1024), dim3(256), 0, st, w, n, opts->seed, (int64_t)0); DMRGX_HIP(hipGetLastError()); }
-        else {
-            DevBuf ref;
-            DMRGX_CHK(ref.alloc((size_t)N * sizeof(double)));
-            hipLaunchKernelGGL(random_fill_kernel, dim3(1024), dim3(256), 0, st, ref.as<double>(), N, opts->seed, (int64_t)0);
-            DMRGX_HIP(hipGetLastError());
-            DMRGX_CHK(dmrgx_kron_vec_to_striped(plan, ref.as<double>(), dX.as<double>(), st));
-            DMRGX_HIP(hipMemcpyAsync(w, dX.as<double>() + I.local_offset, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-            DMRGX_HIP(hipStreamSynchronize(st));
-        }
-    }
-    DMRGX_CHK(multi_dot(0));                                  // c1[0] = w.w
-    double* const pin = opts->use_initial ? pinned_scalars() : nullptr;
-    if (pin) { pin[2] = 0.0; DMRGX_HIP(hipMemcpyAsync(pin + 2, c1, sizeof(double), hipMemcpyDeviceToHost, st)); }      // read after the first synchronisation below
+    DMRGX_CHK(start_vector(w));
+    DMRGX_CHK(multi_dot(0, w, c1, true));                   // c1[0] = w.w
+    DMRGX_CHK(fetch_start_norm2(c1));
     DMRGX_HIP(hipMemcpyAsync(nrm, c1, sizeof(double), hipMemcpyDeviceToDevice, st));
-    DMRGX_CHK(normalise_into(vec(0)));
+    hipLaunchKernelGGL(scale_copy_kernel, dim3(1024), dim3(256), 0, st, w, vec(0), n, nrm);
+    DMRGX_HIP(hipGetLastError());
 
-    // how often the Ritz pair of a caller-supplied start vector is looked at: a look costs one small copy + a stream sync
-    // (~50 us), a MatMult that turns out unnecessary 0.1 .. 10 ms
-    // looks at the Ritz pair of a caller-supplied start vector: pinned slots + events of this host thread (see the step loop)
-    // (also from a random start vector: SLEPc looks at restarts only, but a look costs nothing here and a solve then ends up to ncv / 2 - 1
-    //  MatMults earlier -- the warm-up's cluster-growth steps and the reference-settings runs start random)
+    // The host looks at the Ritz pair after every step, one step behind the queue (see the step loop): a look costs one small copy and
+    // an event, a MatMult that turns out unnecessary 0.1 .. 10 ms.  Also from a random start vector: SLEPc looks at restarts only, but a
+    // look costs nothing here and a solve then ends up to ncv / 2 - 1 MatMults earlier (the warm-up's cluster-growth steps and the
+    // reference-settings runs start random).  Benchmark mode runs its exact number of MatMults and does not look.
     const bool looks = opts->max_matvec <= 0;
-    static thread_local double* look_buf = nullptr;
-    static thread_local hipEvent_t look_ev[2] = {nullptr, nullptr};
-    constexpr size_t look_stride = (size_t)(MAX_NCV + 1) * (MAX_NCV + 2);
-    if (looks && !look_buf) {
-        DMRGX_HIP(hipHostMalloc((void**)&look_buf, 2 * look_stride * sizeof(double), hipHostMallocDefault));
-        DMRGX_HIP(hipEventCreateWithFlags(&look_ev[0], hipEventDisableTiming)); DMRGX_HIP(hipEventCreateWithFlags(&look_ev[1], hipEventDisableTiming));
-    }
     int look_mm[2] = {0, 0};                    // columns covered by the look in flight in each slot (0: none)
-    std::vector<double> T((size_t)m * m, 0.0), theta, Q, hbuf((size_t)(m + 1) * row);
+    std::vector<double> kept, y((size_t)m, 0.0), hbuf((size_t)(m + 1) * row), Qdev;      // kept: the Ritz values a cycle starts from; y: the Ritz vector in the basis
     int k = 0, n_matvec = 0, restarts = 0, converged = 0;
-    double beta_m = 0.0, resid = 0.0, lambda = 0.0;
-    std::vector<double> Qdev;
+    double resid = 0.0, lambda = 0.0;
     // A caller-supplied start vector of zero (or NaN) norm is normalised to the zero vector (scale 0 instead of 1 / 0), every Krylov
     // vector after it is zero and the projected matrix is exactly zero: "converged" at E = 0 with psi = 0.  Seen from the first
     // coefficients that come back to the host -- alpha_0 and beta_0^2 both not positive in magnitude -- the solve is repeated from the
     // random start vector instead (the engine's projected start vectors can lose all their weight).
-    auto null_start = [&]() { return opts->use_initial && restarts == 0 && k == 0 && ((!(std::fabs(hbuf[0]) > 0.0) && !(hbuf[(size_t)m + 1] > 0.0)) || start_too_light(opts, pin)); };
+    auto null_start = [&]() { return opts->use_initial && restarts == 0 && k == 0 && ((!(std::fabs(hbuf[0]) > 0.0) && !(hbuf[(size_t)m + 1] > 0.0)) || start_too_light()); };
     auto redo_from_random = [&]() -> dmrgx_status {
-        // (called right after a synchronisation: nothing is queued on the work space, which the repeated solve allocates again -- ADVICE
-        //  round 4: the rejected attempt's buffers are released first and its MatMults and seconds stay in the returned totals)
-        dV.release(); dW.release(); dTmp.release(); dX.release();
         dmrgx_eigs_opts o2 = *opts;
         o2.use_initial = 0;
-        dmrgx_eigs_stats s2;
-        memset(&s2, 0, sizeof(s2));
-        const dmrgx_status rc = dmrgx_eigs_lowest(plan, &o2, e0, psi_full, &s2, (void*)st);
-        if (stats) { *stats = s2; stats->n_matvec += n_matvec; stats->start_rejected = 1;
-                     stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); }
-        return rc;
+        return solve_again(o2, n_matvec, 0, true);
     };
     while (true) {
         DMRGX_HIP(zero_async(Hrow(k), (size_t)(m + 1 - k) * row * sizeof(double), st));
@@ -819,23 +925,15 @@ extern "C" dmrgx_status dmrgx_eigs_lowest(dmrgx_kron_plan* plan, const dmrgx_eig
             DMRGX_CHK(matvec(vec(j), w));
             ++n_matvec;
             const int nv = j + 1;
-            DMRGX_CHK(multi_dot(nv));                         // pass 1: c1 = V^T w                (one fused all-reduce)
-            if (nv <= FUSE_NV) {
-                // w' = w - V c1 fused with pass 2's dots: c2 = V^T w', w'.w'            (one fused all-reduce)
-                hipLaunchKernelGGL(axpy_dot_kernel<FUSE_NV>, dim3(nblk), dim3(DOT_THREADS), 0, st, V, n, nv, c1, w, n, dPartial.as<double>(), Hrow(j));
+            DMRGX_CHK(multi_dot(nv, w, c1, true));          // pass 1: c1 = V^T w                (one fused all-reduce)
+            if (nv <= FUSE_NV) DMRGX_CHK(project_and_dot<FUSE_NV>(nv, w, Hrow(j)));      // w' = w - V c1 ; c2 = V^T w', w'.w'  (one fused all-reduce)
+            else {                                                                       // the same in two passes over the basis
+                hipLaunchKernelGGL(multi_axpy_kernel, dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, st, V, n, nv, c1, w, n, dPartial.as<double>(), Hrow(j));
                 DMRGX_HIP(hipGetLastError());
-                hipLaunchKernelGGL(reduce_partials_kernel, dim3(nv + 1), dim3(DOT_THREADS), 0, st, dPartial.as<double>(), c2, nv + 1, nblk);
-                DMRGX_HIP(hipGetLastError());
-                DMRGX_CHK(allreduce(c2, nv + 1));
-            } else {
-                DMRGX_CHK(multi_axpy(nv, Hrow(j), false));
-                DMRGX_CHK(multi_dot(nv));
+                DMRGX_CHK(multi_dot(nv, w, c1, true));
                 DMRGX_HIP(hipMemcpyAsync(c2, c1, (size_t)(nv + 1) * sizeof(double), hipMemcpyDeviceToDevice, st));
             }
-            // beta^2 = w'.w' - |c2|^2 ; v_{j+1} = (w' - V c2) / beta
-            if (vec2) hipLaunchKernelGGL(axpy_normalise_kernel<true>, dim3(nblk), dim3(DOT_THREADS), 0, st, V, n, nv, c2, w, vec(j + 1), n, Hrow(j) + m + 1, Hrow(j));
-            else hipLaunchKernelGGL(axpy_normalise_kernel<false>, dim3(nblk), dim3(DOT_THREADS), 0, st, V, n, nv, c2, w, vec(j + 1), n, Hrow(j) + m + 1, Hrow(j));
-            DMRGX_HIP(hipGetLastError());
+            DMRGX_CHK(project_and_normalise(nv, w, vec(j + 1), Hrow(j) + m + 1, Hrow(j)));      // beta^2 = w'.w' - |c2|^2 ; v_{j+1} = (w' - V c2) / beta
             // A start vector supplied by the caller (the sweep engine's transformed ground state) is usually within a few Lanczos steps of
             // convergence, so the Ritz pair is looked at after EVERY step -- one step behind the queue (round 5; rounds 2-4 looked every
             // 1 / 2 / 4 steps with a blocking copy: 0.24 ms of idle GPU per configs[1] step and, on the small superblocks, 1-2 MatMults past
@@ -843,65 +941,41 @@ extern "C" dmrgx_status dmrgx_eigs_lowest(dmrgx_kron_plan* plan, const dmrgx_eig
             // while step j runs.  Convergence seen there ends the solve with the step already queued included.
             if (looks && j + 1 < m) {
                 const int slot = j & 1;
-                DMRGX_HIP(hipMemcpyAsync(look_buf + (size_t)slot * look_stride, dScal.p, (size_t)(m + 1) * row * sizeof(double), hipMemcpyDeviceToHost, st));
-                DMRGX_HIP(hipEventRecord(look_ev[slot], st));
+                DMRGX_HIP(hipMemcpyAsync(host->lanczos_look(slot), dScal.p, (size_t)(m + 1) * row * sizeof(double), hipMemcpyDeviceToHost, st));
+                DMRGX_HIP(hipEventRecord(host->ev[slot], st));
                 look_mm[slot] = j + 1;
             }
             if (looks && j > k && look_mm[(j - 1) & 1] == j) {
                 const int slot = (j - 1) & 1;
                 look_mm[slot] = 0;
-                DMRGX_HIP(hipEventSynchronize(look_ev[slot]));
-                std::copy(look_buf + (size_t)slot * look_stride, look_buf + (size_t)slot * look_stride + (size_t)(m + 1) * row, hbuf.begin());
+                DMRGX_HIP(hipEventSynchronize(host->ev[slot]));
+                std::copy(host->lanczos_look(slot), host->lanczos_look(slot) + (size_t)(m + 1) * row, hbuf.begin());
                 if (null_start()) { DMRGX_HIP(hipStreamSynchronize(st)); return redo_from_random(); }
-                const int mm = j;
-                std::vector<double> A((size_t)mm * mm, 0.0), th, Qs;
-                for (int jj = 0; jj < mm; ++jj) for (int i = 0; i <= jj; ++i) {
-                    const double v = (jj >= k) ? hbuf[(size_t)jj * row + i] : T[(size_t)i * m + jj];
-                    A[(size_t)i * mm + jj] = v; A[(size_t)jj * mm + i] = v;
-                }
-                jacobi_eigh(mm, A, th, Qs);
-                const double r = std::fabs(std::sqrt(std::max(0.0, hbuf[(size_t)(mm - 1) * row + m + 1])) * Qs[(size_t)(mm - 1) * mm + 0]);
-                static const bool trace = getenv("DMRGX_EIGS_TRACE") != nullptr;      // developer aid: Ritz value and residual estimate per look
-                if (trace) fprintf(stderr, "[eigs] look at matvec %d (queued: %d): theta %.12f  |r| %.3e  (target %.3e)\n", n_matvec - 1, n_matvec, th[0], r, tol * std::fabs(th[0]));
-                if (r <= tol * std::max(std::fabs(th[0]), 1e-300)) { jend = j + 1; early = true; break; }      // (step j is queued: its column is part of the final Rayleigh-Ritz)
+                const Ritz look = ritz_of_leading(j, m, row, hbuf, kept);
+                if (eigs_trace()) fprintf(stderr, "[eigs] look at matvec %d (queued: %d): theta %.12f  |r| %.3e  (target %.3e)\n", n_matvec - 1, n_matvec, look.th[0], look.resid, tol * std::fabs(look.th[0]));
+                if (look.resid <= tol * std::max(std::fabs(look.th[0]), 1e-300)) { jend = j + 1; early = true; break; }      // (step j is queued: its column is part of the final Rayleigh-Ritz)
             }
         }
         look_mm[0] = look_mm[1] = 0;
         DMRGX_HIP(hipMemcpyAsync(hbuf.data(), dScal.p, (size_t)(m + 1) * row * sizeof(double), hipMemcpyDeviceToHost, st));
         DMRGX_HIP(hipStreamSynchronize(st));
         if (null_start()) return redo_from_random();
-        if (jend < m) {                                       // truncated cycle: Rayleigh-Ritz on the jend columns built so far
-            const int mm = jend;
-            if (mm < 1) break;
-            std::vector<double> A((size_t)mm * mm, 0.0), th, Qs;
-            for (int j = 0; j < mm; ++j) for (int i = 0; i <= j; ++i) {
-                const double v = (j >= k) ? hbuf[(size_t)j * row + i] : T[(size_t)i * m + j];
-                A[(size_t)i * mm + j] = v; A[(size_t)j * mm + i] = v;
-            }
-            jacobi_eigh(mm, A, th, Qs);
-            lambda = th[0];
-            resid = std::fabs(std::sqrt(std::max(0.0, hbuf[(size_t)(mm - 1) * row + m + 1])) * Qs[(size_t)(mm - 1) * mm + 0]);
-            Q.assign((size_t)m * m, 0.0);
-            for (int i = 0; i < mm; ++i) Q[(size_t)i * m + 0] = Qs[(size_t)i * mm + 0];
-            ++restarts;
-            if (early) converged = 1;
-            break;
-        }
-        // projected matrix: kept Ritz block is diagonal, new columns come from the recorded coefficients
-        for (int j = k; j < m; ++j)
-            for (int i = 0; i <= j; ++i) { T[(size_t)i * m + j] = hbuf[(size_t)j * row + i]; T[(size_t)j * m + i] = T[(size_t)i * m + j]; }
-        beta_m = std::sqrt(std::max(0.0, hbuf[(size_t)(m - 1) * row + m + 1]));
-        std::vector<double> A = T;
-        jacobi_eigh(m, A, theta, Q);
-        lambda = theta[0];
-        resid = std::fabs(beta_m * Q[(size_t)(m - 1) * m + 0]);
+        // Rayleigh-Ritz on the columns built: all m of a full cycle, the first jend of a truncated one (which ends the solve)
+        const int mm = jend;
+        if (mm < 1) break;
+        const Ritz ritz = ritz_of_leading(mm, m, row, hbuf, kept);
+        lambda = ritz.th[0];
+        resid = ritz.resid;
+        std::fill(y.begin(), y.end(), 0.0);
+        for (int i = 0; i < mm; ++i) y[i] = ritz.Q[(size_t)i * mm + 0];
         ++restarts;
+        if (mm < m) { if (early) converged = 1; break; }
         if (resid <= tol * std::max(std::fabs(lambda), 1e-300) || m == N) { converged = 1; break; }
         if (restarts >= max_it || capped) break;
         // thick restart: keep the kk lowest Ritz vectors + the residual direction V[m]
         const int kk = std::max(1, std::min(m / 2, m - 1));
         Qdev.assign((size_t)m * kk, 0.0);
-        for (int i = 0; i < m; ++i) for (int j = 0; j < kk; ++j) Qdev[(size_t)i * kk + j] = Q[(size_t)i * m + j];
+        for (int i = 0; i < m; ++i) for (int j = 0; j < kk; ++j) Qdev[(size_t)i * kk + j] = ritz.Q[(size_t)i * m + j];
         DMRGX_HIP(h2d_async(dQ.p, Qdev.data(), Qdev.size() * sizeof(double), st));
         hipLaunchKernelGGL(basis_rotate_kernel, dim3(1024, (kk + DOT_CHUNK - 1) / DOT_CHUNK), dim3(DOT_THREADS), 0, st,
                            V, n, m, dQ.as<double>(), kk, kk, dTmp.as<double>(), n, n);
@@ -909,33 +983,18 @@ extern "C" dmrgx_status dmrgx_eigs_lowest(dmrgx_kron_plan* plan, const dmrgx_eig
         DMRGX_HIP(hipMemcpyAsync(V, dTmp.p, (size_t)kk * n * sizeof(double), hipMemcpyDeviceToDevice, st));
         DMRGX_HIP(hipMemcpyAsync(vec(kk), vec(m), (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
         DMRGX_HIP(hipStreamSynchronize(st));                  // Qdev is reused by the next cycle
-        std::fill(T.begin(), T.end(), 0.0);
-        for (int i = 0; i < kk; ++i) T[(size_t)i * m + i] = theta[i];
+        kept.assign(ritz.th.begin(), ritz.th.begin() + kk);   // the projected matrix of the kept block is diagonal
         k = kk;
     }
-    // ---- eigenvector: psi = V_m Q[:,0], renormalised -------------------------------------------------------
-    Qdev.assign((size_t)m, 0.0);
-    for (int i = 0; i < m; ++i) Qdev[i] = Q[(size_t)i * m + 0];
-    DMRGX_HIP(h2d_async(dQ.p, Qdev.data(), Qdev.size() * sizeof(double), st));
+    // ---- eigenvector: psi = V_m y, renormalised ------------------------------------------------------------
+    DMRGX_HIP(h2d_async(dQ.p, y.data(), y.size() * sizeof(double), st));
     hipLaunchKernelGGL(basis_rotate_kernel, dim3(1024, 1), dim3(DOT_THREADS), 0, st, V, n, m, dQ.as<double>(), 1, 1, w, n, n);
     DMRGX_HIP(hipGetLastError());
-    DMRGX_CHK(multi_dot(0));
-    DMRGX_HIP(hipMemcpyAsync(nrm, c1, sizeof(double), hipMemcpyDeviceToDevice, st));
-    if (!dist) DMRGX_CHK(normalise_into(psi_full));
-    else {
-        DMRGX_CHK(normalise_into(psi_full + I.local_offset));
-        DMRGX_CHK(gather_full(psi_full));
-    }
-    DMRGX_HIP(hipStreamSynchronize(st));
-    *e0 = lambda;
-    if (stats) {
-        stats->n_matvec = n_matvec; stats->n_restart = restarts; stats->converged = converged; stats->start_rejected = 0; stats->residual = resid;
-        stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-    }
+    DMRGX_CHK(finish_vector(w));
+    finish(lambda, resid, n_matvec, restarts, converged);
     if (!converged) DMRGX_FAIL(DMRGX_ERR_NOTCONV, "eigs_lowest: not converged after %d restarts (residual %.3e)", restarts, resid);
     return DMRGX_OK;
 }
-
 
 // ---- generalized Davidson (opts->method == 1) ---------------------------------------------------------------------------------
 // Basis V (orthonormal), W = H V, projected matrix G = V^T W.  Per iteration: one MatMult (the new basis vector), the new column of G
@@ -947,18 +1006,12 @@ extern "C" dmrgx_status dmrgx_eigs_lowest(dmrgx_kron_plan* plan, const dmrgx_eig
 // the previous iteration's Ritz vector -- the restart that keeps the convergence of the unrestarted method (Stathopoulos & Saad;
 // measured on CPU-side model problems, tests/experiments/gd_restart_basis.py: 12.9 MatMults per solve for every maximal basis from 24 down to 4).
 // Distributed like the Lanczos path: vectors are stripe segments, every dot is all-reduced, x is all-gathered before a MatMult.
-static dmrgx_status eigs_davidson(dmrgx_kron_plan* plan, const dmrgx_eigs_opts* opts, double* e0, double* psi_full, dmrgx_eigs_stats* stats, hipStream_t st)
+dmrgx_status EigsRun::eigs_davidson()
 {
-    dmrgx_kron_info I;
-    DMRGX_CHK(dmrgx_kron_plan_info(plan, &I));
-    const bool dist = I.vec_len != I.n_states;
-    const bool hooks = opts->allgather && opts->allreduce_sum;
-    if (dist && !hooks && !opts->comm) DMRGX_FAIL(DMRGX_ERR_ARG, "eigs_lowest: a striped plan needs a communicator (opts->comm) or the allgather/allreduce hooks");
-    const int64_t n = I.local_len, N = I.n_states;
     // Every work vector is padded to an EVEN length ld with a zero in the pad: basis rows are then 16-byte aligned whatever n is, and the
     // vector kernels run their two-doubles-per-lane form on odd n as well (half of all steps; multi_dot 42 -> 30 us at m = 2048).  The pad
     // stays zero by construction: every kernel writes it as a combination of zeros, the MatMult never touches it.
-    const int64_t ld = (n + 1) & ~(int64_t)1;
+    ld = (n + 1) & ~(int64_t)1;
     // search space: opts->ncv vectors at most (default GD_NV = 8: SLEPc's meaning of ncv for its gd solver), restarted to gd_minv Ritz
     // vectors + the previous Ritz vector.  A basis that could not grow after a restart (fewer than minv + 2 vectors) is widened.
     int m = opts->ncv > 0 ? opts->ncv : GD_NV;
@@ -970,37 +1023,32 @@ static dmrgx_status eigs_davidson(dmrgx_kron_plan* plan, const dmrgx_eigs_opts* 
     const int max_mv = opts->max_it > 0 ? opts->max_it * 16 : std::max<int>(1600, (int)(2 * N));
     const int hand_over = 96;                  // MatMults after which a start vector that was not close after all goes to the Lanczos path
     const double tol = opts->tol > 0 ? opts->tol : 1e-8;
-    const auto t_begin = std::chrono::steady_clock::now();
     const int nblk = DOT_BLOCKS;
     const bool fused = m <= GD_NV;             // the correction kernel also takes the first Gram-Schmidt dots
 
-    static const bool trace_setup = getenv("DMRGX_EIGS_TRACE") != nullptr;      // developer aid: wall time of the set-up stages (synchronising)
-    auto mark = [&](const char* what) {
-        if (!trace_setup) return;
+    auto mark = [&](const char* what) {        // wall time of the set-up stages
+        if (!eigs_trace()) return;
         (void)hipStreamSynchronize(st);
-        fprintf(stderr, "[eigs gd] setup %-12s t = %.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+        fprintf(stderr, "[eigs gd] setup %-12s t = %.3f ms\n", what, 1e3 * seconds());
     };
     mark("enter");
-    DevBuf dV, dW, dT, dX, dD, dTmp, dPartial, dScal, dState;
     DMRGX_CHK(dV.alloc_f64((size_t)(m + 1) * ld, st));
     DMRGX_CHK(dW.alloc_f64((size_t)(m + 1) * ld, st));
     DMRGX_CHK(dT.alloc_f64((size_t)ld, st));
     DMRGX_CHK(dD.alloc_f64((size_t)ld, st));
     DMRGX_CHK(dTmp.alloc_f64((size_t)kk * ld, st));
-    if (dist) DMRGX_CHK(dX.alloc_f64((size_t)I.vec_len, st));
-    DMRGX_CHK(dPartial.alloc_f64((size_t)(MAX_NCV + DOT_CHUNK + 2) * DOT_BLOCKS, st));
+    DMRGX_CHK(alloc_shared());
     DMRGX_CHK(dScal.alloc_f64((size_t)(3 * (MAX_NCV + 2)), st));
     DMRGX_CHK(dState.alloc(sizeof(GdState)));
-    double* V = dV.as<double>();
-    double* W = dW.as<double>();
-    double* t = dT.as<double>();
-    double* c1 = dScal.as<double>();
-    double* c2 = c1 + (MAX_NCV + 2);
-    double* nrm = c2 + (MAX_NCV + 2);
-    GdState* S = dState.as<GdState>();
-    const double* const S_y = (const double*)((const char*)dState.p + offsetof(GdState, y));
-    const double* const S_e0 = (const double*)((const char*)dState.p + offsetof(GdState, e0));
-    const double* const S_Q = (const double*)((const char*)dState.p + offsetof(GdState, Q));
+    layout(dScal.as<double>());
+    double* const W = dW.as<double>();
+    double* const t = dT.as<double>();
+    double* const partial = dPartial.as<double>();
+    const double* const D = dD.as<double>();
+    const GdState* const S = dState.as<GdState>();
+    const double* const S_y = (const double*)((const char*)S + offsetof(GdState, y));
+    const double* const S_e0 = (const double*)((const char*)S + offsetof(GdState, e0));
+    const double* const S_Q = (const double*)((const char*)S + offsetof(GdState, Q));
     auto vec = [&](int j) { return V + (size_t)j * ld; };
     auto wvec = [&](int j) { return W + (size_t)j * ld; };
     // (every basis vector is written whole before it is read; only the padding of a striped segment relies on the initial zeros)
@@ -1015,105 +1063,58 @@ static dmrgx_status eigs_davidson(dmrgx_kron_plan* plan, const dmrgx_eigs_opts* 
         DMRGX_HIP(hipGetLastError());
     }
     mark("diagonal");
-    auto allreduce = [&](double* buf, int64_t count) -> dmrgx_status {
-        if (!dist) return DMRGX_OK;
-        return hooks ? opts->allreduce_sum(opts->user, buf, count, st) : dmrgx_comm_allreduce_sum(opts->comm, buf, count, st);
-    };
-    auto gather_full = [&](double* full) -> dmrgx_status {
-        return hooks ? opts->allgather(opts->user, full, I.seg_stride, st) : dmrgx_comm_allgather(opts->comm, full, I.seg_stride, st);
-    };
-    // per-block partial sums of V[0..nv)^T x and x.x (dPartial); reduce == true: also out[0..nv] = the sums (all-reduced)
-    auto multi_dot = [&](int nv, const double* x, double* out, bool reduce) -> dmrgx_status {
-        const int chunks = (nv + 1 + DOT_CHUNK - 1) / DOT_CHUNK;
-        hipLaunchKernelGGL(multi_dot_kernel<true>, dim3(nblk, chunks), dim3(DOT_THREADS), 0, st, V, ld, nv, x, ld, dPartial.as<double>());
-        DMRGX_HIP(hipGetLastError());
-        if (!reduce) return DMRGX_OK;
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3(nv + 1), dim3(DOT_THREADS), 0, st, dPartial.as<double>(), out, nv + 1, nblk);
-        DMRGX_HIP(hipGetLastError());
-        return allreduce(out, nv + 1);
-    };
     // second half of CGS2 on x, whose first-pass dots c1 = V^T x are reduced: dst = (x - V V^T x) / || . ||; x is overwritten
     auto orthonormalise_tail = [&](int nv, double* x, double* dst) -> dmrgx_status {
-        if (nv <= GD_NV) hipLaunchKernelGGL(axpy_dot_kernel<GD_NV>, dim3(nblk), dim3(DOT_THREADS), 0, st, V, ld, nv, c1, x, ld, dPartial.as<double>(), (double*)nullptr);
-        else hipLaunchKernelGGL(axpy_dot_kernel<FUSE_NV>, dim3(nblk), dim3(DOT_THREADS), 0, st, V, ld, nv, c1, x, ld, dPartial.as<double>(), (double*)nullptr);
-        DMRGX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3(nv + 1), dim3(DOT_THREADS), 0, st, dPartial.as<double>(), c2, nv + 1, nblk);
-        DMRGX_HIP(hipGetLastError());
-        DMRGX_CHK(allreduce(c2, nv + 1));
-        hipLaunchKernelGGL(axpy_normalise_kernel<true>, dim3(nblk), dim3(DOT_THREADS), 0, st, V, ld, nv, c2, x, dst, ld, (double*)nullptr, (double*)nullptr);
-        DMRGX_HIP(hipGetLastError());
-        return DMRGX_OK;
-    };
-    CommTimer ctimer(st);       // (distributed only) HIP events round the all-gather and the apply of every MatMult: dmrgx_eigs_comm_timing
-    auto matvec = [&](const double* v_local, double* y_local) -> dmrgx_status {
-        if (!dist) return dmrgx_kron_apply(plan, v_local, y_local, st);
-        DMRGX_HIP(hipMemcpyAsync(dX.as<double>() + I.local_offset, v_local, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        ctimer.mark();
-        DMRGX_CHK(gather_full(dX.as<double>()));
-        ctimer.mark();
-        const dmrgx_status rc = dmrgx_kron_apply(plan, dX.as<double>(), y_local, st);
-        ctimer.mark();
-        return rc;
+        DMRGX_CHK(nv <= GD_NV ? project_and_dot<GD_NV>(nv, x, nullptr) : project_and_dot<FUSE_NV>(nv, x, nullptr));
+        return project_and_normalise(nv, x, dst, nullptr, nullptr);
     };
 
     // ---- start vector ----------------------------------------------------------------------------------------------------
-    if (opts->use_initial) DMRGX_HIP(hipMemcpyAsync(t, psi_full + I.local_offset, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    else if (!dist) { hipLaunchKernelGGL(random_fill_kernel, dim3(1024), dim3(256), 0, st, t, n, opts->seed, (int64_t)0); DMRGX_HIP(hipGetLastError()); }
-    else {
-        DevBuf ref;
-        DMRGX_CHK(ref.alloc((size_t)N * sizeof(double)));
-        hipLaunchKernelGGL(random_fill_kernel, dim3(1024), dim3(256), 0, st, ref.as<double>(), N, opts->seed, (int64_t)0);
-        DMRGX_HIP(hipGetLastError());
-        DMRGX_CHK(dmrgx_kron_vec_to_striped(plan, ref.as<double>(), dX.as<double>(), st));
-        DMRGX_HIP(hipMemcpyAsync(t, dX.as<double>() + I.local_offset, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        DMRGX_HIP(hipStreamSynchronize(st));
-    }
+    DMRGX_CHK(start_vector(t));
     DMRGX_CHK(multi_dot(0, t, c1, true));
     DMRGX_CHK(orthonormalise_tail(0, t, vec(0)));
-    double* const pin = opts->use_initial ? pinned_scalars() : nullptr;
-    if (pin) { pin[2] = 0.0; DMRGX_HIP(hipMemcpyAsync(pin + 2, c2, sizeof(double), hipMemcpyDeviceToHost, st)); }      // c2[0] = |start vector|^2; read at the first look
+    DMRGX_CHK(fetch_start_norm2(c2));                        // c2[0] = |start vector|^2; read at the first look
     mark("start vector");
 
     // the looks come back through pinned memory behind an event, so that the orthogonalisation of the next direction is already queued
-    // when the host waits for them; one buffer + event per host thread (callers on different threads / devices do not share them)
-    static thread_local double* h_look = nullptr;
-    static thread_local hipEvent_t ev_look = nullptr;
-    if (!h_look) { DMRGX_HIP(hipHostMalloc((void**)&h_look, 64, hipHostMallocDefault)); DMRGX_HIP(hipEventCreateWithFlags(&ev_look, hipEventDisableTiming)); }
-    DevBuf dLook;
+    // when the host waits for them
+    double* const h_look = host->gd_look();
+    const hipEvent_t ev_look = host->ev[2];
     DMRGX_CHK(dLook.alloc(4 * sizeof(double)));
+    double* const look = dLook.as<double>();
     int j = 0, n_matvec = 0, restarts = 0, converged = 0;
     double lambda = 0.0, resid = 0.0;
     const double floor_rel = 1e-3;
     bool warm = false;                          // the device state holds the Ritz basis of the previous iteration in the current basis
     bool rotated = false;                       // a restart has been queued since the last Ritz solve: the Ritz vector is the first basis vector
     int mm = 0;
+    dmrgx_eigs_opts o2 = *opts;                 // what a solve that is given up goes on with
+    o2.method = 0;
     while (true) {
         DMRGX_CHK(matvec(vec(j), wvec(j)));
         ++n_matvec;
         mm = j + 1;
         const bool restart = mm == m;
-        DMRGX_CHK(multi_dot(mm, wvec(j), c1, dist));                               // column j of G = V^T w_j (reduced by the Ritz kernel itself unless an all-reduce must come first)
-        hipLaunchKernelGGL(gd_ritz_kernel, dim3(1), dim3(RITZ_THREADS), 0, st, S, dist ? (const double*)c1 : (const double*)dPartial.as<double>(), dist ? 0 : 1, nblk, mm, warm ? 1 : 0, restart ? 1 : 0, keep);
+        DMRGX_CHK(multi_dot(mm, wvec(j), c1, dist));                             // column j of G = V^T w_j (reduced by the Ritz kernel itself unless an all-reduce must come first)
+        hipLaunchKernelGGL(gd_ritz_kernel, dim3(1), dim3(RITZ_THREADS), 0, st, dState.as<GdState>(), dist ? (const double*)c1 : (const double*)partial, dist ? 0 : 1, nblk, mm, warm ? 1 : 0, restart ? 1 : 0, keep);
         DMRGX_HIP(hipGetLastError());
         warm = !restart;
         rotated = false;
         // correction vector (+ first Gram-Schmidt dots) and |r|^2
         const int look_idx = fused ? mm + 1 : 0;
         double* red_out = fused ? c1 : nrm;
-        if (fused) hipLaunchKernelGGL((ritz_precond_kernel<GD_NV, true>), dim3(nblk), dim3(DOT_THREADS), 0, st, (const double*)V, (const double*)W, ld, mm, (const GdState*)S,
-                                      (const double*)dD.as<double>(), floor_rel, t, ld, dPartial.as<double>());
-        else hipLaunchKernelGGL((ritz_precond_kernel<FUSE_NV, false>), dim3(nblk), dim3(DOT_THREADS), 0, st, (const double*)V, (const double*)W, ld, mm, (const GdState*)S,
-                                (const double*)dD.as<double>(), floor_rel, t, ld, dPartial.as<double>());
+        if (fused) hipLaunchKernelGGL((ritz_precond_kernel<GD_NV, true>), dim3(nblk), dim3(DOT_THREADS), 0, st, (const double*)V, (const double*)W, ld, mm, S, D, floor_rel, t, ld, partial);
+        else hipLaunchKernelGGL((ritz_precond_kernel<FUSE_NV, false>), dim3(nblk), dim3(DOT_THREADS), 0, st, (const double*)V, (const double*)W, ld, mm, S, D, floor_rel, t, ld, partial);
         DMRGX_HIP(hipGetLastError());
         const int nred = fused ? mm + 2 : 1;
-        hipLaunchKernelGGL(gd_reduce_look_kernel, dim3(nred), dim3(DOT_THREADS), 0, st, (const double*)dPartial.as<double>(), red_out, nred, nblk, look_idx, 0, (const GdState*)S, dLook.as<double>());
+        hipLaunchKernelGGL(gd_reduce_look_kernel, dim3(nred), dim3(DOT_THREADS), 0, st, (const double*)partial, red_out, nred, nblk, look_idx, 0, S, look);
         DMRGX_HIP(hipGetLastError());
         if (dist) {
             DMRGX_CHK(allreduce(red_out, nred));
-            hipLaunchKernelGGL(gd_reduce_look_kernel, dim3(nred), dim3(DOT_THREADS), 0, st, (const double*)dPartial.as<double>(), red_out, nred, nblk, look_idx, 1, (const GdState*)S, dLook.as<double>());
+            hipLaunchKernelGGL(gd_reduce_look_kernel, dim3(nred), dim3(DOT_THREADS), 0, st, (const double*)partial, red_out, nred, nblk, look_idx, 1, S, look);
             DMRGX_HIP(hipGetLastError());
         }
-        DMRGX_HIP(hipMemcpyAsync(h_look, dLook.p, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        DMRGX_HIP(hipMemcpyAsync(h_look, look, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
         DMRGX_HIP(hipEventRecord(ev_look, st));
         // queued behind the look, before the host reads it: the restart (when the basis is full) and the next direction
         const bool may_continue = mm < N && n_matvec < max_mv && n_matvec < hand_over;
@@ -1138,63 +1139,49 @@ static dmrgx_status eigs_davidson(dmrgx_kron_plan* plan, const dmrgx_eigs_opts* 
         DMRGX_HIP(hipEventSynchronize(ev_look));
         resid = std::sqrt(std::max(h_look[0], 0.0));
         lambda = h_look[1];
-        if (n_matvec == 1 && (!(h_look[2] > 0.0) || start_too_light(opts, pin))) {      // |H v_0|^2 is not positive: the start vector had zero (or NaN) norm -- see the Lanczos path; or it is lighter than the caller accepts
+        if (n_matvec == 1 && (!(h_look[2] > 0.0) || start_too_light())) {      // |H v_0|^2 is not positive: the start vector had zero (or NaN) norm -- see the Lanczos path; or it is lighter than the caller accepts
             DMRGX_HIP(hipStreamSynchronize(st));
-            dV.release(); dW.release(); dTmp.release(); dT.release(); dD.release();      // (the repeated solve allocates its own work space)
-            dmrgx_eigs_opts o2 = *opts;
-            o2.method = 0; o2.use_initial = 0;
-            dmrgx_eigs_stats s2;
-            memset(&s2, 0, sizeof(s2));
-            const dmrgx_status rc = dmrgx_eigs_lowest(plan, &o2, e0, psi_full, &s2, (void*)st);
-            if (stats) { *stats = s2; stats->n_matvec += n_matvec; stats->start_rejected = 1;
-                         stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); }
-            return rc;
+            o2.use_initial = 0;
+            return solve_again(o2, n_matvec, 0, true);
         }
-        static const bool trace = getenv("DMRGX_EIGS_TRACE") != nullptr;
-        if (trace) fprintf(stderr, "[eigs gd] matvec %d: basis %d theta %.12f  |r| %.3e  (target %.3e)  t = %.3f ms\n", n_matvec, mm, lambda, resid, tol * std::fabs(lambda),
-                           std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+        if (eigs_trace()) fprintf(stderr, "[eigs gd] matvec %d: basis %d theta %.12f  |r| %.3e  (target %.3e)  t = %.3f ms\n", n_matvec, mm, lambda, resid, tol * std::fabs(lambda), 1e3 * seconds());
         if (resid <= tol * std::max(std::fabs(lambda), 1e-300) || mm == N) { converged = 1; break; }
         if (n_matvec >= max_mv) break;
         if (n_matvec >= hand_over) {
-            // a start vector that was not close after all (the preconditioned iteration then trails Lanczos, see above): hand the
-            // current Ritz vector to the Lanczos path instead of iterating on
-            hipLaunchKernelGGL(basis_rotate_kernel, dim3(1024, 1), dim3(DOT_THREADS), 0, st, (const double*)V, ld, mm, S_y, 1, 1,
-                               dist ? psi_full + I.local_offset : psi_full, n, n);
+            // a start vector that was not close after all (the preconditioned iteration then trails Lanczos, see dmrgx_eigs_lowest): hand
+            // the current Ritz vector to the Lanczos path instead of iterating on; whatever its norm, it is the start vector
+            hipLaunchKernelGGL(basis_rotate_kernel, dim3(1024, 1), dim3(DOT_THREADS), 0, st, (const double*)V, ld, mm, S_y, 1, 1, psi_local(), n, n);
             DMRGX_HIP(hipGetLastError());
             DMRGX_HIP(hipStreamSynchronize(st));
-            dV.release(); dW.release(); dTmp.release(); dT.release(); dD.release();
-            dmrgx_eigs_opts o2 = *opts;
-            o2.method = 0; o2.use_initial = 1; o2.min_initial_norm2 = 0.0;
-            dmrgx_eigs_stats s2;
-            memset(&s2, 0, sizeof(s2));
-            const dmrgx_status rc = dmrgx_eigs_lowest(plan, &o2, e0, psi_full, &s2, (void*)st);
-            if (stats) { *stats = s2; stats->n_matvec += n_matvec; stats->n_restart += restarts;
-                         stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); }
-            return rc;
+            o2.use_initial = 1; o2.min_initial_norm2 = 0.0;
+            return solve_again(o2, n_matvec, restarts, false);
         }
         ++j;
     }
-    // ---- eigenvector: psi = V y, renormalised --------------------------------------------------------------------------------
-    {
-        // the Ritz vector: V y in the basis the Ritz problem was solved in -- or, when a restart has been queued since, simply the
-        // first vector of the new basis
-        const int nb = rotated ? 1 : mm;
-        hipLaunchKernelGGL(basis_rotate_kernel, dim3(1024, 1), dim3(DOT_THREADS), 0, st, (const double*)V, ld, nb, rotated ? S_e0 : S_y, 1, 1, t, ld, ld);
-        DMRGX_HIP(hipGetLastError());
-        DMRGX_CHK(multi_dot(0, t, c1, true));
-        DMRGX_HIP(hipMemcpyAsync(nrm, c1, sizeof(double), hipMemcpyDeviceToDevice, st));
-        double* dst = dist ? psi_full + I.local_offset : psi_full;
-        hipLaunchKernelGGL(scale_copy_kernel, dim3(1024), dim3(256), 0, st, (const double*)t, dst, n, (const double*)nrm);
-        DMRGX_HIP(hipGetLastError());
-        if (dist) DMRGX_CHK(gather_full(psi_full));
-        DMRGX_HIP(hipStreamSynchronize(st));
-    }
-    *e0 = lambda;
-    if (stats) {
-        stats->n_matvec = n_matvec; stats->n_restart = restarts; stats->converged = converged; stats->start_rejected = 0; stats->residual = resid;
-        stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-    }
-    if (getenv("DMRGX_EIGS_TRACE")) fprintf(stderr, "[eigs gd] done: %d MatMults, %.3f ms\n", n_matvec, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+    // ---- eigenvector: psi = V y, renormalised: V y in the basis the Ritz problem was solved in -- or, when a restart has been queued
+    // since, simply the first vector of the new basis
+    hipLaunchKernelGGL(basis_rotate_kernel, dim3(1024, 1), dim3(DOT_THREADS), 0, st, (const double*)V, ld, rotated ? 1 : mm, rotated ? S_e0 : S_y, 1, 1, t, ld, ld);
+    DMRGX_HIP(hipGetLastError());
+    DMRGX_CHK(finish_vector(t));
+    finish(lambda, resid, n_matvec, restarts, converged);
+    if (eigs_trace()) fprintf(stderr, "[eigs gd] done: %d MatMults, %.3f ms\n", n_matvec, 1e3 * seconds());
     if (!converged) DMRGX_FAIL(DMRGX_ERR_NOTCONV, "eigs_lowest (gd): not converged after %d MatMults (residual %.3e)", n_matvec, resid);
     return DMRGX_OK;
+}
+
+}  // namespace
+
+extern "C" dmrgx_status dmrgx_eigs_lowest(dmrgx_kron_plan* plan, const dmrgx_eigs_opts* opts, double* e0,
+                                          double* psi_full, dmrgx_eigs_stats* stats, void* stream)
+{
+    if (!plan || !opts || !e0 || !psi_full) DMRGX_FAIL(DMRGX_ERR_ARG, "eigs_lowest: null argument");
+    EigsRun R(plan, opts, e0, psi_full, stats, (hipStream_t)stream);
+    DMRGX_CHK(R.init());
+    // the diagonally preconditioned iteration pays off from a start vector close to the answer (the engine's transformed ground
+    // state: 16-19 MatMults where Lanczos needs 21-27); from a random vector it is twice as slow as Lanczos (measured 140 vs 72),
+    // so without a supplied start vector the request falls through to the Lanczos path
+    // (a search space of fewer than two vectors -- a one-state superblock sector, ncv = 1 -- has nothing to precondition: Lanczos path)
+    const bool gd_space = std::min<int64_t>(opts->ncv > 0 ? opts->ncv : 16, R.N) >= 2;
+    if (opts->method == 1 && opts->use_initial && opts->max_matvec <= 0 && gd_space) return R.eigs_davidson();
+    return R.eigs_lanczos();
 }

@@ -1,7 +1,7 @@
 """Child process of tests/test_gpu_poison.py: runs fixed-input kernels and writes their outputs to an .npz file, so that runs in
 separate processes -- clean or with DMRGX_POOL_POISON=1 -- can be compared bit for bit.
 
-    python tests/bitwise_worker.py OUT.npz apply,solvers,striped,krylov
+    python tests/bitwise_worker.py OUT.npz apply,solvers,solver_paths,striped,krylov
 """
 import hashlib
 import os
@@ -58,6 +58,55 @@ def solvers(out):
             out["rdm_w_%d_%d" % (k, side)] = rdm.eigenvalues(side, k)
             out["rdm_u_%d_%d" % (k, side)] = rdm.eigenvectors(side, k, rdm.size(side, k)).cpu().numpy()
     rdm.destroy()
+
+
+def solver_paths(out):
+    """The branches of dmrgx_eigs_lowest that `solvers` does not reach, on helpers.krylov_superblock at 845 states (odd): rejected and
+    accepted start vectors on both methods, truncated cycles, an exhausted solve, the unfused Davidson iteration and its hand-over to
+    the Lanczos path.  Per case e0, psi and every field of the stats but the seconds; each case asserts that it took its branch."""
+    import ctypes as C
+    from dmrgx_amd import _capi
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from helpers import krylov_superblock
+    fields = [k for k, _ in _capi.EigsStats._fields_ if k != "seconds"]
+
+    def keep(tag, e0, psi, stats):
+        out["paths_%s_e0" % tag], out["paths_%s_psi" % tag] = np.array(e0), psi.cpu().numpy()
+        for k in fields:
+            out["paths_%s_%s" % (tag, k)] = np.array(getattr(stats, k))
+        return stats
+
+    n = 845
+    plan = sbm.KronPlan(krylov_superblock(wl, n))
+    e0, gs, stats = plan.eigs_lowest(tol=1e-12, seed=9)
+    assert keep("plain", e0, gs, stats).converged == 1
+    rng = np.random.default_rng(845)
+    far = torch.from_numpy(rng.standard_normal(n)).cuda()
+    near = gs + 1e-3 * torch.from_numpy(rng.standard_normal(n)).cuda()
+    for method in (0, 1):
+        s = keep("zero_m%d" % method, *plan.eigs_lowest(tol=1e-10, seed=9, method=method, psi0=torch.zeros_like(gs)))
+        assert s.start_rejected == 1 and s.converged == 1, (method, s.start_rejected, s.converged)
+        s = keep("light_m%d" % method, *plan.eigs_lowest(tol=1e-10, seed=9, method=method, psi0=0.3 * gs, min_initial_norm2=0.25))
+        assert s.start_rejected == 1 and s.converged == 1, (method, s.start_rejected, s.converged)
+        s = keep("accepted_m%d" % method, *plan.eigs_lowest(tol=1e-10, seed=9, method=method, psi0=0.6 * gs, min_initial_norm2=0.25))
+        assert s.start_rejected == 0 and s.converged == 1, (method, s.start_rejected, s.converged)
+    s = keep("truncated", *plan.eigs_lowest(ncv=16, max_matvec=3, psi0=far))
+    assert s.n_matvec == 3 and s.n_restart == 1, (s.n_matvec, s.n_restart)
+    s = keep("restarts_truncated", *plan.eigs_lowest(ncv=4, max_matvec=11, psi0=far))
+    assert s.n_matvec == 11 and s.n_restart == 5, (s.n_matvec, s.n_restart)      # 4 + 2 + 2 + 2 MatMults in full cycles, then 1
+    # max_it exhausted, through the C ABI (the wrapper raises): the status and the best pair so far
+    opts, stats, e0 = _capi.EigsOpts(), _capi.EigsStats(), C.c_double(float("nan"))
+    opts.ncv, opts.max_it, opts.tol, opts.seed = 4, 2, 1e-14, 9
+    psi = torch.full((plan.info.vec_len,), float("nan"), dtype=torch.float64, device="cuda")
+    rc = _capi.lib().dmrgx_eigs_lowest(plan._handle, C.byref(opts), C.byref(e0), C.c_void_p(psi.data_ptr()), C.byref(stats), plan._stream_ptr(None))
+    assert rc == _capi.DMRGX_ERR_NOTCONV and keep("exhausted", e0.value, psi, stats).n_restart == 2 and stats.converged == 0
+    out["paths_exhausted_status"] = np.array(rc)
+    s = keep("gd_unfused", *plan.eigs_lowest(tol=1e-10, method=1, ncv=12, psi0=near))
+    assert s.converged == 1 and s.start_rejected == 0 and s.n_matvec <= 96, (s.converged, s.n_matvec)
+    # Davidson from a start vector that is not close: after 96 MatMults the Ritz vector goes to the Lanczos path (112 MatMults in all)
+    s = keep("gd_hand_over", *plan.eigs_lowest(tol=1e-10, method=1, psi0=far))
+    assert s.n_matvec > 96 and s.converged == 1 and s.start_rejected == 0, (s.n_matvec, s.converged)
+    plan.destroy()
 
 
 def striped(out):
@@ -135,6 +184,8 @@ if __name__ == "__main__":
         full_size_applies(res)
     if "solvers" in what:
         solvers(res)
+    if "solver_paths" in what:
+        solver_paths(res)
     if "striped" in what:
         striped(res)
     if "krylov" in what:

@@ -392,11 +392,14 @@ def test_parity_suite_on_poisoned_workspaces():
 def test_outputs_are_bit_identical_on_poisoned_workspaces(tmp_path):
     """Full-size dmrgx_kron_apply (cfg4real, cfg5) in a clean and in a poisoned process: bit-identical (the apply repeats bit for bit).
     Lanczos, generalized Davidson (odd and even sizes), the density-matrix spectra and eigenvectors and the gathered applies of two
-    multi-rank plans (W = 3 and W = 2, both branches of stripe_cut), and the device-resident Krylov calls with dmrgx_dot at 845 and 4097
-    states (the worker's krylov group): two clean processes agree bit for bit, and so must the poisoned one."""
+    multi-rank plans (W = 3 and W = 2, both branches of stripe_cut), the other branches of the eigensolver at 845 states (the worker's
+    solver_paths group: rejected and accepted start vectors, truncated cycles, an exhausted solve, unfused Davidson and its hand-over to
+    Lanczos), and the device-resident Krylov calls with dmrgx_dot at 845 and 4097 states (the worker's krylov group): two clean
+    processes agree bit for bit, and so must the poisoned one."""
     worker = os.path.join("tests", "bitwise_worker.py")
     res = {}
-    for tag, poison, what in (("clean", False, "apply,solvers,striped,krylov"), ("clean2", False, "solvers,striped,krylov"), ("poison", True, "apply,solvers,striped,krylov")):
+    groups = "solvers,solver_paths,striped,krylov"
+    for tag, poison, what in (("clean", False, "apply," + groups), ("clean2", False, groups), ("poison", True, "apply," + groups)):
         path = str(tmp_path / (tag + ".npz"))
         p = _child([worker, path, what], poison, 300)
         assert p.returncode == 0 and "bitwise worker ok" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
