@@ -344,13 +344,24 @@ def lanczos_basis_invariants(plan, H, v0, K, V=None, ref=None):
 # ---- density-matrix eigensolver: planted tridiagonals, clusters, edges (tests/test_rdm_inputs.py, tests/test_gpu_rdm_spectra.py) ----
 # The constants of csrc/symeig.hip / symeig.h the inputs and the order lists were built around; test_rdm_inputs.py parses the sources and
 # fails when one of them is retuned.
-RDM_CONSTANTS = {"DMRGX_DC_LEAF": 16, "DC_FUSE_NL": 384, "DMRGX_WY_NB": 64, "TRID_MAXM": 32, "TRID_PF": 8, "SYMEIG_MAX_N": 3072}
+RDM_CONSTANTS = {"DMRGX_DC_LEAF": 16, "DC_FUSE_NL": 384, "DMRGX_WY_NB": 64, "TRID_MAXM": 32, "TRID_PF": 8, "SYMEIG_MAX_N": 3072,
+                 # the block-Jacobi solver of csrc/rdm.hip and its QR preconditioner (csrc/hqr.hip): the Jacobi block (matrices are padded to
+                 # two of them), the rows up to which a QR panel lives in registers at 4 / 8 / 16 rows per thread (above HR_MAX_ROWS:
+                 # hqr_panel_kernel), the panel width and the column strip of the trailing update
+                 "DMRGX_JB": 16, "HQR_REGS_ROWS_4": 256, "HQR_REGS_ROWS_8": 512, "HR_MAX_ROWS": 1024, "HQR_PANEL": 32, "TM_COLS": 32}
 RDM_LEAF = RDM_CONSTANTS["DMRGX_DC_LEAF"]
 # orders above 40 at the edges of the solver: the tree's halving (63 .. 66, 127 .. 131, 511 .. 514, 1024, 1025), the fused / split Loewner
 # kernels (a top merge of DC_FUSE_NL = 384 +- 1; 768 and 769: level-1 merges of 384 and 385), the last partial WY block (n - 2 = 64 q + r with
 # r = 0, 1, 63) and the 512-column prefetch chunk of the launch-per-column kernel (TRID_PF chunks of 64)
 RDM_EDGE_ORDERS = [63, 64, 65, 66, 127, 128, 129, 130, 131, 383, 384, 385, 511, 512, 513, 514, 768, 769, 1024, 1025]
 RDM_EDGE_CALLS = [[63, 64, 65, 66, 127, 128, 129, 130, 131, 383, 384, 385], [511, 512, 513, 514], [768, 769], [1024, 1025]]
+# the orders at which the QR preconditioner of the block-Jacobi solver changes its panel body (the rows left in the first panel are the
+# order itself): registers with 4 / 8 rows per thread at 256, 8 / 16 at 512, registers / hqr_panel_kernel at HR_MAX_ROWS = 1024.  An order
+# that is no multiple of 32 ends in a panel narrower than 32 and a partial strip of the trailing update; 1025 walks through all four bodies.
+RDM_HQR_EDGE_CALLS = [[255, 256, 257, 258], [511, 512, 513, 514], [1024, 1025]]
+# the automatic switch: the smallest order above SYMEIG_MAX_N, and next to it an order between HR_MAX_ROWS and that, so that both panel
+# kernels of hqr_batched are launched for the same rows
+RDM_SWITCH_SHAPES = [(3073, 24), (1100, 60)]
 
 
 def rdm_tree_bounds(n, leaf=RDM_LEAF):
@@ -448,19 +459,39 @@ def _rdm_named(name):
         return ((_orth(rng, 300) * s) @ _orth(rng, 300).T).ravel()
     if name == "gaussian_100x60":                        # the control: what almost every other RDM test uses
         return rng.standard_normal(100 * 60)
+    if name == "zero_90x70":                             # a block of the state that is exactly zero: rho = 0, every orthonormal basis is right
+        return np.zeros(90 * 70)
+    if name == "rank_one_90x70":
+        return np.outer(rng.standard_normal(90), rng.standard_normal(70)).ravel()
+    if name == "orth_48":                                # rho = 1 / 48 on both sides, up to rounding
+        return (_orth(rng, 48) / np.sqrt(48.0)).ravel()
+    if name in ("gaussian_40x33", "gaussian_1100x60"):
+        rows, cols = (int(v) for v in name[len("gaussian_"):].split("x"))
+        return rng.standard_normal(rows * cols)
+    if name == "planted_3073x24":                        # Psi = U diag(s) V^T: rho_L has the eigenvalues s^2 = exp(-1.4 i) and 3049 zeros
+        U = np.linalg.qr(rng.standard_normal((3073, 24)))[0]
+        return ((U * RDM_PLANTED_S) @ _orth(rng, 24).T).ravel()
     raise KeyError(name)
 
 
 RDM_TRIDIAGONALS = ["k1_20", "k1_40", "k2_20", "toeplitz121_100", "zero_coupling_50", "diagonal_100", "glued_6_1e-8", "glued_6_1e-14", "glued_12_1e-8"]
 RDM_NAMED = RDM_TRIDIAGONALS + ["blockdiag_64", "clusters_200", "graded_pairs_300"]
+# one state whose KronBlocks are exactly zero, of rank one, orthogonal / sqrt(n) and Gaussian (so that the call is not trivial)
+RDM_SPECIAL = ["zero_90x70", "rank_one_90x70", "orth_48", "gaussian_40x33"]
+# the call that switches to the block-Jacobi solver by itself (RDM_SWITCH_SHAPES); the singular values planted in its first block
+RDM_SWITCH = ["planted_3073x24", "gaussian_1100x60"]
+RDM_PLANTED_S = np.exp(-0.7 * np.arange(24.0))
+RDM_PLANTED_S.setflags(write=False)
 _RDM_INPUTS, _RDM_STATS = {}, {}
 
 
 def rdm_input(name):
     """(rows, columns, Psi as a read-only matrix) of a named input; built once per process."""
     if name not in _RDM_INPUTS:
+        import re
         psi = np.ascontiguousarray(_rdm_named(name), dtype=np.float64)
-        rows = 100 if name == "gaussian_100x60" else int(round(np.sqrt(psi.size)))
+        shape = re.search(r"_(\d+)x(\d+)$", name)
+        rows = int(shape.group(1)) if shape else int(round(np.sqrt(psi.size)))
         Psi = psi.reshape(rows, -1)
         Psi.setflags(write=False)
         _RDM_INPUTS[name] = (rows, Psi.shape[1], Psi)
@@ -504,14 +535,53 @@ def rdm_bounds(rho, w_ref):
     return 3e-15 * n * np.abs(w_ref).max() + 1e-17, 3e-15 * n * np.abs(w_ref).max() + 1e-16
 
 
+def rdm_jacobi_bounds(rho, w_ref):
+    """The same pair under the block-Jacobi solver (the project's bounds for it, tests/test_gpu_kron.py::_rdm_check): its eigenvalues are
+    Rayleigh quotients of the finished vectors and keep the bound of rdm_bounds; the residual is 1e-11 |rho|_F + 1e-16, ten times the
+    solver's stop criterion off^2 <= 1e-24 total^2 (rdm_create_impl), which bounds the Frobenius norm of rho U^T - U^T diag(w) by
+    1e-12 |rho|_F before rounding.  Both stay positive at rho = 0."""
+    n = rho.shape[0]
+    return 3e-15 * n * np.abs(w_ref).max() + 1e-17, 1e-11 * np.linalg.norm(rho) + 1e-16
+
+
 RDM_ORTH_TOL = 1e-13          # rows of the eigenvector matrix, orders up to 1100
 
+RDM_GRADED_LAYOUT = ([40, 130, 77, 5], [64, 33, 150, 9], [(0, 3), (1, 2), (2, 1), (3, 0)])
+_RDM_GRADED = []
 
-def rdm_ratios(rho, w, U, w_ref=None):
+
+def rdm_graded_state():
+    """(psi0, psi1, junk) of tests/test_gpu_kron.py::test_rdm_graded_spectrum_few_sweeps_and_warm_hints, same seed and sizes, draw by draw:
+    a state whose KronBlocks (RDM_GRADED_LAYOUT) have the Schmidt values exp(-0.35 k) u_k, u_k in [0.5, 1] -- like a DMRG ground state --,
+    a perturbation of it by 1e-4 max |psi0|, and one random orthogonal matrix per density matrix, {(side, k): n x n}, as a junk warm
+    hint.  Built once per process, read-only."""
+    if not _RDM_GRADED:
+        rng = np.random.default_rng(3)
+        lsz, rsz, blocks = RDM_GRADED_LAYOUT
+        parts = []
+        for a, b in blocks:
+            U, _ = np.linalg.qr(rng.standard_normal((lsz[a], lsz[a])))
+            V, _ = np.linalg.qr(rng.standard_normal((rsz[b], rsz[b])))
+            k = min(lsz[a], rsz[b])
+            s = np.exp(-0.35 * np.arange(k)) * rng.uniform(0.5, 1.0, k)
+            parts.append((U[:, :k] * s) @ V[:, :k].T)
+        psi0 = np.concatenate([p.ravel() for p in parts])
+        psi0 /= np.linalg.norm(psi0)
+        psi1 = psi0 + 1e-4 * rng.standard_normal(psi0.size) * np.abs(psi0).max()
+        psi1 /= np.linalg.norm(psi1)
+        sizes = {(side, k): (lsz[a], rsz[b])[side] for k, (a, b) in enumerate(blocks) for side in (0, 1)}      # (the test's order: k, then side)
+        junk = {key: np.ascontiguousarray(np.linalg.qr(rng.standard_normal((n, n)))[0]) for key, n in sizes.items()}
+        for a in [psi0, psi1] + list(junk.values()):
+            a.setflags(write=False)
+        _RDM_GRADED.append((psi0, psi1, junk))
+    return _RDM_GRADED[0]
+
+
+def rdm_ratios(rho, w, U, w_ref=None, jacobi=False):
     """(eigenvalue error / its bound, residual / its bound, orthogonality error) of eigenvalues w (descending) and eigenvectors U (rows)
-    against numpy's eigvalsh of rho."""
+    against numpy's eigvalsh of rho, with the bounds of the direct solver or of the block-Jacobi solver."""
     if w_ref is None:
         w_ref = np.linalg.eigvalsh(rho)[::-1]
-    be, br = rdm_bounds(rho, w_ref)
+    be, br = (rdm_jacobi_bounds if jacobi else rdm_bounds)(rho, w_ref)
     c = U.shape[0]
     return (np.abs(w - w_ref).max() / be, np.abs(rho @ U.T - U.T * w[:c]).max() / br, np.abs(U @ U.T - np.eye(c)).max())

@@ -358,7 +358,9 @@ def test_rdm_spectra_and_eigenvectors_vs_lapack(mods, sizes):
     """K3/K4 vs numpy (LAPACK, as the reference's EPSLAPACK): eigenvalues of Psi Psi^T / Psi^T Psi, orthonormal
     eigenvector rows that diagonalise the block (eigenvectors are compared through invariants, their phases and
     the basis inside degenerate/null spaces are not pinned by the reference).  The last case has a rank-deficient block of
-    order 1100 (rho_L of a 1100 x 60 slice): all three panel kernels of the QR preconditioner and a 1040-fold null space."""
+    order 1100 (rho_L of a 1100 x 60 slice) with a 1040-fold null space.  All of it goes through the default solver, tridiagonalisation +
+    divide and conquer (csrc/symeig.hip), and the residual bound is the looser one of the block-Jacobi solver this test was written for;
+    that solver and the panel kernels of its QR preconditioner are tested in tests/test_gpu_rdm_spectra.py::test_block_jacobi_solver."""
     sbm, _, _ = mods
     ls, rs = sizes
     blocks = [(i, len(rs) - 1 - i) for i in range(min(len(ls), len(rs)))]
@@ -904,10 +906,12 @@ def test_apply_degenerate_layouts_vs_dense_kron(mods):
 
 
 def test_rdm_graded_spectrum_few_sweeps_and_warm_hints(mods):
-    """Density matrices with a decaying Schmidt spectrum (like a DMRG ground state): the QR-preconditioned block Jacobi
-    converges in a handful of sweeps (the unpreconditioned iteration needs 10-16 on such matrices), and
-    dmrgx_rdm_create_warm accepts any orthogonal starting basis -- the eigenbasis of a nearby state or a random one --
-    with the same spectra and eigenvectors, checked against LAPACK."""
+    """Density matrices with a decaying Schmidt spectrum (like a DMRG ground state): dmrgx_rdm_create_warm accepts any orthogonal
+    starting basis -- the eigenbasis of a nearby state or a random one -- with the same spectra and eigenvectors, checked against
+    LAPACK.  These calls go through the default solver, tridiagonalisation + divide and conquer, for which the bases are only a hint and
+    which reports no sweeps: the bound of 7 sweeps below was written for the QR-preconditioned block Jacobi (the unpreconditioned
+    iteration needs 10-16 on such matrices) and is asserted on that solver, for this very state, in
+    tests/test_gpu_rdm_spectra.py::test_block_jacobi_solver."""
     sbm, wl, _ = mods
     rng = np.random.default_rng(3)
     lsz, rsz = [40, 130, 77, 5], [64, 33, 150, 9]
@@ -933,6 +937,8 @@ def test_rdm_graded_spectrum_few_sweeps_and_warm_hints(mods):
     # (a visit rotates the pairs between its two blocks; the pairs inside a block once per sweep -- one sweep more than with a
     # full cyclic sweep per visit, at half the latency per round)
     assert max(cold0.sweeps, cold1.sweeps, warm1.sweeps, junk1.sweeps) <= 7, (cold0.sweeps, cold1.sweeps, warm1.sweeps, junk1.sweeps)
+    for r in (cold0, cold1, warm1, junk1):
+        assert r.sweeps == 0 and r.report.solver == 0, (r.sweeps, r.report.solver)
     off = 0
     for k, (a, b) in enumerate(blocks):
         Psi = psi1[off:off + lsz[a] * rsz[b]].reshape(lsz[a], rsz[b]); off += lsz[a] * rsz[b]

@@ -156,6 +156,84 @@ def test_lapack_alone_meets_every_bound():
     print("LAPACK worst: %.2e %.2e %.2e" % tuple(max(v[i] for v in worst.values()) for i in range(3)))
 
 
+def _graded_blocks(psi):
+    lsz, rsz, blocks = helpers.RDM_GRADED_LAYOUT
+    out, off = [], 0
+    for a, b in blocks:
+        out.append(psi[off:off + lsz[a] * rsz[b]].reshape(lsz[a], rsz[b]))
+        off += lsz[a] * rsz[b]
+    assert off == psi.size
+    return out
+
+
+def test_lapack_alone_meets_every_jacobi_bound():
+    """The same for the block-Jacobi cases and their bounds (helpers.rdm_jacobi_bounds): the named inputs, the state with a zero, a rank-one
+    and an identity block -- at rho = 0 the bounds are their absolute terms, nothing is divided by a norm --, the graded state, and the
+    planted spectrum of order 3073 against eigh (eigenvalues only: numpy's products with eigh's 3049 null vectors do not finish in minutes
+    on the host; the GPU test forms them on the device)."""
+    inputs = [(name, helpers.rdm_input(name)[2]) for name in helpers.RDM_NAMED + helpers.RDM_SPECIAL + ["gaussian_1100x60"]]
+    inputs += [("graded_%d" % k, Psi) for k, Psi in enumerate(_graded_blocks(helpers.rdm_graded_state()[1]))]
+    for name, Psi in inputs:
+        s2 = np.linalg.svd(Psi, compute_uv=False) ** 2
+        for side, rho in enumerate((Psi @ Psi.T, Psi.T @ Psi)):
+            w, X = np.linalg.eigh(rho)
+            n = rho.shape[0]
+            w_ref = np.concatenate([s2, np.zeros(n - len(s2))])
+            be, br = helpers.rdm_jacobi_bounds(rho, w_ref)
+            assert be > 0.0 and br > 0.0 and np.isfinite([be, br]).all()
+            re, rr, orth = helpers.rdm_ratios(rho, w[::-1], X.T[::-1], w_ref, jacobi=True)
+            print("LAPACK (Jacobi bounds) %-18s side %d n %4d: eigenvalue error / bound %.2e  residual / bound %.2e  orthogonality %.2e" % (name, side, n, re, rr, orth))
+            assert re <= 1.0 and rr <= 1.0 and orth <= helpers.RDM_ORTH_TOL, (name, side, re, rr, orth)
+    Psi = helpers.rdm_input("planted_3073x24")[2]
+    planted = helpers.RDM_PLANTED_S ** 2
+    for side, rho in enumerate((Psi @ Psi.T, Psi.T @ Psi)):
+        n = rho.shape[0]
+        w_ref = np.concatenate([planted, np.zeros(n - 24)])
+        err = np.abs(np.linalg.eigvalsh(rho)[::-1] - w_ref).max()
+        be = helpers.rdm_jacobi_bounds(rho, w_ref)[0]
+        print("LAPACK planted_3073x24 side %d n %d: eigenvalue error %.3e bound %.3e" % (side, n, err, be))
+        assert err <= be
+
+
+def test_special_blocks_and_the_planted_spectrum():
+    """The zero block is zero, the rank-one block has one non-zero singular value, the orthogonal block has 48 equal ones, and the planted
+    block has the singular values it was built from."""
+    zero, one, orth, gauss = (helpers.rdm_input(name)[2] for name in helpers.RDM_SPECIAL)
+    assert zero.shape == one.shape == (90, 70) and not zero.any()
+    s = np.linalg.svd(one, compute_uv=False)
+    assert s[0] > 1.0 and s[1] <= 1e-14 * s[0]
+    assert orth.shape == (48, 48) and np.abs(orth @ orth.T * 48.0 - np.eye(48)).max() <= 1e-14
+    assert gauss.shape == (40, 33) and np.linalg.matrix_rank(gauss) == 33
+    planted, other = (helpers.rdm_input(name)[2] for name in helpers.RDM_SWITCH)
+    assert [planted.shape, other.shape] == helpers.RDM_SWITCH_SHAPES
+    s = np.linalg.svd(planted, compute_uv=False)
+    assert np.abs(s - helpers.RDM_PLANTED_S).max() <= 1e-14 and helpers.RDM_PLANTED_S[0] == 1.0 and np.all(np.diff(helpers.RDM_PLANTED_S) < 0)
+
+
+def test_the_graded_state_is_the_one_of_the_warm_hint_test():
+    """Schmidt values exp(-0.35 k) u_k with u_k in [0.5, 1] per KronBlock, up to the norm c of the state: the j-th largest of a block then
+    lies in c [0.5, 1] exp(-0.35 j) (j + 1 of them are at least the lower end, at most j exceed the upper one).  The perturbed state is
+    1e-4 away; the junk hints are orthogonal matrices of the right orders, one per density matrix."""
+    psi0, psi1, junk = helpers.rdm_graded_state()
+    lsz, rsz, blocks = helpers.RDM_GRADED_LAYOUT
+    assert psi0.size == psi1.size == sum(lsz[a] * rsz[b] for a, b in blocks) and not psi0.flags.writeable and helpers.rdm_graded_state()[0] is psi0
+    assert abs(np.linalg.norm(psi0) - 1.0) <= 1e-15 and abs(np.linalg.norm(psi1) - 1.0) <= 1e-15
+    ratios = []
+    for Psi in _graded_blocks(psi0):
+        s = np.linalg.svd(Psi, compute_uv=False)
+        keep = s > 1e-12 * s[0]                                                   # (below that the computed singular values are rounding)
+        assert keep.sum() >= min(len(s), 60), (len(s), keep.sum())
+        ratios += list((s / np.exp(-0.35 * np.arange(len(s))))[keep])
+    print("graded state: sigma_j / exp(-0.35 j) between", min(ratios), "and", max(ratios))
+    assert min(ratios) >= 0.5 * max(ratios) * (1.0 - 1e-3)
+    d = np.linalg.norm(psi1 - psi0)
+    assert 1e-6 < d < 1e-2
+    assert sorted(junk) == sorted((side, k) for k in range(4) for side in (0, 1))
+    for (side, k), Q in junk.items():
+        n = (lsz[blocks[k][0]], rsz[blocks[k][1]])[side]
+        assert Q.shape == (n, n) and np.abs(Q @ Q.T - np.eye(n)).max() <= 1e-13
+
+
 def test_the_model_meets_every_bound_too():
     """The host model the properties are read from computes the same thing as the library is meant to."""
     for name in helpers.RDM_NAMED:
@@ -165,21 +243,75 @@ def test_the_model_meets_every_bound_too():
         assert re <= 1.0 and rr <= 1.0 and orth <= helpers.RDM_ORTH_TOL, (name, re, rr, orth)
 
 
+def _one(pattern, src, what):
+    m = re.findall(pattern, src)
+    assert len(m) == 1, (what, m)
+    return m[0]
+
+
+def _jacobi_constants():
+    """The constants of the block-Jacobi path as csrc/rdm.hip and csrc/hqr.hip state them: the Jacobi block, the size classes of
+    hqr_panel_regs_kernel (rows, rows per thread), the panel width where the panels are stepped and where they are clipped, the strip of the
+    trailing update."""
+    rdm, hqr = open(os.path.join(CSRC, "rdm.hip")).read(), open(os.path.join(CSRC, "hqr.hip")).read()
+    out = {"DMRGX_JB": int(_one(r"#define\s+DMRGX_JB\s+(\d+)", rdm, "DMRGX_JB")), "HR_MAX_ROWS": int(_one(r"\bHR_MAX_ROWS\s*=\s*(\d+)", hqr, "HR_MAX_ROWS"))}
+    classes = re.findall(r"if\s*\(nrem\s*<=\s*(\d+)\)\s*hqr_panel_regs_body<(\d+)>", hqr)
+    last = _one(r"else\s+hqr_panel_regs_body<(\d+)>", hqr, "the last size class")
+    assert [rr for _, rr in classes] + [last] == ["4", "8", "16"], (classes, last)
+    assert all(int(rows) == 64 * int(rr) for rows, rr in classes) and out["HR_MAX_ROWS"] == 64 * int(last)      # 64 row blocks of rr rows each
+    out["HQR_REGS_ROWS_4"], out["HQR_REGS_ROWS_8"] = (int(rows) for rows, _ in classes)
+    assert _one(r"nrem\s*>\s*(\w+)\)\s*return;", hqr, "the upper end of the register panels") == "HR_MAX_ROWS"
+    assert _one(r"m\.n\s*-\s*r0\s*<=\s*(\w+)\)\s*return;", hqr, "the lower end of hqr_panel_kernel") == "HR_MAX_ROWS"
+    steps = set(re.findall(r"r0\s*\+=\s*(\d+)", hqr)) | set(re.findall(r"pw\s*=\s*(?:std::)?min\((\d+),\s*nrem\)", hqr))
+    assert len(steps) == 1, steps
+    out["HQR_PANEL"] = int(steps.pop())
+    out["TM_COLS"] = int(_one(r"\bTM_COLS\s*=\s*(\d+)\s*\*\s*TM_NBW", hqr, "TM_COLS")) * int(_one(r"\bTM_NBW\s*=\s*(\d+)", hqr, "TM_NBW"))
+    return out
+
+
 def _constants():
     src = open(os.path.join(CSRC, "symeig.hip")).read() + open(os.path.join(CSRC, "symeig.h")).read()
-    out = {}
+    out = _jacobi_constants()
     for name in helpers.RDM_CONSTANTS:
+        if name in out:
+            continue
         m = re.findall(r"(?:#define\s+%s\s+|constexpr\s+int\s+(?:\w+\s*=\s*\d+\s*,\s*)*%s\s*=\s*)(\d+)" % (name, name), src)
         assert len(m) == 1, (name, m)
         out[name] = int(m[0])
     return out
 
 
+def test_the_jacobi_order_lists_straddle_the_library_constants():
+    """The orders of the block-Jacobi cases sit on the edges of csrc/rdm.hip and csrc/hqr.hip as they are today: a retune of the Jacobi block,
+    of a size class of the register panels, of the panel width or of the strip of the trailing update must fail here, not silently move an
+    edge out of the lists."""
+    c = _constants()
+    jb, r4, r8, rmax, panel, strip, max_n = (c[k] for k in ("DMRGX_JB", "HQR_REGS_ROWS_4", "HQR_REGS_ROWS_8", "HR_MAX_ROWS", "HQR_PANEL", "TM_COLS", "SYMEIG_MAX_N"))
+    assert (jb, r4, r8, rmax, panel, strip) == (16, 256, 512, 1024, 32, 32)
+    small, calls = set(range(1, 41)), helpers.RDM_HQR_EDGE_CALLS
+    edge = {n for call in calls for n in call}
+    assert {1, 2, 2 * jb - 1, 2 * jb, 2 * jb + 1} <= small                        # no QR at n = 1; one padded pair up to 2 JB, two blocks more above
+    assert [min(call) <= r <= max(call) - 1 for call, r in zip(calls, (r4, r8, rmax))] == [True] * 3      # one call per edge, both sides in it
+    for r in (r4, r8, rmax):
+        assert {r, r + 1} <= edge                                                # the first panel in either body
+    assert {r4 - 1, r8 - 1} <= edge
+    assert max(edge) > rmax and max(edge) - (max(edge) - rmax + panel - 1) // panel * panel > r8      # the largest order walks down through every class
+    for div in (panel, strip):                                                   # a last panel narrower than 32; a partial strip of the trailing update
+        assert any(n % div for n in edge) and any(n % div == 0 for n in edge)
+    assert {n % panel for n in edge | small} >= {0, 1, 2, panel - 1}
+    (big, _), (mid, _) = helpers.RDM_SWITCH_SHAPES
+    assert big == max_n + 1 and rmax < mid <= 1100                                # the smallest order that switches; the project's orthogonality figure holds up to 1100
+    both = [r0 for r0 in range(0, mid, panel) if big - r0 > rmax and 0 < mid - r0 <= rmax]
+    assert both, "no panel step at which both kernels of hqr_batched are launched"
+    assert max(edge) <= 1100 and max(max(s) for s in helpers.RDM_SWITCH_SHAPES) == big
+
+
 def test_the_order_lists_still_straddle_the_library_constants():
     """A retune of the leaf size, the fused-kernel threshold, the WY block, the matrices per launch, the prefetch depth or the largest order must
     fail here loudly, not silently uncover an edge."""
     c = _constants()
-    assert c == helpers.RDM_CONSTANTS == {"DMRGX_DC_LEAF": 16, "DC_FUSE_NL": 384, "DMRGX_WY_NB": 64, "TRID_MAXM": 32, "TRID_PF": 8, "SYMEIG_MAX_N": 3072}
+    assert c == helpers.RDM_CONSTANTS == {"DMRGX_DC_LEAF": 16, "DC_FUSE_NL": 384, "DMRGX_WY_NB": 64, "TRID_MAXM": 32, "TRID_PF": 8, "SYMEIG_MAX_N": 3072,
+                                          "DMRGX_JB": 16, "HQR_REGS_ROWS_4": 256, "HQR_REGS_ROWS_8": 512, "HR_MAX_ROWS": 1024, "HQR_PANEL": 32, "TM_COLS": 32}
     leaf, fuse, nb, maxm, pf = c["DMRGX_DC_LEAF"], c["DC_FUSE_NL"], c["DMRGX_WY_NB"], c["TRID_MAXM"], c["TRID_PF"]
     small, edge = list(range(1, 41)), helpers.RDM_EDGE_ORDERS
     assert sorted(o for call in helpers.RDM_EDGE_CALLS for o in call) == edge and max(edge) <= c["SYMEIG_MAX_N"]
