@@ -975,6 +975,20 @@ struct GramLayout {
     std::vector<int64_t> ref_off;
 };
 
+// The offsets and the (il, ir) -> index map of a KronBlock list over checked sector tables; `what` names the list in messages.
+dmrgx_status block_layout(const char* fn, const char* what, const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks, const int32_t* block_il, const int32_t* block_ir, GramLayout& L)
+{
+    L.SL = left; L.SR = right; L.nblocks = nblocks; L.il = block_il; L.ir = block_ir;
+    L.ref_off.assign((size_t)nblocks + 1, 0);
+    for (int32_t k = 0; k < nblocks; ++k) {
+        const int32_t il = block_il[k], ir = block_ir[k];
+        if (il < 0 || il >= left->nsec || ir < 0 || ir >= right->nsec) DMRGX_FAIL(DMRGX_ERR_OUTOFRANGE, "%s: %s %d = (%d,%d) out of range", fn, what, k, il, ir);
+        if (!L.kmap.emplace(std::make_pair(il, ir), k).second) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: %s (%d,%d) listed twice", fn, what, il, ir);
+        L.ref_off[k + 1] = L.ref_off[k] + (int64_t)left->size[il] * right->size[ir];
+    }
+    return DMRGX_OK;
+}
+
 dmrgx_status gram_layout(const char* fn, const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks, const int32_t* block_il, const int32_t* block_ir,
                          const double* psi_dev, GramLayout& L)
 {
@@ -983,15 +997,7 @@ dmrgx_status gram_layout(const char* fn, const dmrgx_sectors* left, const dmrgx_
     for (int i = 0; i < right->nsec; ++i) if (right->size[i] <= 0) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: right sector %d has size %d", fn, i, right->size[i]);
     if (nblocks <= 0 || !block_il || !block_ir) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: no KronBlocks", fn);
     if (!psi_dev) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null psi", fn);
-    L.SL = left; L.SR = right; L.nblocks = nblocks; L.il = block_il; L.ir = block_ir;
-    L.ref_off.assign((size_t)nblocks + 1, 0);
-    for (int32_t k = 0; k < nblocks; ++k) {
-        const int32_t il = block_il[k], ir = block_ir[k];
-        if (il < 0 || il >= left->nsec || ir < 0 || ir >= right->nsec) DMRGX_FAIL(DMRGX_ERR_OUTOFRANGE, "%s: KronBlock %d = (%d,%d) out of range", fn, k, il, ir);
-        if (!L.kmap.emplace(std::make_pair(il, ir), k).second) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: KronBlock (%d,%d) listed twice", fn, il, ir);
-        L.ref_off[k + 1] = L.ref_off[k] + (int64_t)left->size[il] * right->size[ir];
-    }
-    return DMRGX_OK;
+    return block_layout(fn, "KronBlock", left, right, nblocks, block_il, block_ir, L);
 }
 
 // The groups of one output block Y (nLa x nRb, leading dimension ldc): the rows are cut at the borders of the left-kind cells, the columns
@@ -1046,14 +1052,15 @@ void emit_groups(GemmBatch& gb, GemmSet& set, double* Y, int32_t ldc, int32_t nL
 }
 
 // The builder behind dmrgx_kron_term_gram and dmrgx_kron_term_apply.  `fn` names the caller in messages.
-// Output mode (Y_dev != nullptr, dmrgx_kron_term_apply): the images themselves are the result.  The image blocks are then the KronBlocks
-// at their offsets in the reference layout, all in one slice whose "workspace" is the caller's Y (vector stride ldy), and no Gram
-// matrix is taken; the groups, products and cell copies are emitted exactly as for the Gram matrix.
+// Output mode (Y_dev != nullptr, dmrgx_kron_term_apply and _apply_to): the images themselves are the result.  The image blocks are then
+// the KronBlocks of the output list Out (a second layout over the same sector tables, never null with Y_dev; dmrgx_kron_term_apply passes L itself) at their
+// offsets in its reference layout, all in one slice whose "workspace" is the caller's Y (vector stride ldy), and no Gram matrix is
+// taken; the sources are looked up in L, and the groups, products and cell copies are emitted exactly as for the Gram matrix.
 dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* psi_dev,
                              int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
                              int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
                              size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, hipStream_t st,
-                             double* Y_dev = nullptr, int64_t ldy = 0)
+                             double* Y_dev = nullptr, int64_t ldy = 0, const GramLayout* Out = nullptr)
 {
     const dmrgx_sectors& SL = *L.SL;
     const dmrgx_sectors& SR = *L.SR;
@@ -1080,13 +1087,14 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
         for (const auto& p : pairs) {
             const int32_t a = L.il[k] - p.first, b = L.ir[k] - p.second;
             if (a < 0 || a >= SL.nsec || b < 0 || b >= SR.nsec) continue;
-            if (Y_dev && !L.kmap.count(std::make_pair(a, b)))
-                DMRGX_FAIL(DMRGX_ERR_ARG, "%s: shifts (%d,%d) map KronBlock %d = (%d,%d) to the sector pair (%d,%d), which is not one of the KronBlocks", fn, p.first, p.second, k, L.il[k], L.ir[k], a, b);
+            if (Y_dev && !Out->kmap.count(std::make_pair(a, b)))
+                DMRGX_FAIL(DMRGX_ERR_ARG, "%s: shifts (%d,%d) map KronBlock %d = (%d,%d) to the sector pair (%d,%d), which is not one of the %sKronBlocks", fn, p.first, p.second, k, L.il[k], L.ir[k], a, b, Out == &L ? "" : "output ");
             if (!Y_dev && imap.emplace(std::make_pair(a, b), (int32_t)imgs.size()).second) imgs.push_back(ImgBlock{a, b, (int64_t)SL.size[a] * SR.size[b], 0, 0});
         }
-        // output mode: every KronBlock is an image block where the layout has it, reached or not
-        if (Y_dev) imgs.push_back(ImgBlock{L.il[k], L.ir[k], L.ref_off[k + 1] - L.ref_off[k], L.ref_off[k], 0});
     }
+    // output mode: every KronBlock of the output list is an image block where its layout has it, reached or not
+    if (Y_dev)
+        for (int32_t k = 0; k < Out->nblocks; ++k) imgs.push_back(ImgBlock{Out->il[k], Out->ir[k], Out->ref_off[k + 1] - Out->ref_off[k], Out->ref_off[k], 0});
     if (Y_dev) slice_len.assign(1, ldy);              // one slice: the caller's vectors, stride ldy
     // slices of image blocks that fit the workspace
     const int64_t bound = (int64_t)((workspace_bytes ? workspace_bytes : ((size_t)1 << 30)) / sizeof(double)) / nvec;
@@ -1174,7 +1182,7 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
         }
 
     DevBuf W, trans, scratch, tab;
-    if (Y_dev) W.view(Y_dev, (size_t)((nvec - 1) * ldy + L.ref_off[L.nblocks]) * sizeof(double));
+    if (Y_dev) W.view(Y_dev, (size_t)((nvec - 1) * ldy + Out->ref_off[Out->nblocks]) * sizeof(double));
     else DMRGX_CHK(W.alloc_f64((size_t)(*std::max_element(slice_len.begin(), slice_len.end())) * nvec, st));
     if (trans_doubles > 0) DMRGX_CHK(trans.alloc_f64((size_t)trans_doubles, st));
     const int64_t scratch_max = *std::max_element(scratch_len.begin(), scratch_len.end());
@@ -1292,7 +1300,29 @@ extern "C" dmrgx_status dmrgx_kron_term_apply(const dmrgx_sectors* left, const d
     const int64_t N = L.ref_off[nblocks];
     if (!Y_dev || ldy < N) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null Y or ldy %lld below the %lld states", fn, (long long)ldy, (long long)N);
     if (Y_dev < psi_dev + N && psi_dev < Y_dev + (int64_t)(nvec - 1) * ldy + N) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: Y overlaps psi", fn);
-    return term_gram_build(fn, L, psi_dev, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, 0, nullptr, 0, nullptr, (hipStream_t)stream, Y_dev, ldy);
+    return term_gram_build(fn, L, psi_dev, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, 0, nullptr, 0, nullptr, (hipStream_t)stream, Y_dev, ldy, &L);      // output list == input list
+}
+
+// dmrgx_kron_term_apply_to: the same images written in the layout of a second KronBlock list (the sector the total shift leads to).
+extern "C" dmrgx_status dmrgx_kron_term_apply_to(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
+                                                 const int32_t* block_il, const int32_t* block_ir, const double* psi_dev,
+                                                 int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
+                                                 int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
+                                                 int32_t n_out, const int32_t* out_il, const int32_t* out_ir,
+                                                 double* Y_dev, int64_t ldy, void* stream)
+{
+    const char* fn = "kron_term_apply_to";
+    GramLayout L, O;
+    DMRGX_CHK(gram_layout(fn, left, right, nblocks, block_il, block_ir, psi_dev, L));
+    int32_t shift = 0;
+    DMRGX_CHK(term_list_check(fn, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, &shift));
+    if (n_out < 0 || (n_out > 0 && (!out_il || !out_ir))) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: bad output KronBlock list (%d blocks)", fn, n_out);
+    if (n_out == 0) return DMRGX_OK;
+    DMRGX_CHK(block_layout(fn, "output KronBlock", left, right, n_out, out_il, out_ir, O));
+    const int64_t N = L.ref_off[nblocks], NO = O.ref_off[n_out];
+    if (!Y_dev || ldy < NO) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null Y or ldy %lld below the %lld output states", fn, (long long)ldy, (long long)NO);
+    if (Y_dev < psi_dev + N && psi_dev < Y_dev + (int64_t)(nvec - 1) * ldy + NO) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: Y overlaps psi", fn);
+    return term_gram_build(fn, L, psi_dev, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, 0, nullptr, 0, nullptr, (hipStream_t)stream, Y_dev, ldy, &O);
 }
 
 // dmrgx_kron_op_gram: one operator per vector, A (x) 1 or 1 (x) B.  It keeps its own builder: the same image blocks, groups and products

@@ -225,12 +225,15 @@ public:
             if (dsf_dimer_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_dimer_steps must be at least 1. Got %lld.", LLD(dsf_dimer_steps));
             ierr = ReadOmegaGridOption("-dsf_dimer_omega", dsf_dimer_omega, dsf_dimer_have_omega); CHKERRQ(ierr);
         }
-        if (use_dsf_cheb) {   /* -dsf_cheb c0,c1,...: the Chebyshev moments of G_ic(w) from every listed site c (CalculateChebyshevCorrelations) */
+        /* -dsf_pm c0,c1,...: the Chebyshev moments of the transverse correlations S^-+_ic(w) and S^+-_ic(w) from every listed site c, run on a
+           plan of the neighbouring total-Sz sector (CalculateTransverseDynamics); steps, grid and window are those of -dsf_cheb */
+        ierr = ReadSiteListOption("-dsf_pm", "the Chebyshev recursion", dsf_pm_sites, use_dsf_pm); CHKERRQ(ierr);
+        if (use_dsf_cheb || use_dsf_pm) {   /* -dsf_cheb c0,c1,...: the Chebyshev moments of G_ic(w) from every listed site c (CalculateChebyshevCorrelations) */
             ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_cheb_steps", &dsf_cheb_steps, NULL); CHKERRQ(ierr);
             if (dsf_cheb_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cheb_steps must be at least 1. Got %lld.", LLD(dsf_cheb_steps));
             ierr = ReadOmegaGridOption("-dsf_cheb_omega", dsf_cheb_omega, dsf_cheb_have_omega); CHKERRQ(ierr);
         }
-        if (use_dsf_cheb || use_dsf_dimer) {   /* the window of the Chebyshev expansion, which the two share */
+        if (use_dsf_cheb || use_dsf_dimer || use_dsf_pm) {   /* the window of the Chebyshev expansion, which the three share */
             ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_cheb_bound_steps", &dsf_cheb_bound_steps, NULL); CHKERRQ(ierr);
             if (dsf_cheb_bound_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cheb_bound_steps must be at least 1. Got %lld.", LLD(dsf_cheb_bound_steps));
             PetscInt nw = 2;
@@ -497,7 +500,7 @@ public:
         spectra_writer.Drain();
         if (fp_entanglement) { fprintf(fp_entanglement, "\n]\n"); fclose(fp_entanglement); fp_entanglement = NULL; }
         if (fp_kron) { fprintf(fp_kron, "\n]\n"); fclose(fp_kron); fp_kron = NULL; }
-        spin_file.Close(); dimer_file.Close(); dsf_file.Close(); dsf_sites_file.Close(); dsf_cheb_file.Close(); dsf_cv_file.Close(); dsf_dimer_file.Close();
+        spin_file.Close(); dimer_file.Close(); dsf_file.Close(); dsf_sites_file.Close(); dsf_cheb_file.Close(); dsf_cv_file.Close(); dsf_dimer_file.Close(); dsf_pm_file.Close();
         if (fp_corr) {
             if (!corr_headers_printed) { PetscErrorCode e2 = PrintCorrelationHeaders(); CHKERRQ(e2); }
             fprintf(fp_corr, "\n  ]\n}\n"); fclose(fp_corr); fp_corr = NULL;
@@ -631,6 +634,7 @@ public:
         if (use_dsf_cv && do_measurements) { ierr = CalculateCorrectionVectors(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
         ierr = MatDestroy_KronSumShell(&H); CHKERRQ(ierr);
         ierr = MatDestroy(&H); CHKERRQ(ierr);
+        if (use_dsf_pm && do_measurements) { ierr = CalculateTransverseDynamics(KronBlocks, gsv_r, Terms, gse_r); CHKERRQ(ierr); }      /* needs psi, not H: its plans are of other sectors, one resident at a time */
         ierr = PetscTime(&tdiag); CHKERRQ(ierr);
         timings.tDiag = tdiag - tkron;
 
@@ -1737,6 +1741,20 @@ public:
             centre = 0.5 * (dsf_cheb_window[0] + dsf_cheb_window[1]); half_width = 0.5 * (dsf_cheb_window[1] - dsf_cheb_window[0]); theta_max = dsf_cheb_window[1];
             return 0;
         }
+        std::vector<double> a, b;
+        int32_t done = 0;
+        PetscErrorCode ierr = ChebyshevBoundRun(H, n, a, b, done); CHKERRQ(ierr);
+        bound_steps = dsf_cheb_bound_steps;
+        const dmrgx_host::ChebyshevWindowResult W = dmrgx_host::ChebyshevWindow(E0, a, b, done);
+        if (!W.ok) SETERRQ2(mpi_comm, 1, "%s: no spectral window from %d Lanczos steps.", name, (int)done);
+        centre = W.centre; half_width = W.half_width; theta_max = W.theta_max; residual = W.residual;
+        return 0;
+    }
+
+    /** alpha, beta and the steps done of -dsf_cheb_bound_steps Lanczos steps (dmrgx_kron_lanczos_coeffs) on the planned Hamiltonian of n states from
+        a fixed pseudo-random vector: what ChebyshevWindow and ChebyshevWindowTwoSided read. */
+    PetscErrorCode ChebyshevBoundRun(Mat& H, int64_t n, std::vector<double>& a, std::vector<double>& b, int32_t& done)
+    {
         const PetscInt B = dsf_cheb_bound_steps;
         dmrgx_host::DevBuffer r((size_t)n);
         {   /* uniform(-1, 1) from a fixed seed, by integer arithmetic on the generator's 64 bits: the same vector everywhere */
@@ -1744,13 +1762,129 @@ public:
             double* h = r.host();
             for (int64_t e = 0; e < n; ++e) h[e] = (double)(gen() >> 11) * (2.0 / 9007199254740992.0) - 1.0;
         }
-        std::vector<double> a((size_t)B, 0.0), b((size_t)B, 0.0);
-        double r2 = 0.0; int32_t done = 0;
+        a.assign((size_t)B, 0.0); b.assign((size_t)B, 0.0);
+        double r2 = 0.0; done = 0;
         if (dmrgx_kron_lanczos_coeffs(H->plan, r.dev_ro(), (int32_t)B, 0.0, &r2, a.data(), b.data(), &done, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_lanczos_coeffs: %s", dmrgx_last_error());
-        bound_steps = B;
-        const dmrgx_host::ChebyshevWindowResult W = dmrgx_host::ChebyshevWindow(E0, a, b, done);
-        if (!W.ok) SETERRQ2(mpi_comm, 1, "%s: no spectral window from %d Lanczos steps.", name, (int)done);
-        centre = W.centre; half_width = W.half_width; theta_max = W.theta_max; residual = W.residual;
+        return 0;
+    }
+
+    /** -dsf_pm c0,c1,... (engine extension): the Chebyshev moments of the transverse dynamical correlations of the ground state,
+            mu_n^{ic} = < O_i psi , T_n(Ht) O_c psi > / <psi|psi>,   Ht = (H' - Centre) / HalfWidth,   for ALL sites i,
+        in two channels: "MinusPlus", O = S^+, the response < S^-_i delta(w - H' + E0) S^+_c >, and "PlusMinus", O = S^- (Sp read
+        transposed), < S^+_i ... S^-_c > -- the magnons of an XXZ model or of a magnetised target, which S^zz (-dsf_cheb) does not hold.
+        O psi lives in the total-Sz sector qn_sector + 1 (- 1), so H' is the superblock Hamiltonian of THAT sector: per channel a
+        KronBlocks_t of the neighbouring sector over the same two blocks, the images of all N sites written in its layout
+        (SzFrame::ImagesTo, dmrgx_kron_term_apply_to) -- N x N_sb' doubles, refused with PETSC_ERR_MEM if they do not fit --, its plan
+        (KronSumConstruct with the settings of the ground-state plan), and one dmrgx_kron_chebyshev_moments run per reference site.  The
+        measurement runs after the ground-state plan is destroyed and destroys each plan before the next: one plan is resident at a time.
+        The window is -dsf_cheb_window lo,hi as given (ThetaMin = lo, ThetaMax = hi), else from -dsf_cheb_bound_steps Lanczos steps on
+        H' from the fixed pseudo-random vector of FindChebyshevWindow, both ends from the Ritz values (ChebyshevWindowTwoSided: the
+        bottom of another sector is not known from E0).  Should the window fail to hold, the library's guard ends the run: StepsDone <
+        Steps in the record and a warning here, not an error.  An empty neighbouring sector (a fully polarised target) gives a record
+        with States 0, no MatMults and StepsDone 0 for every site.
+        One record per measurement and channel in TransverseDynamics.json; Moments, MomentsQ, Diag and SqwGrid as in
+        ChebyshevMoments.json, energies measured from E0 of the target sector: (1/N) sum_c SqwGrid is the Jackson-broadened S^-+(q, w)
+        (S^+-(q, w)), non-negative.  The caveats of -dsf_sites apply, and one more: the bases of the blocks are optimised for the ONE
+        target state, not for the states of the neighbouring sector (single-target DMRG) -- exact while nothing is truncated, an
+        approximation that m controls otherwise.  One rank only (refused at start-up otherwise). */
+    PetscErrorCode CalculateTransverseDynamics(KronBlocks_t& KronBlocks, const Vec& gsv_r, const std::vector<Hamiltonians::Term>& Terms, PetscScalar E0)
+    {
+        PetscErrorCode ierr;
+        const PetscInt K = dsf_cheb_steps;
+        for (int channel = 0; channel < 2; ++channel) {
+            PetscLogDouble t0, t1;
+            PetscTime(&t0);
+            const char* cname = channel == 0 ? "MinusPlus" : "PlusMinus";
+            const PetscReal sector = qn_sector + (channel == 0 ? 1.0 : -1.0);
+            dmrgx_host::SzFrame S;
+            ierr = S.Init(KronBlocks, num_sites, Ham, gsv_r, "Transverse dynamics", channel == 0 ? OpSp : OpSm); CHKERRQ(ierr);
+            const PetscInt N = S.F.N, M = S.M;
+            KronBlocks_t KB1(KronBlocks.LeftBlockRefMod(), KronBlocks.RightBlockRefMod(), {sector}, NULL, GlobIdx);
+            const int64_t n1 = KB1.NumStates(), ld1 = n1 + (n1 & 1);
+
+            struct Run { PetscInt c = 0; double norm2 = 0.0; int32_t done = 0; std::vector<double> diag, mom, momq, grid; };
+            std::vector<Run> runs(dsf_pm_sites.size());
+            for (size_t ir = 0; ir < runs.size(); ++ir) runs[ir].c = dsf_pm_sites[ir];
+            PetscInt bound_steps = 0, matmults = 0;
+            double centre = 0.0, half_width = 0.0, theta_min = 0.0, theta_max = 0.0;
+            if (n1 > 0) {
+                /* the images of all sites in the layout of KB1, row s = O_s psi */
+                std::vector<int32_t> out_il, out_ir;
+                for (PetscInt k = 0; k < KB1.size(); ++k) { out_il.push_back((int32_t)KB1.LeftIdx(k)); out_ir.push_back((int32_t)KB1.RightIdx(k)); }
+                std::unique_ptr<dmrgx_host::DevBuffer> U;
+                try { U.reset(new dmrgx_host::DevBuffer((size_t)(N * ld1), dmrgx_host::DevBuffer::device_only_t{})); }
+                catch (const std::exception& e) { SETERRQ4(mpi_comm, PETSC_ERR_MEM, "Transverse dynamics: no memory for the images of %lld sites x %lld states (%.3f GB): %s", LLD(N), LLD(n1), (double)(N * ld1) * 8e-9, e.what()); }
+                ierr = S.ImagesTo(S.op_of.data(), N, out_il, out_ir, U->dev_uninitialised(), ld1); CHKERRQ(ierr);
+                /* the plan of the neighbouring sector */
+                Mat H1 = nullptr;
+                ierr = KB1.KronSumSetRedistribute(PETSC_TRUE); CHKERRQ(ierr);
+                ierr = KB1.KronSumSetToleranceFromOptions(); CHKERRQ(ierr);
+                ierr = KB1.KronSumSetShellMatrix(do_shell); CHKERRQ(ierr);
+                ierr = KB1.KronSumConstruct(Terms, H1); CHKERRQ(ierr);
+                if (!H1) SETERRQ(mpi_comm, 1, "Transverse dynamics: H is null.");
+                /* the window */
+                if (dsf_cheb_have_window) {
+                    theta_min = dsf_cheb_window[0]; theta_max = dsf_cheb_window[1];
+                    centre = 0.5 * (theta_min + theta_max); half_width = 0.5 * (theta_max - theta_min);
+                } else {
+                    std::vector<double> a, b;
+                    int32_t done = 0;
+                    ierr = ChebyshevBoundRun(H1, n1, a, b, done); CHKERRQ(ierr);
+                    bound_steps = dsf_cheb_bound_steps;
+                    const dmrgx_host::ChebyshevWindowTwoSidedResult W = dmrgx_host::ChebyshevWindowTwoSided(a, b, done);
+                    if (!W.ok) SETERRQ2(mpi_comm, 1, "Transverse dynamics (%s): no spectral window from %d Lanczos steps.", cname, (int)done);
+                    centre = W.centre; half_width = W.half_width; theta_min = W.theta_min; theta_max = W.theta_max;
+                }
+                matmults = bound_steps;
+                std::vector<double> cross((size_t)((K + 1) * N));
+                for (Run& R : runs) {
+                    R.diag.assign((size_t)(2 * K + 1), 0.0);
+                    if (dmrgx_kron_chebyshev_moments(H1->plan, U->dev_ro() + R.c * ld1, centre, half_width, (int32_t)K, (int32_t)N, U->dev_ro(), ld1, &R.norm2, R.diag.data(), cross.data(), &R.done, nullptr))
+                        SETERRQ1(mpi_comm, 1, "dmrgx_kron_chebyshev_moments: %s", dmrgx_last_error());
+                    matmults += K;
+                    const PetscInt D = R.done, nm = D + 1;
+                    if (R.norm2 == 0.0) printf("  * -dsf_pm (%s): the image of site %lld is zero in the bases of the blocks; no run.\n", cname, LLD(R.c));
+                    else if (D < K) printf("  * WARNING: -dsf_pm (%s): the run from site %lld left the window [%.6f, %.6f] after %lld of %lld steps; the record holds the moments up to there.\n", cname, LLD(R.c), centre - half_width, centre + half_width, LLD(D), LLD(K));
+                    R.diag.resize((size_t)(2 * D + 1));
+                    for (double& x : R.diag) x /= S.norm;
+                    R.mom.assign((size_t)(N * nm), 0.0);
+                    for (PetscInt s = 0; s < N; ++s) for (PetscInt k = 0; k < nm; ++k) R.mom[(size_t)(s * nm + k)] = cross[(size_t)(k * N + s)] / S.norm;
+                    R.momq = dmrgx_host::SiteCosineSum(S.Lx, S.Ly, S.rx.data(), S.ry.data(), R.c, R.mom.data(), N, nm);
+                    if (dsf_cheb_have_omega) {
+                        const PetscInt nw = (PetscInt)dsf_cheb_omega.size();
+                        R.grid.assign((size_t)(M * nw), 0.0);
+                        for (PetscInt q = 0; q < M; ++q) for (PetscInt k = 0; k < nw; ++k)
+                            R.grid[(size_t)(q * nw + k)] = dmrgx_host::ChebyshevJackson(R.momq.data() + q * nm, nm, (dsf_cheb_omega[(size_t)k] + (double)E0 - centre) / half_width) / half_width;
+                    }
+                }
+                ierr = MatDestroy_KronSumShell(&H1); CHKERRQ(ierr);
+                ierr = MatDestroy(&H1); CHKERRQ(ierr);
+            }                                                       /* (the images go back to the pool here) */
+            PetscTime(&t1);
+            if (verbose) printf("  * Transverse dynamics (%s): sector %g, %lld reference sites, %lld steps per run, window [%.6f, %.6f] from %lld Lanczos steps, %lld MatMults on %lld states, tDsfPm %.6f s\n",
+                                cname, (double)sector, LLD(runs.size()), LLD(K), centre - half_width, centre + half_width, LLD(bound_steps), LLD(matmults), LLD(n1), t1 - t0);
+            ierr = dsf_pm_file.BeginDynamical(data_dir + "TransverseDynamics.json", GlobIdx, LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, S.norm); CHKERRQ(ierr);
+            FILE* fp = dsf_pm_file.fp;
+            fprintf(fp, ", \"Channel\": \"%s\", \"Sector\": %.17g, \"States\": %lld, \"Steps\": %lld, \"Centre\": %.17g, \"HalfWidth\": %.17g, \"BoundSteps\": %lld, \"ThetaMin\": %.17g, \"ThetaMax\": %.17g, \"tDsfPm\": %.9g, \"MatMults\": %lld,\n",
+                    cname, (double)sector, LLD(n1), LLD(K), centre, half_width, LLD(bound_steps), theta_min, theta_max, t1 - t0, LLD(matmults));
+            if (dsf_cheb_have_omega) { fprintf(fp, "   \"Omega\": "); dsf_pm_file.Row(dsf_cheb_omega); fprintf(fp, ",\n"); }
+            fprintf(fp, "   \"Sites\": [\n");
+            for (size_t ir = 0; ir < runs.size(); ++ir) {
+                const Run& R = runs[ir];
+                const PetscInt nm = R.done + 1;
+                const char* end = ir + 1 < runs.size() ? "},\n" : "}\n";
+                dsf_pm_file.OpenSite(R.c, S.rx[(size_t)R.c], S.ry[(size_t)R.c], R.norm2);
+                fprintf(fp, ", \"StepsDone\": %d", (int)R.done);
+                if (n1 == 0) { fprintf(fp, "%s", end); continue; }          /* no run: no moments */
+                fprintf(fp, ",\n   \"Diag\": ");
+                dsf_pm_file.Row(R.diag); fprintf(fp, ",\n");
+                dsf_pm_file.Table("Moments", R.mom, N, nm, ",\n");
+                dsf_pm_file.Table("MomentsQ", R.momq, M, nm, dsf_cheb_have_omega ? ",\n" : end);
+                if (dsf_cheb_have_omega) dsf_pm_file.Table("SqwGrid", R.grid, M, (PetscInt)dsf_cheb_omega.size(), end);
+            }
+            fprintf(fp, "   ]}");
+            fflush(fp);
+        }
         return 0;
     }
 
@@ -2284,7 +2418,7 @@ public:
             for (const Op& o : c.SysOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
             for (const Op& o : c.EnvOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
         }
-        if (use_corr_matrix || use_corr_dimer || use_dsf || use_dsf_sites || use_dsf_cheb || use_dsf_cv || use_dsf_dimer) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer, -dsf, -dsf_sites, -dsf_cheb, -dsf_cv, -dsf_dimer: Sz and Sp of every site of both centre blocks, on every rank */
+        if (use_corr_matrix || use_corr_dimer || use_dsf || use_dsf_sites || use_dsf_cheb || use_dsf_cv || use_dsf_dimer || use_dsf_pm) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer, -dsf, -dsf_sites, -dsf_cheb, -dsf_cv, -dsf_dimer, -dsf_pm: Sz and Sp of every site of both centre blocks, on every rank */
         need_built = true;
         return 0;
     }
@@ -2551,6 +2685,9 @@ private:
     PetscBool dsf_dimer_have_omega = PETSC_FALSE;
     std::vector<double> dsf_dimer_omega;        /* -dsf_dimer_omega w0,w1,nw: the grid of the Jackson-broadened SqwGrid */
     dmrgx_host::JsonRecordFile dsf_dimer_file{"%.17g"}; /* created at the first measurement with -dsf_dimer */
+    PetscBool use_dsf_pm = PETSC_FALSE;         /* -dsf_pm c0,c1,...: Chebyshev moments of the transverse correlations, TransverseDynamics.json (CalculateTransverseDynamics); shares the -dsf_cheb_* options */
+    std::vector<PetscInt> dsf_pm_sites;         /* the reference sites c, lattice numbering of To1D */
+    dmrgx_host::JsonRecordFile dsf_pm_file{"%.17g"};    /* created at the first measurement with -dsf_pm */
     PetscBool use_dsf_cv = PETSC_FALSE;         /* -dsf_cv c0,c1,...: correction vectors of G_ic(w + i eta), CorrectionVectors.json (CalculateCorrectionVectors) */
     std::vector<PetscInt> dsf_cv_sites;         /* the reference sites c, lattice numbering of To1D */
     std::vector<double> dsf_cv_omega;           /* -dsf_cv_omega w0,w1,nw: the frequencies, one solve per site and frequency */

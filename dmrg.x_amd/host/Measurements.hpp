@@ -5,7 +5,8 @@
     -dsf_dimer (CalculateDimerCorrelations, CalculateDimerDynamics): DimerFrame, the bond operators as terms, and BondsOfOrientation.  The four
     dynamical ones, -dsf, -dsf_sites, -dsf_cheb and -dsf_cv (CalculateDynamicalStructureFactor, CalculateDynamicalCorrelations,
     CalculateChebyshevCorrelations, CalculateCorrectionVectors): SzFrame, SiteCosineSum, the w0,w1,nw grid, the openings of their records;
-    the phase coefficients of -dsf, the window and the Jackson-damped sum of -dsf_cheb.  host_tool.cpp runs the pure parts without a GPU. */
+    the phase coefficients of -dsf, the window and the Jackson-damped sum of -dsf_cheb; -dsf_pm (CalculateTransverseDynamics): SzFrame over Sp or Sm
+    and the two-sided window.  host_tool.cpp runs the pure parts without a GPU. */
 #include <cmath>
 #include <deque>
 #include "DMRGKron.hpp"
@@ -91,7 +92,8 @@ private:
 /** Sz of every site of the centre superblock and the ground state it acts on: the set-up of -dsf, -dsf_sites, -dsf_cheb and -dsf_cv.
     Operator a of the table T is Sz of lattice site site[a], op_of is the inverse; (rx, ry)[s] is where LATTICE site s sits on the
     Lx x Ly lattice of M = Lx Ly sites.  psi: the n states on the device, norm = <psi|psi>; ld = n rounded up to even, the row length
-    of a family of vectors (the library streams rows in 16-byte loads). */
+    of a family of vectors (the library streams rows in 16-byte loads).  Init(..., OpSp) or (..., OpSm) gives the same frame over Sp or Sm
+    (Sp read transposed) of every site: the set-up of -dsf_pm, whose images live in another sector (ImagesTo). */
 struct SzFrame {
     CentreFrame F;
     SiteOperators T{F};
@@ -99,10 +101,10 @@ struct SzFrame {
     PetscInt Lx = 0, Ly = 0, M = 0;
     int64_t n = 0, ld = 0;
     const double* psi = nullptr; double norm = 0.0;
-    template<class Hamiltonian> PetscErrorCode Init(KronBlocks_t& KronBlocks, PetscInt num_sites, const Hamiltonian& Ham, const Vec& gsv_r, const char* display_name)
+    template<class Hamiltonian> PetscErrorCode Init(KronBlocks_t& KronBlocks, PetscInt num_sites, const Hamiltonian& Ham, const Vec& gsv_r, const char* display_name, Op_t type = OpSz)
     {
         PetscErrorCode ierr = F.Init(KronBlocks, num_sites, display_name); CHKERRQ(ierr);
-        ierr = T.AllSites(OpSz, site); CHKERRQ(ierr);
+        ierr = T.AllSites(type, site); CHKERRQ(ierr);
         op_of.assign((size_t)F.N, -1); rx.resize((size_t)F.N); ry.resize((size_t)F.N);
         for (PetscInt a = 0; a < F.N; ++a) op_of[(size_t)site[(size_t)a]] = a;
         for (PetscInt s = 0; s < F.N; ++s) {
@@ -114,7 +116,7 @@ struct SzFrame {
         if (dmrgx_dot(n, psi, psi, &norm, nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "dmrgx_dot: %s", dmrgx_last_error());
         return 0;
     }
-    /** coeff Sz of operator a, as a term of one vector. */
+    /** coeff times operator a (Sz of its site), as a term of one vector. */
     dmrgx_term term(PetscInt a, double coeff = 1.0) const { return a < F.nsites[0] ? dmrgx_term{coeff, (int32_t)a, -1} : dmrgx_term{coeff, -1, (int32_t)(a - F.nsites[0])}; }
     /** dmrgx_kron_term_apply on psi: vector j = the sum of terms[vec_first[j] .. vec_first[j + 1]), written to dst + j ld_dst. */
     PetscErrorCode Apply(PetscInt nvec, const int32_t* vec_first, const dmrgx_term* terms, double* dst, int64_t ld_dst) const
@@ -134,6 +136,22 @@ struct SzFrame {
             terms.clear(); vec_first.assign(1, 0);
             for (PetscInt j = j0; j < j0 + cnt; ++j) { terms.push_back(term(ops[j])); vec_first.push_back((int32_t)terms.size()); }
             PetscErrorCode ierr = Apply(cnt, vec_first.data(), terms.data(), dst + j0 * ld_dst, ld_dst); CHKERRQ(ierr);
+        }
+        return 0;
+    }
+    /** dst + j ld_dst = operator ops[j] on psi, j < count, written in the layout of the KronBlocks (out_il, out_ir)[0 .. n_out) of the sector
+        the operators lead to (dmrgx_kron_term_apply_to), in chunks of at most 1 GiB of images. */
+    PetscErrorCode ImagesTo(const PetscInt* ops, PetscInt count, const std::vector<int32_t>& out_il, const std::vector<int32_t>& out_ir, double* dst, int64_t ld_dst) const
+    {
+        const PetscInt per = std::max<PetscInt>(1, std::min<PetscInt>(F.N, (PetscInt)((((int64_t)1 << 30) / (int64_t)sizeof(double)) / std::max<int64_t>(ld_dst, 1))));
+        std::vector<dmrgx_term> terms; std::vector<int32_t> vec_first;
+        for (PetscInt j0 = 0; j0 < count; j0 += per) {
+            const PetscInt cnt = std::min<PetscInt>(per, count - j0);
+            terms.clear(); vec_first.assign(1, 0);
+            for (PetscInt j = j0; j < j0 + cnt; ++j) { terms.push_back(term(ops[j])); vec_first.push_back((int32_t)terms.size()); }
+            if (dmrgx_kron_term_apply_to(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
+                                         (int32_t)cnt, vec_first.data(), terms.data(), (int32_t)out_il.size(), out_il.data(), out_ir.data(), dst + j0 * ld_dst, ld_dst, nullptr))
+                SETERRQ1(PETSC_COMM_SELF, 1, "dmrgx_kron_term_apply_to: %s", dmrgx_last_error());
         }
         return 0;
     }
@@ -201,6 +219,31 @@ inline ChebyshevWindowResult ChebyshevWindow(double E0, const std::vector<double
     W.theta_max = theta[(size_t)top];
     W.residual = (size_t)done < alpha.size() ? 0.0 : beta[(size_t)(done - 1)] * std::fabs(vec[(size_t)(top * done + done - 1)]);
     const double width = W.theta_max - E0, hi = W.theta_max + W.residual + 0.02 * width, lo = E0 - 0.01 * width;
+    W.centre = 0.5 * (hi + lo); W.half_width = 0.5 * (hi - lo);
+    W.ok = W.half_width > 0.0 && std::isfinite(W.half_width) && std::isfinite(W.centre);
+    return W;
+}
+
+/** The window of a Chebyshev expansion in a sector whose bottom is not known (-dsf_pm: the neighbouring total-Sz sector, for which E0 of
+    the target sector is neither an upper nor a lower bound): both extreme Ritz values theta_min, theta_max of the Lanczos matrix of order
+    `done` (alpha, beta, done as for ChebyshevWindow) with their residual bounds res = beta_{done-1} |last component of the eigenvector|,
+    0 after a breakdown.  With width = theta_max - theta_min:  E_lo = theta_min - res_min - 0.02 width,  E_hi = theta_max + res_max +
+    0.02 width.  A residual bounds the distance to SOME eigenvalue, not to the extreme one: a window that is too tight is caught by the
+    guard of dmrgx_kron_chebyshev_moments (StepsDone < Steps).  ok false: done < 1, the QL iteration failed, or a window of no width. */
+struct ChebyshevWindowTwoSidedResult { double centre = 0.0, half_width = 0.0, theta_min = 0.0, theta_max = 0.0, res_min = 0.0, res_max = 0.0; bool ok = false; };
+inline ChebyshevWindowTwoSidedResult ChebyshevWindowTwoSided(const std::vector<double>& alpha, const std::vector<double>& beta, PetscInt done)
+{
+    ChebyshevWindowTwoSidedResult W;
+    if (done < 1 || (size_t)done > alpha.size() || beta.size() < alpha.size()) return W;
+    std::vector<double> theta(alpha.begin(), alpha.begin() + done), e(beta.begin(), beta.begin() + done), vec;
+    if (!TridiagQLVectors(theta, e, vec)) return W;
+    PetscInt top = 0, bot = 0;
+    for (PetscInt k = 1; k < done; ++k) { if (theta[(size_t)k] > theta[(size_t)top]) top = k; if (theta[(size_t)k] < theta[(size_t)bot]) bot = k; }
+    W.theta_max = theta[(size_t)top]; W.theta_min = theta[(size_t)bot];
+    const bool broke = (size_t)done < alpha.size();
+    W.res_max = broke ? 0.0 : beta[(size_t)(done - 1)] * std::fabs(vec[(size_t)(top * done + done - 1)]);
+    W.res_min = broke ? 0.0 : beta[(size_t)(done - 1)] * std::fabs(vec[(size_t)(bot * done + done - 1)]);
+    const double width = W.theta_max - W.theta_min, hi = W.theta_max + W.res_max + 0.02 * width, lo = W.theta_min - W.res_min - 0.02 * width;
     W.centre = 0.5 * (hi + lo); W.half_width = 0.5 * (hi - lo);
     W.ok = W.half_width > 0.0 && std::isfinite(W.half_width) && std::isfinite(W.centre);
     return W;

@@ -218,7 +218,14 @@ int main()
             for (double& x : b) is >> x;
             const dmrgx_host::ChebyshevWindowResult W = dmrgx_host::ChebyshevWindow(E0, a, b, done);
             printf("chebwindow %d %.17g %.17g %.17g %.17g\n", (int)W.ok, W.centre, W.half_width, W.theta_max, W.residual);
-        } else if (cmd == "chebjackson") {       /* chebjackson M nx mu_0 .. mu_{M-1} x_0 .. x_{nx-1}  ->  the damped sum at every x */
+        } else if (cmd == "chebwindow2") {       /* chebwindow2 nsteps done alpha_0 .. alpha_{nsteps-1} beta_0 .. beta_{nsteps-1}  ->  ok centre half_width theta_min theta_max res_min res_max */
+            size_t nsteps; PetscInt done; is >> nsteps >> done;
+            std::vector<double> a(nsteps), b(nsteps);
+            for (double& x : a) is >> x;
+            for (double& x : b) is >> x;
+            const dmrgx_host::ChebyshevWindowTwoSidedResult W = dmrgx_host::ChebyshevWindowTwoSided(a, b, done);
+            printf("chebwindow2 %d %.17g %.17g %.17g %.17g %.17g %.17g\n", (int)W.ok, W.centre, W.half_width, W.theta_min, W.theta_max, W.res_min, W.res_max);
+        } else if (cmd == "chebjackson") {      /* chebjackson M nx mu_0 .. mu_{M-1} x_0 .. x_{nx-1}  ->  the damped sum at every x */
             PetscInt M, nx; is >> M >> nx;
             std::vector<double> mu((size_t)M), xs((size_t)nx);
             for (double& v : mu) is >> v;

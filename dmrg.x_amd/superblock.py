@@ -386,6 +386,32 @@ def term_apply(sb_or_layout, psi, left_ops, right_ops, vectors, out=None):
     return out
 
 
+def term_apply_to(sb_or_layout, psi, left_ops, right_ops, vectors, out_blocks, out=None):
+    """Y[a, :n_out_states] = v_a as in term_apply, written in the reference layout of the KronBlock list out_blocks over the same sector
+    tables (dmrgx_kron_term_apply_to): the terms share one total sector shift of any value, and every sector pair they reach must be in
+    out_blocks.  out: as in term_apply with n_out_states in place of n_states; default: a new (len(vectors), n_out_states) tensor.
+    Returns Y."""
+    _capi.require_device()
+    args, psi, keep = _gram_arguments(sb_or_layout, psi, left_ops, right_ops)
+    left_sizes, right_sizes = (sb_or_layout.left_sizes, sb_or_layout.right_sizes) if hasattr(sb_or_layout, "blocks") else sb_or_layout[:2]
+    n = len(vectors)
+    first = _i32(list(np.cumsum([0] + [len(v) for v in vectors])))
+    flat = [t for v in vectors for t in v]
+    terms = (_capi.Term * max(len(flat), 1))()
+    for i, (c, l, r) in enumerate(flat):
+        terms[i].a, terms[i].left_op, terms[i].right_op = float(c), (-1 if l is None else int(l)), (-1 if r is None else int(r))
+    oil, oir = _i32([b[0] for b in out_blocks]), _i32([b[1] for b in out_blocks])
+    if out is None:
+        ns = sum(left_sizes[il] * right_sizes[ir] for il, ir in out_blocks)
+        out = torch.empty((max(n, 1), ns), dtype=torch.float64, device=psi.device)
+    assert out.dtype == torch.float64 and out.dim() == 2 and out.shape[0] >= n and (out.shape[1] <= 1 or out.stride(1) == 1)
+    ldy = out.stride(0) if out.shape[0] > 1 else out.shape[1]
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _capi.check(_capi.lib().dmrgx_kron_term_apply_to(*args, n, first, terms, len(out_blocks), oil, oir, C.c_void_p(out.data_ptr()), ldy, st))
+    torch.cuda.current_stream().synchronize()       # the operator copies in `keep` are read by the queued work
+    return out
+
+
 class ReducedDensityMatrices:
     """Device RDM blocks + spectra of a superblock state (GetTruncation's rank-0 loop,
     include/DMRGBlockContainer.hpp:1715-1775).  psi: device tensor in the reference's vector layout."""

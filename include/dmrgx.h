@@ -28,6 +28,7 @@
  *   dmrgx_kron_term_apply    <- nothing in the reference: engine extensions like the Gram calls.  The image vectors sum_t c_t (A_t (x) B_t) psi
  *   dmrgx_kron_lanczos_coeffs   themselves (the Gram calls only hand back their inner products) and the Lanczos coefficients of the planned
  *                               superblock Hamiltonian from such a vector: the continued fraction behind a dynamical structure factor
+ *   dmrgx_kron_term_apply_to    the same images written in the layout of another total-Sz sector: S+_i psi as start vectors of that sector's plan (-dsf_pm)
  *   dmrgx_kron_lanczos_basis    (-dsf); the same run with the basis kept and reorthogonalised, for overlaps with it (-dsf_sites)
  *   dmrgx_kron_chebyshev_moments  the Chebyshev recursion on the planned Hamiltonian and its moments with a family of vectors (-dsf_cheb)
  *   dmrgx_kron_correction_vector  the correction vector 1 / (sigma + i eta - H) v0 by a device-resident conjugate-gradient run, and its
@@ -470,6 +471,23 @@ dmrgx_status dmrgx_kron_term_apply(const dmrgx_sectors* left, const dmrgx_sector
                                    int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
                                    int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
                                    double* Y_dev, int64_t ldy, void* stream);
+/* Y[a*ldy + n] = v_a[n], n < n_out_states:  the same images written in the reference vector layout of a SECOND KronBlock list
+ * (n_out, out_il, out_ir) over the same two sector tables -- the nested list order, block j an n_L(out_il[j]) x n_R(out_ir[j]) row-major
+ * matrix, n_out_states the sum of those sizes.  This is how S+_i psi becomes a start vector for a plan of the neighbouring total-Sz
+ * sector.  Every other argument, and its checks, are those of dmrgx_kron_term_apply, which is this function with the output list equal
+ * to the input list (same bits).  Every term of a call has the same total shift s (DMRGX_ERR_ARG otherwise), and s may be any value.  A
+ * term with shifts (sA, sB) maps source KronBlock (IL, IR) to (IL - sA, IR - sB); a pair whose shifted sector does not exist contributes
+ * nothing, a pair that exists but is not in the output list is refused (DMRGX_ERR_ARG), not dropped.  An output KronBlock out of range
+ * gives DMRGX_ERR_OUTOFRANGE, one listed twice DMRGX_ERR_ARG.  Every element [0, n_out_states) of every vector is written exactly once --
+ * output blocks that no term reaches as exact zeros --, the columns from n_out_states to ldy are not touched.  ldy >= n_out_states; Y
+ * must not overlap psi; a null Y is DMRGX_ERR_ARG.  n_out == 0 is DMRGX_OK with nothing written (out_il, out_ir may then be NULL).
+ * Memory from the pool as for dmrgx_kron_term_apply.  No atomics: two calls give the same bits. */
+dmrgx_status dmrgx_kron_term_apply_to(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
+                                      const int32_t* block_il, const int32_t* block_ir, const double* psi_dev,
+                                      int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
+                                      int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
+                                      int32_t n_out, const int32_t* out_il, const int32_t* out_ir,
+                                      double* Y_dev, int64_t ldy, void* stream);
 
 /* ---- Lanczos coefficients from a given start vector (continued fractions: S(q, w)) ------------------------------------ */
 /* The plain three-term recursion with q_0 = v0 / |v0| on the planned Hamiltonian (world_size == 1; a striped plan is refused with
