@@ -1450,7 +1450,7 @@ public:
         }
         if (mpi_rank) return 0;
         ierr = spin_file.Begin(data_dir + "SpinCorrelations.json"); CHKERRQ(ierr);
-        fprintf(spin_file.fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"tCorrMatrix\": %.9g, \"Norm\": %.15g,\n   \"Sz\": ", LLD(GlobIdx), LoopType == WarmupStep ? "Warmup" : "Sweep", t1 - t0, norm);
+        fprintf(spin_file.fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"tCorrMatrix\": %.9g, \"Norm\": %.15g,\n   \"Sz\": ", LLD(GlobIdx), LoopTypeName(), t1 - t0, norm);
         spin_file.Row(Sz);
         fprintf(spin_file.fp, ",\n");
         spin_file.Table("SzSz", SzSz, N, N, ",\n"); spin_file.Table("SmSp", SmSp, N, N, ",\n"); spin_file.Table("SpSm", SpSm, N, N, ",\n"); spin_file.Table("SS", SS, N, N, ",\n"); spin_file.Table("StructureFactor", Sq, Lx, Ly, "}");
@@ -1522,7 +1522,7 @@ public:
         }
         PetscTime(&t1);
         if (verbose) printf("  * Dynamical structure factor: %lld q points, %lld Lanczos steps per run, %lld MatMults on %lld states, tDsf %.6f s\n", LLD(points.size()), LLD(dsf_steps), LLD(matmults), LLD(n), t1 - t0);
-        ierr = dsf_file.BeginDynamical(data_dir + "DynamicalStructureFactor.json", GlobIdx, LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, S.norm); CHKERRQ(ierr);
+        ierr = dsf_file.BeginDynamical(data_dir + "DynamicalStructureFactor.json", GlobIdx, LoopTypeName(), (double)E0, S.norm); CHKERRQ(ierr);
         FILE* fp_dsf = dsf_file.fp;
         fprintf(fp_dsf, ", \"Steps\": %lld, \"tDsf\": %.9g, \"MatMults\": %lld,\n   \"Points\": [\n", LLD(dsf_steps), t1 - t0, LLD(matmults));
         for (size_t iq = 0; iq < points.size(); ++iq) {
@@ -1624,7 +1624,7 @@ public:
         }
         PetscTime(&t1);
         if (verbose) printf("  * Dynamical correlations: %lld reference sites, %lld Lanczos steps per run with the basis kept, %lld MatMults on %lld states, images in chunks of %lld, tDsfSites %.6f s, of it the Lanczos runs %.6f s\n", LLD(runs.size()), LLD(K), LLD(matmults), LLD(n), LLD(chunk), t1 - t0, t_runs);
-        ierr = dsf_sites_file.BeginDynamical(data_dir + "DynamicalCorrelations.json", GlobIdx, LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, S.norm); CHKERRQ(ierr);
+        ierr = dsf_sites_file.BeginDynamical(data_dir + "DynamicalCorrelations.json", GlobIdx, LoopTypeName(), (double)E0, S.norm); CHKERRQ(ierr);
         FILE* fp = dsf_sites_file.fp;
         fprintf(fp, ", \"Steps\": %lld, \"tDsfSites\": %.9g, \"MatMults\": %lld,\n   \"Sites\": [\n", LLD(K), t1 - t0, LLD(matmults));
         for (size_t ir = 0; ir < runs.size(); ++ir) {
@@ -1666,88 +1666,62 @@ public:
         PetscErrorCode ierr = S.Init(KronBlocks, num_sites, Ham, gsv_r, "Chebyshev correlations"); CHKERRQ(ierr);
         const PetscInt N = S.F.N, M = S.M, K = dsf_cheb_steps;
         const int64_t n = S.n, ld = S.ld;
+        const std::vector<double>* omega = dsf_cheb_have_omega ? &dsf_cheb_omega : nullptr;
         /* the images of all sites, row s = Sz_s psi */
         std::unique_ptr<dmrgx_host::DevBuffer> U;
-        try { U.reset(new dmrgx_host::DevBuffer((size_t)(N * ld), dmrgx_host::DevBuffer::device_only_t{})); }
-        catch (const std::exception& e) { SETERRQ3(mpi_comm, PETSC_ERR_MEM, "Chebyshev correlations: no memory for the images of %lld sites x %lld states (%.3f GB): %s", LLD(N), LLD(n), (double)(N * ld) * 8e-9, e.what()); }
-        ierr = S.Images(S.op_of.data(), N, U->dev_uninitialised(), ld); CHKERRQ(ierr);
+        ierr = S.AllImages(U, n); CHKERRQ(ierr);
 
         /* the window */
-        PetscInt bound_steps = 0;
-        double centre, half_width, theta_max, residual = 0.0;
-        ierr = FindChebyshevWindow(H, n, (double)E0, "Chebyshev correlations", centre, half_width, theta_max, residual, bound_steps); CHKERRQ(ierr);
-        PetscInt matmults = bound_steps;
+        const double e0 = (double)E0;
+        dmrgx_host::ChebyshevSpectralWindow W;
+        ierr = FindChebyshevWindow(H, n, &e0, "Chebyshev correlations", W); CHKERRQ(ierr);
+        PetscInt matmults = W.bound_steps;
 
-        struct Run { PetscInt c = 0; double norm2 = 0.0; int32_t done = 0; std::vector<double> diag, mom, momq, grid; };
-        std::vector<Run> runs(dsf_cheb_sites.size());
-        std::vector<double> cross((size_t)((K + 1) * N));
+        std::vector<dmrgx_host::MomentRun> runs(dsf_cheb_sites.size());
+        std::vector<double> cross;
         double t_runs = 0.0;
         for (size_t ir = 0; ir < runs.size(); ++ir) {
-            Run& R = runs[ir];
+            dmrgx_host::MomentRun& R = runs[ir];
             R.c = dsf_cheb_sites[ir];
-            R.diag.assign((size_t)(2 * K + 1), 0.0);
-            PetscLogDouble tr0 = 0.0, tr1 = 0.0;
-            if (verbose) { if (dmrgx_stream_sync(nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error()); PetscTime(&tr0); }      /* the run alone, for the log */
-            if (dmrgx_kron_chebyshev_moments(H->plan, U->dev_ro() + R.c * ld, centre, half_width, (int32_t)K, (int32_t)N, U->dev_ro(), ld, &R.norm2, R.diag.data(), cross.data(), &R.done, nullptr))
-                SETERRQ1(mpi_comm, 1, "dmrgx_kron_chebyshev_moments: %s", dmrgx_last_error());
-            if (verbose) { PetscTime(&tr1); t_runs += tr1 - tr0; }
+            ierr = dmrgx_host::ChebyshevMomentRun(H->plan, U->dev_ro(), ld, N, W, K, S.norm, cross, R, verbose ? &t_runs : nullptr); CHKERRQ(ierr);
             matmults += K;
-            const PetscInt D = R.done, nm = D + 1;
-            if (D < K) printf("  * WARNING: -dsf_cheb: the run from site %lld left the window [%.6f, %.6f] after %lld of %lld steps; the record holds the moments up to there.\n", LLD(R.c), centre - half_width, centre + half_width, LLD(D), LLD(K));
-            R.diag.resize((size_t)(2 * D + 1));
-            for (double& x : R.diag) x /= S.norm;
-            R.mom.assign((size_t)(N * nm), 0.0);
-            for (PetscInt s = 0; s < N; ++s) for (PetscInt k = 0; k < nm; ++k) R.mom[(size_t)(s * nm + k)] = cross[(size_t)(k * N + s)] / S.norm;
-            R.momq = dmrgx_host::SiteCosineSum(S.Lx, S.Ly, S.rx.data(), S.ry.data(), R.c, R.mom.data(), N, nm);
-            if (dsf_cheb_have_omega) {
-                const PetscInt nw = (PetscInt)dsf_cheb_omega.size();
-                R.grid.assign((size_t)(M * nw), 0.0);
-                for (PetscInt q = 0; q < M; ++q) for (PetscInt k = 0; k < nw; ++k)
-                    R.grid[(size_t)(q * nw + k)] = dmrgx_host::ChebyshevJackson(R.momq.data() + q * nm, nm, (dsf_cheb_omega[(size_t)k] + (double)E0 - centre) / half_width) / half_width;
-            }
+            dmrgx_host::WarnLeftWindow("-dsf_cheb", nullptr, "site", R, W, K);
+            R.momq = dmrgx_host::SiteCosineSum(S.Lx, S.Ly, S.rx.data(), S.ry.data(), R.c, R.mom.data(), N, R.done + 1);
+            if (omega) R.grid = dmrgx_host::ChebyshevGrid(R.momq, R.done + 1, *omega, e0, W.centre, W.half_width);
         }
         PetscTime(&t1);
         if (verbose) printf("  * Chebyshev correlations: %lld reference sites, %lld steps per run, window [%.6f, %.6f] from %lld Lanczos steps, %lld MatMults on %lld states, tDsfCheb %.6f s, of it the Chebyshev runs %.6f s\n",
-                            LLD(runs.size()), LLD(K), centre - half_width, centre + half_width, LLD(bound_steps), LLD(matmults), LLD(n), t1 - t0, t_runs);
-        ierr = dsf_cheb_file.BeginDynamical(data_dir + "ChebyshevMoments.json", GlobIdx, LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, S.norm); CHKERRQ(ierr);
+                            LLD(runs.size()), LLD(K), W.centre - W.half_width, W.centre + W.half_width, LLD(W.bound_steps), LLD(matmults), LLD(n), t1 - t0, t_runs);
+        ierr = dsf_cheb_file.BeginDynamical(data_dir + "ChebyshevMoments.json", GlobIdx, LoopTypeName(), e0, S.norm); CHKERRQ(ierr);
         FILE* fp = dsf_cheb_file.fp;
         fprintf(fp, ", \"Steps\": %lld, \"Centre\": %.17g, \"HalfWidth\": %.17g, \"BoundSteps\": %lld, \"ThetaMax\": %.17g, \"Residual\": %.17g, \"tDsfCheb\": %.9g, \"MatMults\": %lld,\n",
-                LLD(K), centre, half_width, LLD(bound_steps), theta_max, residual, t1 - t0, LLD(matmults));
-        if (dsf_cheb_have_omega) { fprintf(fp, "   \"Omega\": "); dsf_cheb_file.Row(dsf_cheb_omega); fprintf(fp, ",\n"); }
+                LLD(K), W.centre, W.half_width, LLD(W.bound_steps), W.theta_max, W.residual, t1 - t0, LLD(matmults));
+        dsf_cheb_file.Omega(omega);
         fprintf(fp, "   \"Sites\": [\n");
         for (size_t ir = 0; ir < runs.size(); ++ir) {
-            const Run& R = runs[ir];
-            const PetscInt nm = R.done + 1;
-            const char* end = ir + 1 < runs.size() ? "},\n" : "}\n";
+            const dmrgx_host::MomentRun& R = runs[ir];
             dsf_cheb_file.OpenSite(R.c, S.rx[(size_t)R.c], S.ry[(size_t)R.c], R.norm2);
-            fprintf(fp, ", \"StepsDone\": %d,\n   \"Diag\": ", (int)R.done);
-            dsf_cheb_file.Row(R.diag); fprintf(fp, ",\n");
-            dsf_cheb_file.Table("Moments", R.mom, N, nm, ",\n");
-            dsf_cheb_file.Table("MomentsQ", R.momq, M, nm, dsf_cheb_have_omega ? ",\n" : end);
-            if (dsf_cheb_have_omega) dsf_cheb_file.Table("SqwGrid", R.grid, M, (PetscInt)dsf_cheb_omega.size(), end);
+            fprintf(fp, ", \"StepsDone\": %d", (int)R.done);
+            dsf_cheb_file.Moments(R, N, M, omega, ir + 1 < runs.size() ? "},\n" : "}\n");
         }
         fprintf(fp, "   ]}");
         fflush(fp);
         return 0;
     }
 
-    /** The window [centre - half_width, centre + half_width] of a Chebyshev expansion on the planned Hamiltonian of n states, for -dsf_cheb and
-        -dsf_dimer: -dsf_cheb_window lo,hi as given (bound_steps 0, theta_max = hi), else from -dsf_cheb_bound_steps Lanczos steps
-        (dmrgx_kron_lanczos_coeffs) from a fixed pseudo-random vector and the known bottom E0 (ChebyshevWindow, Measurements.hpp). */
-    PetscErrorCode FindChebyshevWindow(Mat& H, int64_t n, double E0, const char* name, double& centre, double& half_width, double& theta_max, double& residual, PetscInt& bound_steps)
+    /** The window of a Chebyshev expansion on the planned Hamiltonian of n states, for -dsf_cheb, -dsf_dimer and -dsf_pm: -dsf_cheb_window lo,hi as given
+        (bound_steps 0, theta_min = lo, theta_max = hi), else from -dsf_cheb_bound_steps Lanczos steps from a fixed pseudo-random vector (ChebyshevBoundRun):
+        above the known bottom *E0 (ChebyshevWindow, Measurements.hpp), or, E0 null, a sector whose bottom is not known (ChebyshevWindowTwoSided). */
+    PetscErrorCode FindChebyshevWindow(Mat& H, int64_t n, const double* E0, const std::string& name, dmrgx_host::ChebyshevSpectralWindow& W)
     {
-        residual = 0.0; bound_steps = 0;
-        if (dsf_cheb_have_window) {
-            centre = 0.5 * (dsf_cheb_window[0] + dsf_cheb_window[1]); half_width = 0.5 * (dsf_cheb_window[1] - dsf_cheb_window[0]); theta_max = dsf_cheb_window[1];
-            return 0;
-        }
+        const double lo = dsf_cheb_window[0], hi = dsf_cheb_window[1];
+        if (dsf_cheb_have_window) { W = dmrgx_host::ChebyshevSpectralWindow{0.5 * (lo + hi), 0.5 * (hi - lo), lo, hi, 0.0, 0.0, 0, true}; return 0; }
         std::vector<double> a, b;
         int32_t done = 0;
         PetscErrorCode ierr = ChebyshevBoundRun(H, n, a, b, done); CHKERRQ(ierr);
-        bound_steps = dsf_cheb_bound_steps;
-        const dmrgx_host::ChebyshevWindowResult W = dmrgx_host::ChebyshevWindow(E0, a, b, done);
-        if (!W.ok) SETERRQ2(mpi_comm, 1, "%s: no spectral window from %d Lanczos steps.", name, (int)done);
-        centre = W.centre; half_width = W.half_width; theta_max = W.theta_max; residual = W.residual;
+        W = E0 ? dmrgx_host::ChebyshevWindow(*E0, a, b, done) : dmrgx_host::ChebyshevWindowTwoSided(a, b, done);
+        W.bound_steps = dsf_cheb_bound_steps;
+        if (!W.ok) SETERRQ2(mpi_comm, 1, "%s: no spectral window from %d Lanczos steps.", name.c_str(), (int)done);
         return 0;
     }
 
@@ -1774,7 +1748,7 @@ public:
         transposed), < S^+_i ... S^-_c > -- the magnons of an XXZ model or of a magnetised target, which S^zz (-dsf_cheb) does not hold.
         O psi lives in the total-Sz sector qn_sector + 1 (- 1), so H' is the superblock Hamiltonian of THAT sector: per channel a
         KronBlocks_t of the neighbouring sector over the same two blocks, the images of all N sites written in its layout
-        (SzFrame::ImagesTo, dmrgx_kron_term_apply_to) -- N x N_sb' doubles, refused with PETSC_ERR_MEM if they do not fit --, its plan
+        (SzFrame::AllImages, dmrgx_kron_term_apply_to) -- N x N_sb' doubles, refused with PETSC_ERR_MEM if they do not fit --, its plan
         (KronSumConstruct with the settings of the ground-state plan), and one dmrgx_kron_chebyshev_moments run per reference site.  The
         measurement runs after the ground-state plan is destroyed and destroys each plan before the next: one plan is resident at a time.
         The window is -dsf_cheb_window lo,hi as given (ThetaMin = lo, ThetaMax = hi), else from -dsf_cheb_bound_steps Lanczos steps on
@@ -1802,19 +1776,17 @@ public:
             KronBlocks_t KB1(KronBlocks.LeftBlockRefMod(), KronBlocks.RightBlockRefMod(), {sector}, NULL, GlobIdx);
             const int64_t n1 = KB1.NumStates(), ld1 = n1 + (n1 & 1);
 
-            struct Run { PetscInt c = 0; double norm2 = 0.0; int32_t done = 0; std::vector<double> diag, mom, momq, grid; };
-            std::vector<Run> runs(dsf_pm_sites.size());
+            const std::vector<double>* omega = dsf_cheb_have_omega ? &dsf_cheb_omega : nullptr;
+            std::vector<dmrgx_host::MomentRun> runs(dsf_pm_sites.size());
             for (size_t ir = 0; ir < runs.size(); ++ir) runs[ir].c = dsf_pm_sites[ir];
-            PetscInt bound_steps = 0, matmults = 0;
-            double centre = 0.0, half_width = 0.0, theta_min = 0.0, theta_max = 0.0;
+            PetscInt matmults = 0;
+            dmrgx_host::ChebyshevSpectralWindow W;
             if (n1 > 0) {
                 /* the images of all sites in the layout of KB1, row s = O_s psi */
                 std::vector<int32_t> out_il, out_ir;
                 for (PetscInt k = 0; k < KB1.size(); ++k) { out_il.push_back((int32_t)KB1.LeftIdx(k)); out_ir.push_back((int32_t)KB1.RightIdx(k)); }
                 std::unique_ptr<dmrgx_host::DevBuffer> U;
-                try { U.reset(new dmrgx_host::DevBuffer((size_t)(N * ld1), dmrgx_host::DevBuffer::device_only_t{})); }
-                catch (const std::exception& e) { SETERRQ4(mpi_comm, PETSC_ERR_MEM, "Transverse dynamics: no memory for the images of %lld sites x %lld states (%.3f GB): %s", LLD(N), LLD(n1), (double)(N * ld1) * 8e-9, e.what()); }
-                ierr = S.ImagesTo(S.op_of.data(), N, out_il, out_ir, U->dev_uninitialised(), ld1); CHKERRQ(ierr);
+                ierr = S.AllImages(U, n1, &out_il, &out_ir); CHKERRQ(ierr);
                 /* the plan of the neighbouring sector */
                 Mat H1 = nullptr;
                 ierr = KB1.KronSumSetRedistribute(PETSC_TRUE); CHKERRQ(ierr);
@@ -1822,65 +1794,37 @@ public:
                 ierr = KB1.KronSumSetShellMatrix(do_shell); CHKERRQ(ierr);
                 ierr = KB1.KronSumConstruct(Terms, H1); CHKERRQ(ierr);
                 if (!H1) SETERRQ(mpi_comm, 1, "Transverse dynamics: H is null.");
-                /* the window */
-                if (dsf_cheb_have_window) {
-                    theta_min = dsf_cheb_window[0]; theta_max = dsf_cheb_window[1];
-                    centre = 0.5 * (theta_min + theta_max); half_width = 0.5 * (theta_max - theta_min);
-                } else {
-                    std::vector<double> a, b;
-                    int32_t done = 0;
-                    ierr = ChebyshevBoundRun(H1, n1, a, b, done); CHKERRQ(ierr);
-                    bound_steps = dsf_cheb_bound_steps;
-                    const dmrgx_host::ChebyshevWindowTwoSidedResult W = dmrgx_host::ChebyshevWindowTwoSided(a, b, done);
-                    if (!W.ok) SETERRQ2(mpi_comm, 1, "Transverse dynamics (%s): no spectral window from %d Lanczos steps.", cname, (int)done);
-                    centre = W.centre; half_width = W.half_width; theta_min = W.theta_min; theta_max = W.theta_max;
-                }
-                matmults = bound_steps;
-                std::vector<double> cross((size_t)((K + 1) * N));
-                for (Run& R : runs) {
-                    R.diag.assign((size_t)(2 * K + 1), 0.0);
-                    if (dmrgx_kron_chebyshev_moments(H1->plan, U->dev_ro() + R.c * ld1, centre, half_width, (int32_t)K, (int32_t)N, U->dev_ro(), ld1, &R.norm2, R.diag.data(), cross.data(), &R.done, nullptr))
-                        SETERRQ1(mpi_comm, 1, "dmrgx_kron_chebyshev_moments: %s", dmrgx_last_error());
+                /* the window: the bottom of this sector is not known */
+                ierr = FindChebyshevWindow(H1, n1, nullptr, std::string("Transverse dynamics (") + cname + ")", W); CHKERRQ(ierr);
+                matmults = W.bound_steps;
+                std::vector<double> cross;
+                for (dmrgx_host::MomentRun& R : runs) {
+                    ierr = dmrgx_host::ChebyshevMomentRun(H1->plan, U->dev_ro(), ld1, N, W, K, S.norm, cross, R, nullptr); CHKERRQ(ierr);
                     matmults += K;
-                    const PetscInt D = R.done, nm = D + 1;
                     if (R.norm2 == 0.0) printf("  * -dsf_pm (%s): the image of site %lld is zero in the bases of the blocks; no run.\n", cname, LLD(R.c));
-                    else if (D < K) printf("  * WARNING: -dsf_pm (%s): the run from site %lld left the window [%.6f, %.6f] after %lld of %lld steps; the record holds the moments up to there.\n", cname, LLD(R.c), centre - half_width, centre + half_width, LLD(D), LLD(K));
-                    R.diag.resize((size_t)(2 * D + 1));
-                    for (double& x : R.diag) x /= S.norm;
-                    R.mom.assign((size_t)(N * nm), 0.0);
-                    for (PetscInt s = 0; s < N; ++s) for (PetscInt k = 0; k < nm; ++k) R.mom[(size_t)(s * nm + k)] = cross[(size_t)(k * N + s)] / S.norm;
-                    R.momq = dmrgx_host::SiteCosineSum(S.Lx, S.Ly, S.rx.data(), S.ry.data(), R.c, R.mom.data(), N, nm);
-                    if (dsf_cheb_have_omega) {
-                        const PetscInt nw = (PetscInt)dsf_cheb_omega.size();
-                        R.grid.assign((size_t)(M * nw), 0.0);
-                        for (PetscInt q = 0; q < M; ++q) for (PetscInt k = 0; k < nw; ++k)
-                            R.grid[(size_t)(q * nw + k)] = dmrgx_host::ChebyshevJackson(R.momq.data() + q * nm, nm, (dsf_cheb_omega[(size_t)k] + (double)E0 - centre) / half_width) / half_width;
-                    }
+                    else dmrgx_host::WarnLeftWindow("-dsf_pm", cname, "site", R, W, K);
+                    R.momq = dmrgx_host::SiteCosineSum(S.Lx, S.Ly, S.rx.data(), S.ry.data(), R.c, R.mom.data(), N, R.done + 1);
+                    if (omega) R.grid = dmrgx_host::ChebyshevGrid(R.momq, R.done + 1, *omega, (double)E0, W.centre, W.half_width);
                 }
                 ierr = MatDestroy_KronSumShell(&H1); CHKERRQ(ierr);
                 ierr = MatDestroy(&H1); CHKERRQ(ierr);
             }                                                       /* (the images go back to the pool here) */
             PetscTime(&t1);
             if (verbose) printf("  * Transverse dynamics (%s): sector %g, %lld reference sites, %lld steps per run, window [%.6f, %.6f] from %lld Lanczos steps, %lld MatMults on %lld states, tDsfPm %.6f s\n",
-                                cname, (double)sector, LLD(runs.size()), LLD(K), centre - half_width, centre + half_width, LLD(bound_steps), LLD(matmults), LLD(n1), t1 - t0);
-            ierr = dsf_pm_file.BeginDynamical(data_dir + "TransverseDynamics.json", GlobIdx, LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, S.norm); CHKERRQ(ierr);
+                                cname, (double)sector, LLD(runs.size()), LLD(K), W.centre - W.half_width, W.centre + W.half_width, LLD(W.bound_steps), LLD(matmults), LLD(n1), t1 - t0);
+            ierr = dsf_pm_file.BeginDynamical(data_dir + "TransverseDynamics.json", GlobIdx, LoopTypeName(), (double)E0, S.norm); CHKERRQ(ierr);
             FILE* fp = dsf_pm_file.fp;
             fprintf(fp, ", \"Channel\": \"%s\", \"Sector\": %.17g, \"States\": %lld, \"Steps\": %lld, \"Centre\": %.17g, \"HalfWidth\": %.17g, \"BoundSteps\": %lld, \"ThetaMin\": %.17g, \"ThetaMax\": %.17g, \"tDsfPm\": %.9g, \"MatMults\": %lld,\n",
-                    cname, (double)sector, LLD(n1), LLD(K), centre, half_width, LLD(bound_steps), theta_min, theta_max, t1 - t0, LLD(matmults));
-            if (dsf_cheb_have_omega) { fprintf(fp, "   \"Omega\": "); dsf_pm_file.Row(dsf_cheb_omega); fprintf(fp, ",\n"); }
+                    cname, (double)sector, LLD(n1), LLD(K), W.centre, W.half_width, LLD(W.bound_steps), W.theta_min, W.theta_max, t1 - t0, LLD(matmults));
+            dsf_pm_file.Omega(omega);
             fprintf(fp, "   \"Sites\": [\n");
             for (size_t ir = 0; ir < runs.size(); ++ir) {
-                const Run& R = runs[ir];
-                const PetscInt nm = R.done + 1;
+                const dmrgx_host::MomentRun& R = runs[ir];
                 const char* end = ir + 1 < runs.size() ? "},\n" : "}\n";
                 dsf_pm_file.OpenSite(R.c, S.rx[(size_t)R.c], S.ry[(size_t)R.c], R.norm2);
                 fprintf(fp, ", \"StepsDone\": %d", (int)R.done);
-                if (n1 == 0) { fprintf(fp, "%s", end); continue; }          /* no run: no moments */
-                fprintf(fp, ",\n   \"Diag\": ");
-                dsf_pm_file.Row(R.diag); fprintf(fp, ",\n");
-                dsf_pm_file.Table("Moments", R.mom, N, nm, ",\n");
-                dsf_pm_file.Table("MomentsQ", R.momq, M, nm, dsf_cheb_have_omega ? ",\n" : end);
-                if (dsf_cheb_have_omega) dsf_pm_file.Table("SqwGrid", R.grid, M, (PetscInt)dsf_cheb_omega.size(), end);
+                if (n1 == 0) fprintf(fp, "%s", end);                       /* no run: no moments */
+                else dsf_pm_file.Moments(R, N, M, omega, end);
             }
             fprintf(fp, "   ]}");
             fflush(fp);
@@ -1925,76 +1869,50 @@ public:
         if (dmrgx_vec_project_out((int32_t)nb, n, U->dev_uninitialised(), ld, B.psi, D.data(), &norm, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_vec_project_out: %s", dmrgx_last_error());
         if (!(norm > 0.0)) SETERRQ(mpi_comm, 1, "Dimer dynamics: the ground state has no norm.");
 
-        PetscInt bound_steps = 0;
-        double centre, half_width, theta_max, residual = 0.0;
-        ierr = FindChebyshevWindow(H, n, (double)E0, "Dimer dynamics", centre, half_width, theta_max, residual, bound_steps); CHKERRQ(ierr);
-        PetscInt matmults = bound_steps;
+        const double e0 = (double)E0;
+        const std::vector<double>* omega = dsf_dimer_have_omega ? &dsf_dimer_omega : nullptr;
+        dmrgx_host::ChebyshevSpectralWindow W;
+        ierr = FindChebyshevWindow(H, n, &e0, "Dimer dynamics", W); CHKERRQ(ierr);
+        PetscInt matmults = W.bound_steps;
 
         const dmrgx_host::OrientedBonds oriented[2] = {dmrgx_host::BondsOfOrientation(B.bonds, 'x'), dmrgx_host::BondsOfOrientation(B.bonds, 'y')};
-        struct Run { PetscInt c = 0; double norm2 = 0.0, elastic = 0.0; int32_t done = 0; std::vector<double> diag, mom, momq, grid; };
-        std::vector<Run> runs(dsf_dimer_bonds.size());
-        std::vector<double> cross((size_t)((K + 1) * nb));
+        std::vector<dmrgx_host::MomentRun> runs(dsf_dimer_bonds.size());
+        std::vector<double> cross;
         double t_runs = 0.0;
         for (size_t ir = 0; ir < runs.size(); ++ir) {
-            Run& R = runs[ir];
+            dmrgx_host::MomentRun& R = runs[ir];
             R.c = dsf_dimer_bonds[ir];
-            R.diag.assign((size_t)(2 * K + 1), 0.0);
-            const double* v0 = U->dev_ro() + R.c * ld;
-            PetscLogDouble tr0 = 0.0, tr1 = 0.0;
-            if (verbose) { if (dmrgx_stream_sync(nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error()); PetscTime(&tr0); }      /* the run alone, for the log */
-            if (dmrgx_kron_chebyshev_moments(H->plan, v0, centre, half_width, (int32_t)K, (int32_t)nb, U->dev_ro(), ld, &R.norm2, R.diag.data(), cross.data(), &R.done, nullptr))
-                SETERRQ1(mpi_comm, 1, "dmrgx_kron_chebyshev_moments: %s", dmrgx_last_error());
-            if (verbose) { PetscTime(&tr1); t_runs += tr1 - tr0; }
+            ierr = dmrgx_host::ChebyshevMomentRun(H->plan, U->dev_ro(), ld, nb, W, K, norm, cross, R, verbose ? &t_runs : nullptr); CHKERRQ(ierr);
             matmults += K;
             double overlap = 0.0;
-            if (dmrgx_dot(n, B.psi, v0, &overlap, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
+            if (dmrgx_dot(n, B.psi, U->dev_ro() + R.c * ld, &overlap, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
             R.elastic = R.norm2 > 0.0 ? overlap / std::sqrt(norm * R.norm2) : 0.0;
-            const PetscInt Dn = R.done, nm = Dn + 1;
-            if (Dn < K) printf("  * WARNING: -dsf_dimer: the run from bond %lld left the window [%.6f, %.6f] after %lld of %lld steps; the record holds the moments up to there.\n", LLD(R.c), centre - half_width, centre + half_width, LLD(Dn), LLD(K));
-            R.diag.resize((size_t)(2 * Dn + 1));
-            for (double& x : R.diag) x /= norm;
-            R.mom.assign((size_t)(nb * nm), 0.0);
-            for (PetscInt b = 0; b < nb; ++b) for (PetscInt k = 0; k < nm; ++k) R.mom[(size_t)(b * nm + k)] = cross[(size_t)(k * nb + b)] / norm;
+            dmrgx_host::WarnLeftWindow("-dsf_dimer", nullptr, "bond", R, W, K);
             /* the cosine sum over the bonds of c's orientation, from c */
+            const PetscInt nm = R.done + 1;
             const dmrgx_host::OrientedBonds& O = oriented[B.bonds[(size_t)R.c].orient == 'x' ? 0 : 1];
             const PetscInt no = (PetscInt)O.of.size(), c_in = (PetscInt)(std::find(O.of.begin(), O.of.end(), R.c) - O.of.begin());
             std::vector<double> sel((size_t)(no * nm));
             for (PetscInt k = 0; k < no; ++k) std::copy(R.mom.begin() + O.of[(size_t)k] * nm, R.mom.begin() + (O.of[(size_t)k] + 1) * nm, sel.begin() + k * nm);
             R.momq = dmrgx_host::SiteCosineSum(Lx, Ly, O.x.data(), O.y.data(), c_in, sel.data(), no, nm);
-            if (dsf_dimer_have_omega) {
-                const PetscInt nw = (PetscInt)dsf_dimer_omega.size();
-                R.grid.assign((size_t)(M * nw), 0.0);
-                for (PetscInt q = 0; q < M; ++q) for (PetscInt k = 0; k < nw; ++k)
-                    R.grid[(size_t)(q * nw + k)] = dmrgx_host::ChebyshevJackson(R.momq.data() + q * nm, nm, (dsf_dimer_omega[(size_t)k] + (double)E0 - centre) / half_width) / half_width;
-            }
+            if (omega) R.grid = dmrgx_host::ChebyshevGrid(R.momq, nm, *omega, e0, W.centre, W.half_width);
         }
         PetscTime(&t1);
         if (verbose) printf("  * Dimer dynamics: %lld reference bonds of %lld, %lld steps per run, window [%.6f, %.6f] from %lld Lanczos steps, %lld MatMults on %lld states, tDimerDyn %.6f s, of it the Chebyshev runs %.6f s\n",
-                            LLD(runs.size()), LLD(nb), LLD(K), centre - half_width, centre + half_width, LLD(bound_steps), LLD(matmults), LLD(n), t1 - t0, t_runs);
-        ierr = dsf_dimer_file.BeginDynamical(data_dir + "DimerDynamics.json", GlobIdx, LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, norm); CHKERRQ(ierr);
+                            LLD(runs.size()), LLD(nb), LLD(K), W.centre - W.half_width, W.centre + W.half_width, LLD(W.bound_steps), LLD(matmults), LLD(n), t1 - t0, t_runs);
+        ierr = dsf_dimer_file.BeginDynamical(data_dir + "DimerDynamics.json", GlobIdx, LoopTypeName(), e0, norm); CHKERRQ(ierr);
         FILE* fp = dsf_dimer_file.fp;
-        fprintf(fp, ", \"Steps\": %lld, \"Centre\": %.17g, \"HalfWidth\": %.17g, \"BoundSteps\": %lld, \"ThetaMax\": %.17g, \"Residual\": %.17g, \"tDimerDyn\": %.9g, \"MatMults\": %lld,\n   \"Bonds\": [",
-                LLD(K), centre, half_width, LLD(bound_steps), theta_max, residual, t1 - t0, LLD(matmults));
-        for (PetscInt b = 0; b < nb; ++b) fprintf(fp, "%s[%lld, %lld]", b ? ", " : "", LLD(B.bonds[(size_t)b].i), LLD(B.bonds[(size_t)b].j));
-        fprintf(fp, "],\n   \"Orientation\": [");
-        for (PetscInt b = 0; b < nb; ++b) fprintf(fp, "%s\"%c\"", b ? ", " : "", B.bonds[(size_t)b].orient);
-        fprintf(fp, "],\n   \"Position\": [");
-        for (PetscInt b = 0; b < nb; ++b) fprintf(fp, "%s[%lld, %lld]", b ? ", " : "", LLD(B.bonds[(size_t)b].ix), LLD(B.bonds[(size_t)b].jy));
-        fprintf(fp, "],\n   \"D\": ");
-        dsf_dimer_file.Row(D); fprintf(fp, ",\n");
-        if (dsf_dimer_have_omega) { fprintf(fp, "   \"Omega\": "); dsf_dimer_file.Row(dsf_dimer_omega); fprintf(fp, ",\n"); }
+        fprintf(fp, ", \"Steps\": %lld, \"Centre\": %.17g, \"HalfWidth\": %.17g, \"BoundSteps\": %lld, \"ThetaMax\": %.17g, \"Residual\": %.17g, \"tDimerDyn\": %.9g, \"MatMults\": %lld,\n",
+                LLD(K), W.centre, W.half_width, LLD(W.bound_steps), W.theta_max, W.residual, t1 - t0, LLD(matmults));
+        dsf_dimer_file.BondHeader(B.bonds, D);
+        dsf_dimer_file.Omega(omega);
         fprintf(fp, "   \"RefBonds\": [\n");
         for (size_t ir = 0; ir < runs.size(); ++ir) {
-            const Run& R = runs[ir];
+            const dmrgx_host::MomentRun& R = runs[ir];
             const dmrgx_host::DimerBond& bc = B.bonds[(size_t)R.c];
-            const PetscInt nm = R.done + 1;
-            const char* end = ir + 1 < runs.size() ? "},\n" : "}\n";
-            fprintf(fp, "   {\"Bond\": %lld, \"Sites\": [%lld, %lld], \"Orientation\": \"%c\", \"Norm2\": %.17g, \"Elastic\": %.17g, \"StepsDone\": %d,\n   \"Diag\": ",
+            fprintf(fp, "   {\"Bond\": %lld, \"Sites\": [%lld, %lld], \"Orientation\": \"%c\", \"Norm2\": %.17g, \"Elastic\": %.17g, \"StepsDone\": %d",
                     LLD(R.c), LLD(bc.i), LLD(bc.j), bc.orient, R.norm2, R.elastic, (int)R.done);
-            dsf_dimer_file.Row(R.diag); fprintf(fp, ",\n");
-            dsf_dimer_file.Table("Moments", R.mom, nb, nm, ",\n");
-            dsf_dimer_file.Table("MomentsQ", R.momq, M, nm, dsf_dimer_have_omega ? ",\n" : end);
-            if (dsf_dimer_have_omega) dsf_dimer_file.Table("SqwGrid", R.grid, M, (PetscInt)dsf_dimer_omega.size(), end);
+            dsf_dimer_file.Moments(R, nb, M, omega, ir + 1 < runs.size() ? "},\n" : "}\n");
         }
         fprintf(fp, "   ]}");
         fflush(fp);
@@ -2062,7 +1980,7 @@ public:
         PetscTime(&t1);
         if (verbose) printf("  * Correction vectors: %lld reference sites x %lld frequencies, eta %.6f, %lld iterations, %lld MatMults on %lld states, tDsfCv %.6f s\n",
                             LLD(runs.size()), LLD(nw), dsf_cv_eta, LLD(iterations), LLD(matmults), LLD(n), t1 - t0);
-        ierr = dsf_cv_file.BeginDynamical(data_dir + "CorrectionVectors.json", GlobIdx, LoopType == WarmupStep ? "Warmup" : "Sweep", (double)E0, S.norm); CHKERRQ(ierr);
+        ierr = dsf_cv_file.BeginDynamical(data_dir + "CorrectionVectors.json", GlobIdx, LoopTypeName(), (double)E0, S.norm); CHKERRQ(ierr);
         FILE* fp = dsf_cv_file.fp;
         fprintf(fp, ", \"Eta\": %.17g, \"Tol\": %.17g, \"MaxIt\": %lld, \"tDsfCv\": %.9g, \"MatMults\": %lld,\n   \"Omega\": ", dsf_cv_eta, dsf_cv_tol, LLD(dsf_cv_maxit), t1 - t0, LLD(matmults));
         dsf_cv_file.Row(dsf_cv_omega);
@@ -2129,15 +2047,8 @@ public:
         if (mpi_rank) return 0;
         ierr = dimer_file.Begin(data_dir + "DimerCorrelations.json"); CHKERRQ(ierr);
         FILE* fp_dimer = dimer_file.fp;
-        fprintf(fp_dimer, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"tDimer\": %.9g, \"Norm\": %.15g,\n   \"Bonds\": [", LLD(GlobIdx), LoopType == WarmupStep ? "Warmup" : "Sweep", t1 - t0, norm);
-        for (PetscInt b = 0; b < nb; ++b) fprintf(fp_dimer, "%s[%lld, %lld]", b ? ", " : "", LLD(bonds[(size_t)b].i), LLD(bonds[(size_t)b].j));
-        fprintf(fp_dimer, "],\n   \"Orientation\": [");
-        for (PetscInt b = 0; b < nb; ++b) fprintf(fp_dimer, "%s\"%c\"", b ? ", " : "", bonds[(size_t)b].orient);
-        fprintf(fp_dimer, "],\n   \"Position\": [");
-        for (PetscInt b = 0; b < nb; ++b) fprintf(fp_dimer, "%s[%lld, %lld]", b ? ", " : "", LLD(bonds[(size_t)b].ix), LLD(bonds[(size_t)b].jy));
-        fprintf(fp_dimer, "],\n   \"D\": ");
-        dimer_file.Row(D);
-        fprintf(fp_dimer, ",\n");
+        fprintf(fp_dimer, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"tDimer\": %.9g, \"Norm\": %.15g,\n", LLD(GlobIdx), LoopTypeName(), t1 - t0, norm);
+        dimer_file.BondHeader(bonds, D);
         dimer_file.Table("DD", DD, nb, nb, ",\n"); dimer_file.Table("Connected", Conn, nb, nb, ",\n"); dimer_file.Table("StructureFactorX", Sq[0], Lx, Ly, ",\n"); dimer_file.Table("StructureFactorY", Sq[1], Lx, Ly, "}");
         fflush(fp_dimer);
         return 0;
@@ -2484,6 +2395,7 @@ private:
     typedef enum { SWEEP_MODE_NULL, SWEEP_MODE_NSWEEPS, SWEEP_MODE_MSWEEPS, SWEEP_MODE_TOLERANCE_TEST } SweepMode_t;
 
     Block& AddSite() { return SingleSite; }
+    const char* LoopTypeName() const { return LoopType == WarmupStep ? "Warmup" : "Sweep"; }      /* "LoopType" in the record of a measurement */
 
     void PrintBlocks(const PetscInt& nsys, const PetscInt& nenv) const { printf("  [%lld]-* *-[%lld]\n", LLD(nsys), LLD(nenv)); }
 

@@ -2,11 +2,11 @@
 #define DMRGX_HOST_MEASUREMENTS_HPP
 /** What the measurements of DMRGBlockContainer.hpp share.  All of them: the two blocks as the library sees them, the site operators of
     one Gram / term call, the JSON record file; -corr_matrix and -corr_dimer: the bond list and the lattice Fourier sum; -corr_dimer and
-    -dsf_dimer (CalculateDimerCorrelations, CalculateDimerDynamics): DimerFrame, the bond operators as terms, and BondsOfOrientation.  The four
-    dynamical ones, -dsf, -dsf_sites, -dsf_cheb and -dsf_cv (CalculateDynamicalStructureFactor, CalculateDynamicalCorrelations,
+    -dsf_dimer (CalculateDimerCorrelations, CalculateDimerDynamics): DimerFrame, the bond operators as terms, BondsOfOrientation, the bond header.
+    The four dynamical ones, -dsf, -dsf_sites, -dsf_cheb and -dsf_cv (CalculateDynamicalStructureFactor, CalculateDynamicalCorrelations,
     CalculateChebyshevCorrelations, CalculateCorrectionVectors): SzFrame, SiteCosineSum, the w0,w1,nw grid, the openings of their records;
-    the phase coefficients of -dsf, the window and the Jackson-damped sum of -dsf_cheb; -dsf_pm (CalculateTransverseDynamics): SzFrame over Sp or Sm
-    and the two-sided window.  host_tool.cpp runs the pure parts without a GPU. */
+    the phase coefficients of -dsf; -dsf_pm (CalculateTransverseDynamics): SzFrame over Sp or Sm.  The Chebyshev three, -dsf_cheb, -dsf_pm and
+    -dsf_dimer: the window, the moment run (MomentRun), the Jackson-damped grid and the moment part of a record.  host_tool.cpp runs the pure parts without a GPU. */
 #include <cmath>
 #include <deque>
 #include "DMRGKron.hpp"
@@ -93,7 +93,7 @@ private:
     Operator a of the table T is Sz of lattice site site[a], op_of is the inverse; (rx, ry)[s] is where LATTICE site s sits on the
     Lx x Ly lattice of M = Lx Ly sites.  psi: the n states on the device, norm = <psi|psi>; ld = n rounded up to even, the row length
     of a family of vectors (the library streams rows in 16-byte loads).  Init(..., OpSp) or (..., OpSm) gives the same frame over Sp or Sm
-    (Sp read transposed) of every site: the set-up of -dsf_pm, whose images live in another sector (ImagesTo). */
+    (Sp read transposed) of every site: the set-up of -dsf_pm, whose images live in another sector (Images with out_il, out_ir). */
 struct SzFrame {
     CentreFrame F;
     SiteOperators T{F};
@@ -127,33 +127,31 @@ struct SzFrame {
     }
     /** Images of at most 1 GiB per term_apply (its intermediates grow with its vectors). */
     PetscInt chunk() const { return std::max<PetscInt>(1, std::min<PetscInt>(F.N, (PetscInt)((((int64_t)1 << 30) / (int64_t)sizeof(double)) / ld))); }
-    /** dst + j ld_dst = Sz of operator ops[j] on psi, j < count, in chunks. */
-    PetscErrorCode Images(const PetscInt* ops, PetscInt count, double* dst, int64_t ld_dst) const
+    /** dst + j ld_dst = operator ops[j] on psi, j < count, in chunks: in the layout of psi, or, with out_il and out_ir, in the layout of the KronBlocks
+        (out_il, out_ir)[0 .. n_out) of the sector the operators lead to (dmrgx_kron_term_apply_to; there a chunk is 1 GiB of rows of ld_dst). */
+    PetscErrorCode Images(const PetscInt* ops, PetscInt count, double* dst, int64_t ld_dst, const std::vector<int32_t>* out_il = nullptr, const std::vector<int32_t>* out_ir = nullptr) const
     {
-        std::vector<dmrgx_term> terms; std::vector<int32_t> vec_first;
-        for (PetscInt j0 = 0; j0 < count; j0 += chunk()) {
-            const PetscInt cnt = std::min<PetscInt>(chunk(), count - j0);
-            terms.clear(); vec_first.assign(1, 0);
-            for (PetscInt j = j0; j < j0 + cnt; ++j) { terms.push_back(term(ops[j])); vec_first.push_back((int32_t)terms.size()); }
-            PetscErrorCode ierr = Apply(cnt, vec_first.data(), terms.data(), dst + j0 * ld_dst, ld_dst); CHKERRQ(ierr);
-        }
-        return 0;
-    }
-    /** dst + j ld_dst = operator ops[j] on psi, j < count, written in the layout of the KronBlocks (out_il, out_ir)[0 .. n_out) of the sector
-        the operators lead to (dmrgx_kron_term_apply_to), in chunks of at most 1 GiB of images. */
-    PetscErrorCode ImagesTo(const PetscInt* ops, PetscInt count, const std::vector<int32_t>& out_il, const std::vector<int32_t>& out_ir, double* dst, int64_t ld_dst) const
-    {
-        const PetscInt per = std::max<PetscInt>(1, std::min<PetscInt>(F.N, (PetscInt)((((int64_t)1 << 30) / (int64_t)sizeof(double)) / std::max<int64_t>(ld_dst, 1))));
+        const PetscInt per = out_il ? std::max<PetscInt>(1, std::min<PetscInt>(F.N, (PetscInt)((((int64_t)1 << 30) / (int64_t)sizeof(double)) / std::max<int64_t>(ld_dst, 1)))) : chunk();
         std::vector<dmrgx_term> terms; std::vector<int32_t> vec_first;
         for (PetscInt j0 = 0; j0 < count; j0 += per) {
             const PetscInt cnt = std::min<PetscInt>(per, count - j0);
             terms.clear(); vec_first.assign(1, 0);
             for (PetscInt j = j0; j < j0 + cnt; ++j) { terms.push_back(term(ops[j])); vec_first.push_back((int32_t)terms.size()); }
-            if (dmrgx_kron_term_apply_to(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
-                                         (int32_t)cnt, vec_first.data(), terms.data(), (int32_t)out_il.size(), out_il.data(), out_ir.data(), dst + j0 * ld_dst, ld_dst, nullptr))
+            if (!out_il) { PetscErrorCode ierr = Apply(cnt, vec_first.data(), terms.data(), dst + j0 * ld_dst, ld_dst); CHKERRQ(ierr); }
+            else if (dmrgx_kron_term_apply_to(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
+                                              (int32_t)cnt, vec_first.data(), terms.data(), (int32_t)out_il->size(), out_il->data(), out_ir->data(), dst + j0 * ld_dst, ld_dst, nullptr))
                 SETERRQ1(PETSC_COMM_SELF, 1, "dmrgx_kron_term_apply_to: %s", dmrgx_last_error());
         }
         return 0;
+    }
+    /** U: Images of all N sites, row s = the operator of LATTICE site s on psi, in rows of n_out rounded up to even doubles (n_out = n in
+        the layout of psi).  They stay on the device while U lives; PETSC_ERR_MEM if they do not fit. */
+    PetscErrorCode AllImages(std::unique_ptr<DevBuffer>& U, int64_t n_out, const std::vector<int32_t>* out_il = nullptr, const std::vector<int32_t>* out_ir = nullptr) const
+    {
+        const int64_t ld_out = n_out + (n_out & 1);
+        try { U.reset(new DevBuffer((size_t)(F.N * ld_out), DevBuffer::device_only_t{})); }
+        catch (const std::exception& e) { SETERRQ5(PETSC_COMM_SELF, PETSC_ERR_MEM, "%s: no memory for the images of %lld sites x %lld states (%.3f GB): %s", F.name, LLD(F.N), LLD(n_out), (double)(F.N * ld_out) * 8e-9, e.what()); }
+        return Images(op_of.data(), F.N, U->dev_uninitialised(), ld_out, out_il, out_ir);
     }
 };
 
@@ -202,52 +200,34 @@ inline double DsfPhaseCoefficient(int part, PetscInt p, PetscInt M)
     return (2 * p) % M == 0 ? 0.0 : std::sin(two_pi * (double)p / (double)M);
 }
 
-/** The window [E_lo, E_hi] of a Chebyshev expansion from `done` steps of a Lanczos run (alpha, beta of dmrgx_kron_lanczos_coeffs; the
-    vectors hold the steps asked for, done < alpha.size() is a breakdown) and the known lowest eigenvalue E0.  theta_max: the largest
-    eigenvalue of the Lanczos matrix of order `done`; residual = beta_{done-1} |last component of its eigenvector|, the bound
-    |lambda - theta_max| <= residual for some eigenvalue lambda of H -- 0 after a breakdown, where the Krylov space is invariant.
-    E_hi = theta_max + residual + 0.02 (theta_max - E0), E_lo = E0 - 0.01 (theta_max - E0).  ok false: done < 1 or the QL iteration failed. */
-struct ChebyshevWindowResult { double centre = 0.0, half_width = 0.0, theta_max = 0.0, residual = 0.0; bool ok = false; };
-inline ChebyshevWindowResult ChebyshevWindow(double E0, const std::vector<double>& alpha, const std::vector<double>& beta, PetscInt done)
+/** The window [centre - half_width, centre + half_width] = [E_lo, E_hi] of a Chebyshev expansion from `done` steps of a Lanczos run (alpha, beta
+    of dmrgx_kron_lanczos_coeffs; the vectors hold the steps asked for, done < alpha.size() is a breakdown).  theta_min, theta_max: the extreme
+    eigenvalues of the Lanczos matrix of order `done`; residual_min, residual = beta_{done-1} |last component of the eigenvector|, the bound
+    |lambda - theta| <= residual for SOME eigenvalue lambda of H -- 0 after a breakdown, where the Krylov space is invariant.
+    ChebyshevWindow, the lowest eigenvalue E0 known (it stands for theta_min, residual_min = 0):  E_hi = theta_max + residual + 0.02 width,
+    E_lo = E0 - 0.01 width, width = theta_max - E0.  ChebyshevWindowTwoSided, a sector whose bottom is not known (-dsf_pm: the neighbouring
+    total-Sz sector, for which E0 of the target sector is neither an upper nor a lower bound):  E_hi as before, E_lo = theta_min - residual_min -
+    0.02 width, width = theta_max - theta_min; a window that is too tight is caught by the guard of dmrgx_kron_chebyshev_moments (StepsDone < Steps).
+    ok false: done < 1, the QL iteration failed, or a window of no width.  bound_steps is for who ran the steps (0: a window that was given). */
+struct ChebyshevSpectralWindow { double centre = 0.0, half_width = 0.0, theta_min = 0.0, theta_max = 0.0, residual_min = 0.0, residual = 0.0; PetscInt bound_steps = 0; bool ok = false; };
+inline ChebyshevSpectralWindow RitzWindow(const double* bottom, const std::vector<double>& alpha, const std::vector<double>& beta, PetscInt done)
 {
-    ChebyshevWindowResult W;
-    if (done < 1 || (size_t)done > alpha.size() || beta.size() < alpha.size()) return W;
-    std::vector<double> theta(alpha.begin(), alpha.begin() + done), e(beta.begin(), beta.begin() + done), vec;
-    if (!TridiagQLVectors(theta, e, vec)) return W;
-    PetscInt top = 0;
-    for (PetscInt k = 1; k < done; ++k) if (theta[(size_t)k] > theta[(size_t)top]) top = k;
-    W.theta_max = theta[(size_t)top];
-    W.residual = (size_t)done < alpha.size() ? 0.0 : beta[(size_t)(done - 1)] * std::fabs(vec[(size_t)(top * done + done - 1)]);
-    const double width = W.theta_max - E0, hi = W.theta_max + W.residual + 0.02 * width, lo = E0 - 0.01 * width;
-    W.centre = 0.5 * (hi + lo); W.half_width = 0.5 * (hi - lo);
-    W.ok = W.half_width > 0.0 && std::isfinite(W.half_width) && std::isfinite(W.centre);
-    return W;
-}
-
-/** The window of a Chebyshev expansion in a sector whose bottom is not known (-dsf_pm: the neighbouring total-Sz sector, for which E0 of
-    the target sector is neither an upper nor a lower bound): both extreme Ritz values theta_min, theta_max of the Lanczos matrix of order
-    `done` (alpha, beta, done as for ChebyshevWindow) with their residual bounds res = beta_{done-1} |last component of the eigenvector|,
-    0 after a breakdown.  With width = theta_max - theta_min:  E_lo = theta_min - res_min - 0.02 width,  E_hi = theta_max + res_max +
-    0.02 width.  A residual bounds the distance to SOME eigenvalue, not to the extreme one: a window that is too tight is caught by the
-    guard of dmrgx_kron_chebyshev_moments (StepsDone < Steps).  ok false: done < 1, the QL iteration failed, or a window of no width. */
-struct ChebyshevWindowTwoSidedResult { double centre = 0.0, half_width = 0.0, theta_min = 0.0, theta_max = 0.0, res_min = 0.0, res_max = 0.0; bool ok = false; };
-inline ChebyshevWindowTwoSidedResult ChebyshevWindowTwoSided(const std::vector<double>& alpha, const std::vector<double>& beta, PetscInt done)
-{
-    ChebyshevWindowTwoSidedResult W;
+    ChebyshevSpectralWindow W;
     if (done < 1 || (size_t)done > alpha.size() || beta.size() < alpha.size()) return W;
     std::vector<double> theta(alpha.begin(), alpha.begin() + done), e(beta.begin(), beta.begin() + done), vec;
     if (!TridiagQLVectors(theta, e, vec)) return W;
     PetscInt top = 0, bot = 0;
     for (PetscInt k = 1; k < done; ++k) { if (theta[(size_t)k] > theta[(size_t)top]) top = k; if (theta[(size_t)k] < theta[(size_t)bot]) bot = k; }
-    W.theta_max = theta[(size_t)top]; W.theta_min = theta[(size_t)bot];
-    const bool broke = (size_t)done < alpha.size();
-    W.res_max = broke ? 0.0 : beta[(size_t)(done - 1)] * std::fabs(vec[(size_t)(top * done + done - 1)]);
-    W.res_min = broke ? 0.0 : beta[(size_t)(done - 1)] * std::fabs(vec[(size_t)(bot * done + done - 1)]);
-    const double width = W.theta_max - W.theta_min, hi = W.theta_max + W.res_max + 0.02 * width, lo = W.theta_min - W.res_min - 0.02 * width;
+    const double last = (size_t)done < alpha.size() ? 0.0 : beta[(size_t)(done - 1)];
+    W.theta_max = theta[(size_t)top]; W.residual = last * std::fabs(vec[(size_t)(top * done + done - 1)]);
+    W.theta_min = bottom ? *bottom : theta[(size_t)bot]; W.residual_min = bottom ? 0.0 : last * std::fabs(vec[(size_t)(bot * done + done - 1)]);
+    const double width = W.theta_max - W.theta_min, hi = W.theta_max + W.residual + 0.02 * width, lo = W.theta_min - W.residual_min - (bottom ? 0.01 : 0.02) * width;
     W.centre = 0.5 * (hi + lo); W.half_width = 0.5 * (hi - lo);
     W.ok = W.half_width > 0.0 && std::isfinite(W.half_width) && std::isfinite(W.centre);
     return W;
 }
+inline ChebyshevSpectralWindow ChebyshevWindow(double E0, const std::vector<double>& alpha, const std::vector<double>& beta, PetscInt done) { return RitzWindow(&E0, alpha, beta, done); }
+inline ChebyshevSpectralWindow ChebyshevWindowTwoSided(const std::vector<double>& alpha, const std::vector<double>& beta, PetscInt done) { return RitzWindow(nullptr, alpha, beta, done); }
 
 /** The Jackson-damped Chebyshev sum of M moments mu[0..M) at x:
         ( g_0 mu_0 + 2 sum_{n=1}^{M-1} g_n mu_n T_n(x) ) / ( pi sqrt(1 - x^2) ),
@@ -263,6 +243,57 @@ inline double ChebyshevJackson(const double* mu, PetscInt M, double x)
         sum += (n ? 2.0 : 1.0) * g * mu[n] * std::cos((double)n * phi);
     }
     return sum / (pi * std::sqrt(1.0 - x * x));
+}
+
+/** One dmrgx_kron_chebyshev_moments run from row c (a site, a bond) of a family of `count` images, as -dsf_cheb, -dsf_pm and -dsf_dimer record
+    it: norm2 = <v0, v0>, `done` steps inside the window, diag[m] = mu_m^{cc}, m <= 2 done, mom (count x (done + 1), row-major) the moments against
+    every image, momq their lattice sum (the caller's: which rows enter differs), grid of ChebyshevGrid; elastic: -dsf_dimer alone. */
+struct MomentRun { PetscInt c = 0; double norm2 = 0.0, elastic = 0.0; int32_t done = 0; std::vector<double> diag, mom, momq, grid; };
+
+/** What the library returned, as the record holds it: diag (2 K + 1 values) cut to 2 done + 1, cross[k * count + s], k <= done,
+    transposed into mom[s * (done + 1) + k], both divided by norm = <psi|psi>.  One division per entry. */
+inline void ScaleMoments(MomentRun& R, const std::vector<double>& cross, PetscInt count, double norm)
+{
+    const PetscInt nm = R.done + 1;
+    R.diag.resize((size_t)(2 * R.done + 1));
+    for (double& x : R.diag) x /= norm;
+    R.mom.assign((size_t)(count * nm), 0.0);
+    for (PetscInt s = 0; s < count; ++s) for (PetscInt k = 0; k < nm; ++k) R.mom[(size_t)(s * nm + k)] = cross[(size_t)(k * count + s)] / norm;
+}
+/** K Chebyshev steps of the planned Hamiltonian in the window W from row R.c of the family U (count rows of ld doubles, on the device),
+    <u_i, t_n> of all rows taken by the library, then ScaleMoments by norm; `cross` is the callers' scratch, kept between runs.
+    *seconds, unless null, gains the time of the run alone (for the log): a stream sync before it, the library's own after. */
+inline PetscErrorCode ChebyshevMomentRun(dmrgx_kron_plan* plan, const double* U, int64_t ld, PetscInt count, const ChebyshevSpectralWindow& W, PetscInt K, double norm,
+                                         std::vector<double>& cross, MomentRun& R, double* seconds)
+{
+    R.diag.assign((size_t)(2 * K + 1), 0.0);
+    cross.resize((size_t)((K + 1) * count));
+    PetscLogDouble tr0 = 0.0, tr1 = 0.0;
+    if (seconds) { if (dmrgx_stream_sync(nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "%s", dmrgx_last_error()); PetscTime(&tr0); }
+    if (dmrgx_kron_chebyshev_moments(plan, U + R.c * ld, W.centre, W.half_width, (int32_t)K, (int32_t)count, U, ld, &R.norm2, R.diag.data(), cross.data(), &R.done, nullptr))
+        SETERRQ1(PETSC_COMM_SELF, 1, "dmrgx_kron_chebyshev_moments: %s", dmrgx_last_error());
+    if (seconds) { PetscTime(&tr1); *seconds += tr1 - tr0; }
+    ScaleMoments(R, cross, count, norm);
+    return 0;
+}
+
+/** grid[q][k] = ChebyshevJackson(momq[q], nm, x_k) / half_width at x_k = (omega[k] + E0 - centre) / half_width, for every row q of momq
+    (rows of nm moments): the Jackson-broadened spectral density at the frequencies omega, measured from E0. */
+inline std::vector<double> ChebyshevGrid(const std::vector<double>& momq, PetscInt nm, const std::vector<double>& omega, double E0, double centre, double half_width)
+{
+    const PetscInt M = (PetscInt)momq.size() / nm, nw = (PetscInt)omega.size();
+    std::vector<double> grid((size_t)(M * nw), 0.0);
+    for (PetscInt q = 0; q < M; ++q) for (PetscInt k = 0; k < nw; ++k)
+        grid[(size_t)(q * nw + k)] = ChebyshevJackson(momq.data() + q * nm, nm, (omega[(size_t)k] + E0 - centre) / half_width) / half_width;
+    return grid;
+}
+
+/** The warning of a run that the library's guard ended before its K steps: "-option[ (channel)]: the run from <noun> c left the window". */
+inline void WarnLeftWindow(const char* option, const char* channel, const char* noun, const MomentRun& R, const ChebyshevSpectralWindow& W, PetscInt K)
+{
+    if (R.done >= K) return;
+    printf("  * WARNING: %s%s%s%s: the run from %s %lld left the window [%.6f, %.6f] after %lld of %lld steps; the record holds the moments up to there.\n",
+           option, channel ? " (" : "", channel ? channel : "", channel ? ")" : "", noun, LLD(R.c), W.centre - W.half_width, W.centre + W.half_width, LLD(R.done), LLD(K));
 }
 
 /** A nearest-neighbour bond of the lattice: sites i < j, the site (ix, jy) from which NearestNeighbors generates it, 'x' if the two
@@ -493,6 +524,32 @@ struct JsonRecordFile {
         return ierr;
     }
     void OpenSite(PetscInt c, PetscInt x, PetscInt y, double norm2) const { fprintf(fp, "   {\"Site\": %lld, \"r\": [%lld, %lld], \"Norm2\": %.17g", LLD(c), LLD(x), LLD(y), norm2); }
+    /** The optional "Omega" row in the head of a Chebyshev record. */
+    void Omega(const std::vector<double>* omega) const { if (omega) { fprintf(fp, "   \"Omega\": "); Row(*omega); fprintf(fp, ",\n"); } }
+    /** The moment part of the entry of one run, after the caller's "..., \"StepsDone\": d": Diag, Moments (rows x (done + 1)), MomentsQ
+        (M x (done + 1)) and, where frequencies were asked for, SqwGrid (M x their number); `end` closes the entry. */
+    void Moments(const MomentRun& R, PetscInt rows, PetscInt M, const std::vector<double>* omega, const char* end) const
+    {
+        const PetscInt nm = R.done + 1;
+        fprintf(fp, ",\n   \"Diag\": ");
+        Row(R.diag); fprintf(fp, ",\n");
+        Table("Moments", R.mom, rows, nm, ",\n");
+        Table("MomentsQ", R.momq, M, nm, omega ? ",\n" : end);
+        if (omega) Table("SqwGrid", R.grid, M, (PetscInt)omega->size(), end);
+    }
+    /** "Bonds", "Orientation", "Position" of the bonds and "D" = < D_b >, as -corr_dimer and -dsf_dimer write them, each line closed. */
+    void BondHeader(const std::vector<DimerBond>& bonds, const std::vector<double>& D) const
+    {
+        const size_t nb = bonds.size();
+        fprintf(fp, "   \"Bonds\": [");
+        for (size_t b = 0; b < nb; ++b) fprintf(fp, "%s[%lld, %lld]", b ? ", " : "", LLD(bonds[b].i), LLD(bonds[b].j));
+        fprintf(fp, "],\n   \"Orientation\": [");
+        for (size_t b = 0; b < nb; ++b) fprintf(fp, "%s\"%c\"", b ? ", " : "", bonds[b].orient);
+        fprintf(fp, "],\n   \"Position\": [");
+        for (size_t b = 0; b < nb; ++b) fprintf(fp, "%s[%lld, %lld]", b ? ", " : "", LLD(bonds[b].ix), LLD(bonds[b].jy));
+        fprintf(fp, "],\n   \"D\": ");
+        Row(D); fprintf(fp, ",\n");
+    }
     void Close() { if (fp) { fprintf(fp, "\n]\n"); fclose(fp); fp = NULL; } }
 };
 

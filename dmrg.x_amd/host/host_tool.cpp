@@ -26,6 +26,8 @@ static void dump_mat(const char* tag, PetscInt site, const Mat& m)
     }
 }
 
+static void print_numbers(const char* tag, const std::vector<double>& v) { printf("%s", tag); for (double x : v) printf(" %.17g", x); printf("\n"); }
+
 int main()
 {
     std::map<std::string, Block::SpinBase> blocks;
@@ -145,9 +147,8 @@ int main()
             const std::vector<int> owner = dmrgx_host::DealCorrelators(sites, N, W, &carried);
             printf("owners");
             for (int o : owner) printf(" %d", o);
-            printf("\ncarried");
-            for (double c : carried) printf(" %.17g", c);
             printf("\n");
+            print_numbers("carried", carried);
         } else if (cmd == "tridiag") {           /* tridiag n d_0 .. d_{n-1} e_0 .. e_{n-2}  ->  eigenvalues and first eigenvector components */
             size_t n; is >> n;
             std::vector<double> d(n), e(n ? n - 1 : 0), z;
@@ -201,30 +202,24 @@ int main()
             for (double& v : T) is >> v;
             double norm;
             if (!(is >> norm)) norm = (double)n;
-            printf("%s", cmd.c_str());
-            for (double v : c < 0 ? dmrgx_host::LatticeFourier(Lx, Ly, x.data(), y.data(), T.data(), n, norm) : dmrgx_host::SiteCosineSum(Lx, Ly, x.data(), y.data(), c, T.data(), n, ncol)) printf(" %.17g", v);
-            printf("\n");
+            print_numbers(cmd.c_str(), c < 0 ? dmrgx_host::LatticeFourier(Lx, Ly, x.data(), y.data(), T.data(), n, norm) : dmrgx_host::SiteCosineSum(Lx, Ly, x.data(), y.data(), c, T.data(), n, ncol));
         } else if (cmd == "omegagrid") {         /* omegagrid w0 w1 nw  ->  1 and the grid, or 0 */
             std::vector<double> om, grid;
             for (double v; is >> v;) om.push_back(v);
             const bool ok = dmrgx_host::OmegaGrid(om.data(), (PetscInt)om.size(), grid);
-            printf("omegagrid %d", (int)ok);
-            for (double v : grid) printf(" %.17g", v);
-            printf("\n");
-        } else if (cmd == "chebwindow") {        /* chebwindow E0 nsteps done alpha_0 .. alpha_{nsteps-1} beta_0 .. beta_{nsteps-1}  ->  ok centre half_width theta_max residual */
-            double E0; size_t nsteps; PetscInt done; is >> E0 >> nsteps >> done;
+            print_numbers(ok ? "omegagrid 1" : "omegagrid 0", grid);
+        } else if (cmd == "chebwindow" || cmd == "chebwindow2") {
+            /* chebwindow E0 nsteps done alpha_0 .. alpha_{nsteps-1} beta_0 .. beta_{nsteps-1}  ->  ok centre half_width theta_max residual
+               chebwindow2 nsteps done alpha_0 .. alpha_{nsteps-1} beta_0 .. beta_{nsteps-1}  ->  ok centre half_width theta_min theta_max res_min res_max */
+            double E0 = 0.0; size_t nsteps; PetscInt done;
+            if (cmd == "chebwindow") is >> E0;
+            is >> nsteps >> done;
             std::vector<double> a(nsteps), b(nsteps);
             for (double& x : a) is >> x;
             for (double& x : b) is >> x;
-            const dmrgx_host::ChebyshevWindowResult W = dmrgx_host::ChebyshevWindow(E0, a, b, done);
-            printf("chebwindow %d %.17g %.17g %.17g %.17g\n", (int)W.ok, W.centre, W.half_width, W.theta_max, W.residual);
-        } else if (cmd == "chebwindow2") {       /* chebwindow2 nsteps done alpha_0 .. alpha_{nsteps-1} beta_0 .. beta_{nsteps-1}  ->  ok centre half_width theta_min theta_max res_min res_max */
-            size_t nsteps; PetscInt done; is >> nsteps >> done;
-            std::vector<double> a(nsteps), b(nsteps);
-            for (double& x : a) is >> x;
-            for (double& x : b) is >> x;
-            const dmrgx_host::ChebyshevWindowTwoSidedResult W = dmrgx_host::ChebyshevWindowTwoSided(a, b, done);
-            printf("chebwindow2 %d %.17g %.17g %.17g %.17g %.17g %.17g\n", (int)W.ok, W.centre, W.half_width, W.theta_min, W.theta_max, W.res_min, W.res_max);
+            const dmrgx_host::ChebyshevSpectralWindow W = cmd == "chebwindow" ? dmrgx_host::ChebyshevWindow(E0, a, b, done) : dmrgx_host::ChebyshevWindowTwoSided(a, b, done);
+            if (cmd == "chebwindow") printf("chebwindow %d %.17g %.17g %.17g %.17g\n", (int)W.ok, W.centre, W.half_width, W.theta_max, W.residual);
+            else printf("chebwindow2 %d %.17g %.17g %.17g %.17g %.17g %.17g\n", (int)W.ok, W.centre, W.half_width, W.theta_min, W.theta_max, W.residual_min, W.residual);
         } else if (cmd == "chebjackson") {      /* chebjackson M nx mu_0 .. mu_{M-1} x_0 .. x_{nx-1}  ->  the damped sum at every x */
             PetscInt M, nx; is >> M >> nx;
             std::vector<double> mu((size_t)M), xs((size_t)nx);
@@ -233,7 +228,39 @@ int main()
             printf("chebjackson");
             for (double x : xs) printf(" %.17g", dmrgx_host::ChebyshevJackson(mu.data(), M, x));
             printf("\n");
-        } else if (cmd == "jsonrec") {           /* jsonrec path format nrec: nrec records {"K": k, "R": row of 3, "T": 2 x 3 table} of thirds, then Close() */
+        } else if (cmd == "chebmoments") {       /* chebmoments count K done norm diag_0 .. diag_{2K} cross_0 .. cross_{(K+1) count - 1}  ->  two lines: diag, mom of ScaleMoments */
+            PetscInt count, K; dmrgx_host::MomentRun R; double norm; is >> count >> K >> R.done >> norm;
+            std::vector<double> cross((size_t)((K + 1) * count));
+            R.diag.resize((size_t)(2 * K + 1));
+            for (double& v : R.diag) is >> v;
+            for (double& v : cross) is >> v;
+            dmrgx_host::ScaleMoments(R, cross, count, norm);
+            print_numbers("diag", R.diag); print_numbers("mom", R.mom);
+        } else if (cmd == "chebgrid") {          /* chebgrid M nm nw E0 centre half_width momq_00 .. momq_{M-1,nm-1} omega_0 .. omega_{nw-1}  ->  the M x nw grid of ChebyshevGrid, row by row */
+            PetscInt M, nm, nw; double E0, centre, half_width; is >> M >> nm >> nw >> E0 >> centre >> half_width;
+            std::vector<double> momq((size_t)(M * nm)), omega((size_t)nw);
+            for (double& v : momq) is >> v;
+            for (double& v : omega) is >> v;
+            print_numbers("chebgrid", dmrgx_host::ChebyshevGrid(momq, nm, omega, E0, centre, half_width));
+        } else if (cmd == "momentrec") {         /* momentrec path have_omega nsites: one dynamical record (%.17g) whose entry s is a run of s + 1 steps over 2 rows and 2 q of thirds, then Close() */
+            std::string path; int have_omega; PetscInt nsites; is >> path >> have_omega >> nsites;
+            dmrgx_host::JsonRecordFile J("%.17g");
+            const std::vector<double> grid_omega{1.0 / 3.0, 2.0 / 3.0}, *omega = have_omega ? &grid_omega : nullptr;
+            ierr = J.BeginDynamical(path, 7, "Sweep", -1.0 / 3.0, 2.0 / 3.0);
+            if (!ierr) { fprintf(J.fp, ",\n"); J.Omega(omega); fprintf(J.fp, "   \"Sites\": [\n"); }
+            for (PetscInt s = 0; s < nsites && !ierr; ++s) {
+                dmrgx_host::MomentRun R;
+                R.c = s; R.done = (int32_t)(s + 1); R.norm2 = (double)(s + 1) / 3.0;
+                auto thirds = [s](PetscInt cnt, PetscInt from) { std::vector<double> v; for (PetscInt i = 0; i < cnt; ++i) v.push_back((double)(from + s + i) / 3.0); return v; };
+                R.diag = thirds(2 * R.done + 1, 0); R.mom = thirds(2 * (R.done + 1), 10); R.momq = thirds(2 * (R.done + 1), 20); R.grid = thirds(2 * 2, 30);
+                J.OpenSite(R.c, s, 0, R.norm2);
+                fprintf(J.fp, ", \"StepsDone\": %d", (int)R.done);
+                J.Moments(R, 2, 2, omega, s + 1 < nsites ? "},\n" : "}\n");
+            }
+            if (!ierr) fprintf(J.fp, "   ]}");
+            J.Close();
+            printf("rc %d\n", ierr);
+        } else if (cmd == "jsonrec") {          /* jsonrec path format nrec: nrec records {"K": k, "R": row of 3, "T": 2 x 3 table} of thirds, then Close() */
             std::string path, fmt; PetscInt nrec; is >> path >> fmt >> nrec;
             dmrgx_host::JsonRecordFile J(fmt.c_str());
             for (PetscInt k = 0; k < nrec && !ierr; ++k) {
