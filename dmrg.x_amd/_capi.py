@@ -181,6 +181,9 @@ SIGNATURES = {
     "dmrgx_kron_term_apply_to": (C.c_int32, [C.POINTER(Sectors), C.POINTER(Sectors), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
                                              C.c_int32, C.POINTER(SecOp), C.c_int32, C.POINTER(SecOp), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Term),
                                              C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_int64, C.c_void_p]),
+    "dmrgx_kron_noise_expand": (C.c_int32, [C.POINTER(Sectors), C.POINTER(Sectors), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
+                                            C.c_int32, C.c_int32, C.POINTER(SecOp), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                            C.c_void_p, C.c_void_p]),
     "dmrgx_kron_lanczos_coeffs": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                               C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p]),
     "dmrgx_kron_lanczos_basis": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int64, C.POINTER(C.c_double),

@@ -989,16 +989,70 @@ dmrgx_status block_layout(const char* fn, const char* what, const dmrgx_sectors*
     return DMRGX_OK;
 }
 
-dmrgx_status gram_layout(const char* fn, const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks, const int32_t* block_il, const int32_t* block_ir,
-                         const double* psi_dev, GramLayout& L)
+// The same after the checks of the sector tables themselves: everything a call can refuse without looking at psi.
+dmrgx_status kron_layout(const char* fn, const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks, const int32_t* block_il, const int32_t* block_ir, GramLayout& L)
 {
     if (!left || !right || left->nsec <= 0 || right->nsec <= 0 || !left->size || !right->size) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: empty sector table", fn);
     for (int i = 0; i < left->nsec; ++i) if (left->size[i] <= 0) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: left sector %d has size %d", fn, i, left->size[i]);
     for (int i = 0; i < right->nsec; ++i) if (right->size[i] <= 0) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: right sector %d has size %d", fn, i, right->size[i]);
     if (nblocks <= 0 || !block_il || !block_ir) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: no KronBlocks", fn);
-    if (!psi_dev) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null psi", fn);
     return block_layout(fn, "KronBlock", left, right, nblocks, block_il, block_ir, L);
 }
+
+dmrgx_status gram_layout(const char* fn, const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks, const int32_t* block_il, const int32_t* block_ir,
+                         const double* psi_dev, GramLayout& L)
+{
+    if (!psi_dev) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null psi", fn);
+    return kron_layout(fn, left, right, nblocks, block_il, block_ir, L);
+}
+
+// The operands of one call.  The NN GEMM reads a left cell as A (row-major nr x nc) and a right cell as B = cell^T (row-major nc x nr): cells
+// stored the other way round, and cells that carry a coefficient, are materialised once per call (as the plan's cell_copy writes B^T).
+// One entry per (side, operator, coefficient) in use.  Order of use: use_of for every operand, storage for trans_doubles, bind, the two
+// tables into the call's PackedUpload, launch_copies ahead of the first GEMM.
+struct OperandUses {
+    std::map<std::tuple<int, int32_t, uint64_t>, std::vector<UCell>> uses;
+    std::vector<CopyTask> copies;
+    std::vector<CopyTile> copy_tiles;
+    int64_t trans_doubles = 0;
+    static uint64_t bits_of(double coeff) { uint64_t bits; memcpy(&bits, &coeff, sizeof bits); return bits; }      // a coefficient as a map key
+    // cells: the normalised cells of operator `op` of `side`
+    dmrgx_status use_of(const char* fn, int side, int32_t op, double coeff, const std::vector<NCell>& cells, const std::vector<UCell>** out)
+    {
+        auto ins = uses.emplace(std::make_tuple(side, op, bits_of(coeff)), std::vector<UCell>());
+        *out = &ins.first->second;
+        if (!ins.second) return DMRGX_OK;
+        const bool is_left = side == SIDE_LEFT;
+        for (const NCell& c : cells) {
+            UCell u{c.q, c.r0, c.c0, c.nr, c.nc, c.kind, c.scale * coeff, c.data, 0, -1};
+            if (c.kind == DMRGX_CELL_DENSE) {
+                if (c.ld > INT32_MAX) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: %s operator %d: leading dimension %lld of a cell too large", fn, is_left ? "left" : "right", op, (long long)c.ld);
+                u.ld = (int32_t)c.ld;
+                const bool flip = c.tr == is_left;      // left and stored transposed, or right and stored plainly
+                if (flip || coeff != 1.0) {
+                    const int32_t dr = is_left ? c.nr : c.nc, dc = is_left ? c.nc : c.nr;
+                    copies.push_back(CopyTask{trans_doubles, c.data, c.ld, dr, dc, dc, flip ? 1 : 0, coeff, 0});
+                    for (int32_t ti = 0; ti < (dr + 31) / 32; ++ti)
+                        for (int32_t tj = 0; tj < (dc + 31) / 32; ++tj) copy_tiles.push_back(CopyTile{(int32_t)copies.size() - 1, ti, tj, 0});
+                    u.trans_off = trans_doubles;
+                    u.ld = dc;
+                    trans_doubles += (int64_t)dr * dc;
+                }
+            }
+            ins.first->second.push_back(u);
+        }
+        return DMRGX_OK;
+    }
+    void bind(double* trans) { for (auto& kv : uses) for (UCell& u : kv.second) if (u.trans_off >= 0) u.data = trans + u.trans_off; }
+    dmrgx_status launch_copies(const DevBuf& tab, size_t o_tiles, size_t o_tasks, double* trans, hipStream_t st) const
+    {
+        if (copy_tiles.empty()) return DMRGX_OK;
+        hipLaunchKernelGGL(cell_copy_kernel, dim3((unsigned)copy_tiles.size()), dim3(256), 0, st, (const CopyTile*)packed_at<CopyTile>(tab, o_tiles),
+                           (const CopyTask*)packed_at<CopyTask>(tab, o_tasks), trans);
+        DMRGX_HIP(hipGetLastError());
+        return DMRGX_OK;
+    }
+};
 
 // The groups of one output block Y (nLa x nRb, leading dimension ldc): the rows are cut at the borders of the left-kind cells, the columns
 // at the borders of the right-kind cells, and every rectangle of that grid is one group -- scaled copies first, then the GEMM products --
@@ -1119,39 +1173,10 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
         return it == L.kmap.end() ? -1 : it->second;
     };
 
-    // Operands.  The NN GEMM reads a left cell as A (row-major nr x nc) and a right cell as B = cell^T (row-major nc x nr): cells stored the
-    // other way round, and cells that carry a coefficient, are materialised once per call (as the plan's cell_copy writes B^T).  One
-    // entry per (side, operator, coefficient) in use.
-    std::map<std::tuple<int, int32_t, uint64_t>, std::vector<UCell>> uses;
-    std::vector<CopyTask> copies;
-    std::vector<CopyTile> copy_tiles;
-    int64_t trans_doubles = 0;
-    auto bits_of = [](double coeff) { uint64_t bits; memcpy(&bits, &coeff, sizeof bits); return bits; };      // a coefficient as a map key
-    auto use_of = [&](int side, int32_t op, double coeff, const std::vector<UCell>** out) -> dmrgx_status {
-        auto ins = uses.emplace(std::make_tuple(side, op, bits_of(coeff)), std::vector<UCell>());
-        *out = &ins.first->second;
-        if (!ins.second) return DMRGX_OK;
-        const bool is_left = side == SIDE_LEFT;
-        for (const NCell& c : (is_left ? cellsL : cellsR)[op]) {
-            UCell u{c.q, c.r0, c.c0, c.nr, c.nc, c.kind, c.scale * coeff, c.data, 0, -1};
-            if (c.kind == DMRGX_CELL_DENSE) {
-                if (c.ld > INT32_MAX) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: %s operator %d: leading dimension %lld of a cell too large", fn, is_left ? "left" : "right", op, (long long)c.ld);
-                u.ld = (int32_t)c.ld;
-                const bool flip = c.tr == is_left;      // left and stored transposed, or right and stored plainly
-                if (flip || coeff != 1.0) {
-                    const int32_t dr = is_left ? c.nr : c.nc, dc = is_left ? c.nc : c.nr;
-                    copies.push_back(CopyTask{trans_doubles, c.data, c.ld, dr, dc, dc, flip ? 1 : 0, coeff, 0});
-                    for (int32_t ti = 0; ti < (dr + 31) / 32; ++ti)
-                        for (int32_t tj = 0; tj < (dc + 31) / 32; ++tj) copy_tiles.push_back(CopyTile{(int32_t)copies.size() - 1, ti, tj, 0});
-                    u.trans_off = trans_doubles;
-                    u.ld = dc;
-                    trans_doubles += (int64_t)dr * dc;
-                }
-            }
-            ins.first->second.push_back(u);
-        }
-        return DMRGX_OK;
-    };
+    // Operands: one entry per (side, operator, coefficient) in use.
+    OperandUses ou;
+    auto bits_of = OperandUses::bits_of;
+    auto use_of = [&](int side, int32_t op, double coeff, const std::vector<UCell>** out) { return ou.use_of(fn, side, op, coeff, (side == SIDE_LEFT ? cellsL : cellsR)[op], out); };
     // identity (x) identity: one scaled-identity cell per left sector, per coefficient
     std::map<uint64_t, std::vector<UCell>> ident_uses;
     auto ident_of = [&](double coeff) -> const std::vector<UCell>* {
@@ -1184,12 +1209,10 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
     DevBuf W, trans, scratch, tab;
     if (Y_dev) W.view(Y_dev, (size_t)((nvec - 1) * ldy + Out->ref_off[Out->nblocks]) * sizeof(double));
     else DMRGX_CHK(W.alloc_f64((size_t)(*std::max_element(slice_len.begin(), slice_len.end())) * nvec, st));
-    if (trans_doubles > 0) DMRGX_CHK(trans.alloc_f64((size_t)trans_doubles, st));
+    if (ou.trans_doubles > 0) DMRGX_CHK(trans.alloc_f64((size_t)ou.trans_doubles, st));
     const int64_t scratch_max = *std::max_element(scratch_len.begin(), scratch_len.end());
     if (scratch_max > 0) DMRGX_CHK(scratch.alloc_f64((size_t)scratch_max, st));
-    for (auto& kv : uses)
-        for (UCell& u : kv.second)
-            if (u.trans_off >= 0) u.data = trans.as<double>() + u.trans_off;
+    ou.bind(trans.as<double>());
 
     GemmBatch gb;
     std::vector<GemmSet> sets1(nslices), sets2(nslices);      // stage 1: the intermediates of a slice; stage 2: its images
@@ -1199,7 +1222,7 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
         const int32_t s = std::get<0>(kv.first), r = std::get<1>(kv.first), k = std::get<2>(kv.first);
         const int32_t nl = SL.size[L.il[k]], b = L.ir[k] - right_ops[r].shift, ldx = SR.size[L.ir[k]];
         lefts.clear();
-        rights.assign(1, ImgContrib{&uses.at(std::make_tuple((int)SIDE_RIGHT, r, bits_of(1.0))), psi_dev + L.ref_off[k], ldx});
+        rights.assign(1, ImgContrib{&ou.uses.at(std::make_tuple((int)SIDE_RIGHT, r, bits_of(1.0))), psi_dev + L.ref_off[k], ldx});
         emit_groups(gb, sets1[s], scratch.as<double>() + kv.second, SR.size[b], nl, SR.size[b], -1, b, lefts, rights, emit);
     }
     for (const ImgBlock& im : imgs) {
@@ -1222,14 +1245,10 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
     gb.pack(pk);
     for (GemmSet& s : sets1) gb.pack(s, pk);
     for (GemmSet& s : sets2) gb.pack(s, pk);
-    const size_t o_tasks = pk.add(copies), o_tiles = pk.add(copy_tiles);
+    const size_t o_tasks = pk.add(ou.copies), o_tiles = pk.add(ou.copy_tiles);
     DMRGX_CHK(pk.upload(tab, st));
     gb.bind(tab);
-    if (!copy_tiles.empty()) {
-        hipLaunchKernelGGL(cell_copy_kernel, dim3((unsigned)copy_tiles.size()), dim3(256), 0, st, (const CopyTile*)packed_at<CopyTile>(tab, o_tiles),
-                           (const CopyTask*)packed_at<CopyTask>(tab, o_tasks), trans.as<double>());
-        DMRGX_HIP(hipGetLastError());
-    }
+    DMRGX_CHK(ou.launch_copies(tab, o_tiles, o_tasks, trans.as<double>(), st));
     dmrgx_gram_report total{0, nslices, 0};
     for (int32_t s = 0; s < nslices; ++s) {               // fixed order: slice s is added to the sum of the slices before it
         DMRGX_CHK(gb.launch(sets1[s], tab, st));
@@ -1323,6 +1342,97 @@ extern "C" dmrgx_status dmrgx_kron_term_apply_to(const dmrgx_sectors* left, cons
     if (!Y_dev || ldy < NO) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null Y or ldy %lld below the %lld output states", fn, (long long)ldy, (long long)NO);
     if (Y_dev < psi_dev + N && psi_dev < Y_dev + (int64_t)(nvec - 1) * ldy + NO) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: Y overlaps psi", fn);
     return term_gram_build(fn, L, psi_dev, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, 0, nullptr, 0, nullptr, (hipStream_t)stream, Y_dev, ldy, &O);
+}
+
+// dmrgx_kron_noise_expand: psi with the images c_a A_a psi of one side's operators set beside it (side 0: as further columns of the
+// KronBlock they land in, side 1: as further rows), so that the density matrix of the expansion is White's perturbed one
+//   rho'_q = Psi_q Psi_q^T + sum_a c_a^2 sum_k' (A_a Psi_k')(A_a Psi_k')^T        (PRB 72, 180403)
+// and the density-matrix solver needs nothing but wider sector tables.  Every panel is one emit_groups call of the term builder -- the
+// products and scaled copies of a one-sided term -- with the panel's corner as the output and the expanded leading dimension; the
+// coefficient goes into the materialised operand (OperandUses), a zero coefficient makes its panels groups without products.  The
+// Psi_k parts are strided device copies: bit for bit.
+extern "C" dmrgx_status dmrgx_kron_noise_expand(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
+                                                const int32_t* block_il, const int32_t* block_ir, const double* psi_dev,
+                                                int32_t side, int32_t n_ops, const dmrgx_secop* ops, const double* coef,
+                                                int32_t* extent, int64_t* n_out, double* Y_dev, void* stream)
+{
+    const char* fn = "kron_noise_expand";
+    hipStream_t st = (hipStream_t)stream;
+    if (side != 0 && side != 1) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: side %d is neither 0 (columns, for rho_L) nor 1 (rows, for rho_R)", fn, side);
+    if (n_ops < 0 || (n_ops > 0 && (!ops || !coef))) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: bad operator list (%d operators)", fn, n_ops);
+    if (!extent || !n_out) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null extent or n_out", fn);
+    if (Y_dev && !psi_dev) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null psi", fn);
+    GramLayout L;
+    DMRGX_CHK(kron_layout(fn, left, right, nblocks, block_il, block_ir, L));
+    const dmrgx_sectors& SL = *left;
+    const dmrgx_sectors& SR = *right;
+    const dmrgx_sectors& SS = side == 0 ? SL : SR;                      // the table the operators live on
+    const int32_t* sec_of = side == 0 ? block_il : block_ir;           // a KronBlock's sector on that side
+    std::vector<std::vector<NCell>> cells((size_t)n_ops);
+    for (int32_t a = 0; a < n_ops; ++a) {
+        if (!std::isfinite(coef[a])) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: coefficient %d is not finite", fn, a);
+        DMRGX_CHK(normalise_op(&ops[a], SS, side == 0 ? "kron_noise_expand left op" : "kron_noise_expand right op", cells[a]));
+    }
+    // the panels of every output block: (operator, source KronBlock), operators ascending, sources ascending
+    // fixed dimension of block k: n_L(IL_k) rows on side 0, n_R(IR_k) columns on side 1; the expanded one starts with psi's own
+    struct Panel { int32_t a, src, at; };                               // at: first column (row) of the panel in its block
+    std::vector<std::vector<Panel>> panels((size_t)nblocks);
+    std::vector<int64_t> out_off((size_t)nblocks + 1, 0);
+    for (int32_t k = 0; k < nblocks; ++k) {
+        int64_t ext = side == 0 ? SR.size[block_ir[k]] : SL.size[block_il[k]];
+        for (int32_t a = 0; a < n_ops; ++a)
+            for (int32_t s = 0; s < nblocks; ++s) {
+                if (sec_of[s] - ops[a].shift != sec_of[k]) continue;
+                panels[k].push_back(Panel{a, s, (int32_t)ext});
+                ext += side == 0 ? SR.size[block_ir[s]] : SL.size[block_il[s]];
+                if (ext > INT32_MAX) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: the expansion of KronBlock %d is wider than 2^31 - 1", fn, k);
+            }
+        extent[k] = (int32_t)ext;
+        out_off[k + 1] = out_off[k] + ext * (side == 0 ? SL.size[block_il[k]] : SR.size[block_ir[k]]);
+    }
+    *n_out = out_off[nblocks];
+    if (!Y_dev) return DMRGX_OK;                                        // sizes only: no device call so far
+    const int64_t N = L.ref_off[nblocks];
+    if (Y_dev < psi_dev + N && psi_dev < Y_dev + *n_out) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: Y overlaps psi", fn);
+
+    OperandUses ou;
+    std::vector<const std::vector<UCell>*> use((size_t)n_ops, nullptr);
+    for (int32_t k = 0; k < nblocks; ++k)
+        for (const Panel& p : panels[k])
+            if (coef[p.a] != 0.0 && !use[p.a]) DMRGX_CHK(ou.use_of(fn, side, p.a, coef[p.a], cells[p.a], &use[p.a]));
+    DevBuf trans, tab;
+    if (ou.trans_doubles > 0) DMRGX_CHK(trans.alloc_f64((size_t)ou.trans_doubles, st));
+    ou.bind(trans.as<double>());
+
+    GemmBatch gb;
+    GemmSet set;
+    EmitScratch emit;
+    std::vector<ImgContrib> lefts, rights;
+    for (int32_t k = 0; k < nblocks; ++k) {
+        const int32_t nl = SL.size[block_il[k]], nr = SR.size[block_ir[k]];
+        double* Yk = Y_dev + out_off[k];
+        const int32_t ldc = side == 0 ? extent[k] : nr;
+        // psi's own block: the leading columns (side 0) or rows (side 1)
+        DMRGX_HIP(hipMemcpy2DAsync(Yk, (size_t)ldc * sizeof(double), psi_dev + L.ref_off[k], (size_t)nr * sizeof(double), (size_t)nr * sizeof(double), (size_t)nl,
+                                   hipMemcpyDeviceToDevice, st));
+        for (const Panel& p : panels[k]) {
+            const int32_t sl = SL.size[block_il[p.src]], sr = SR.size[block_ir[p.src]];
+            double* Yp = side == 0 ? Yk + p.at : Yk + (int64_t)p.at * ldc;
+            const int32_t pm = side == 0 ? nl : sl, pn = side == 0 ? sr : nr;      // the panel: A Psi_src is n_L(IL_k) x n_R(IR_src), Psi_src B^T n_L(IL_src) x n_R(IR_k)
+            lefts.clear(); rights.clear();
+            if (use[p.a]) (side == 0 ? lefts : rights).push_back(ImgContrib{use[p.a], psi_dev + L.ref_off[p.src], sr});
+            // (without a contribution -- a zero coefficient -- the panel is one group without products: zeros)
+            emit_groups(gb, set, Yp, ldc, pm, pn, side == 0 ? block_il[k] : -1, side == 0 ? -1 : block_ir[k], lefts, rights, emit);
+        }
+    }
+    PackedUpload pk;
+    gb.pack(pk);
+    gb.pack(set, pk);
+    const size_t o_tasks = pk.add(ou.copies), o_tiles = pk.add(ou.copy_tiles);
+    DMRGX_CHK(pk.upload(tab, st));
+    gb.bind(tab);
+    DMRGX_CHK(ou.launch_copies(tab, o_tiles, o_tasks, trans.as<double>(), st));
+    return gb.launch(set, tab, st);
 }
 
 // dmrgx_kron_op_gram: one operator per vector, A (x) 1 or 1 (x) B.  It keeps its own builder: the same image blocks, groups and products

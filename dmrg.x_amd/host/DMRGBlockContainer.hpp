@@ -38,6 +38,7 @@
 #include "CorrelatorDealing.hpp"
 #include "TridiagQL.hpp"
 #include "Measurements.hpp"
+#include "Noise.hpp"
 
 /** One eigenpair of a reduced-density-matrix block */
 struct Eigen_t
@@ -201,6 +202,9 @@ public:
         ierr = PetscOptionsGetBool(NULL, NULL, "-corr_matrix", &use_corr_matrix, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-corr_dimer", &use_corr_dimer, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-prune_ops", &prune_ops, NULL); CHKERRQ(ierr);
+        /* -noise a0,a1,... / -noise_warmup a: White's density-matrix perturbation, weight per sweep (GetTruncation) */
+        ierr = dmrgx_host::ReadNoiseOptions(mpi_comm, noise); CHKERRQ(ierr);
+        if (noise.Any() && mpi_size > 1) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-noise is not available on more than one rank (got %d): the expansion of the density matrix is not striped.", (int)mpi_size);
         ierr = PetscOptionsGetBool(NULL, NULL, "-dsf", &use_dsf, NULL); CHKERRQ(ierr);
         if (use_dsf) {   /* -dsf 1: S^zz(q, w) at every measurement point (CalculateDynamicalStructureFactor) */
             if (mpi_size > 1) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-dsf 1 is not available on more than one rank (got %d): the Lanczos run behind S(q,w) has no collectives.", (int)mpi_size);
@@ -510,7 +514,10 @@ public:
             for (size_t i = 0; i < sweeps_mstates.size(); ++i) fprintf(fp_data, "%s%lld", i ? ", " : "", LLD(sweeps_mstates[i]));
             size_t in_use = 0, cached = 0, peak = 0;
             dmrgx_mem_stats(&in_use, &cached, &peak);
-            fprintf(fp_data, "],\n  \"GSEnergy\": %.16g,\n  \"MatMults\": %lld,\n  \"LastSweepSeconds\": %.9g,\n  \"LastSweepSteps\": %lld,\n  \"LastSweepMatMults\": %lld,\n  \"EigensolveSeconds\": %.9g,\n"
+            /* the schedule of the density-matrix perturbation as given (one weight per sweep, the last one holds on), and what it cost */
+            fprintf(fp_data, "],\n  \"Noise\": %s,\n  \"NoiseWarmup\": %.17g,\n  \"NoiseExpansions\": %lld,\n  \"NoiseMaxExpansionBytes\": %lld,\n  \"NoiseOperatorsLeft\": %lld,\n  \"NoiseOperatorsRight\": %lld",
+                    noise.Json().c_str(), noise.warmup, LLD(noise_expansions), (long long)noise_max_bytes, LLD(noise_ops[0]), LLD(noise_ops[1]));
+            fprintf(fp_data, ",\n  \"GSEnergy\": %.16g,\n  \"MatMults\": %lld,\n  \"LastSweepSeconds\": %.9g,\n  \"LastSweepSteps\": %lld,\n  \"LastSweepMatMults\": %lld,\n  \"EigensolveSeconds\": %.9g,\n"
                              "  \"DeviceBytesResidentAfterSweep\": %zu,\n  \"DeviceBytesPeak\": %zu,\n  \"DeviceBytesCached\": %zu,\n  \"StartVectorsTransformed\": %lld,\n  \"StartVectorsThroughOverlap\": %lld,\n  \"StartVectorsRejected\": %lld,\n"
                              "  \"RdmCalls\": %lld,\n  \"RdmBlockJacobiCalls\": %lld,\n  \"TridPersistentCalls\": %lld,\n  \"TridLaunchPathCalls\": %lld,\n  \"TridFallbacks\": %lld,\n"
                              "  \"TridMaxWorkgroupsPerMatrix\": %lld,\n  \"RdmMaxMergeLevels\": %lld,\n  \"RdmMaxWyBlocks\": %lld,\n  \"Ranks\": %d\n}\n",
@@ -641,7 +648,8 @@ public:
         BasisTransformation BT_L, BT_R;
         /* a side whose output block no later step reads needs its spectrum (truncation error, sector table) but no eigenvectors */
         const bool vec_sys = !(hints && hints->dead_sys && !same), vec_env = !(hints && hints->dead_env && !same);
-        ierr = GetTruncation(KronBlocks, gsv_r, MStates, BT_L, BT_R, BlockIndex(SysBlockOut), BlockIndex(EnvBlockOut), vec_sys, vec_env); CHKERRQ(ierr);
+        step.Noise = noise.At(LoopType == WarmupStep, LoopIdx - 1);      /* (the warm-up is loop 0, sweep s loop s + 1: also after a restart) */
+        ierr = GetTruncation(KronBlocks, gsv_r, MStates, BT_L, BT_R, BlockIndex(SysBlockOut), BlockIndex(EnvBlockOut), vec_sys, vec_env, step.Noise, &Terms); CHKERRQ(ierr);
         ierr = CalculateCorrelations_BlockDiag(KronBlocks, gsv_r, do_measurements); CHKERRQ(ierr);
         if (use_guess) {   /* what the next step needs to carry this ground state over */
             prev.valid = false;
@@ -1097,7 +1105,7 @@ public:
         std::ofstream f(filename);
         if (!f) SETERRQ1(mpi_comm, PETSC_ERR_FILE_OPEN, "cannot write %s", filename.c_str());
         char val[4096]; PetscBool set;
-        for (const char* key : {"-spin", "-mstates", "-mwarmup", "-nsweeps", "-msweeps", "-maxnsweeps", "-min_block"}) {
+        for (const char* key : {"-spin", "-mstates", "-mwarmup", "-nsweeps", "-msweeps", "-maxnsweeps", "-min_block", "-noise", "-noise_warmup"}) {
             PetscErrorCode ierr = PetscOptionsGetString(NULL, NULL, key, val, sizeof(val), &set); CHKERRQ(ierr);
             if (set) f << key << " " << (val[0] ? val : "yes") << "\n";
         }
@@ -2061,8 +2069,52 @@ public:
         again).  Its spectrum is then taken from the OTHER side of the same KronBlock -- Psi Psi^T and Psi^T Psi share their
         non-zero eigenvalues, the rest are exact zeros -- so the density matrices of that side are neither built nor
         diagonalised; truncation error and kept-sector table follow from the same sort / cut rules as ever. */
+    /** Density-matrix noise of weight a (White, PRB 72, 180403): for each side that is solved, psi expanded by the images sqrt(a) A psi of
+        the block operators of the step's inter-block terms (and the transposes of those with a shift) -- dmrgx_kron_noise_expand -- and
+        the density matrices of that side only, built on the expansion by dmrgx_rdm_create_subset with the expanded extents as the other
+        side's sector table, one sector per KronBlock.  rdm_of[side] and expansion[side] are the caller's to release, in that order. */
+    PetscErrorCode NoisyDensityMatrices(const KronBlocks_t& KronBlocks, const Vec& gsv_r, const double a, const std::vector<Hamiltonians::Term>& Terms,
+                                        const dmrgx_sectors& sl, const dmrgx_sectors& sr, const std::vector<int32_t>& bil, const std::vector<int32_t>& bir,
+                                        const bool need_vec[2], dmrgx_rdm* rdm_of[2], std::shared_ptr<dmrgx_host::DevBuffer> expansion[2])
+    {
+        std::vector<dmrgx_secop> plan_ops[2];
+        std::vector<std::vector<dmrgx_cell>> store;
+        PetscErrorCode ierr = KronBlocks.CrossOperators(Terms, plan_ops[0], plan_ops[1], store); CHKERRQ(ierr);
+        const int32_t nb = (int32_t)bil.size();
+        std::vector<int32_t> own((size_t)nb);
+        for (int32_t k = 0; k < nb; ++k) own[(size_t)k] = k;
+        for (int side = 0; side < 2; ++side) {
+            if (!need_vec[side]) continue;
+            std::vector<dmrgx_secop> ops;
+            std::vector<double> coef;
+            dmrgx_host::NoiseOperators(plan_ops[side], a, ops, coef);
+            std::vector<int32_t> extent((size_t)nb, 0);
+            int64_t n_out = 0;
+            if (dmrgx_kron_noise_expand(&sl, &sr, nb, bil.data(), bir.data(), nullptr, side, (int32_t)ops.size(), ops.data(), coef.data(), extent.data(), &n_out, nullptr, nullptr))
+                SETERRQ1(mpi_comm, 1, "dmrgx_kron_noise_expand: %s", dmrgx_last_error());
+            expansion[side] = std::make_shared<dmrgx_host::DevBuffer>((size_t)n_out, dmrgx_host::DevBuffer::device_only_t{});
+            if (dmrgx_kron_noise_expand(&sl, &sr, nb, bil.data(), bir.data(), gsv_r->buf->dev_ro(), side, (int32_t)ops.size(), ops.data(), coef.data(), extent.data(), &n_out,
+                                        expansion[side]->dev_uninitialised(), nullptr))
+                SETERRQ1(mpi_comm, 1, "dmrgx_kron_noise_expand: %s", dmrgx_last_error());
+            const dmrgx_sectors se{nb, extent.data()};
+            const std::vector<uint8_t> mask((size_t)nb, (uint8_t)(1 << side));
+            if (dmrgx_rdm_create_subset(side == 0 ? &sl : &se, side == 0 ? &se : &sr, nb, side == 0 ? bil.data() : own.data(), side == 0 ? own.data() : bir.data(),
+                                        expansion[side]->dev_uninitialised(), mask.data(), nullptr, &rdm_of[side]))
+                SETERRQ1(mpi_comm, 1, "dmrgx_rdm_create_subset: %s", dmrgx_last_error());
+            noise_max_bytes = std::max<int64_t>(noise_max_bytes, n_out * (int64_t)sizeof(double));
+            noise_ops[side] = std::max<PetscInt>(noise_ops[side], (PetscInt)ops.size());
+            ++noise_expansions;
+        }
+        return 0;
+    }
+
+    /*  noise_a > 0 (engine extension, -noise; one rank): White's density-matrix perturbation.  Each side that is solved gets a density-matrix
+        object of its own, built by the unchanged solver on the expansion of dmrgx_kron_noise_expand (NoisyDensityMatrices); spectra,
+        selection and eigenvectors of a side are read from that side's object, and the spectra are divided by the trace of the perturbed
+        matrix.  noise_a == 0 is the code path and the call sequence of before. */
     PetscErrorCode GetTruncation(const KronBlocks_t& KronBlocks, const Vec& gsv_r, const PetscInt& MStates, BasisTransformation& BT_L, BasisTransformation& BT_R,
-                                 const PetscInt keyL = -1, const PetscInt keyR = -1, const bool need_vec_L = true, const bool need_vec_R = true)
+                                 const PetscInt keyL = -1, const PetscInt keyR = -1, const bool need_vec_L = true, const bool need_vec_R = true,
+                                 const double noise_a = 0.0, const std::vector<Hamiltonians::Term>* noise_terms = nullptr)
     {
         PetscErrorCode ierr;
         if (gsv_r->n != KronBlocks.NumStates()) SETERRQ2(PETSC_COMM_SELF, 1, "Incorrect vector length. Expected %lld. Got %lld.", LLD(KronBlocks.NumStates()), LLD(gsv_r->n));
@@ -2076,6 +2128,11 @@ public:
         }
         dmrgx_sectors sl{(int32_t)ls.size(), ls.data()}, sr{(int32_t)rs.size(), rs.data()};
         dmrgx_rdm* rdm = nullptr;
+        const bool noisy = noise_a > 0.0;
+        if (noisy && (!noise_terms || dmrgx_host::WorldComm())) SETERRQ(mpi_comm, PETSC_ERR_SUP, "Density-matrix noise needs the terms of the step and one rank.");
+        dmrgx_rdm* rdm_of[2] = {nullptr, nullptr};                       /* the object a side is read from: one for both, or one each under noise */
+        std::shared_ptr<dmrgx_host::DevBuffer> expansion[2];            /* under noise: what that side's object was built on */
+        auto drop = [&]() { if (rdm_of[0]) dmrgx_rdm_destroy(rdm_of[0]); if (rdm_of[1] && rdm_of[1] != rdm_of[0]) dmrgx_rdm_destroy(rdm_of[1]); rdm_of[0] = rdm_of[1] = nullptr; };
         PetscLogDouble tr0, tr1;
         PetscTime(&tr0);
         /* warm start of the block-Jacobi eigensolver: the eigenbasis found at the previous visit of the block being created
@@ -2083,7 +2140,7 @@ public:
         const PetscInt keys[2] = {keyL, keyR};
         std::vector<const double*> v0((size_t)(2 * nb), nullptr);
         PetscInt nwarm = 0;
-        if (use_rdm_warm && !dmrgx_host::WorldComm()) for (int side = 0; side < 2; ++side) {
+        if (use_rdm_warm && !noisy && !dmrgx_host::WorldComm()) for (int side = 0; side < 2; ++side) {
             auto it = rdm_basis.find({keys[side], (keyR == keyL) ? 0 : side});      /* centre step: both sides are the same block */
             if (keys[side] < 0 || it == rdm_basis.end() || it->second.sizes != (side == 0 ? ls : rs)) continue;
             for (PetscInt k = 0; k < nb; ++k) {
@@ -2112,7 +2169,8 @@ public:
             std::vector<double> load((size_t)W, 0.0);
             for (const auto& u : units) { int best = 0; for (int w = 1; w < W; ++w) if (load[(size_t)w] < load[(size_t)best]) best = w; load[(size_t)best] += u.first; owner[(size_t)u.second] = best; }
         }
-        if (W > 1 || partial) {
+        if (noisy) { ierr = NoisyDensityMatrices(KronBlocks, gsv_r, noise_a, *noise_terms, sl, sr, bil, bir, need_vec, rdm_of, expansion); if (ierr) { drop(); CHKERRQ(ierr); } }
+        else if (W > 1 || partial) {
             std::vector<uint8_t> mask((size_t)nb, 0);
             for (PetscInt k = 0; k < nb; ++k) mask[(size_t)k] = (uint8_t)((owner[(size_t)(2 * k)] == me ? 1 : 0) | (owner[(size_t)(2 * k + 1)] == me ? 2 : 0));
             if (dmrgx_rdm_create_subset(&sl, &sr, (int32_t)nb, bil.data(), bir.data(), gsv_r->buf->dev_ro(), mask.data(), nullptr, &rdm))
@@ -2120,13 +2178,21 @@ public:
         }
         else if (dmrgx_rdm_create_warm(&sl, &sr, (int32_t)nb, bil.data(), bir.data(), gsv_r->buf->dev_ro(), nwarm ? v0.data() : nullptr, nullptr, &rdm))
             SETERRQ1(mpi_comm, 1, "dmrgx_rdm_create: %s", dmrgx_last_error());
+        if (!noisy) rdm_of[0] = rdm_of[1] = rdm;
         /* spectra of every matrix on every rank */
         std::vector<int64_t> spec_off((size_t)(2 * nb + 1), 0);
         for (PetscInt k = 0; k < nb; ++k) { spec_off[(size_t)(2 * k + 1)] = spec_off[(size_t)(2 * k)] + ls[bil[k]]; spec_off[(size_t)(2 * k + 2)] = spec_off[(size_t)(2 * k + 1)] + rs[bir[k]]; }
         std::vector<double> spectra((size_t)spec_off[(size_t)(2 * nb)], 0.0);
         for (PetscInt k = 0; k < nb; ++k) for (int side = 0; side < 2; ++side) {
             if (owner[(size_t)(2 * k + side)] != me) continue;
-            if (dmrgx_rdm_eigenvalues(rdm, side, (int32_t)k, spectra.data() + spec_off[(size_t)(2 * k + side)])) { dmrgx_rdm_destroy(rdm); SETERRQ1(mpi_comm, 1, "dmrgx_rdm_eigenvalues: %s", dmrgx_last_error()); }
+            if (dmrgx_rdm_eigenvalues(rdm_of[side], side, (int32_t)k, spectra.data() + spec_off[(size_t)(2 * k + side)])) { drop(); SETERRQ1(mpi_comm, 1, "dmrgx_rdm_eigenvalues: %s", dmrgx_last_error()); }
+        }
+        if (noisy) for (int side = 0; side < 2; ++side) {      /* Tr rho' = |psi|^2 + a sum |A psi|^2 over the KronBlocks: the sum of that side's eigenvalues */
+            if (!need_vec[side]) continue;
+            double tr = 0.0;
+            for (PetscInt k = 0; k < nb; ++k) for (int64_t e = spec_off[(size_t)(2 * k + side)]; e < spec_off[(size_t)(2 * k + side + 1)]; ++e) tr += spectra[(size_t)e];
+            if (!(tr > 0.0) || !std::isfinite(tr)) { drop(); SETERRQ1(mpi_comm, 1, "The perturbed density matrix has trace %g.", tr); }
+            for (PetscInt k = 0; k < nb; ++k) for (int64_t e = spec_off[(size_t)(2 * k + side)]; e < spec_off[(size_t)(2 * k + side + 1)]; ++e) spectra[(size_t)e] /= tr;
         }
         if (W > 1) {
             std::vector<double> all(spectra.size() * (size_t)W);
@@ -2142,7 +2208,7 @@ public:
             const int64_t nd = spec_off[(size_t)(2 * k + dead + 1)] - spec_off[(size_t)(2 * k + dead)], nl = spec_off[(size_t)(2 * k + live + 1)] - spec_off[(size_t)(2 * k + live)];
             for (int64_t e = 0; e < nd; ++e) spectra[(size_t)(spec_off[(size_t)(2 * k + dead)] + e)] = e < nl ? spectra[(size_t)(spec_off[(size_t)(2 * k + live)] + e)] : 0.0;
         }
-        if (use_rdm_warm && W == 1) for (int side = 0; side < 2; ++side) {      /* remember this visit's eigenbases (all eigenvectors, as rows) */
+        if (use_rdm_warm && !noisy && W == 1) for (int side = 0; side < 2; ++side) {      /* remember this visit's eigenbases (all eigenvectors, as rows) */
             if (keys[side] < 0 || (side == 1 && keyR == keyL)) continue;
             /* a side whose spectrum was borrowed (dead block of a pruned sweep) has no eigenvectors: drop what an earlier visit stored */
             if (!need_vec[side]) { rdm_basis.erase({keys[side], side}); continue; }
@@ -2158,10 +2224,11 @@ public:
             }
         }
         PetscTime(&tr1);
-        {
+        for (int obj = 0; obj < 2; ++obj) {
             /* which path the density-matrix solver took: a time-out fallback or an unexpected launch path must show in DMRGRun.json, not only on stderr */
+            if (!rdm_of[obj] || (obj == 1 && rdm_of[1] == rdm_of[0])) continue;      /* (one object, or one per solved side under noise) */
             dmrgx_rdm_report rr;
-            if (dmrgx_rdm_info(rdm, &rr)) { dmrgx_rdm_destroy(rdm); SETERRQ1(mpi_comm, 1, "dmrgx_rdm_info: %s", dmrgx_last_error()); }
+            if (dmrgx_rdm_info(rdm_of[obj], &rr)) { drop(); SETERRQ1(mpi_comm, 1, "dmrgx_rdm_info: %s", dmrgx_last_error()); }
             ++rdm_calls;
             if (rr.solver == 1) ++rdm_jacobi_calls;
             if (rr.timed_out) ++trid_fallbacks;
@@ -2220,7 +2287,10 @@ public:
         {
             std::vector<int32_t> counts((size_t)(2 * nb), 0);
             for (int side = 0; side < 2; ++side) for (const auto& kv : per_side[side]) counts[(size_t)(2 * kv.second.first + side)] = (int32_t)kv.second.second;
-            if (dmrgx_rdm_select(rdm, counts.data(), nullptr)) { dmrgx_rdm_destroy(rdm); SETERRQ1(mpi_comm, 1, "dmrgx_rdm_select: %s", dmrgx_last_error()); }
+            for (int obj = 0; obj < 2; ++obj) {      /* (entries of matrices an object did not build are ignored) */
+                if (!rdm_of[obj] || (obj == 1 && rdm_of[1] == rdm_of[0])) continue;
+                if (dmrgx_rdm_select(rdm_of[obj], counts.data(), nullptr)) { drop(); SETERRQ1(mpi_comm, 1, "dmrgx_rdm_select: %s", dmrgx_last_error()); }
+            }
         }
         for (int side = 0; side < 2; ++side) {
             const std::map<PetscInt, std::pair<PetscInt, PetscInt>>& per = per_side[side];
@@ -2255,7 +2325,7 @@ public:
                 qn_list.push_back(M[side]->List(blk)); qn_size.push_back(cnt);
             }
             /* the kept rows of all sectors of this side in one launch */
-            if (!vec_tasks.empty() && dmrgx_rdm_eigenvectors_batch(rdm, (int32_t)vec_tasks.size(), vec_tasks.data(), nullptr)) { dmrgx_rdm_destroy(rdm); SETERRQ1(mpi_comm, 1, "dmrgx_rdm_eigenvectors_batch: %s", dmrgx_last_error()); }
+            if (!vec_tasks.empty() && dmrgx_rdm_eigenvectors_batch(rdm_of[side], (int32_t)vec_tasks.size(), vec_tasks.data(), nullptr)) { drop(); SETERRQ1(mpi_comm, 1, "dmrgx_rdm_eigenvectors_batch: %s", dmrgx_last_error()); }
             if (W > 1) {
                 for (int w = 0; w < W; ++w)
                     if (staging[(size_t)w] && dmrgx_comm_bcast(comm, staging[(size_t)w]->dev_uninitialised(), (size_t)stage_len[(size_t)w] * sizeof(double), w, nullptr)) { dmrgx_rdm_destroy(rdm); SETERRQ1(mpi_comm, 1, "dmrgx_comm_bcast: %s", dmrgx_last_error()); }
@@ -2279,6 +2349,17 @@ public:
            eigenpairs (eigenvalues against the Rayleigh quotients of the finished vectors), which by then has long arrived -- destroying it
            here made the host wait for the GPU to drain (5 % of a configs[1] step, profiles/r05_hostprof_m512.txt) before it could queue the
            rotations.  Everything queued above is stream-ordered; the rotation rows live in buffers of their own. */
+        if (noisy) {
+            /* under noise the objects go at once, each before the expansion it was built on: the verification is read here, at the price of
+               waiting for the queue -- paid in the noisy sweeps only, and the expansions are the largest buffers of the step */
+            for (int side = 0; side < 2; ++side) {
+                dmrgx_rdm* r = rdm_of[side];
+                rdm_of[side] = nullptr;
+                if (r && dmrgx_rdm_destroy(r)) { drop(); SETERRQ1(mpi_comm, 1, "dmrgx_rdm_destroy: %s", dmrgx_last_error()); }
+                expansion[side].reset();
+            }
+            return 0;
+        }
         if (W > 1) dmrgx_stream_sync(nullptr);
         dmrgx_rdm* old_rdm = W > 1 ? rdm : rdm_pending;
         rdm_pending = W > 1 ? nullptr : rdm;
@@ -2388,6 +2469,7 @@ private:
         PetscInt NumSites_Sys = 0, NumSites_Env = 0, NumSites_SysEnl = 0, NumSites_EnvEnl = 0;
         PetscInt NumStates_Sys = 0, NumStates_Env = 0, NumStates_SysEnl = 0, NumStates_EnvEnl = 0, NumStates_SysRot = 0, NumStates_EnvRot = 0, NumStates_H = 0;
         PetscScalar GSEnergy = 0; PetscReal TruncErr_Sys = 0, TruncErr_Env = 0;
+        PetscReal Noise = 0;    /* weight of the density-matrix perturbation of this step's truncation */
     };
     struct TimingsData { PetscLogDouble tEnlr = 0, tKron = 0, tDiag = 0, tRdms = 0, tRotb = 0, Total = 0; PetscInt nMatMult = 0, nRotOps = 0;
                          double msAllGather = 0, msApply = 0; };      /* (ranks > 1) HIP-event time of the step's all-gathers / applies on this rank */
@@ -2441,15 +2523,15 @@ private:
     {
         fprintf(fp_step, "{\n  \"headers\" : [\"GlobIdx\", \"LoopType\", \"LoopIdx\", \"StepIdx\", \"NSites_Sys\", \"NSites_Env\", \"NSites_SysEnl\", \"NSites_EnvEnl\", "
                          "\"NStates_Sys\", \"NStates_Env\", \"NStates_SysEnl\", \"NStates_EnvEnl\", \"NStates_SysRot\", \"NStates_EnvRot\", \"NumStates_H\", "
-                         "\"TruncErr_Sys\", \"TruncErr_Env\", \"GSEnergy\"  ],\n  \"table\" : ");
+                         "\"Noise\", \"TruncErr_Sys\", \"TruncErr_Env\", \"GSEnergy\"  ],\n  \"table\" : ");
         return 0;
     }
     PetscErrorCode SaveStepData(const StepData& d)
     {
-        fprintf(fp_step, "%s    [ %lld, %s, %lld, %lld, %lld, %lld, %lld, %lld, %lld, %lld, %lld, %lld, %lld, %lld, %lld, %.12g, %.12g, %.12g]", rows_written ? ",\n" : "",
+        fprintf(fp_step, "%s    [ %lld, %s, %lld, %lld, %lld, %lld, %lld, %lld, %lld, %lld, %lld, %lld, %lld, %lld, %lld, %.17g, %.12g, %.12g, %.12g]", rows_written ? ",\n" : "",
                 LLD(GlobIdx), LoopType ? "\"Sweep\"" : "\"Warmup\"", LLD(LoopIdx), LLD(StepIdx), LLD(d.NumSites_Sys), LLD(d.NumSites_Env), LLD(d.NumSites_SysEnl), LLD(d.NumSites_EnvEnl),
                 LLD(d.NumStates_Sys), LLD(d.NumStates_Env), LLD(d.NumStates_SysEnl), LLD(d.NumStates_EnvEnl), LLD(d.NumStates_SysRot), LLD(d.NumStates_EnvRot), LLD(d.NumStates_H),
-                d.TruncErr_Sys, d.TruncErr_Env, d.GSEnergy);
+                d.Noise, d.TruncErr_Sys, d.TruncErr_Env, d.GSEnergy);
         fflush(fp_step);
         return 0;
     }
@@ -2597,6 +2679,9 @@ private:
     PetscBool dsf_dimer_have_omega = PETSC_FALSE;
     std::vector<double> dsf_dimer_omega;        /* -dsf_dimer_omega w0,w1,nw: the grid of the Jackson-broadened SqwGrid */
     dmrgx_host::JsonRecordFile dsf_dimer_file{"%.17g"}; /* created at the first measurement with -dsf_dimer */
+    dmrgx_host::NoiseSchedule noise;            /* -noise a0,a1,... / -noise_warmup a: the weight of the density-matrix perturbation per sweep (Noise.hpp) */
+    int64_t noise_max_bytes = 0;                /* the largest expansion a truncation held (DMRGRun.json NoiseMaxExpansionBytes) */
+    PetscInt noise_ops[2] = {0, 0}, noise_expansions = 0;      /* operators per side of the largest list; expansions built */
     PetscBool use_dsf_pm = PETSC_FALSE;         /* -dsf_pm c0,c1,...: Chebyshev moments of the transverse correlations, TransverseDynamics.json (CalculateTransverseDynamics); shares the -dsf_cheb_* options */
     std::vector<PetscInt> dsf_pm_sites;         /* the reference sites c, lattice numbering of To1D */
     dmrgx_host::JsonRecordFile dsf_pm_file{"%.17g"};    /* created at the first measurement with -dsf_pm */

@@ -147,6 +147,17 @@ public:
         return ierr;
     }
 
+    /** The left and right operator lists of the plan descriptor that KronSumConstruct(Terms, .) builds -- the block operators through
+        which the Hamiltonian couples the two blocks (density-matrix noise perturbs with exactly these).  `store` owns their cells. */
+    PetscErrorCode CrossOperators(const std::vector<Hamiltonians::Term>& Terms, std::vector<dmrgx_secop>& lops, std::vector<dmrgx_secop>& rops,
+                                  std::vector<std::vector<dmrgx_cell>>& store) const
+    {
+        std::vector<Hamiltonians::Term> TermsLR;
+        PetscErrorCode ierr = ClassifyTerms(Terms, TermsLR); CHKERRQ(ierr);
+        std::vector<dmrgx_term> terms;
+        return CollectOperators(TermsLR, lops, rops, store, terms);
+    }
+
 private:
     static Mat OpOf(Block::SpinBase& blk, Op_t op, PetscInt site, const Mat& extra)
     {
@@ -154,11 +165,13 @@ private:
         return op == OpSz ? blk.Sz(site) : blk.Sp(site);      /* Sm(i) is read as Sp(i) transposed */
     }
 
-    PetscErrorCode BuildPlan(const Mat& HL, const Mat& HR, const std::vector<Hamiltonians::Term>& TermsLR, Mat& MatOut, const bool distributed = false)
+    /** The distinct (operator, site) operators of the classified terms on each side, in the order the terms first name them, as the plan
+        descriptor lists them; `store` owns their cells; terms[t] names the two operators of TermsLR[t]. */
+    PetscErrorCode CollectOperators(const std::vector<Hamiltonians::Term>& TermsLR, std::vector<dmrgx_secop>& lops, std::vector<dmrgx_secop>& rops,
+                                    std::vector<std::vector<dmrgx_cell>>& store, std::vector<dmrgx_term>& terms) const
     {
         std::map<std::pair<int, PetscInt>, int32_t> li, ri;
-        std::vector<dmrgx_secop> lops, rops;
-        std::vector<std::vector<dmrgx_cell>> store;
+        lops.clear(); rops.clear(); store.clear(); terms.clear();
         store.reserve(2 * TermsLR.size() + 4);
         auto add = [&](Block::SpinBase& blk, std::map<std::pair<int, PetscInt>, int32_t>& idx, std::vector<dmrgx_secop>& ops, Op_t op, PetscInt site, const Mat& extra) -> int32_t {
             auto key = std::make_pair((int)op, site);
@@ -175,12 +188,20 @@ private:
             idx[key] = (int32_t)ops.size() - 1;
             return idx[key];
         };
-        std::vector<dmrgx_term> terms;
         for (const Hamiltonians::Term& t : TermsLR) {
             const int32_t l = add(LeftBlock, li, lops, t.Iop, t.Isite, extra_left), r = add(RightBlock, ri, rops, t.Jop, t.Jsite, extra_right);
             if (l < 0 || r < 0) SETERRQ(mpi_comm, PETSC_ERR_ARG_CORRUPT, "Term refers to an operator that does not exist.");
             terms.push_back(dmrgx_term{t.a, l, r});
         }
+        return 0;
+    }
+
+    PetscErrorCode BuildPlan(const Mat& HL, const Mat& HR, const std::vector<Hamiltonians::Term>& TermsLR, Mat& MatOut, const bool distributed = false)
+    {
+        std::vector<dmrgx_secop> lops, rops;
+        std::vector<std::vector<dmrgx_cell>> store;
+        std::vector<dmrgx_term> terms;
+        PetscErrorCode ierr = CollectOperators(TermsLR, lops, rops, store, terms); CHKERRQ(ierr);
         dmrgx_secop hl, hr;
         std::vector<dmrgx_cell> hls, hrs;
         if (HL) HL->to_secop(hl, hls);

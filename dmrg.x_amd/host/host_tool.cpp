@@ -12,6 +12,7 @@
 #include "CorrelatorDealing.hpp"
 #include "TridiagQL.hpp"
 #include "Measurements.hpp"
+#include "Noise.hpp"
 
 static void dump_mat(const char* tag, PetscInt site, const Mat& m)
 {
@@ -275,6 +276,31 @@ int main()
             }
             J.Close();
             printf("rc %d\n", ierr);
+        } else if (cmd == "noise") {            /* noise <-noise value or "none"> <-noise_warmup value or "none"> nsweeps  ->  rc, then the warm-up's weight and that of every sweep, then the JSON */
+            std::string sched, warm; PetscInt nsweeps; is >> sched >> warm >> nsweeps;
+            dmrgx_host::Options::Global().Clear();
+            if (sched != "none") PetscOptionsSetValue(NULL, "-noise", sched == "empty" ? "" : sched.c_str());
+            if (warm != "none") PetscOptionsSetValue(NULL, "-noise_warmup", warm.c_str());
+            dmrgx_host::NoiseSchedule S;
+            ierr = dmrgx_host::ReadNoiseOptions(PETSC_COMM_WORLD, S);
+            printf("rc %d\n", ierr);
+            if (!ierr) {
+                std::vector<double> v{S.At(true, 0)};
+                for (PetscInt s = 0; s < nsweeps; ++s) v.push_back(S.At(false, s));
+                print_numbers("noise", v);
+                printf("any %d json %s\n", (int)S.Any(), S.Json().c_str());
+            }
+        } else if (cmd == "noiseops") {         /* noiseops a n, then n x (shift transposed id): plan operators, id names the stored cell set  ->  the list of NoiseOperators as shift:transposed:id, then the coefficient */
+            double a; PetscInt n; is >> a >> n;
+            std::vector<dmrgx_cell> sets(64);
+            for (size_t i = 0; i < sets.size(); ++i) sets[i] = dmrgx_cell{0, 0, 0, 2, 2, DMRGX_CELL_DENSE, 0.0, reinterpret_cast<const double*>(sets.data()) + i % 32, 2};      /* (addresses never read; set 32 + i is a second descriptor of the blocks of set i) */
+            std::vector<dmrgx_secop> plan_ops, ops;
+            for (PetscInt i = 0; i < n; ++i) { PetscInt s, t, id; is >> s >> t >> id; plan_ops.push_back(dmrgx_secop{(int32_t)s, (int32_t)t, 1, &sets[(size_t)id]}); }
+            std::vector<double> coef;
+            dmrgx_host::NoiseOperators(plan_ops, a, ops, coef);
+            printf("noiseops");
+            for (const dmrgx_secop& o : ops) printf(" %d:%d:%d", o.shift, o.transposed, (int)(o.cells - sets.data()));
+            printf("\ncoef %.17g %d\n", coef.empty() ? 0.0 : coef[0], (int)coef.size());
         } else printf("unknown %s\n", cmd.c_str());
         fflush(stdout);
     }

@@ -412,12 +412,47 @@ def term_apply_to(sb_or_layout, psi, left_ops, right_ops, vectors, out_blocks, o
     return out
 
 
+def noise_expand(sb_or_layout, psi, side, ops, coef, out=None):
+    """psi with the images coef[a] * ops[a] psi of one block's operators beside it (dmrgx_kron_noise_expand): side 0 expands the columns of
+    every KronBlock with operators of the left block, side 1 the rows with operators of the right block, so that the density matrix of
+    the expansion on that side is White's perturbed one.  Layout, psi and operators (a SectorOperator, or (SectorOperator, True) for its
+    transpose; any shifts) as in op_gram.  out: a contiguous 1-D f64 device tensor of at least n_out elements (elements beyond n_out are
+    left alone); default: a new tensor of n_out.  Returns (Y, extent, n_out); `noise_rdm_layout` turns extent into the layout the
+    density-matrix solver takes."""
+    _capi.require_device()
+    args, psi, keep = _gram_arguments(sb_or_layout, psi, ops if side == 0 else [], ops if side != 0 else [])
+    head, (nl, larr, nr, rarr) = args[:6], args[6:]
+    n_ops, arr = (nl, larr) if side == 0 else (nr, rarr)
+    assert len(coef) == n_ops
+    cf = (C.c_double * max(n_ops, 1))(*[float(c) for c in coef])
+    extent, n_out = (C.c_int32 * head[2])(), C.c_int64(0)
+    L = _capi.lib()
+    _capi.check(L.dmrgx_kron_noise_expand(*head, side, n_ops, arr, cf, extent, C.byref(n_out), None, None))
+    if out is None:
+        out = torch.empty(n_out.value, dtype=torch.float64, device=psi.device)
+    assert out.dtype == torch.float64 and out.dim() == 1 and out.is_contiguous() and out.numel() >= n_out.value
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _capi.check(L.dmrgx_kron_noise_expand(*head, side, n_ops, arr, cf, extent, C.byref(n_out), C.c_void_p(out.data_ptr()), st))
+    torch.cuda.current_stream().synchronize()       # the operator copies in `keep` are read by the queued work
+    return out, list(extent), n_out.value
+
+
+def noise_rdm_layout(sb_or_layout, side, extent):
+    """(left_sizes, right_sizes, blocks, side_mask) under which ReducedDensityMatrices reads an expansion of noise_expand: the expanded
+    extents are the sector table of the other side, one sector per KronBlock, and only the density matrices of `side` are built."""
+    left_sizes, right_sizes, blocks = (sb_or_layout.left_sizes, sb_or_layout.right_sizes, sb_or_layout.blocks) if hasattr(sb_or_layout, "blocks") else sb_or_layout
+    if side == 0:
+        return list(left_sizes), list(extent), [(b[0], k) for k, b in enumerate(blocks)], [1] * len(blocks)
+    return list(extent), list(right_sizes), [(k, b[1]) for k, b in enumerate(blocks)], [2] * len(blocks)
+
+
 class ReducedDensityMatrices:
     """Device RDM blocks + spectra of a superblock state (GetTruncation's rank-0 loop,
     include/DMRGBlockContainer.hpp:1715-1775).  psi: device tensor in the reference's vector layout."""
 
-    def __init__(self, left_sizes, right_sizes, blocks, psi, warm=None):
-        """warm: optional {(side, k): (n x n) device tensor of eigenvectors as rows from a previous solve} (warm start)."""
+    def __init__(self, left_sizes, right_sizes, blocks, psi, warm=None, side_mask=None):
+        """warm: optional {(side, k): (n x n) device tensor of eigenvectors as rows from a previous solve} (warm start).
+        side_mask: optional per-KronBlock bits (1: rho_L, 2: rho_R) of the density matrices to build (dmrgx_rdm_create_subset)."""
         L = _capi.lib()
         self.left_sizes, self.right_sizes, self.blocks = list(left_sizes), list(right_sizes), list(blocks)
         ls, rs = _i32(left_sizes), _i32(right_sizes)
@@ -428,8 +463,13 @@ class ReducedDensityMatrices:
         # request): a temporary tensor would go back to torch's allocator and be handed out again before then
         self._psi = psi
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if warm:
-            ptrs = (C.c_void_p * (2 * len(blocks)))()
+        if side_mask is not None:
+            assert not warm and len(side_mask) == len(blocks)
+            mask = (C.c_uint8 * len(blocks))(*[int(b) for b in side_mask])
+            _capi.check(L.dmrgx_rdm_create_subset(C.byref(sl), C.byref(sr), len(blocks), bil, bir, C.c_void_p(psi.data_ptr()), C.cast(mask, C.c_void_p), st,
+                                                  C.byref(self._handle)))
+        elif warm:
+            ptrs =(C.c_void_p * (2 * len(blocks)))()
             for (side, k), t in warm.items():
                 assert t.is_contiguous() and t.dtype == torch.float64 and t.shape == (self.size(side, k),) * 2
                 ptrs[2 * k + side] = t.data_ptr()

@@ -33,6 +33,8 @@
  *   dmrgx_kron_chebyshev_moments  the Chebyshev recursion on the planned Hamiltonian and its moments with a family of vectors (-dsf_cheb)
  *   dmrgx_kron_correction_vector  the correction vector 1 / (sigma + i eta - H) v0 by a device-resident conjugate-gradient run, and its
  *                               overlaps with a family of vectors: G_ic(w + i eta) under a true Lorentzian (-dsf_cv)
+ *   dmrgx_kron_noise_expand     psi with the images of one block's operators beside it: White's density-matrix perturbation as a wider input
+ *                               of dmrgx_rdm_create_subset (-noise)
  *   dmrgx_vec_project_out       one vector removed from a family of vectors, coefficients returned: (D_b - <D_b>) psi for all bonds (-dsf_dimer)
  *   dmrgx_comm_*             <- the communicator of the reference's MPI path: VecScatter-to-all of x inside every MatMult
  *                               (src/DMRGKron.cpp:1833-1834) and the MPI_Allreduce behind SLEPc's VecDot / VecNorm
@@ -488,6 +490,43 @@ dmrgx_status dmrgx_kron_term_apply_to(const dmrgx_sectors* left, const dmrgx_sec
                                       int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
                                       int32_t n_out, const int32_t* out_il, const int32_t* out_ir,
                                       double* Y_dev, int64_t ldy, void* stream);
+
+/* ---- density-matrix noise: psi with the images of one block's operators set beside it --------------------------------- */
+/* White's perturbation of the reduced density matrix (PRB 72, 180403) without a new density-matrix build.  For the left block and a
+ * KronBlock k = (IL, IR), q = IL,
+ *   rho'_q = Psi_q Psi_q^T + sum_a coef[a]^2 sum_k' (A_a Psi_k')(A_a Psi_k')^T,      k' over the KronBlocks with IL_k' - shift_a == q,
+ * is Psi'_q Psi'_q^T of the column-expanded Psi'_q = [ Psi_q | coef[a] A_a Psi_k' | ... ]; for the right block the rows are stacked,
+ * Psi''_k = [ Psi_k ; coef[b] Psi_k' B_b^T ; ... ] and rho'_R = Psi''^T Psi''.  This call writes the expansion; dmrgx_rdm_create_subset
+ * then runs on it unchanged, with `extent` as the sector table of the other side (side 0: right table = extent, block_ir'[k] = k, side mask
+ * bit 0; side 1: left table = extent, block_il'[k] = k, bit 1).
+ * Sector tables, KronBlocks and psi (reference vector layout, only read) as in dmrgx_kron_term_apply.  side: 0 expands columns with
+ * operators of the LEFT block, 1 expands rows with operators of the RIGHT block.  ops[a] (cells, `transposed`, any shift, shifts may differ
+ * within a call) live on the sector table of that side; coef: host array [n_ops], finite, any sign.  n_ops == 0 copies psi.
+ * Output: block k follows block k - 1 (the nested list order of the KronBlocks) and is row-major.
+ *   side 0: n_L(IL_k) x extent[k].  Columns [0, n_R(IR_k)) are Psi_k, copied bit for bit.  Then, for every operator a in ascending order and
+ *           for every source KronBlock k' in ascending order with IL_k' - shift_a == IL_k, one panel coef[a] * A_a Psi_k' of n_R(IR_k') columns.
+ *   side 1: extent[k] x n_R(IR_k).  Rows [0, n_L(IL_k)) are Psi_k.  Then, in the same order, for every k' with IR_k' - shift_b == IR_k, one
+ *           panel coef[b] * Psi_k' B_b^T of n_L(IL_k') rows.
+ * A source KronBlock whose shifted sector exists but is the sector of no KronBlock contributes nothing, like one whose shifted sector does
+ * not exist: the perturbation never creates a sector the target state cannot use.  An operator without cells in a panel's sector block
+ * gives a panel of zeros; coef[a] == 0 gives its panels as exact zeros whatever psi and the cells hold.
+ * extent (host [nblocks]) and *n_out (host: the doubles of the whole expansion, sum_k extent[k] times the block's other dimension) are
+ * always written.  Y_dev == NULL: sizes only -- nothing else is done, no device is touched, psi_dev may be NULL.  Otherwise every element
+ * of [0, *n_out) of Y is written exactly once (Y may hold anything on entry).  Y must not overlap psi.
+ * Every panel is a list of grouped-GEMM products (dense cells) and scaled copies (identity cells) with the panel's corner as the output and
+ * the block's leading dimension, built and launched as the one-sided terms of dmrgx_kron_term_apply are; the coefficient is applied once,
+ * as there.  One grouped launch per tile size for all panels, one strided device copy per KronBlock.  Memory from the pool: one copy of every dense cell
+ * that is stored the other way round than the GEMM reads it or that carries a coefficient other than 1 (those of coefficient 0: none).
+ * Refused (DMRGX_ERR_ARG): a null sector table, KronBlock list, extent or n_out; ops or coef NULL with n_ops > 0; n_ops < 0; a side that
+ * is not 0 or 1; a coefficient that is not finite; a null psi with Y given; Y overlapping psi; a KronBlock listed twice; an expanded
+ * extent above 2^31 - 1.  DMRGX_ERR_OUTOFRANGE: a KronBlock or a cell's sector outside the tables, a cell outside its sector block.
+ * No atomics: two calls give the same bits. */
+dmrgx_status dmrgx_kron_noise_expand(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
+                                     const int32_t* block_il, const int32_t* block_ir, const double* psi_dev,
+                                     int32_t side, int32_t n_ops, const dmrgx_secop* ops, const double* coef /* host [n_ops] */,
+                                     int32_t* extent /* host [nblocks]: expanded width (side 0) / height (side 1) of block k */,
+                                     int64_t* n_out /* host: total doubles of the expansion */,
+                                     double* Y_dev /* NULL: sizes only */, void* stream);
 
 /* ---- Lanczos coefficients from a given start vector (continued fractions: S(q, w)) ------------------------------------ */
 /* The plain three-term recursion with q_0 = v0 / |v0| on the planned Hamiltonian (world_size == 1; a striped plan is refused with
