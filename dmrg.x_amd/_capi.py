@@ -42,6 +42,10 @@ class Term(C.Structure):
     _fields_ = [("a", C.c_double), ("left_op", C.c_int32), ("right_op", C.c_int32)]
 
 
+class SecOpString(C.Structure):
+    _fields_ = [("coeff", C.c_double), ("nfac", C.c_int32), ("fac", C.c_int32 * 3)]
+
+
 class KronDesc(C.Structure):
     _fields_ = [("left", Sectors), ("right", Sectors), ("nblocks", C.c_int32),
                 ("block_il", C.POINTER(C.c_int32)), ("block_ir", C.POINTER(C.c_int32)),
@@ -184,6 +188,8 @@ SIGNATURES = {
     "dmrgx_kron_noise_expand": (C.c_int32, [C.POINTER(Sectors), C.POINTER(Sectors), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
                                             C.c_int32, C.c_int32, C.POINTER(SecOp), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                             C.c_void_p, C.c_void_p]),
+    "dmrgx_secop_compose": (C.c_int32, [C.POINTER(Sectors), C.c_int32, C.POINTER(SecOp), C.c_int32, C.POINTER(C.c_int32), C.POINTER(SecOpString),
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(Cell), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
     "dmrgx_kron_lanczos_coeffs": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                               C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p]),
     "dmrgx_kron_lanczos_basis": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int64, C.POINTER(C.c_double),

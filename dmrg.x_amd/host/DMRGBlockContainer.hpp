@@ -201,6 +201,8 @@ public:
         ierr = PetscOptionsGetBool(NULL, NULL, "-corr_batch", &use_corr_batch, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-corr_matrix", &use_corr_matrix, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-corr_dimer", &use_corr_dimer, NULL); CHKERRQ(ierr);
+        ierr = PetscOptionsGetBool(NULL, NULL, "-corr_chiral", &use_corr_chiral, NULL); CHKERRQ(ierr);
+        if (use_corr_chiral && mpi_size > 1) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-corr_chiral 1 is not available on more than one rank (got %d): the triangles are not dealt over the ranks.", (int)mpi_size);
         ierr = PetscOptionsGetBool(NULL, NULL, "-prune_ops", &prune_ops, NULL); CHKERRQ(ierr);
         /* -noise a0,a1,... / -noise_warmup a: White's density-matrix perturbation, weight per sweep (GetTruncation) */
         ierr = dmrgx_host::ReadNoiseOptions(mpi_comm, noise); CHKERRQ(ierr);
@@ -504,7 +506,7 @@ public:
         spectra_writer.Drain();
         if (fp_entanglement) { fprintf(fp_entanglement, "\n]\n"); fclose(fp_entanglement); fp_entanglement = NULL; }
         if (fp_kron) { fprintf(fp_kron, "\n]\n"); fclose(fp_kron); fp_kron = NULL; }
-        spin_file.Close(); dimer_file.Close(); dsf_file.Close(); dsf_sites_file.Close(); dsf_cheb_file.Close(); dsf_cv_file.Close(); dsf_dimer_file.Close(); dsf_pm_file.Close();
+        spin_file.Close(); dimer_file.Close(); chiral_file.Close(); dsf_file.Close(); dsf_sites_file.Close(); dsf_cheb_file.Close(); dsf_cv_file.Close(); dsf_dimer_file.Close(); dsf_pm_file.Close();
         if (fp_corr) {
             if (!corr_headers_printed) { PetscErrorCode e2 = PrintCorrelationHeaders(); CHKERRQ(e2); }
             fprintf(fp_corr, "\n  ]\n}\n"); fclose(fp_corr); fp_corr = NULL;
@@ -1387,6 +1389,7 @@ public:
         }
         if (use_corr_matrix) { ierr = CalculateCorrelationMatrix(KronBlocks, gsv_r); CHKERRQ(ierr); }
         if (use_corr_dimer) { ierr = CalculateDimerCorrelations(KronBlocks, gsv_r); CHKERRQ(ierr); }
+        if (use_corr_chiral) { ierr = CalculateChiralCorrelations(KronBlocks, gsv_r); CHKERRQ(ierr); }
         return 0;
     }
 
@@ -2062,6 +2065,62 @@ public:
         return 0;
     }
 
+    /** -corr_chiral 1 (engine extension): the table < chi_a chi_b > of the scalar chirality chi_ijk = S_i . (S_j x S_k) over all pairs of
+        triangles of the lattice's plaquettes, at every measurement point.  chi = i K with the real, antisymmetric
+          K_ijk = [ Sz_i (Sp_j Sm_k - Sm_j Sp_k) + Sz_j (Sp_k Sm_i - Sm_k Sp_i) + Sz_k (Sp_i Sm_j - Sm_i Sp_j) ] / 2,
+        so for the real psi < chi_a chi_b > = < K_a psi , K_b psi >: ONE dmrgx_kron_term_gram call over psi (vector 0: the norm and
+        K[a] = < psi , K_a psi >, zero in an exact basis and reported as the truncation diagnostic it is) and the images K_a psi.  The
+        triangles, their strings, the split at the cut and the composed operators are ChiralFrame's (Measurements.hpp).
+        CC[a][b] is < K_a psi , K_b psi >: it equals < chi_a chi_b > when nothing was truncated -- truncated operators of one block do
+        not commute, the caveat of the SpSm table.  PlaquetteCC[p][p'] sums CC over the four triangles of p and of p';
+        StructureFactor(q) = (1 / N_p) sum_pp' cos(q . (r_p - r_p')) PlaquetteCC[p][p'] / Norm over the plaquette positions.  One rank. */
+    PetscErrorCode CalculateChiralCorrelations(KronBlocks_t& KronBlocks, const Vec& gsv_r)
+    {
+        PetscLogDouble t0, t1;
+        PetscTime(&t0);
+        dmrgx_host::ChiralFrame B;
+        PetscErrorCode ierr = B.Init(KronBlocks, num_sites, Ham, gsv_r, "Chiral correlations"); CHKERRQ(ierr);
+        const PetscInt nt = B.nt, nv = nt + 1, np = (PetscInt)B.plaquettes.size();
+        std::vector<double> G;
+        ierr = B.Gram(G); CHKERRQ(ierr);
+        const double norm = G[0];
+        std::vector<double> K((size_t)nt, 0.0), CC((size_t)(nt * nt), 0.0), PCC((size_t)(np * np), 0.0);
+        for (PetscInt a = 0; a < nt; ++a) {
+            K[(size_t)a] = G[(size_t)(1 + a)];
+            for (PetscInt b = 0; b < nt; ++b) CC[(size_t)(a * nt + b)] = G[(size_t)((1 + a) * nv + 1 + b)];
+        }
+        for (PetscInt a = 0; a < nt; ++a) for (PetscInt b = 0; b < nt; ++b) PCC[(size_t)(B.triangles[(size_t)a].plaq * np + B.triangles[(size_t)b].plaq)] += CC[(size_t)(a * nt + b)];
+        const PetscInt Lx = Ham.Lx(), Ly = Ham.Ly();
+        std::vector<PetscInt> px, py;
+        for (const dmrgx_host::ChiralPlaquette& p : B.plaquettes) { px.push_back(p.x); py.push_back(p.y); }
+        std::vector<double> Sq((size_t)(Lx * Ly), 0.0);
+        if (np > 0) Sq = dmrgx_host::LatticeFourier(Lx, Ly, px.data(), py.data(), PCC.data(), np, norm * (double)np);
+        PetscTime(&t1);
+        if (!mpi_rank && verbose)
+            printf("  * Chiral correlations: %lld triangles, Gram of %lld vectors x %lld, %lld bytes of composed operators held, tChiral %.6f s\n", LLD(nt), LLD(nv), LLD(gsv_r->n), LLD(B.composed_doubles * (int64_t)sizeof(double)), t1 - t0);
+        if (mpi_rank) return 0;
+        ierr = chiral_file.Begin(data_dir + "ChiralCorrelations.json"); CHKERRQ(ierr);
+        FILE* fp = chiral_file.fp;
+        fprintf(fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"tChiral\": %.9g, \"Norm\": %.17g,\n", LLD(GlobIdx), LoopTypeName(), t1 - t0, norm);
+        fprintf(fp, "   \"Triangles\": [");
+        for (PetscInt a = 0; a < nt; ++a) fprintf(fp, "%s[%lld, %lld, %lld]", a ? ", " : "", LLD(B.triangles[(size_t)a].i), LLD(B.triangles[(size_t)a].j), LLD(B.triangles[(size_t)a].k));
+        fprintf(fp, "],\n   \"Kind\": [");
+        for (PetscInt a = 0; a < nt; ++a) fprintf(fp, "%s%d", a ? ", " : "", B.triangles[(size_t)a].kind);
+        fprintf(fp, "],\n   \"Position\": [");
+        for (PetscInt a = 0; a < nt; ++a) fprintf(fp, "%s[%lld, %lld]", a ? ", " : "", LLD(B.triangles[(size_t)a].x), LLD(B.triangles[(size_t)a].y));
+        fprintf(fp, "],\n   \"Side\": [");
+        for (PetscInt a = 0; a < nt; ++a) fprintf(fp, "%s%d", a ? ", " : "", B.side_of[(size_t)a]);
+        fprintf(fp, "],\n   \"Plaquettes\": [");
+        for (PetscInt p = 0; p < np; ++p) fprintf(fp, "%s[%lld, %lld, %lld, %lld]", p ? ", " : "", LLD(B.plaquettes[(size_t)p].s[0]), LLD(B.plaquettes[(size_t)p].s[1]), LLD(B.plaquettes[(size_t)p].s[2]), LLD(B.plaquettes[(size_t)p].s[3]));
+        fprintf(fp, "],\n   \"PlaquettePosition\": [");
+        for (PetscInt p = 0; p < np; ++p) fprintf(fp, "%s[%lld, %lld]", p ? ", " : "", LLD(B.plaquettes[(size_t)p].x), LLD(B.plaquettes[(size_t)p].y));
+        fprintf(fp, "],\n   \"K\": ");
+        chiral_file.Row(K); fprintf(fp, ",\n");
+        chiral_file.Table("CC", CC, nt, nt, ",\n"); chiral_file.Table("PlaquetteCC", PCC, np, np, ",\n"); chiral_file.Table("StructureFactor", Sq, Lx, Ly, "}");
+        fflush(fp);
+        return 0;
+    }
+
     /** Reduced density matrices of both sides, their full spectra (device), the global cut to MStates states and the
         rotation matrices.  The ordering rules are the reference's: concatenate the spectra KronBlock by KronBlock,
         stable-sort by decreasing eigenvalue, keep the first min(MStates, #), stable-sort the survivors by sector. */
@@ -2410,7 +2469,7 @@ public:
             for (const Op& o : c.SysOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
             for (const Op& o : c.EnvOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
         }
-        if (use_corr_matrix || use_corr_dimer || use_dsf || use_dsf_sites || use_dsf_cheb || use_dsf_cv || use_dsf_dimer || use_dsf_pm) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer, -dsf, -dsf_sites, -dsf_cheb, -dsf_cv, -dsf_dimer, -dsf_pm: Sz and Sp of every site of both centre blocks, on every rank */
+        if (use_corr_matrix || use_corr_dimer || use_corr_chiral || use_dsf || use_dsf_sites || use_dsf_cheb || use_dsf_cv || use_dsf_dimer || use_dsf_pm) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer, -corr_chiral, -dsf, -dsf_sites, -dsf_cheb, -dsf_cv, -dsf_dimer, -dsf_pm: Sz and Sp of every site of both centre blocks, on every rank */
         need_built = true;
         return 0;
     }
@@ -2656,6 +2715,8 @@ private:
     dmrgx_host::JsonRecordFile spin_file{"%.15g"};      /* created at the first measurement with -corr_matrix, rank 0 only */
     PetscBool use_corr_dimer = PETSC_FALSE;     /* -corr_dimer 1: dimer-dimer table over all bond pairs through dmrgx_kron_term_gram, DimerCorrelations.json (CalculateDimerCorrelations) */
     dmrgx_host::JsonRecordFile dimer_file{"%.15g"};     /* created at the first measurement with -corr_dimer, rank 0 only */
+    PetscBool use_corr_chiral = PETSC_FALSE;    /* -corr_chiral 1: scalar-chirality table over all triangle pairs through dmrgx_secop_compose and dmrgx_kron_term_gram, ChiralCorrelations.json (CalculateChiralCorrelations) */
+    dmrgx_host::JsonRecordFile chiral_file{"%.17g"};    /* created at the first measurement with -corr_chiral */
     PetscBool use_dsf = PETSC_FALSE;            /* -dsf 1: S^zz(q, w) by the Lanczos-vector method, DynamicalStructureFactor.json (CalculateDynamicalStructureFactor) */
     std::vector<PetscInt> dsf_q;                /* -dsf_q: nx0, ny0, nx1, ny1, ... */
     PetscInt dsf_steps = 100;                   /* -dsf_steps: Lanczos steps per run */

@@ -492,6 +492,242 @@ private:
     }
 };
 
+/** A plaquette of the lattice: the sites a = (x, y), b = (x + 1, y), c = (x + 1, y + 1), d = (x, y + 1) in s[0 .. 4), y + 1 taken round
+    the periodic direction, generated from the corner a = (x, y). */
+struct ChiralPlaquette { PetscInt s[4], x, y; };
+/** The plaquettes all four of whose edges a-b, b-c, c-d, d-a are among the distinct pairs of Ham.NeighborPairs(), in order of (x, y),
+    each set of four sites once: on Ly = 2 the plaquette generated at y = 1 is the one of y = 0 again and is dropped, as DimerBonds drops
+    the doubled vertical pair. */
+template<class Hamiltonian> std::vector<ChiralPlaquette> ChiralPlaquettes(const Hamiltonian& Ham)
+{
+    std::set<std::pair<PetscInt, PetscInt>> nn;
+    for (const std::vector<PetscInt>& p : Ham.NeighborPairs()) nn.insert({std::min(p[0], p[1]), std::max(p[0], p[1])});
+    std::vector<ChiralPlaquette> plaq;
+    std::set<std::vector<PetscInt>> seen;
+    const PetscInt Lx = Ham.Lx(), Ly = Ham.Ly();
+    for (PetscInt x = 0; x + 1 < Lx; ++x) for (PetscInt y = 0; y < Ly; ++y) {
+        const PetscInt y1 = (y + 1) % Ly;
+        const ChiralPlaquette P{{Ham.To1D(x, y), Ham.To1D(x + 1, y), Ham.To1D(x + 1, y1), Ham.To1D(x, y1)}, x, y};
+        bool edges = true;
+        for (int e = 0; e < 4; ++e) edges = edges && nn.count({std::min(P.s[e], P.s[(e + 1) % 4]), std::max(P.s[e], P.s[(e + 1) % 4])});
+        std::vector<PetscInt> key(P.s, P.s + 4);
+        std::sort(key.begin(), key.end());
+        if (edges && seen.insert(key).second) plaq.push_back(P);
+    }
+    return plaq;
+}
+
+/** A triangle of a plaquette: the ordered, counter-clockwise triple (i, j, k) = three consecutive corners starting at corner `kind` --
+    kind 0 .. 3 = (a, b, c), (b, c, d), (c, d, a), (d, a, b) --, its plaquette and that plaquette's position. */
+struct ChiralTriangle { PetscInt i, j, k; int kind; PetscInt plaq, x, y; };
+inline std::vector<ChiralTriangle> ChiralTriangles(const std::vector<ChiralPlaquette>& plaq)
+{
+    std::vector<ChiralTriangle> tri;
+    for (size_t p = 0; p < plaq.size(); ++p)
+        for (int kind = 0; kind < 4; ++kind) tri.push_back(ChiralTriangle{plaq[p].s[kind], plaq[p].s[(kind + 1) % 4], plaq[p].s[(kind + 2) % 4], kind, (PetscInt)p, plaq[p].x, plaq[p].y});
+    return tri;
+}
+
+/** One string c O_1(s_1) O_2(s_2) O_3(s_3) of three site operators on lattice sites. */
+struct ChiralString { double coeff; Op_t type[3]; PetscInt site[3]; };
+/** chi_ijk = S_i . (S_j x S_k) = i K_ijk with the real, antisymmetric
+      K_ijk = [ Sz_i (Sp_j Sm_k - Sm_j Sp_k) + Sz_j (Sp_k Sm_i - Sm_k Sp_i) + Sz_k (Sp_i Sm_j - Sm_i Sp_j) ] / 2:
+    its six strings in this order, the site operators of each in the order written. */
+inline std::vector<ChiralString> ChiralStrings(PetscInt i, PetscInt j, PetscInt k)
+{
+    const PetscInt s[3] = {i, j, k};
+    std::vector<ChiralString> out;
+    for (int r = 0; r < 3; ++r) {
+        const PetscInt a = s[r], b = s[(r + 1) % 3], c = s[(r + 2) % 3];
+        out.push_back(ChiralString{+0.5, {OpSz, OpSp, OpSm}, {a, b, c}});
+        out.push_back(ChiralString{-0.5, {OpSz, OpSm, OpSp}, {a, b, c}});
+    }
+    return out;
+}
+
+/** The factors of a string that fall on one side of the cut behind the first n_left lattice sites, in their order in the string: (operator,
+    BLOCK site) pairs -- site s of the right block is lattice site N - 1 - s.  The two parts of a string have opposite sector shifts. */
+typedef std::vector<std::pair<int, PetscInt>> ChiralPart;
+inline ChiralPart ChiralStringPart(const ChiralString& S, int side, PetscInt n_left, PetscInt N)
+{
+    ChiralPart part;
+    for (int f = 0; f < 3; ++f)
+        if ((S.site[f] < n_left ? 0 : 1) == side) part.push_back({(int)S.type[f], side == 0 ? S.site[f] : N - 1 - S.site[f]});
+    return part;
+}
+
+/** K_a of every triangle of the lattice as terms on the ground state: the set-up of -corr_chiral.  A string of K_a splits at the cut into
+    a left and a right part of 0 to 3 factors, each side's factors in their order in the string.  A part of one factor is the resident site
+    operator; a part of two factors is a composed operator -- dmrgx_secop_compose, one per (ordered block sites, operator kinds), shared by
+    every triangle that uses it --; a triangle wholly inside a block is ONE composed operator of shift 0, the sum of its six strings, and one
+    one-sided term.  A triangle across the cut is six two-sided terms.  Triangle a is terms[vec_first[a] .. vec_first[a + 1]) over the
+    operators of T.  side_of[a]: 0 / 1 inside the left / right block, 2: two sites left and one right, 3: one left and two right.
+    The composed operators (composed_doubles doubles) live as long as the frame; they are built in chunks of about 2 GiB of operators
+    and prefixes per call. */
+struct ChiralFrame {
+    CentreFrame F;
+    SiteOperators T{F};
+    std::vector<ChiralPlaquette> plaquettes;
+    std::vector<ChiralTriangle> triangles;
+    std::vector<int> side_of;
+    std::vector<Mat> composed;
+    std::vector<int32_t> vec_first;
+    std::vector<dmrgx_term> terms;
+    PetscInt nt = 0;
+    int64_t n = 0, composed_doubles = 0;
+    const double* psi = nullptr;
+    template<class Hamiltonian> PetscErrorCode Init(KronBlocks_t& KronBlocks, PetscInt num_sites, const Hamiltonian& Ham, const Vec& gsv_r, const char* display_name)
+    {
+        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, display_name); CHKERRQ(ierr);
+        plaquettes = ChiralPlaquettes(Ham);
+        triangles = ChiralTriangles(plaquettes);
+        nt = (PetscInt)triangles.size();
+        n = gsv_r->n; psi = gsv_r->buf->dev_ro();
+        /* a term names a part by (composed, index): the index of a site operator in T.ops[side], or of an output in want[side] */
+        struct Ref { bool composed; int32_t idx; };
+        struct Pending { double coeff; Ref part[2]; };
+        std::vector<Pending> pending;
+        vec_first.assign(1, 0);
+        for (const ChiralTriangle& t : triangles) {
+            const PetscInt nl = (t.i < F.nsites[0]) + (t.j < F.nsites[0]) + (t.k < F.nsites[0]);
+            const std::vector<ChiralString> strings = ChiralStrings(t.i, t.j, t.k);
+            side_of.push_back(nl == 3 ? 0 : (nl == 0 ? 1 : (nl == 2 ? 2 : 3)));
+            if (nl == 3 || nl == 0) {
+                const int side = nl == 3 ? 0 : 1;
+                Output O;
+                for (const ChiralString& S : strings) { ierr = AddString(side, S.coeff, ChiralStringPart(S, side, F.nsites[0], F.N), O); CHKERRQ(ierr); }
+                want[side].push_back(O);
+                Pending P{1.0, {{false, -1}, {false, -1}}};
+                P.part[side] = Ref{true, (int32_t)want[side].size() - 1};
+                pending.push_back(P);
+            } else {
+                for (const ChiralString& S : strings) {
+                    Pending P{S.coeff, {{false, -1}, {false, -1}}};
+                    for (int side = 0; side < 2; ++side) {
+                        const ChiralPart part = ChiralStringPart(S, side, F.nsites[0], F.N);
+                        if (part.size() == 1) { ierr = T.Site(side, (Op_t)part[0].first, part[0].second, P.part[side].idx); CHKERRQ(ierr); continue; }
+                        auto ins = shared[side].emplace(part, (int32_t)want[side].size());
+                        if (ins.second) { Output O; ierr = AddString(side, 1.0, part, O); CHKERRQ(ierr); want[side].push_back(O); }
+                        P.part[side] = Ref{true, ins.first->second};
+                    }
+                    pending.push_back(P);
+                }
+            }
+            vec_first.push_back((int32_t)pending.size());
+        }
+        int32_t first_composed[2] = {0, 0};
+        for (int side = 0; side < 2; ++side) { first_composed[side] = (int32_t)T.ops[side].size(); ierr = Compose(side); CHKERRQ(ierr); }
+        for (const Pending& P : pending) {
+            int32_t idx[2];
+            for (int side = 0; side < 2; ++side) idx[side] = P.part[side].composed ? first_composed[side] + P.part[side].idx : P.part[side].idx;
+            terms.push_back(dmrgx_term{P.coeff, idx[0], idx[1]});
+        }
+        for (int side = 0; side < 2; ++side) { want[side].clear(); shared[side].clear(); }
+        return 0;
+    }
+    /** G ((nt + 1) x (nt + 1), row-major, host): the Gram matrix of psi (vector 0) and the images K_a psi (vector 1 + a), ONE dmrgx_kron_term_gram call. */
+    PetscErrorCode Gram(std::vector<double>& G) const
+    {
+        const PetscInt nv = nt + 1;
+        std::vector<int32_t> first{0};
+        std::vector<dmrgx_term> all;
+        all.push_back(dmrgx_term{1.0, -1, -1});
+        all.insert(all.end(), terms.begin(), terms.end());
+        for (int32_t f : vec_first) first.push_back(f + 1);
+        /* the workspace holds at least the largest image block of every vector: a part shifts by at most one sector, the blocks (IL - d, IR + d) */
+        int64_t largest = 1;
+        for (size_t k = 0; k < F.bil.size(); ++k)
+            for (int32_t d = -1; d <= 1; ++d) {
+                const int32_t a = F.bil[k] - d, c = F.bir[k] + d;
+                if (a >= 0 && a < (int32_t)F.sizes[0].size() && c >= 0 && c < (int32_t)F.sizes[1].size()) largest = std::max<int64_t>(largest, (int64_t)F.sizes[0][(size_t)a] * F.sizes[1][(size_t)c]);
+            }
+        const size_t workspace = std::max<size_t>((size_t)1 << 30, (size_t)largest * (size_t)nv * sizeof(double));
+        G.assign((size_t)(nv * nv), 0.0);
+        DevBuffer g((size_t)(nv * nv), DevBuffer::device_only_t{});
+        if (dmrgx_kron_term_gram(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
+                                 (int32_t)nv, first.data(), all.data(), workspace, g.dev_uninitialised(), nv, nullptr, nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "dmrgx_kron_term_gram: %s", dmrgx_last_error());
+        if (dmrgx_memcpy_d2h(G.data(), g.dev_ro(), G.size() * sizeof(double), nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "%s", dmrgx_last_error());
+        return 0;
+    }
+    /** dst + a ld = K_a psi for all nt triangles, through dmrgx_kron_term_apply in chunks of at most 1 GiB of images (as DimerFrame::Images). */
+    PetscErrorCode Images(double* dst, int64_t ld) const
+    {
+        const PetscInt chunk = std::max<PetscInt>(1, std::min<PetscInt>(nt, (PetscInt)((((int64_t)1 << 30) / (int64_t)sizeof(double)) / std::max<int64_t>(ld, 1))));
+        std::vector<int32_t> first;
+        for (PetscInt a0 = 0; a0 < nt; a0 += chunk) {
+            const PetscInt cnt = std::min<PetscInt>(chunk, nt - a0);
+            const int32_t t0 = vec_first[(size_t)a0];
+            first.clear();
+            for (PetscInt a = a0; a <= a0 + cnt; ++a) first.push_back(vec_first[(size_t)a] - t0);
+            if (dmrgx_kron_term_apply(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
+                                      (int32_t)cnt, first.data(), terms.data() + t0, dst + a0 * ld, ld, nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "dmrgx_kron_term_apply: %s", dmrgx_last_error());
+        }
+        return 0;
+    }
+private:
+    typedef std::vector<dmrgx_secop_string> Output;             /* the strings of one composed operator, factors by index into T.ops[side] */
+    std::vector<Output> want[2];
+    std::map<ChiralPart, int32_t> shared[2];                    /* two-factor part -> its output in want[side] */
+    PetscErrorCode AddString(int side, double coeff, const ChiralPart& part, Output& O)
+    {
+        dmrgx_secop_string s{coeff, (int32_t)part.size(), {0, 0, 0}};
+        for (size_t f = 0; f < part.size(); ++f) { PetscErrorCode ierr = T.Site(side, (Op_t)part[f].first, part[f].second, s.fac[f]); CHKERRQ(ierr); }
+        O.push_back(s);
+        return 0;
+    }
+    /** The outputs of want[side] through dmrgx_secop_compose, appended to T.ops[side] in their order. */
+    PetscErrorCode Compose(int side)
+    {
+        const std::vector<int32_t>& sz = F.sizes[side];
+        const int32_t ns = (int32_t)sz.size(), n_in = (int32_t)T.ops[side].size();
+        int64_t block = 0;                                          /* an upper bound of one operator or prefix: the largest shift-s table */
+        for (int32_t s = -1; s <= 1; ++s) { int64_t b = 0; for (int32_t q = 0; q < ns; ++q) if (q + s >= 0 && q + s < ns) b += (int64_t)sz[(size_t)q] * sz[(size_t)(q + s)]; block = std::max(block, b); }
+        const int64_t chunk_limit = (int64_t)1 << 28;
+        const std::vector<dmrgx_secop> inputs(T.ops[side].begin(), T.ops[side].begin() + n_in);
+        for (size_t o0 = 0; o0 < want[side].size();) {
+            std::vector<int32_t> first{0};
+            std::vector<dmrgx_secop_string> strings;
+            int64_t cost = 0;
+            size_t o1 = o0;
+            for (; o1 < want[side].size(); ++o1) {
+                int64_t c = block;
+                for (const dmrgx_secop_string& s : want[side][o1]) if (s.nfac == 3) c += block;
+                if (o1 > o0 && cost + c > chunk_limit) break;
+                cost += c;
+                strings.insert(strings.end(), want[side][o1].begin(), want[side][o1].end());
+                first.push_back((int32_t)strings.size());
+            }
+            const int32_t cnt = (int32_t)(o1 - o0);
+            std::vector<int32_t> shift((size_t)cnt), cell_first((size_t)cnt + 1);
+            std::vector<dmrgx_cell> cells((size_t)cnt * (size_t)ns);
+            int64_t total = 0;
+            if (dmrgx_secop_compose(&F.sectors[side], n_in, inputs.data(), cnt, first.data(), strings.data(), shift.data(), cell_first.data(), cells.data(), &total, nullptr, nullptr))
+                SETERRQ2(PETSC_COMM_SELF, 1, "%s: dmrgx_secop_compose: %s", F.name, dmrgx_last_error());
+            std::shared_ptr<DevBuffer> arena;
+            try { arena = std::make_shared<DevBuffer>((size_t)std::max<int64_t>(total, 1), DevBuffer::device_only_t{}); }
+            catch (const std::exception& e) { SETERRQ4(PETSC_COMM_SELF, PETSC_ERR_MEM, "%s: no memory for %d composed operators (%.3f GB): %s", F.name, (int)cnt, (double)total * 8e-9, e.what()); }
+            double* base = arena->dev_uninitialised();
+            if (dmrgx_secop_compose(&F.sectors[side], n_in, inputs.data(), cnt, first.data(), strings.data(), shift.data(), cell_first.data(), cells.data(), &total, base, nullptr))
+                SETERRQ2(PETSC_COMM_SELF, 1, "%s: dmrgx_secop_compose: %s", F.name, dmrgx_last_error());
+            for (int32_t o = 0; o < cnt; ++o) {
+                Mat C = std::make_shared<SectorMat>();
+                C->shift = shift[(size_t)o]; C->sizes = sz;
+                for (int32_t ci = cell_first[(size_t)o]; ci < cell_first[(size_t)o + 1]; ++ci) {
+                    const dmrgx_cell& d = cells[(size_t)ci];
+                    MatCell c;
+                    c.q = d.row_sector; c.nr = d.nr; c.nc = d.nc; c.ld = d.ld; c.buf = arena; c.off = (int64_t)(d.data - base);
+                    C->cells.push_back(c);
+                }
+                T.Add(side, C);
+                composed.push_back(C);
+            }
+            composed_doubles += total;
+            o0 = o1;
+        }
+        return 0;
+    }
+};
+
 /** A JSON file that holds one list of records, one per measurement: created by the first Begin(), finished by Close().  The caller
     writes the record itself to fp; numbers of Row() and Table() go through `number`, a printf format for one double. */
 struct JsonRecordFile {

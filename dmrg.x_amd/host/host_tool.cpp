@@ -191,6 +191,27 @@ int main()
             printf("bondsof %zu", O.of.size());
             for (size_t k = 0; k < O.of.size(); ++k) printf(" %lld,%lld,%lld", LLD(O.of[k]), LLD(O.x[k]), LLD(O.y[k]));
             printf("\n");
+        } else if (cmd == "plaquettes") {        /* the plaquettes of ham: a,b,c,d,x,y */
+            printf("plaquettes");
+            for (const dmrgx_host::ChiralPlaquette& p : dmrgx_host::ChiralPlaquettes(ham)) printf(" %lld,%lld,%lld,%lld,%lld,%lld", LLD(p.s[0]), LLD(p.s[1]), LLD(p.s[2]), LLD(p.s[3]), LLD(p.x), LLD(p.y));
+            printf("\n");
+        } else if (cmd == "triangles") {         /* the triangles of ham's plaquettes: i,j,k,kind,plaquette,x,y */
+            printf("triangles");
+            for (const dmrgx_host::ChiralTriangle& t : dmrgx_host::ChiralTriangles(dmrgx_host::ChiralPlaquettes(ham))) printf(" %lld,%lld,%lld,%d,%lld,%lld,%lld", LLD(t.i), LLD(t.j), LLD(t.k), t.kind, LLD(t.plaq), LLD(t.x), LLD(t.y));
+            printf("\n");
+        } else if (cmd == "chiralsplit") {       /* chiralsplit i j k n_left N  ->  per string of K_ijk: coefficient | left part | right part, a part as op:blocksite,... or - */
+            PetscInt i, j, k, nl, N; is >> i >> j >> k >> nl >> N;
+            printf("chiralsplit");
+            for (const dmrgx_host::ChiralString& S : dmrgx_host::ChiralStrings(i, j, k)) {
+                printf(" %.17g", S.coeff);
+                for (int side = 0; side < 2; ++side) {
+                    const dmrgx_host::ChiralPart part = dmrgx_host::ChiralStringPart(S, side, nl, N);
+                    printf("|");
+                    if (part.empty()) printf("-");
+                    for (size_t f = 0; f < part.size(); ++f) printf("%s%d:%lld", f ? "," : "", part[f].first, LLD(part[f].second));
+                }
+            }
+            printf("\n");
         } else if (cmd == "fourier" || cmd == "cossum") {
             /* fourier Lx Ly n x_0 .. x_{n-1} y_0 .. y_{n-1} T_00 .. T_{n-1,n-1} [norm]  ->  the Lx x Ly table of LatticeFourier, norm n unless given
                cossum Lx Ly n c ncol x_0 .. x_{n-1} y_0 .. y_{n-1} T_00 .. T_{n-1,ncol-1}  ->  the (Lx Ly) x ncol table of SiteCosineSum, row by row */

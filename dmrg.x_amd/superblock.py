@@ -437,6 +437,47 @@ def noise_expand(sb_or_layout, psi, side, ops, coef, out=None):
     return out, list(extent), n_out.value
 
 
+def _compose_arguments(sizes, ops, outputs, device="cuda"):
+    """The arguments of dmrgx_secop_compose up to the arena, as ctypes values, and the list that keeps every buffer behind them alive.
+    outputs: a list of outputs, each a list of strings (coeff, [operator indices])."""
+    dummy = torch.zeros(sizes[0] * sizes[0], dtype=torch.float64, device=device)
+    args, _, keep = _gram_arguments((list(sizes), list(sizes), [(0, 0)]), dummy, ops, [])
+    sec, n_ops, arr = args[0], args[6], args[7]
+    first = _i32(list(np.cumsum([0] + [len(o) for o in outputs])))
+    flat = [s for o in outputs for s in o]
+    strings = (_capi.SecOpString * max(len(flat), 1))()
+    for i, (c, fac) in enumerate(flat):
+        strings[i].coeff, strings[i].nfac = float(c), len(fac)
+        for f, idx in enumerate(fac[:3]):
+            strings[i].fac[f] = int(idx)
+    n = len(outputs)
+    shift, cell_first = (C.c_int32 * max(n, 1))(), (C.c_int32 * (n + 1))()
+    cells = (_capi.Cell * max(n * len(sizes), 1))()
+    total = C.c_int64(-1)
+    return (sec, n_ops, arr, n, first, strings, shift, cell_first, cells, C.byref(total)), total, keep
+
+
+def secop_compose(sizes, ops, outputs, out=None):
+    """C_o = sum over the strings (coeff, [i1, i2, i3]) of outputs[o] of coeff * ops[i1] ops[i2] ops[i3] (one to three factors) on the
+    block with sector table `sizes` (dmrgx_secop_compose).  ops: SectorOperators, or (SectorOperator, True) for the transpose.  out: a
+    contiguous 1-D f64 device tensor of at least n_doubles elements; default: a new one.  Returns (arena, shifts, blocks) with
+    blocks[o] = [(row sector, offset into the arena, rows, columns)]: output o dense over its sector blocks, row-major."""
+    _capi.require_device()
+    args, total, keep = _compose_arguments(sizes, ops, outputs)
+    L = _capi.lib()
+    _capi.check(L.dmrgx_secop_compose(*args, None, None))
+    if out is None:
+        out = torch.empty(max(total.value, 1), dtype=torch.float64, device="cuda")
+    assert out.dtype == torch.float64 and out.dim() == 1 and out.is_contiguous() and out.numel() >= total.value
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _capi.check(L.dmrgx_secop_compose(*args, C.c_void_p(out.data_ptr()), st))
+    torch.cuda.current_stream().synchronize()       # the operator copies in `keep` are read by the queued work
+    shift, cell_first, cells = args[6], args[7], args[8]
+    blocks = [[(cells[c].row_sector, (cells[c].data - out.data_ptr()) // 8, cells[c].nr, cells[c].nc) for c in range(cell_first[o], cell_first[o + 1])]
+              for o in range(len(outputs))]
+    return out, list(shift[:len(outputs)]), blocks
+
+
 def noise_rdm_layout(sb_or_layout, side, extent):
     """(left_sizes, right_sizes, blocks, side_mask) under which ReducedDensityMatrices reads an expansion of noise_expand: the expanded
     extents are the sector table of the other side, one sector per KronBlock, and only the density matrices of `side` are built."""

@@ -35,6 +35,8 @@
  *                               overlaps with a family of vectors: G_ic(w + i eta) under a true Lorentzian (-dsf_cv)
  *   dmrgx_kron_noise_expand     psi with the images of one block's operators beside it: White's density-matrix perturbation as a wider input
  *                               of dmrgx_rdm_create_subset (-noise)
+ *   dmrgx_secop_compose         sums of products of two and three operators of one block, dense per sector: the parts of S_i . (S_j x S_k)
+ *                               on one side of the cut (-corr_chiral)
  *   dmrgx_vec_project_out       one vector removed from a family of vectors, coefficients returned: (D_b - <D_b>) psi for all bonds (-dsf_dimer)
  *   dmrgx_comm_*             <- the communicator of the reference's MPI path: VecScatter-to-all of x inside every MatMult
  *                               (src/DMRGKron.cpp:1833-1834) and the MPI_Allreduce behind SLEPc's VecDot / VecNorm
@@ -527,6 +529,45 @@ dmrgx_status dmrgx_kron_noise_expand(const dmrgx_sectors* left, const dmrgx_sect
                                      int32_t* extent /* host [nblocks]: expanded width (side 0) / height (side 1) of block k */,
                                      int64_t* n_out /* host: total doubles of the expansion */,
                                      double* Y_dev /* NULL: sizes only */, void* stream);
+
+/* ---- products of sector operators of one block (observables of three site operators: the scalar chirality) ------------- */
+/* C_o = sum over the strings t of output o of  coeff_t * F_{t,1} F_{t,2} [F_{t,3}],  o < n_out:  sums of products of one, two or three
+ * operators of ONE block, formed on the device in dense per-sector form.  Nothing in the reference does this: its correlators multiply
+ * site operators pair by pair with MatMatMult (include/DMRGBlockContainer.hpp:2378-2395).
+ * sectors: the block's sector table.  ops[0 .. n_ops): the input operators (cells, `transposed`, any shift; only read).  Output o owns
+ * strings[out_first[o] .. out_first[o + 1]) (out_first[0] = 0, every output at least one string); a string names its 1, 2 or 3 factors by
+ * index into ops, and they multiply in the order given -- truncated block operators do not commute, the order is part of the contract.
+ * Every string of one output has the same net shift s_o = the sum of its factors' shifts (DMRGX_ERR_ARG otherwise); outputs may differ.
+ * With shifts s1, s2, s3 the block (q -> q + s_o) of a string is F_1[q -> q + s1] F_2[q + s1 -> q + s1 + s2] F_3[.. -> q + s_o]: where a
+ * middle sector does not exist, or a factor has no cell there, the string contributes nothing.
+ * Host outputs, always written: out_shift[o] = s_o; cells[cell_first[o] .. cell_first[o + 1]) = the cells of output o, one DENSE cell per
+ * sector block (q -> q + s_o) whose two sectors exist, ascending q, covering the whole block (r0 = c0 = 0, ld = nc = the size of sector
+ * q + s_o); `cells` has room for n_out * nsec entries.  Cell c starts where cell c - 1 ends, the first at arena_dev: *n_doubles is the
+ * sum of their sizes.  With shift = out_shift[o] and transposed = 0 the cells are a dmrgx_secop for every other call of this header.
+ * arena_dev == NULL: sizes only -- the cells' `data` are NULL, no device is touched.  Otherwise every element of [0, *n_doubles) of the
+ * arena is written exactly once (it may hold anything on entry), a block that no string reaches as exact zeros.
+ * At most two grouped launches per tile size, through the batch builder of dmrgx_kron_term_apply: (1) the distinct two-factor prefixes
+ * (coeff F_1) F_2 of the three-factor strings -- distinct over the whole call by (F_1, F_2, coeff) -- into pool scratch; (2) every block of
+ * every output as the groups of its strings.  Identity cells become scaled copies, as there; the coefficient is applied once, in the
+ * first factor: in the scale of an identity cell or in a materialised copy of a dense one (exact for the +-1/2 of the chirality).
+ * Memory from the pool: the prefixes, about one operator each; one copy of every dense cell that is used transposed or as a first factor
+ * with a coefficient other than 1; a unit matrix of the order of the largest identity cell where two identity cells meet or a
+ * one-factor string is one.
+ * Refused (DMRGX_ERR_ARG): a null sector table, operator list (n_ops > 0), out_first, string list or host output; n_ops < 0, n_out < 0;
+ * an output without strings; a factor count outside 1..3; strings of one output with different net shifts; a coefficient that is not
+ * finite; an arena that overlaps a dense cell of an input.  DMRGX_ERR_OUTOFRANGE: a factor index outside ops; a cell's sector outside
+ * the table; a cell outside its sector block.  A refused call leaves the arena untouched.  n_out == 0: DMRGX_OK, nothing written.
+ * No atomics, fixed order: two calls give the same bits. */
+typedef struct {
+    double  coeff;
+    int32_t nfac;         /* 1, 2 or 3                                                                    */
+    int32_t fac[3];       /* indices into ops, leftmost factor first; entries from nfac on are ignored   */
+} dmrgx_secop_string;
+dmrgx_status dmrgx_secop_compose(const dmrgx_sectors* sectors, int32_t n_ops, const dmrgx_secop* ops,
+                                 int32_t n_out, const int32_t* out_first, const dmrgx_secop_string* strings,
+                                 int32_t* out_shift /* host [n_out] */, int32_t* cell_first /* host [n_out + 1] */,
+                                 dmrgx_cell* cells /* host [n_out * nsec] */, int64_t* n_doubles /* host */,
+                                 double* arena_dev /* NULL: sizes only */, void* stream);
 
 /* ---- Lanczos coefficients from a given start vector (continued fractions: S(q, w)) ------------------------------------ */
 /* The plain three-term recursion with q_0 = v0 / |v0| on the planned Hamiltonian (world_size == 1; a striped plan is refused with
