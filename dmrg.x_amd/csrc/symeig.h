@@ -1,6 +1,6 @@
 // Batched symmetric eigensolver (f64) for the reduced density matrices: Householder tridiagonalisation, tridiagonal divide and
 // conquer, blocked back-transformation (symeig.hip).  Replaces the QR-preconditioned block-Jacobi iteration of rounds 1-2
-// (rdm.hip keeps it behind DMRGX_RDM_SOLVER=jacobi and for matrices above SYMEIG_MAX_N).
+// (rdm_jacobi.hip keeps it behind DMRGX_RDM_SOLVER=jacobi and for matrices above SYMEIG_MAX_N).
 //
 // Takes the place of the reference's EPSLAPACK call in EigRDM_BlockDiag (include/DMRGBlockContainer.hpp:1976-1982: all
 // eigenpairs of one dense symmetric block): same mathematical result (eigenvalues to c n eps ||A||, eigenvectors orthogonal to

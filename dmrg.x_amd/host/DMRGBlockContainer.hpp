@@ -198,6 +198,7 @@ public:
         ierr = PetscOptionsGetBool(NULL, NULL, "-wavefunction_guess", &use_guess, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-wavefunction_guess_overlap", &use_guess_overlap, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-rdm_warm_start", &use_rdm_warm, NULL); CHKERRQ(ierr);
+        if (use_rdm_warm && !mpi_rank) printf("NOTE: -rdm_warm_start 1 has no effect: the density-matrix solvers never read a starting basis (the block-Jacobi path preconditions with a QR step of its own, the direct solver has no use for one).\n");
         ierr = PetscOptionsGetBool(NULL, NULL, "-corr_batch", &use_corr_batch, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-corr_matrix", &use_corr_matrix, NULL); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-corr_dimer", &use_corr_dimer, NULL); CHKERRQ(ierr);
@@ -651,7 +652,7 @@ public:
         /* a side whose output block no later step reads needs its spectrum (truncation error, sector table) but no eigenvectors */
         const bool vec_sys = !(hints && hints->dead_sys && !same), vec_env = !(hints && hints->dead_env && !same);
         step.Noise = noise.At(LoopType == WarmupStep, LoopIdx - 1);      /* (the warm-up is loop 0, sweep s loop s + 1: also after a restart) */
-        ierr = GetTruncation(KronBlocks, gsv_r, MStates, BT_L, BT_R, BlockIndex(SysBlockOut), BlockIndex(EnvBlockOut), vec_sys, vec_env, step.Noise, &Terms); CHKERRQ(ierr);
+        ierr = GetTruncation(KronBlocks, gsv_r, MStates, BT_L, BT_R, vec_sys, vec_env, step.Noise, &Terms); CHKERRQ(ierr);
         ierr = CalculateCorrelations_BlockDiag(KronBlocks, gsv_r, do_measurements); CHKERRQ(ierr);
         if (use_guess) {   /* what the next step needs to carry this ground state over */
             prev.valid = false;
@@ -2172,7 +2173,7 @@ public:
         selection and eigenvectors of a side are read from that side's object, and the spectra are divided by the trace of the perturbed
         matrix.  noise_a == 0 is the code path and the call sequence of before. */
     PetscErrorCode GetTruncation(const KronBlocks_t& KronBlocks, const Vec& gsv_r, const PetscInt& MStates, BasisTransformation& BT_L, BasisTransformation& BT_R,
-                                 const PetscInt keyL = -1, const PetscInt keyR = -1, const bool need_vec_L = true, const bool need_vec_R = true,
+                                 const bool need_vec_L = true, const bool need_vec_R = true,
                                  const double noise_a = 0.0, const std::vector<Hamiltonians::Term>* noise_terms = nullptr)
     {
         PetscErrorCode ierr;
@@ -2194,19 +2195,6 @@ public:
         auto drop = [&]() { if (rdm_of[0]) dmrgx_rdm_destroy(rdm_of[0]); if (rdm_of[1] && rdm_of[1] != rdm_of[0]) dmrgx_rdm_destroy(rdm_of[1]); rdm_of[0] = rdm_of[1] = nullptr; };
         PetscLogDouble tr0, tr1;
         PetscTime(&tr0);
-        /* warm start of the block-Jacobi eigensolver: the eigenbasis found at the previous visit of the block being created
-           (same index, same sector sizes) almost diagonalises the new density matrix once the sweeps settle */
-        const PetscInt keys[2] = {keyL, keyR};
-        std::vector<const double*> v0((size_t)(2 * nb), nullptr);
-        PetscInt nwarm = 0;
-        if (use_rdm_warm && !noisy && !dmrgx_host::WorldComm()) for (int side = 0; side < 2; ++side) {
-            auto it = rdm_basis.find({keys[side], (keyR == keyL) ? 0 : side});      /* centre step: both sides are the same block */
-            if (keys[side] < 0 || it == rdm_basis.end() || it->second.sizes != (side == 0 ? ls : rs)) continue;
-            for (PetscInt k = 0; k < nb; ++k) {
-                auto e = it->second.E.find(side == 0 ? bil[k] : bir[k]);
-                if (e != it->second.E.end() && e->second) { v0[(size_t)(2 * k + side)] = e->second->dev_ro(); ++nwarm; }
-            }
-        }
         /* Multi-GPU (the reference solves every density matrix on rank 0 and broadcasts the rotation,
            include/DMRGBlockContainer.hpp:1673-1677, 1812-1925): the 2 nb density matrices are dealt over the ranks by their n^3
            cost, heaviest first to the least loaded rank (the same deterministic deal on every rank); each rank builds and
@@ -2235,7 +2223,7 @@ public:
             if (dmrgx_rdm_create_subset(&sl, &sr, (int32_t)nb, bil.data(), bir.data(), gsv_r->buf->dev_ro(), mask.data(), nullptr, &rdm))
                 SETERRQ1(mpi_comm, 1, "dmrgx_rdm_create_subset: %s", dmrgx_last_error());
         }
-        else if (dmrgx_rdm_create_warm(&sl, &sr, (int32_t)nb, bil.data(), bir.data(), gsv_r->buf->dev_ro(), nwarm ? v0.data() : nullptr, nullptr, &rdm))
+        else if (dmrgx_rdm_create(&sl, &sr, (int32_t)nb, bil.data(), bir.data(), gsv_r->buf->dev_ro(), nullptr, &rdm))
             SETERRQ1(mpi_comm, 1, "dmrgx_rdm_create: %s", dmrgx_last_error());
         if (!noisy) rdm_of[0] = rdm_of[1] = rdm;
         /* spectra of every matrix on every rank */
@@ -2267,21 +2255,6 @@ public:
             const int64_t nd = spec_off[(size_t)(2 * k + dead + 1)] - spec_off[(size_t)(2 * k + dead)], nl = spec_off[(size_t)(2 * k + live + 1)] - spec_off[(size_t)(2 * k + live)];
             for (int64_t e = 0; e < nd; ++e) spectra[(size_t)(spec_off[(size_t)(2 * k + dead)] + e)] = e < nl ? spectra[(size_t)(spec_off[(size_t)(2 * k + live)] + e)] : 0.0;
         }
-        if (use_rdm_warm && !noisy && W == 1) for (int side = 0; side < 2; ++side) {      /* remember this visit's eigenbases (all eigenvectors, as rows) */
-            if (keys[side] < 0 || (side == 1 && keyR == keyL)) continue;
-            /* a side whose spectrum was borrowed (dead block of a pruned sweep) has no eigenvectors: drop what an earlier visit stored */
-            if (!need_vec[side]) { rdm_basis.erase({keys[side], side}); continue; }
-            WarmBasis& wb = rdm_basis[{keys[side], side}];
-            wb.sizes = side == 0 ? ls : rs;
-            wb.E.clear();
-            for (PetscInt k = 0; k < nb; ++k) {
-                const int32_t sec = side == 0 ? bil[k] : bir[k], n = (side == 0 ? ls : rs)[(size_t)sec];
-                if (n == 0) continue;
-                auto buf = std::make_shared<dmrgx_host::DevBuffer>((size_t)n * n, dmrgx_host::DevBuffer::device_only_t{});
-                if (dmrgx_rdm_eigenvectors(rdm, side, (int32_t)k, n, buf->dev_uninitialised(), n, nullptr)) { dmrgx_rdm_destroy(rdm); SETERRQ1(mpi_comm, 1, "dmrgx_rdm_eigenvectors: %s", dmrgx_last_error()); }
-                wb.E[sec] = buf;
-            }
-        }
         PetscTime(&tr1);
         for (int obj = 0; obj < 2; ++obj) {
             /* which path the density-matrix solver took: a time-out fallback or an unexpected launch path must show in DMRGRun.json, not only on stderr */
@@ -2296,8 +2269,8 @@ public:
             trid_max_wgs = std::max<PetscInt>(trid_max_wgs, rr.max_workgroups_per_matrix);
             rdm_max_levels = std::max<PetscInt>(rdm_max_levels, rr.merge_levels);
             rdm_max_wy_blocks = std::max<PetscInt>(rdm_max_wy_blocks, rr.wy_blocks_max);
-            if (!mpi_rank && verbose) printf("  RDM: %lld KronBlocks, %lld warm-started, block-Jacobi sweeps %d, persistent / launch-path matrices %d / %d, workgroups per matrix <= %d, merge levels %d, create %.6f s\n",
-                                             LLD(nb), LLD(nwarm), rr.n_sweeps, rr.trid_persistent_matrices, rr.trid_launch_matrices, rr.max_workgroups_per_matrix, rr.merge_levels, tr1 - tr0);
+            if (!mpi_rank && verbose) printf("  RDM: %lld KronBlocks, block-Jacobi sweeps %d, persistent / launch-path matrices %d / %d, workgroups per matrix <= %d, merge levels %d, create %.6f s\n",
+                                             LLD(nb), rr.n_sweeps, rr.trid_persistent_matrices, rr.trid_launch_matrices, rr.max_workgroups_per_matrix, rr.merge_levels, tr1 - tr0);
         }
         BasisTransformation* BT[2] = {&BT_L, &BT_R};
         /* Two phases (round 5): first the m-cut of both sides on the spectra alone, then -- dmrgx_rdm_select -- the eigenvectors of the kept
@@ -2707,10 +2680,7 @@ private:
     PetscBool use_guess = PETSC_TRUE;
     PetscBool use_guess_overlap = PETSC_TRUE;   /* -wavefunction_guess_overlap 0: no start vector where the stored chain of bases is broken (round-2 behaviour) */
     PetscInt guesses_used = 0;
-    /* eigenbases of the density matrices at the previous visit of every block: warm start of the Jacobi eigensolver */
-    struct WarmBasis { std::vector<int32_t> sizes; std::map<int32_t, std::shared_ptr<dmrgx_host::DevBuffer>> E; };
-    std::map<std::pair<PetscInt, int>, WarmBasis> rdm_basis;
-    PetscBool use_rdm_warm = PETSC_FALSE;
+    PetscBool use_rdm_warm = PETSC_FALSE;       /* -rdm_warm_start: still recognised, does nothing (a line at start-up says so) */
     PetscBool use_corr_matrix = PETSC_FALSE;    /* -corr_matrix 1: all-pairs tables through dmrgx_kron_op_gram, SpinCorrelations.json (CalculateCorrelationMatrix) */
     dmrgx_host::JsonRecordFile spin_file{"%.15g"};      /* created at the first measurement with -corr_matrix, rank 0 only */
     PetscBool use_corr_dimer = PETSC_FALSE;     /* -corr_dimer 1: dimer-dimer table over all bond pairs through dmrgx_kron_term_gram, DimerCorrelations.json (CalculateDimerCorrelations) */

@@ -310,11 +310,10 @@ typedef struct dmrgx_rdm dmrgx_rdm;
 dmrgx_status dmrgx_rdm_create(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
                               const int32_t* block_il, const int32_t* block_ir, const double* psi_dev,
                               void* stream, dmrgx_rdm** out);
-/* The same with a starting basis: v0_rows[2*k + side] is NULL or a device pointer to an n x n row-major ORTHOGONAL matrix whose
- * rows approximately diagonalise that block's density matrix (the rows written by dmrgx_rdm_eigenvectors(count = n) at the
- * previous visit of the same block).  Results do not depend on v0_rows, only the number of Jacobi sweeps can.  It is a
- * hint: the default solver preconditions every matrix with one Householder-QR step on the sorted matrix (csrc/hqr.hip),
- * which supersedes it; with DMRGX_RDM_QR=0 the matrix is transformed into the supplied basis before the iteration. */
+/* dmrgx_rdm_create_warm is dmrgx_rdm_create with a starting-basis argument that is accepted for compatibility only: v0_rows (NULL, or
+ * per matrix 2*k + side NULL or a device pointer to an orthogonal n x n basis) is never dereferenced, and neither the results nor the
+ * sweep counts depend on it.  The Householder-QR preconditioning step of the block-Jacobi solver (csrc/hqr.hip) made it redundant,
+ * and the direct solver never had a use for it. */
 /* Multi-GPU form: only the density matrices selected by side_mask[k] (bit 0: rho_L, bit 1: rho_R of KronBlock k) are built and
  * diagonalised by this rank -- the matrices of a step are dealt over the ranks by their n^3 cost; psi_dev is the
  * whole vector on every rank.  Queries for a matrix that was not selected fail with DMRGX_ERR_ARG. */

@@ -345,7 +345,7 @@ def lanczos_basis_invariants(plan, H, v0, K, V=None, ref=None):
 # The constants of csrc/symeig.hip / symeig.h the inputs and the order lists were built around; test_rdm_inputs.py parses the sources and
 # fails when one of them is retuned.
 RDM_CONSTANTS = {"DMRGX_DC_LEAF": 16, "DC_FUSE_NL": 384, "DMRGX_WY_NB": 64, "TRID_MAXM": 32, "TRID_PF": 8, "SYMEIG_MAX_N": 3072,
-                 # the block-Jacobi solver of csrc/rdm.hip and its QR preconditioner (csrc/hqr.hip): the Jacobi block (matrices are padded to
+                 # the block-Jacobi solver of csrc/rdm_jacobi.hip and its QR preconditioner (csrc/hqr.hip): the Jacobi block (matrices are padded to
                  # two of them), the rows up to which a QR panel lives in registers at 4 / 8 / 16 rows per thread (above HR_MAX_ROWS:
                  # hqr_panel_kernel), the panel width and the column strip of the trailing update
                  "DMRGX_JB": 16, "HQR_REGS_ROWS_4": 256, "HQR_REGS_ROWS_8": 512, "HR_MAX_ROWS": 1024, "HQR_PANEL": 32, "TM_COLS": 32}

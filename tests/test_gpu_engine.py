@@ -224,8 +224,8 @@ def test_unsupported_reference_options_are_refused(tmp_path):
 
 
 def test_rdm_warm_start_option_gives_the_same_run(tmp_path):
-    """-rdm_warm_start 1 hands the eigenbases of a block's previous visit to dmrgx_rdm_create_warm as a hint (only the Jacobi path
-    uses it; the direct solver ignores it): energies and truncation errors of a warm-up + two sweeps equal the run without it."""
+    """-rdm_warm_start is still a recognised option and does nothing (neither density-matrix solver reads a starting basis; the engine
+    says so at start-up): energies and truncation errors of a warm-up + two sweeps equal the run without it."""
     model = ["-Lx", 6, "-Ly", 2, "-J1", 1, "-Jz1", 0.9, "-J2", 0.5, "-Jz2", 0.4, "-qn_sector", 1, "-mwarmup", 12, "-nsweeps", 2, "-H_eps_tol", 1e-12]
     r0, _, _ = run_engine(tmp_path / "cold", *model, "-rdm_warm_start", 0)
     r1, _, _ = run_engine(tmp_path / "warm", *model, "-rdm_warm_start", 1)
@@ -251,8 +251,8 @@ def test_medium_m_step_by_step_against_the_oracle(tmp_path, name, ranks, extra):
     up small, grow m sweep by sweep and turn round `-min_block` sites before the edge: only then is every m-cut decided by the spectrum
     and not by round-off.  Up to the first ill-defined cut -- 70-180 steps into a run, in its last sweep -- sizes, energies and both
     truncation errors agree at 1e-10; across the four runs that is more than 150 steps at m >= 24.  After it, energies agree at the
-    truncation-error scale.  The smallest run is repeated on three ranks (density matrices dealt over the ranks, striped solve), with the
-    warm-started density-matrix solver and with the generalized-Davidson solver type.  Match: include/DMRGBlockContainer.hpp:1656-2057, src/DMRGBlock.cpp:766-771."""
+    truncation-error scale.  The smallest run is repeated on three ranks (density matrices dealt over the ranks, striped solve), with
+    -rdm_warm_start 1 (an option that no longer does anything) and with the generalized-Davidson solver type.  Match: include/DMRGBlockContainer.hpp:1656-2057, src/DMRGBlock.cpp:766-771."""
     g = _medium_golden()[name]
     o = g["options"]
     rows, run, _ = run_engine(tmp_path, "-Lx", o["Lx"], "-Ly", o["Ly"], "-J1", o["J1"], "-Jz1", o["Jz1"], "-J2", o["J2"], "-Jz2", o["Jz2"], "-qn_sector", g["qn_sector"],
@@ -520,7 +520,7 @@ def test_checkpoint_restart_continues_the_run(tmp_path):
     # -wavefunction_guess 0: with the reference's random start vectors every step depends only on the restored blocks and the
     # global step index, so the continuation is bit-identical (a transformed start vector would need the previous step's
     # ground state, which a checkpoint does not carry: the first step after a restart then starts from a random vector;
-    # likewise -rdm_warm_start 0: the eigenbases of the previous visit are not part of a checkpoint)
+    # -rdm_warm_start no longer does anything, with either value)
     model = ["-Lx", 6, "-Ly", 2, "-J1", 1, "-Jz1", 1, "-J2", 0.5, "-Jz2", 0.5, "-mwarmup", 24, "-H_eps_tol", 1e-12, "-wavefunction_guess", 0, "-rdm_warm_start", 0]
     (tmp_path / "a").mkdir(); (tmp_path / "b1").mkdir(); (tmp_path / "b2").mkdir()
     rows_a, run_a, _ = run_engine(tmp_path / "a", *model, "-nsweeps", 2)

@@ -908,8 +908,9 @@ def test_apply_degenerate_layouts_vs_dense_kron(mods):
 def test_rdm_graded_spectrum_few_sweeps_and_warm_hints(mods):
     """Density matrices with a decaying Schmidt spectrum (like a DMRG ground state): dmrgx_rdm_create_warm accepts any orthogonal
     starting basis -- the eigenbasis of a nearby state or a random one -- with the same spectra and eigenvectors, checked against
-    LAPACK.  These calls go through the default solver, tridiagonalisation + divide and conquer, for which the bases are only a hint and
-    which reports no sweeps: the bound of 7 sweeps below was written for the QR-preconditioned block Jacobi (the unpreconditioned
+    LAPACK.  The bases are accepted for compatibility and never read, by either solver.  These calls go through the default solver,
+    tridiagonalisation + divide and conquer, which reports no sweeps: the bound of 7 sweeps below was written for the
+    QR-preconditioned block Jacobi (the unpreconditioned
     iteration needs 10-16 on such matrices) and is asserted on that solver, for this very state, in
     tests/test_gpu_rdm_spectra.py::test_block_jacobi_solver."""
     sbm, wl, _ = mods

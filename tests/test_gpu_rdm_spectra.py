@@ -16,7 +16,7 @@ every KronBlock:
                   time-out, persistent kernel not switched off
 Every figure is printed before it is asserted (pytest -s), with LAPACK's own figure beside it.
 
-The other solver, the QR-preconditioned block Jacobi of csrc/rdm.hip and csrc/hqr.hip, is what EVERY density matrix of a call goes through
+The other solver, the QR-preconditioned block Jacobi of csrc/rdm_jacobi.hip and csrc/hqr.hip, is what EVERY density matrix of a call goes through
 once one of its sectors exceeds SYMEIG_MAX_N = 3072.  The same checker holds it to the same inputs (_check_call with solver=1: the
 report says Jacobi, eigenvalues as above, residual <= 1e-11 |rho|_F + 1e-16 -- ten times the solver's stop criterion --, orthonormality
 as above, dmrgx_rdm_select a no-op) in a child process with DMRGX_RDM_SOLVER=jacobi (run_jacobi_cases), in the same child on poisoned
@@ -28,7 +28,7 @@ workspaces, and once in this process by the automatic switch itself, at order 30
   orders 1024, 1025                                  9          1.2e-03                 1.1e-14
   clusters_200, graded_pairs_300, glued, diagonal   18          7.5e-03                 8.3e-15
   zero, rank-one, orthogonal / sqrt(48), Gaussian    6          4.4e-03                 2.2e-15
-  graded state, cold / junk hints (bound: 7)     7 / 7          6.0e-05                 2.7e-15
+  graded state, without / with ignored bases (7)  7 / 7          6.0e-05                 2.7e-15
   subset (four matrices of order 0 in the call)      7
   3073 x 24 with 1100 x 60, no switch set            6          1.8e-04                 3.2e-14
 The same counts and figures came out on poisoned workspaces.  Orthogonality at order 3073: 3.235e-14 for the device, 4.996e-15 for
@@ -82,14 +82,14 @@ def _check_call(mods, tag, mats, counts=None, solver=0, layout=None, warm=None, 
     """One dmrgx_rdm_create over the KronBlocks (i, i) of the matrices `mats` (each Psi of one block), optionally dmrgx_rdm_select(counts)
     (counts[2 k + side]), and the assertions of the module's docstring.  Returns the report as a dict.
 
-    solver: the solver the call is expected to report.  0 (direct): everything as it was.  1 (block Jacobi, csrc/rdm.hip + hqr.hip): the
+    solver: the solver the call is expected to report.  0 (direct): everything as it was.  1 (block Jacobi, csrc/rdm_jacobi.hip + hqr.hip): the
     report says Jacobi and no tridiagonalisation; the eigenvalues -- Rayleigh quotients of the finished vectors -- keep the bound of the
     direct solver; the residual bound is the project's bound for this solver, 1e-11 |rho|_F + 1e-16, ten times the solver's stop criterion
-    off^2 <= 1e-24 total^2 (rdm_create_impl), which bounds |rho U^T - U^T diag(w)|_F by 1e-12 |rho|_F before rounding; orthogonality
+    off^2 <= 1e-24 total^2 (rdm_solve_jacobi), which bounds |rho U^T - U^T diag(w)|_F by 1e-12 |rho|_F before rounding; orthogonality
     1e-13 up to order 1100 and, above, max(1e-13, 10 x LAPACK's own figure for the same rho) (each column sees O(n sweeps) rotations where
     LAPACK applies O(n) reflectors), both figures by _device_figures; dmrgx_rdm_select is a no-op there -- every eigenvector exists from the
     start -- so the row c + 1 is NOT refused, and the first c rows of that request are the kept rows bit for bit.
-    layout: (left sizes, right sizes, blocks) where the KronBlocks are not (i, i).  warm: {(side, k): orthogonal n x n} (dmrgx_rdm_create_warm).
+    layout: (left sizes, right sizes, blocks) where the KronBlocks are not (i, i).  warm: {(side, k): orthogonal n x n} (dmrgx_rdm_create_warm: accepted, never read).
     exact: {2 k + side: spectrum} where the eigenvalues are planted and LAPACK is not the reference.  max_sweeps: the bound on n_sweeps."""
     sbm, capi = mods
     ls, rs, blocks = layout or ([m.shape[0] for m in mats], [m.shape[1] for m in mats], [(i, i) for i in range(len(mats))])
@@ -427,7 +427,7 @@ def test_zero_rank_one_and_identity_blocks(mods):
     assert nmat == 8 and rep["trid_persistent_matrices"] + rep["trid_launch_matrices"] == 8, rep
 
 
-# ---- the block-Jacobi solver (csrc/rdm.hip, csrc/hqr.hip) -----------------------------------------------------------------------------------
+# ---- the block-Jacobi solver (csrc/rdm_jacobi.hip, csrc/hqr.hip) -----------------------------------------------------------------------------------
 def _jacobi_child(extra_env):
     """run_jacobi_cases in a child process with DMRGX_RDM_SOLVER=jacobi; returns its [(case, solver, n_sweeps)]."""
     code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r);"

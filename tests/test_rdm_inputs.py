@@ -250,10 +250,10 @@ def _one(pattern, src, what):
 
 
 def _jacobi_constants():
-    """The constants of the block-Jacobi path as csrc/rdm.hip and csrc/hqr.hip state them: the Jacobi block, the size classes of
-    hqr_panel_regs_kernel (rows, rows per thread), the panel width where the panels are stepped and where they are clipped, the strip of the
-    trailing update."""
-    rdm, hqr = open(os.path.join(CSRC, "rdm.hip")).read(), open(os.path.join(CSRC, "hqr.hip")).read()
+    """The constants of the block-Jacobi path as csrc/rdm.h (the Jacobi block: it also sets the padding of every matrix) and csrc/hqr.hip
+    state them: the Jacobi block, the size classes of hqr_panel_regs_kernel (rows, rows per thread), the panel width where the panels are
+    stepped and where they are clipped, the strip of the trailing update."""
+    rdm, hqr = open(os.path.join(CSRC, "rdm.h")).read(), open(os.path.join(CSRC, "hqr.hip")).read()
     out = {"DMRGX_JB": int(_one(r"#define\s+DMRGX_JB\s+(\d+)", rdm, "DMRGX_JB")), "HR_MAX_ROWS": int(_one(r"\bHR_MAX_ROWS\s*=\s*(\d+)", hqr, "HR_MAX_ROWS"))}
     classes = re.findall(r"if\s*\(nrem\s*<=\s*(\d+)\)\s*hqr_panel_regs_body<(\d+)>", hqr)
     last = _one(r"else\s+hqr_panel_regs_body<(\d+)>", hqr, "the last size class")
@@ -282,7 +282,7 @@ def _constants():
 
 
 def test_the_jacobi_order_lists_straddle_the_library_constants():
-    """The orders of the block-Jacobi cases sit on the edges of csrc/rdm.hip and csrc/hqr.hip as they are today: a retune of the Jacobi block,
+    """The orders of the block-Jacobi cases sit on the edges of csrc/rdm_jacobi.hip and csrc/hqr.hip as they are today: a retune of the Jacobi block,
     of a size class of the register panels, of the panel width or of the strip of the trailing update must fail here, not silently move an
     edge out of the lists."""
     c = _constants()
