@@ -49,7 +49,7 @@ struct dmrgx_rdm {
     std::vector<int64_t> perm_off;
     std::vector<uint8_t> selected;             // per matrix: built and diagonalised by this rank (dmrgx_rdm_create_subset)
     int32_t sweeps = 0;
-    int32_t solver = 0;                        // 0: tridiagonalisation + divide and conquer (symeig.hip), 1: block Jacobi
+    int32_t solver = 0;                        // 0: tridiagonalisation + divide and conquer (symeig*.hip), 1: block Jacobi
     dmrgx::SymEigReport symeig;                // what the direct solver did (solver == 0)
     // ---- second phase (dmrgx_rdm_select; direct solver only): the eigenvectors of the kept states are formed once the caller has cut ----
     dmrgx::SymEigDeferred deferred;            // pending: the spectra are final, the eigenvectors are not formed yet

@@ -4,7 +4,7 @@
 // KronBlock k, Psi = n_L x n_R row-major slice of psi (:1731), rho_L = Psi Psi^T, rho_R = Psi^T Psi (:1733-1734),
 // then EigRDM_BlockDiag = all eigenpairs of each block by LAPACK (:1962-2003).  Here all 2*nblocks matrices are
 // built by ONE launch of the grouped MFMA-f64 GEMM and diagonalised together on the device by the direct solver of
-// symeig.hip (tridiagonalisation, divide and conquer; rdm_solve_direct below): first the spectra, then -- once the
+// symeig*.hip (tridiagonalisation, divide and conquer; rdm_solve_direct below): first the spectra, then -- once the
 // caller has cut (dmrgx_rdm_select) -- the eigenvectors of the kept states.  A call with a sector above SYMEIG_MAX_N,
 // or under DMRGX_RDM_SOLVER=jacobi, goes to the block-Jacobi iteration of rdm_jacobi.hip instead.  Sorting, the
 // global m-cut and the stable re-sort by sector (:1795,1850-1853) stay on the host (caller), which fetches spectra
@@ -140,7 +140,7 @@ dmrgx_status dmrgx::rdm_solve_direct(dmrgx_rdm& P, hipStream_t st)
         const MatDesc& m = P.mats[mi];
         if (m.n > 0) sm.push_back(SymEigMat{m.n, m.npad, m.npad, 0, buf + m.a_off, buf + m.v_off, buf + P.ew_base + (P.diag_off[mi] - P.diag_base)});
     }
-    DMRGX_CHK(symeig_batched(sm, st, &P.symeig, &P.deferred));
+    DMRGX_CHK(symeig_batched(sm, st, P.symeig, P.deferred));
     P.stage("symeig");
     std::vector<double> ew((size_t)P.dtot);
     if (!ew.empty()) DMRGX_HIP(hipMemcpyAsync(ew.data(), buf + P.ew_base, ew.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -150,7 +150,7 @@ dmrgx_status dmrgx::rdm_solve_direct(dmrgx_rdm& P, hipStream_t st)
         // (the density matrices themselves were only read).
         symeig_note_timeout(bad);
         P.deferred.dbuf.release(); P.deferred.ibuf.release(); P.deferred.pending = false;
-        DMRGX_CHK(symeig_batched(sm, st, &P.symeig, &P.deferred));
+        DMRGX_CHK(symeig_batched(sm, st, P.symeig, P.deferred));
         P.symeig.timed_out = bad;
         if (!ew.empty()) DMRGX_HIP(hipMemcpyAsync(ew.data(), buf + P.ew_base, ew.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         DMRGX_HIP(hipStreamSynchronize(st));

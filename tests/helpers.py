@@ -342,7 +342,7 @@ def lanczos_basis_invariants(plan, H, v0, K, V=None, ref=None):
 
 
 # ---- density-matrix eigensolver: planted tridiagonals, clusters, edges (tests/test_rdm_inputs.py, tests/test_gpu_rdm_spectra.py) ----
-# The constants of csrc/symeig.hip / symeig.h the inputs and the order lists were built around; test_rdm_inputs.py parses the sources and
+# The constants of csrc/symeig*.hip / symeig*.h the inputs and the order lists were built around; test_rdm_inputs.py parses the sources and
 # fails when one of them is retuned.
 RDM_CONSTANTS = {"DMRGX_DC_LEAF": 16, "DC_FUSE_NL": 384, "DMRGX_WY_NB": 64, "TRID_MAXM": 32, "TRID_PF": 8, "SYMEIG_MAX_N": 3072,
                  # the block-Jacobi solver of csrc/rdm_jacobi.hip and its QR preconditioner (csrc/hqr.hip): the Jacobi block (matrices are padded to

@@ -270,7 +270,7 @@ def _jacobi_constants():
 
 
 def _constants():
-    src = open(os.path.join(CSRC, "symeig.hip")).read() + open(os.path.join(CSRC, "symeig.h")).read()
+    src = "".join(open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.startswith("symeig") and f.endswith((".hip", ".h")))
     out = _jacobi_constants()
     for name in helpers.RDM_CONSTANTS:
         if name in out:

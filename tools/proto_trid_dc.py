@@ -1,4 +1,4 @@
-"""Numpy prototype of the round-3 density-matrix eigensolver (csrc/trid.hip, csrc/stedc.hip), written in the exact data
+"""Numpy prototype of the round-3 density-matrix eigensolver (csrc/symeig_trid.hip, csrc/symeig_dc.hip; back-transformation: csrc/symeig.hip), written in the exact data
 flow of the HIP kernels so that index conventions, the deflation scan, the secular solver and the rotation chains can be
 checked on the CPU before they are debugged on a GPU box:
 

@@ -1,5 +1,5 @@
 // Workgroup-to-workgroup exchange latency by placement: two workgroups of the SAME XCD against two of different XCDs, with the
-// relaxed agent-scope 8-byte granules the persistent tridiagonalisation uses (symeig.hip), and a one-to-many variant (one
+// relaxed agent-scope 8-byte granules the persistent tridiagonalisation uses (symeig_trid.hip), and a one-to-many variant (one
 // producer, G-1 pollers, as in its per-column all-gather).  Prints the XCC_ID of every workgroup so the id -> XCD rule is seen.
 #include <hip/hip_runtime.h>
 #include <cstdio>
