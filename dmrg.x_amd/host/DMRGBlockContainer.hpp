@@ -32,12 +32,11 @@
 #include <functional>
 #include <memory>
 #include <mutex>
-#include <random>
 #include <thread>
 #include "DMRGKron.hpp"
 #include "CorrelatorDealing.hpp"
 #include "TridiagQL.hpp"
-#include "Measurements.hpp"
+#include "EngineMeasurements.hpp"
 #include "Noise.hpp"
 
 /** One eigenpair of a reduced-density-matrix block */
@@ -200,66 +199,12 @@ public:
         ierr = PetscOptionsGetBool(NULL, NULL, "-rdm_warm_start", &use_rdm_warm, NULL); CHKERRQ(ierr);
         if (use_rdm_warm && !mpi_rank) printf("NOTE: -rdm_warm_start 1 has no effect: the density-matrix solvers never read a starting basis (the block-Jacobi path preconditions with a QR step of its own, the direct solver has no use for one).\n");
         ierr = PetscOptionsGetBool(NULL, NULL, "-corr_batch", &use_corr_batch, NULL); CHKERRQ(ierr);
-        ierr = PetscOptionsGetBool(NULL, NULL, "-corr_matrix", &use_corr_matrix, NULL); CHKERRQ(ierr);
-        ierr = PetscOptionsGetBool(NULL, NULL, "-corr_dimer", &use_corr_dimer, NULL); CHKERRQ(ierr);
-        ierr = PetscOptionsGetBool(NULL, NULL, "-corr_chiral", &use_corr_chiral, NULL); CHKERRQ(ierr);
-        if (use_corr_chiral && mpi_size > 1) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-corr_chiral 1 is not available on more than one rank (got %d): the triangles are not dealt over the ranks.", (int)mpi_size);
         ierr = PetscOptionsGetBool(NULL, NULL, "-prune_ops", &prune_ops, NULL); CHKERRQ(ierr);
         /* -noise a0,a1,... / -noise_warmup a: White's density-matrix perturbation, weight per sweep (GetTruncation) */
         ierr = dmrgx_host::ReadNoiseOptions(mpi_comm, noise); CHKERRQ(ierr);
         if (noise.Any() && mpi_size > 1) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-noise is not available on more than one rank (got %d): the expansion of the density matrix is not striped.", (int)mpi_size);
-        ierr = PetscOptionsGetBool(NULL, NULL, "-dsf", &use_dsf, NULL); CHKERRQ(ierr);
-        if (use_dsf) {   /* -dsf 1: S^zz(q, w) at every measurement point (CalculateDynamicalStructureFactor) */
-            if (mpi_size > 1) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-dsf 1 is not available on more than one rank (got %d): the Lanczos run behind S(q,w) has no collectives.", (int)mpi_size);
-            PetscBool have_q = PETSC_FALSE;
-            PetscInt nq = 2048;
-            dsf_q.assign((size_t)nq, 0);
-            ierr = PetscOptionsGetIntArray(NULL, NULL, "-dsf_q", dsf_q.data(), &nq, &have_q); CHKERRQ(ierr);
-            dsf_q.resize((size_t)nq);
-            if (!have_q || nq < 2 || nq % 2) SETERRQ1(mpi_comm, PETSC_ERR_ARG_WRONG, "-dsf 1 needs -dsf_q nx0,ny0,nx1,ny1,...: pairs of integers, q = (2 pi nx / Lx, 2 pi ny / Ly). Got %lld numbers.", LLD(nq));
-            ierr = ReadLanczosStepOptions(); CHKERRQ(ierr);
-        }
-        /* -dsf_sites c0,c1,...: the real-space dynamical correlations G_ic(w) from every listed site c (CalculateDynamicalCorrelations) */
-        ierr = ReadSiteListOption("-dsf_sites", "the Lanczos run behind G_ic(w)", dsf_sites, use_dsf_sites); CHKERRQ(ierr);
-        if (use_dsf_sites && !use_dsf) { ierr = ReadLanczosStepOptions(); CHKERRQ(ierr); }      /* (-dsf has read them above) */
-        ierr = ReadSiteListOption("-dsf_cheb", "the Chebyshev recursion", dsf_cheb_sites, use_dsf_cheb); CHKERRQ(ierr);
-        /* -dsf_dimer b0,b1,...: the Chebyshev moments of the dimer correlations D_bc(w) from every listed bond c, numbered as the Bonds of
-           DimerCorrelations.json (CalculateDimerDynamics).  On the device: the images of all bonds and the 34 vectors of a moment run. */
-        ierr = ReadSiteListOption("-dsf_dimer", "the Chebyshev recursion", dsf_dimer_bonds, use_dsf_dimer, (PetscInt)dmrgx_host::DimerBonds(Ham).size(), "bond",
-                                  "the nearest-neighbour bonds in the order of Bonds in DimerCorrelations.json"); CHKERRQ(ierr);
-        if (use_dsf_dimer) {
-            ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_dimer_steps", &dsf_dimer_steps, NULL); CHKERRQ(ierr);
-            if (dsf_dimer_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_dimer_steps must be at least 1. Got %lld.", LLD(dsf_dimer_steps));
-            ierr = ReadOmegaGridOption("-dsf_dimer_omega", dsf_dimer_omega, dsf_dimer_have_omega); CHKERRQ(ierr);
-        }
-        /* -dsf_pm c0,c1,...: the Chebyshev moments of the transverse correlations S^-+_ic(w) and S^+-_ic(w) from every listed site c, run on a
-           plan of the neighbouring total-Sz sector (CalculateTransverseDynamics); steps, grid and window are those of -dsf_cheb */
-        ierr = ReadSiteListOption("-dsf_pm", "the Chebyshev recursion", dsf_pm_sites, use_dsf_pm); CHKERRQ(ierr);
-        if (use_dsf_cheb || use_dsf_pm) {   /* -dsf_cheb c0,c1,...: the Chebyshev moments of G_ic(w) from every listed site c (CalculateChebyshevCorrelations) */
-            ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_cheb_steps", &dsf_cheb_steps, NULL); CHKERRQ(ierr);
-            if (dsf_cheb_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cheb_steps must be at least 1. Got %lld.", LLD(dsf_cheb_steps));
-            ierr = ReadOmegaGridOption("-dsf_cheb_omega", dsf_cheb_omega, dsf_cheb_have_omega); CHKERRQ(ierr);
-        }
-        if (use_dsf_cheb || use_dsf_dimer || use_dsf_pm) {   /* the window of the Chebyshev expansion, which the three share */
-            ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_cheb_bound_steps", &dsf_cheb_bound_steps, NULL); CHKERRQ(ierr);
-            if (dsf_cheb_bound_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cheb_bound_steps must be at least 1. Got %lld.", LLD(dsf_cheb_bound_steps));
-            PetscInt nw = 2;
-            ierr = PetscOptionsGetRealArray(NULL, NULL, "-dsf_cheb_window", dsf_cheb_window, &nw, &dsf_cheb_have_window); CHKERRQ(ierr);
-            if (dsf_cheb_have_window && !(nw == 2 && dsf_cheb_window[0] < dsf_cheb_window[1] && std::isfinite(dsf_cheb_window[0]) && std::isfinite(dsf_cheb_window[1])))
-                SETERRQ1(mpi_comm, PETSC_ERR_ARG_WRONG, "-dsf_cheb_window needs lo,hi: two finite energies, lo < hi. Got %lld numbers.", LLD(nw));
-        }
-        ierr = ReadSiteListOption("-dsf_cv", "the conjugate-gradient run", dsf_cv_sites, use_dsf_cv); CHKERRQ(ierr);
-        if (use_dsf_cv) {   /* -dsf_cv c0,c1,...: the correction vectors of G_ic(w + i eta) from every listed site c (CalculateCorrectionVectors) */
-            PetscBool have_omega = PETSC_FALSE;
-            ierr = ReadOmegaGridOption("-dsf_cv_omega", dsf_cv_omega, have_omega); CHKERRQ(ierr);
-            if (!have_omega) SETERRQ(mpi_comm, PETSC_ERR_ARG_WRONG, "-dsf_cv needs -dsf_cv_omega w0,w1,nw: the frequencies at which the correction vectors are solved.");
-            ierr = PetscOptionsGetReal(NULL, NULL, "-dsf_cv_eta", &dsf_cv_eta, NULL); CHKERRQ(ierr);
-            if (!(dsf_cv_eta > 0.0) || !std::isfinite(dsf_cv_eta)) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cv_eta must be positive and finite. Got %g.", dsf_cv_eta);
-            ierr = PetscOptionsGetReal(NULL, NULL, "-dsf_cv_tol", &dsf_cv_tol, NULL); CHKERRQ(ierr);
-            if (!(dsf_cv_tol > 0.0) || dsf_cv_tol >= 1.0) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cv_tol must lie in (0, 1). Got %g.", dsf_cv_tol);
-            ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_cv_maxit", &dsf_cv_maxit, NULL); CHKERRQ(ierr);
-            if (dsf_cv_maxit < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_cv_maxit must be at least 1. Got %lld.", LLD(dsf_cv_maxit));
-        }
+        /* -corr_matrix, -corr_dimer, -corr_chiral, -dsf, -dsf_sites, -dsf_cheb, -dsf_dimer, -dsf_pm, -dsf_cv and what goes with them (EngineMeasurements.hpp) */
+        ierr = engine_measurements.ReadOptions(mpi_comm, mpi_rank, mpi_size, num_sites, Ham); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-step_profile", &step_profile, NULL); CHKERRQ(ierr);
 
         PetscBool opt = PETSC_FALSE;
@@ -507,7 +452,7 @@ public:
         spectra_writer.Drain();
         if (fp_entanglement) { fprintf(fp_entanglement, "\n]\n"); fclose(fp_entanglement); fp_entanglement = NULL; }
         if (fp_kron) { fprintf(fp_kron, "\n]\n"); fclose(fp_kron); fp_kron = NULL; }
-        spin_file.Close(); dimer_file.Close(); chiral_file.Close(); dsf_file.Close(); dsf_sites_file.Close(); dsf_cheb_file.Close(); dsf_cv_file.Close(); dsf_dimer_file.Close(); dsf_pm_file.Close();
+        engine_measurements.Close();
         if (fp_corr) {
             if (!corr_headers_printed) { PetscErrorCode e2 = PrintCorrelationHeaders(); CHKERRQ(e2); }
             fprintf(fp_corr, "\n  ]\n}\n"); fclose(fp_corr); fp_corr = NULL;
@@ -637,14 +582,11 @@ public:
             ierr = SaveKronStats(kinfo, SysBlock, EnvBlock, (PetscInt)Terms.size(), st.n_matvec, st.seconds, ms4, napp); CHKERRQ(ierr);
         }
         step.GSEnergy = gse_r;
-        if (use_dsf && do_measurements) { ierr = CalculateDynamicalStructureFactor(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* needs the plan */
-        if (use_dsf_sites && do_measurements) { ierr = CalculateDynamicalCorrelations(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
-        if (use_dsf_cheb && do_measurements) { ierr = CalculateChebyshevCorrelations(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
-        if (use_dsf_dimer && do_measurements) { ierr = CalculateDimerDynamics(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
-        if (use_dsf_cv && do_measurements) { ierr = CalculateCorrectionVectors(KronBlocks, gsv_r, H, gse_r); CHKERRQ(ierr); }      /* likewise */
+        const dmrgx_host::MeasurementContext mctx{KronBlocks, gsv_r, &H, Terms, gse_r, num_sites, qn_sector, GlobIdx, LoopTypeName(), verbose, do_shell, mpi_comm, mpi_rank, mpi_size, data_dir};
+        if (do_measurements) { ierr = engine_measurements.RunWithPlan(mctx, Ham); CHKERRQ(ierr); }      /* -dsf, -dsf_sites, -dsf_cheb, -dsf_dimer, -dsf_cv: they need the plan */
         ierr = MatDestroy_KronSumShell(&H); CHKERRQ(ierr);
         ierr = MatDestroy(&H); CHKERRQ(ierr);
-        if (use_dsf_pm && do_measurements) { ierr = CalculateTransverseDynamics(KronBlocks, gsv_r, Terms, gse_r); CHKERRQ(ierr); }      /* needs psi, not H: its plans are of other sectors, one resident at a time */
+        if (do_measurements) { ierr = engine_measurements.RunAfterPlan(mctx, Ham); CHKERRQ(ierr); }      /* -dsf_pm */
         ierr = PetscTime(&tdiag); CHKERRQ(ierr);
         timings.tDiag = tdiag - tkron;
 
@@ -653,7 +595,7 @@ public:
         const bool vec_sys = !(hints && hints->dead_sys && !same), vec_env = !(hints && hints->dead_env && !same);
         step.Noise = noise.At(LoopType == WarmupStep, LoopIdx - 1);      /* (the warm-up is loop 0, sweep s loop s + 1: also after a restart) */
         ierr = GetTruncation(KronBlocks, gsv_r, MStates, BT_L, BT_R, vec_sys, vec_env, step.Noise, &Terms); CHKERRQ(ierr);
-        ierr = CalculateCorrelations_BlockDiag(KronBlocks, gsv_r, do_measurements); CHKERRQ(ierr);
+        ierr = CalculateCorrelations_BlockDiag(KronBlocks, gsv_r, do_measurements, &mctx); CHKERRQ(ierr);
         if (use_guess) {   /* what the next step needs to carry this ground state over */
             prev.valid = false;
             prev.insys = BlockIndex(SysBlock); prev.inenv = BlockIndex(EnvBlock); prev.outsys = BlockIndex(SysBlockOut); prev.outenv = BlockIndex(EnvBlockOut);
@@ -1209,8 +1151,9 @@ public:
     }
 
     /** < psi | (product of SysOps) (x) (product of EnvOps) | psi > for every registered correlator, through a one-term
-        superblock plan, one MatMult and one dot product each (include/DMRGBlockContainer.hpp:2255-2303). */
-    PetscErrorCode CalculateCorrelations_BlockDiag(KronBlocks_t& KronBlocks, const Vec& gsv_r, const PetscBool flg = PETSC_TRUE)
+        superblock plan, one MatMult and one dot product each (include/DMRGBlockContainer.hpp:2255-2303).  With the step's mctx, the engine's
+        own centre measurements follow (EngineMeasurements::RunAtCentre). */
+    PetscErrorCode CalculateCorrelations_BlockDiag(KronBlocks_t& KronBlocks, const Vec& gsv_r, const PetscBool flg = PETSC_TRUE, const dmrgx_host::MeasurementContext* mctx = nullptr)
     {
         PetscErrorCode ierr = PrintCorrelationHeaders(); CHKERRQ(ierr);
         if (!flg) return 0;
@@ -1388,737 +1331,7 @@ public:
             fprintf(fp_corr, " ]");
             fflush(fp_corr);
         }
-        if (use_corr_matrix) { ierr = CalculateCorrelationMatrix(KronBlocks, gsv_r); CHKERRQ(ierr); }
-        if (use_corr_dimer) { ierr = CalculateDimerCorrelations(KronBlocks, gsv_r); CHKERRQ(ierr); }
-        if (use_corr_chiral) { ierr = CalculateChiralCorrelations(KronBlocks, gsv_r); CHKERRQ(ierr); }
-        return 0;
-    }
-
-    /** -corr_matrix 1 (engine extension): the full tables < Sz_i Sz_j >, < Sm_i Sp_j > and < Sp_i Sm_j > over all pairs of lattice sites,
-        the spin correlation function < S_i . S_j > and its Fourier transform, the static structure factor, at every measurement point.
-        < psi | O_i^T O_j | psi > = < O_i psi , O_j psi >: a table is the Gram matrix of the vectors O_i psi, so each is ONE
-        dmrgx_kron_op_gram call -- the identity (which adds < Sz_i > and the norm) and Sz of every site of both blocks, shift 0; Sp of
-        every site, shift +1; Sm of every site (Sp read transposed), shift -1 -- instead of a plan, a MatMult and a dot product per pair.
-        < Sp_i Sm_j > is a table of its own because two TRUNCATED operators of one block do not commute: it equals < Sm_j Sp_i > only
-        across the cut or when nothing was truncated, and the registered correlators multiply the operators in the order they name.
-        Site s of the right block is lattice site N - 1 - s, as in SetUpCorrelation.  On several ranks every rank computes the same
-        tables from the replicated psi (no collective); rank 0 writes one record per measurement to SpinCorrelations.json. */
-    PetscErrorCode CalculateCorrelationMatrix(KronBlocks_t& KronBlocks, const Vec& gsv_r)
-    {
-        PetscLogDouble t0, t1;
-        PetscTime(&t0);
-        dmrgx_host::CentreFrame F;
-        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, "Correlation matrix"); CHKERRQ(ierr);
-        const PetscInt N = F.N;
-        std::vector<PetscInt> site;                                 /* lattice site of vector a of a family (identity: -1) */
-        std::vector<double> G;
-        /* one family: [identity] + the operator of every left site + of every right site; its Gram matrix G, and as a table over lattice sites */
-        auto family = [&](Op_t type, bool with_identity, std::vector<double>& table) -> PetscErrorCode {
-            dmrgx_host::SiteOperators T(F);
-            site.clear();
-            if (with_identity) { T.AddIdentity(0); site.push_back(-1); }
-            PetscErrorCode e = T.AllSites(type, site); CHKERRQ(e);
-            const PetscInt n = (PetscInt)site.size();
-            dmrgx_host::DevBuffer g((size_t)(n * n), dmrgx_host::DevBuffer::device_only_t{});
-            if (dmrgx_kron_op_gram(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), gsv_r->buf->dev_ro(), (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
-                                   0, g.dev_uninitialised(), n, nullptr, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_op_gram: %s", dmrgx_last_error());
-            G.assign((size_t)(n * n), 0.0);
-            if (dmrgx_memcpy_d2h(G.data(), g.dev_ro(), G.size() * sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
-            const PetscInt first = with_identity ? 1 : 0;
-            for (PetscInt a = first; a < n; ++a) for (PetscInt b = first; b < n; ++b) table[(size_t)(site[(size_t)a] * N + site[(size_t)b])] = G[(size_t)(a * n + b)];
-            return 0;
-        };
-        std::vector<double> SzSz((size_t)(N * N), 0.0), SmSp((size_t)(N * N), 0.0), SpSm((size_t)(N * N), 0.0), Sz((size_t)N, 0.0);
-        ierr = family(OpSz, true, SzSz); CHKERRQ(ierr);
-        const double norm = G[0];
-        for (PetscInt a = 1; a <= N; ++a) Sz[(size_t)site[(size_t)a]] = G[(size_t)a];     /* < psi , Sz_i psi > */
-        ierr = family(OpSp, false, SmSp); CHKERRQ(ierr);
-        ierr = family(OpSm, false, SpSm); CHKERRQ(ierr);
-        /* S_i . S_j = Sz_i Sz_j + (Sp_i Sm_j + Sm_i Sp_j) / 2: off the diagonal the spins commute and the state is real, so both halves equal
-           < Sm_i Sp_j >; on the diagonal Sp Sm = Sm Sp + 2 Sz */
-        std::vector<double> SS((size_t)(N * N), 0.0);
-        for (PetscInt i = 0; i < N; ++i) for (PetscInt j = 0; j < N; ++j) SS[(size_t)(i * N + j)] = SzSz[(size_t)(i * N + j)] + SmSp[(size_t)(i * N + j)] + (i == j ? Sz[(size_t)i] : 0.0);
-        /* S(q) = (1/N) sum_ij cos(q . (r_i - r_j)) SS_ij,  q = (2 pi nx / Lx, 2 pi ny / Ly) */
-        const PetscInt Lx = Ham.Lx(), Ly = Ham.Ly();
-        std::vector<PetscInt> rx((size_t)N), ry((size_t)N);
-        for (PetscInt i = 0; i < N; ++i) { ierr = Ham.To2D(i, rx[(size_t)i], ry[(size_t)i]); CHKERRQ(ierr); }
-        const std::vector<double> Sq = dmrgx_host::LatticeFourier(Lx, Ly, rx.data(), ry.data(), SS.data(), N, (double)N);
-        PetscTime(&t1);
-        if (!mpi_rank && verbose) {
-            /* what the two Gram kernels must read: vectors x length of the image space (shift 0: the target sector itself) */
-            int64_t len_shifted[2] = {0, 0};                         /* image space of Sp (sector shift +1), of Sm (-1) */
-            for (int d = 0; d < 2; ++d) {
-                const int32_t sh = d == 0 ? 1 : -1;
-                std::set<std::pair<int32_t, int32_t>> img;
-                for (size_t k = 0; k < F.bil.size(); ++k) {
-                    const int32_t a = F.bil[k] - sh, b = F.bir[k] - sh;
-                    if (a >= 0 && a < (int32_t)F.sizes[0].size()) img.insert({a, F.bir[k]});
-                    if (b >= 0 && b < (int32_t)F.sizes[1].size()) img.insert({F.bil[k], b});
-                }
-                for (const auto& ab : img) len_shifted[d] += (int64_t)F.sizes[0][(size_t)ab.first] * F.sizes[1][(size_t)ab.second];
-            }
-            printf("  * Correlation matrix: %lld x %lld pairs, Gram of %lld vectors x %lld (Sz), %lld x %lld (Sp), %lld x %lld (Sm), tCorrMatrix %.6f s\n", LLD(N), LLD(N), LLD(N + 1), LLD(gsv_r->n),
-                   LLD(N), LLD(len_shifted[0]), LLD(N), LLD(len_shifted[1]), t1 - t0);
-        }
-        if (mpi_rank) return 0;
-        ierr = spin_file.Begin(data_dir + "SpinCorrelations.json"); CHKERRQ(ierr);
-        fprintf(spin_file.fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"tCorrMatrix\": %.9g, \"Norm\": %.15g,\n   \"Sz\": ", LLD(GlobIdx), LoopTypeName(), t1 - t0, norm);
-        spin_file.Row(Sz);
-        fprintf(spin_file.fp, ",\n");
-        spin_file.Table("SzSz", SzSz, N, N, ",\n"); spin_file.Table("SmSp", SmSp, N, N, ",\n"); spin_file.Table("SpSm", SpSm, N, N, ",\n"); spin_file.Table("SS", SS, N, N, ",\n"); spin_file.Table("StructureFactor", Sq, Lx, Ly, "}");
-        fflush(spin_file.fp);
-        return 0;
-    }
-
-    /** -dsf 1 (engine extension): the dynamical spin structure factor S^zz(q, w) of the ground state at every measurement point, by the
-        Lanczos-vector (continued-fraction) method.  With O_q = N^(-1/2) sum_r e^(-i q.r) Sz_r = C_q - i S_q (cosine and sine part) and a
-        real psi,  S^zz(q, w) = sum_n ( |<n|C_q|0>|^2 + |<n|S_q|0>|^2 ) delta(w - E_n + E_0):  two real runs per q.  A run forms
-        v = C_q psi with ONE dmrgx_kron_term_apply over Sz of every site of both blocks, then dmrgx_kron_lanczos_coeffs gives |v|^2 and
-        the tridiagonal T of H from v without a host round trip per step; T is diagonalised here (TridiagQL.hpp): poles w = theta - E0,
-        weights |v|^2 z_k^2 / <psi|psi>.  It runs right after the eigensolve, while the plan of the superblock Hamiltonian still exists.
-        The block bases were optimised for the ground state alone (single target): |v|^2 -- the static S^zz(q) -- and the first moments
-        are exact in the superblock basis, the line shape is as good as that basis represents the excited states.
-        cos and sin are taken of the exact fraction 2 pi p / (Lx Ly) with their exact zeros, so that a part that vanishes by symmetry
-        vanishes in the coefficients too; a part whose |v|^2 <= 1e-20 <psi|psi> (rounding of Sz_tot psi at q = 0, for instance) holds no
-        weight a double could resolve next to the others and is recorded without a run: StepsDone 0.
-        Set-up (operators, site maps, psi): SzFrame, Measurements.hpp.  One rank only (refused at start-up otherwise). */
-    PetscErrorCode CalculateDynamicalStructureFactor(KronBlocks_t& KronBlocks, const Vec& gsv_r, Mat& H, PetscScalar E0)
-    {
-        PetscLogDouble t0, t1;
-        PetscTime(&t0);
-        dmrgx_host::SzFrame S;
-        PetscErrorCode ierr = S.Init(KronBlocks, num_sites, Ham, gsv_r, "Dynamical structure factor"); CHKERRQ(ierr);
-        const PetscInt N = S.F.N, Lx = S.Lx, Ly = S.Ly, M = S.M;
-        const int64_t n = S.n;
-        std::vector<dmrgx_term> terms;
-        terms.reserve((size_t)N);
-        dmrgx_host::DevBuffer v((size_t)n, dmrgx_host::DevBuffer::device_only_t{});
-
-        struct Part { double norm2 = 0.0; int32_t done = 0; std::vector<double> alpha, beta, theta, z; };
-        struct Point { PetscInt nx, ny; Part part[2]; std::vector<double> poles, weights; double total = 0.0; };
-        std::vector<Point> points(dsf_q.size() / 2);
-        PetscInt matmults = 0;
-        for (size_t iq = 0; iq < points.size(); ++iq) {
-            Point& P = points[iq];
-            P.nx = dsf_q[2 * iq]; P.ny = dsf_q[2 * iq + 1];
-            for (int part = 0; part < 2; ++part) {
-                Part& A = P.part[part];
-                terms.clear();
-                for (PetscInt i = 0; i < N; ++i) {
-                    const PetscInt s = S.site[(size_t)i];                /* operator i of the frame is Sz of lattice site s */
-                    const PetscInt p = (((P.nx * S.rx[(size_t)s] * Ly + P.ny * S.ry[(size_t)s] * Lx) % M) + M) % M;      /* q . r = 2 pi p / M exactly */
-                    const double c = dmrgx_host::DsfPhaseCoefficient(part, p, M);
-                    /* a site whose coefficient is exactly zero takes no part: its Sz cells are neither copied nor multiplied */
-                    if (c == 0.0) continue;
-                    terms.push_back(S.term(i, c / std::sqrt((double)N)));
-                }
-                if (terms.empty()) continue;                            /* the part vanishes on the lattice: Norm2 0, no run */
-                const int32_t vec_first[2] = {0, (int32_t)terms.size()};
-                ierr = S.Apply(1, vec_first, terms.data(), v.dev_uninitialised(), n); CHKERRQ(ierr);
-                if (dmrgx_dot(n, v.dev_ro(), v.dev_ro(), &A.norm2, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
-                if (A.norm2 != A.norm2) SETERRQ3(mpi_comm, 1, "Dynamical structure factor: the %s part of q = (%lld,%lld) is not a number.", part == 0 ? "cosine" : "sine", LLD(P.nx), LLD(P.ny));
-                if (!(A.norm2 > dsf_no_weight * S.norm)) continue;        /* no weight: no run */
-                A.alpha.assign((size_t)dsf_steps, 0.0); A.beta.assign((size_t)dsf_steps, 0.0);
-                if (dmrgx_kron_lanczos_coeffs(H->plan, v.dev_ro(), (int32_t)dsf_steps, dsf_breakdown_tol, &A.norm2, A.alpha.data(), A.beta.data(), &A.done, nullptr))
-                    SETERRQ1(mpi_comm, 1, "dmrgx_kron_lanczos_coeffs: %s", dmrgx_last_error());
-                matmults += dsf_steps;
-                A.alpha.resize((size_t)A.done); A.beta.resize((size_t)A.done);
-                A.theta = A.alpha;
-                if (!dmrgx_host::TridiagQLFirstRow(A.theta, A.beta, A.z)) SETERRQ2(mpi_comm, 1, "Dynamical structure factor: the QL iteration on the Lanczos matrix of q = (%lld,%lld) did not converge.", LLD(P.nx), LLD(P.ny));
-            }
-            /* the poles of both parts, ascending */
-            std::vector<std::pair<double, double>> pw;
-            for (const Part& A : P.part) for (size_t k = 0; k < A.theta.size(); ++k) pw.push_back({A.theta[k] - E0, A.norm2 * A.z[k] * A.z[k] / S.norm});
-            std::sort(pw.begin(), pw.end());
-            for (const auto& x : pw) { P.poles.push_back(x.first); P.weights.push_back(x.second); P.total += x.second; }
-        }
-        PetscTime(&t1);
-        if (verbose) printf("  * Dynamical structure factor: %lld q points, %lld Lanczos steps per run, %lld MatMults on %lld states, tDsf %.6f s\n", LLD(points.size()), LLD(dsf_steps), LLD(matmults), LLD(n), t1 - t0);
-        ierr = dsf_file.BeginDynamical(data_dir + "DynamicalStructureFactor.json", GlobIdx, LoopTypeName(), (double)E0, S.norm); CHKERRQ(ierr);
-        FILE* fp_dsf = dsf_file.fp;
-        fprintf(fp_dsf, ", \"Steps\": %lld, \"tDsf\": %.9g, \"MatMults\": %lld,\n   \"Points\": [\n", LLD(dsf_steps), t1 - t0, LLD(matmults));
-        for (size_t iq = 0; iq < points.size(); ++iq) {
-            const Point& P = points[iq];
-            fprintf(fp_dsf, "     {\"q\": [%lld, %lld],\n", LLD(P.nx), LLD(P.ny));
-            for (int part = 0; part < 2; ++part) {
-                const Part& A = P.part[part];
-                fprintf(fp_dsf, "      \"%s\": {\"Norm2\": %.17g, \"StepsDone\": %d, \"Alpha\": ", part == 0 ? "Cos" : "Sin", A.norm2, (int)A.done);
-                dsf_file.Row(A.alpha); fprintf(fp_dsf, ", \"Beta\": "); dsf_file.Row(A.beta); fprintf(fp_dsf, "},\n");
-            }
-            fprintf(fp_dsf, "      \"Poles\": "); dsf_file.Row(P.poles); fprintf(fp_dsf, ",\n      \"Weights\": "); dsf_file.Row(P.weights);
-            fprintf(fp_dsf, ",\n      \"StaticSzz\": %.17g}%s\n", P.total, iq + 1 < points.size() ? "," : "");
-        }
-        fprintf(fp_dsf, "   ]}");
-        fflush(fp_dsf);
-        return 0;
-    }
-
-    /** -dsf_sites c0,c1,... (engine extension): the real-space dynamical correlations of the ground state from every listed site c,
-            G_ic(w) = sum_n <0|Sz_i|n> <n|Sz_c|0> delta(w - E_n + E_0)   for ALL sites i,
-        from ONE Lanczos run per c, where -dsf needs two runs per wave vector.  dmrgx_kron_lanczos_basis runs the recursion from
-        v = Sz_c psi with the basis V kept and fully reorthogonalised, so that T = V H V^T and V V^T = 1 hold to rounding; the overlaps
-        M[i][k] = <u_i, q_k> with the images u_i = Sz_i psi (SzFrame::Images, a chunk at a time) are one dmrgx_vec_gram(chunk, V) each.
-        With T = S Theta S^T (TridiagQL.hpp, all eigenvectors) the Galerkin approximation of G in the Krylov space of v is
-            Poles[n] = theta_n - E0,   Amplitudes[i][n] = (M S)[i][n] |v| S[0][n] / <psi|psi>,
-        and Sqw[q][n] = sum_i cos(q . (r_i - r_c)) Amplitudes[i][n] (SiteCosineSum) at all Lx Ly wave vectors q = (2 pi nx / Lx,
-        2 pi ny / Ly), row nx Ly + ny: (1/N) sum_c Sqw is S^zz(q, w).  Static[i] = sum_n Amplitudes[i][n] = <Sz_i Sz_c> exactly (S is
-        orthogonal), and the moments sum_n Amplitudes[i][n] Poles[n]^p equal <u_i, (H - E0)^p v> for p < steps done.
-        The psi component of v is left in: it shows as a pole at w = 0 whose amplitude at i is <Sz_i> <Sz_c>.  Amplitudes[c] are the
-        weights |v|^2 S[0][n]^2 >= 0 of the continued fraction of v; for i != c they carry either sign, and Sqw of ONE site is an
-        estimator that need not be positive where the lattice is not translation invariant (an open cylinder) -- only the average over c
-        is S^zz(q, w).  The block bases were optimised for the ground state alone: the caveat of -dsf applies unchanged.
-        Memory: the basis, steps x N_sb doubles on the device for the whole measurement (2.6 GB at 20 x 8, m = 2048, 100 steps), beside
-        one chunk of images.  One rank only (refused at start-up otherwise). */
-    PetscErrorCode CalculateDynamicalCorrelations(KronBlocks_t& KronBlocks, const Vec& gsv_r, Mat& H, PetscScalar E0)
-    {
-        PetscLogDouble t0, t1;
-        PetscTime(&t0);
-        dmrgx_host::SzFrame S;
-        PetscErrorCode ierr = S.Init(KronBlocks, num_sites, Ham, gsv_r, "Dynamical correlations"); CHKERRQ(ierr);
-        const PetscInt N = S.F.N, M = S.M, K = dsf_steps, chunk = S.chunk();
-        const int64_t n = S.n, ld = S.ld;
-        std::vector<PetscInt> ops((size_t)N);                        /* the images are taken in the order of the operators */
-        for (PetscInt a = 0; a < N; ++a) ops[(size_t)a] = a;
-        std::unique_ptr<dmrgx_host::DevBuffer> v, V, U, Mdev;
-        try {
-            v.reset(new dmrgx_host::DevBuffer((size_t)n, dmrgx_host::DevBuffer::device_only_t{}));
-            V.reset(new dmrgx_host::DevBuffer((size_t)(K * ld), dmrgx_host::DevBuffer::device_only_t{}));
-            U.reset(new dmrgx_host::DevBuffer((size_t)(chunk * ld), dmrgx_host::DevBuffer::device_only_t{}));
-            Mdev.reset(new dmrgx_host::DevBuffer((size_t)(chunk * K), dmrgx_host::DevBuffer::device_only_t{}));
-        } catch (const std::exception& e) { SETERRQ3(mpi_comm, PETSC_ERR_MEM, "Dynamical correlations: no memory for the basis of %lld steps x %lld states: %s", LLD(K), LLD(n), e.what()); }
-
-        struct Run { PetscInt c = 0; double norm2 = 0.0; int32_t done = 0; std::vector<double> alpha, beta, poles, amp, stat, sqw; };
-        std::vector<Run> runs(dsf_sites.size());
-        std::vector<double> Mh((size_t)(N * K)), Mchunk((size_t)(chunk * K)), theta, vec;
-        PetscInt matmults = 0;
-        double t_runs = 0.0;
-        for (size_t ir = 0; ir < runs.size(); ++ir) {
-            Run& R = runs[ir];
-            R.c = dsf_sites[ir];
-            /* v = Sz_c psi, then the run from it */
-            ierr = S.Images(&S.op_of[(size_t)R.c], 1, v->dev_uninitialised(), n); CHKERRQ(ierr);
-            R.alpha.assign((size_t)K, 0.0); R.beta.assign((size_t)K, 0.0);
-            PetscLogDouble tr0 = 0.0, tr1 = 0.0;
-            if (verbose) { if (dmrgx_stream_sync(nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error()); PetscTime(&tr0); }      /* the run alone, for the log */
-            if (dmrgx_kron_lanczos_basis(H->plan, v->dev_ro(), (int32_t)K, dsf_breakdown_tol, V->dev_uninitialised(), ld, &R.norm2, R.alpha.data(), R.beta.data(), &R.done, nullptr))
-                SETERRQ1(mpi_comm, 1, "dmrgx_kron_lanczos_basis: %s", dmrgx_last_error());
-            if (verbose) { PetscTime(&tr1); t_runs += tr1 - tr0; }
-            matmults += K;
-            /* M[s][k] = < Sz_s psi , q_k > for every lattice site s */
-            for (PetscInt a0 = 0; a0 < N; a0 += chunk) {
-                const PetscInt cnt = std::min<PetscInt>(chunk, N - a0);
-                ierr = S.Images(ops.data() + a0, cnt, U->dev_uninitialised(), ld); CHKERRQ(ierr);
-                if (dmrgx_vec_gram((int32_t)cnt, (int32_t)K, n, U->dev_ro(), ld, V->dev_ro(), ld, Mdev->dev_uninitialised(), K, 0, nullptr, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_vec_gram: %s", dmrgx_last_error());
-                if (dmrgx_memcpy_d2h(Mchunk.data(), Mdev->dev_ro(), (size_t)(cnt * K) * sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
-                for (PetscInt a = a0; a < a0 + cnt; ++a) std::copy(Mchunk.begin() + (a - a0) * K, Mchunk.begin() + (a - a0 + 1) * K, Mh.begin() + S.site[(size_t)a] * K);
-            }
-            /* T = S Theta S^T on the host, the poles ascending */
-            const PetscInt D = R.done;
-            R.alpha.resize((size_t)D); R.beta.resize((size_t)D);
-            theta = R.alpha;
-            if (!dmrgx_host::TridiagQLVectors(theta, R.beta, vec)) SETERRQ1(mpi_comm, 1, "Dynamical correlations: the QL iteration on the Lanczos matrix of site %lld did not converge.", LLD(R.c));
-            std::vector<PetscInt> order((size_t)D);
-            for (PetscInt k = 0; k < D; ++k) order[(size_t)k] = k;
-            std::sort(order.begin(), order.end(), [&](PetscInt a, PetscInt b) { return theta[(size_t)a] < theta[(size_t)b]; });
-            const double vnorm = std::sqrt(R.norm2);
-            R.poles.resize((size_t)D); R.amp.assign((size_t)(N * D), 0.0); R.stat.assign((size_t)N, 0.0);
-            for (PetscInt p = 0; p < D; ++p) {
-                const double* z = vec.data() + order[(size_t)p] * D;            /* eigenvector of pole p: z[k] = S[k][n] */
-                R.poles[(size_t)p] = theta[(size_t)order[(size_t)p]] - (double)E0;
-                for (PetscInt s = 0; s < N; ++s) {
-                    double acc = 0.0;
-                    for (PetscInt k = 0; k < D; ++k) acc += Mh[(size_t)(s * K + k)] * z[k];
-                    R.amp[(size_t)(s * D + p)] = acc * vnorm * z[0] / S.norm;
-                }
-            }
-            for (PetscInt s = 0; s < N; ++s) for (PetscInt p = 0; p < D; ++p) R.stat[(size_t)s] += R.amp[(size_t)(s * D + p)];
-            R.sqw = dmrgx_host::SiteCosineSum(S.Lx, S.Ly, S.rx.data(), S.ry.data(), R.c, R.amp.data(), N, D);
-        }
-        PetscTime(&t1);
-        if (verbose) printf("  * Dynamical correlations: %lld reference sites, %lld Lanczos steps per run with the basis kept, %lld MatMults on %lld states, images in chunks of %lld, tDsfSites %.6f s, of it the Lanczos runs %.6f s\n", LLD(runs.size()), LLD(K), LLD(matmults), LLD(n), LLD(chunk), t1 - t0, t_runs);
-        ierr = dsf_sites_file.BeginDynamical(data_dir + "DynamicalCorrelations.json", GlobIdx, LoopTypeName(), (double)E0, S.norm); CHKERRQ(ierr);
-        FILE* fp = dsf_sites_file.fp;
-        fprintf(fp, ", \"Steps\": %lld, \"tDsfSites\": %.9g, \"MatMults\": %lld,\n   \"Sites\": [\n", LLD(K), t1 - t0, LLD(matmults));
-        for (size_t ir = 0; ir < runs.size(); ++ir) {
-            const Run& R = runs[ir];
-            const PetscInt D = R.done;
-            dsf_sites_file.OpenSite(R.c, S.rx[(size_t)R.c], S.ry[(size_t)R.c], R.norm2);
-            fprintf(fp, ", \"StepsDone\": %d,\n   \"Alpha\": ", (int)R.done);
-            dsf_sites_file.Row(R.alpha); fprintf(fp, ",\n   \"Beta\": "); dsf_sites_file.Row(R.beta); fprintf(fp, ",\n   \"Poles\": "); dsf_sites_file.Row(R.poles);
-            fprintf(fp, ",\n   \"Static\": "); dsf_sites_file.Row(R.stat); fprintf(fp, ",\n");
-            dsf_sites_file.Table("Amplitudes", R.amp, N, D, ",\n"); dsf_sites_file.Table("Sqw", R.sqw, M, D, ir + 1 < runs.size() ? "},\n" : "}\n");
-        }
-        fprintf(fp, "   ]}");
-        fflush(fp);
-        return 0;
-    }
-
-    /** -dsf_cheb c0,c1,... (engine extension): the Chebyshev moments of the real-space dynamical correlations of the ground state,
-            mu_n^{ic} = < Sz_i psi , T_n(Ht) Sz_c psi > / <psi|psi>,   Ht = (H - Centre) / HalfWidth,   for ALL sites i,
-        from one dmrgx_kron_chebyshev_moments run per reference site c: the three-term recursion t_{n+1} = 2 Ht t_n - t_{n-1} needs two
-        earlier vectors, no kept basis and no reorthogonalisation, so its cost is linear in the number of moments where -dsf_sites
-        grows with the square.  The images u_i = Sz_i psi of all N sites (SzFrame::Images, lattice order) stay on the device for
-        the whole measurement -- N x N_sb doubles, refused with PETSC_ERR_MEM if they do not fit --; row c is the start vector of run
-        c, and the library takes <u_i, t_n> of all i with one Gram call per 16 vectors.
-        The window must contain the spectrum of the superblock Hamiltonian.  Unless -dsf_cheb_window lo,hi gives it, it is found once
-        per measurement: -dsf_cheb_bound_steps Lanczos steps (dmrgx_kron_lanczos_coeffs) from a fixed pseudo-random vector give the top
-        Ritz value and its residual bound, E0 is the bottom (ChebyshevWindow, Measurements.hpp).  Should the window fail to hold, the
-        library's guard ends the run: StepsDone < Steps in the record and a warning here, not an error.
-        Moments (N x (D + 1), lattice numbering), their lattice Fourier transform MomentsQ[q][n] = sum_i cos(q . (r_i - r_c))
-        Moments[i][n] (row nx Ly + ny) and Diag[m] = mu_m^{cc}, m <= 2D (the doubling identities), D = StepsDone.  With -dsf_cheb_omega
-        w0,w1,nw also SqwGrid[q][k] = ChebyshevJackson(MomentsQ[q], D + 1, x_k) / HalfWidth at x_k = (w_k + E0 - Centre) / HalfWidth:
-        (1/N) sum_c SqwGrid is the Jackson-broadened S^zz(q, w), non-negative and free of ghosts; its resolution is about
-        pi HalfWidth / (D + 1).  The caveats of -dsf_sites (one site is an estimator; bases optimised for the ground state) apply.
-        One rank only (refused at start-up otherwise). */
-    PetscErrorCode CalculateChebyshevCorrelations(KronBlocks_t& KronBlocks, const Vec& gsv_r, Mat& H, PetscScalar E0)
-    {
-        PetscLogDouble t0, t1;
-        PetscTime(&t0);
-        dmrgx_host::SzFrame S;
-        PetscErrorCode ierr = S.Init(KronBlocks, num_sites, Ham, gsv_r, "Chebyshev correlations"); CHKERRQ(ierr);
-        const PetscInt N = S.F.N, M = S.M, K = dsf_cheb_steps;
-        const int64_t n = S.n, ld = S.ld;
-        const std::vector<double>* omega = dsf_cheb_have_omega ? &dsf_cheb_omega : nullptr;
-        /* the images of all sites, row s = Sz_s psi */
-        std::unique_ptr<dmrgx_host::DevBuffer> U;
-        ierr = S.AllImages(U, n); CHKERRQ(ierr);
-
-        /* the window */
-        const double e0 = (double)E0;
-        dmrgx_host::ChebyshevSpectralWindow W;
-        ierr = FindChebyshevWindow(H, n, &e0, "Chebyshev correlations", W); CHKERRQ(ierr);
-        PetscInt matmults = W.bound_steps;
-
-        std::vector<dmrgx_host::MomentRun> runs(dsf_cheb_sites.size());
-        std::vector<double> cross;
-        double t_runs = 0.0;
-        for (size_t ir = 0; ir < runs.size(); ++ir) {
-            dmrgx_host::MomentRun& R = runs[ir];
-            R.c = dsf_cheb_sites[ir];
-            ierr = dmrgx_host::ChebyshevMomentRun(H->plan, U->dev_ro(), ld, N, W, K, S.norm, cross, R, verbose ? &t_runs : nullptr); CHKERRQ(ierr);
-            matmults += K;
-            dmrgx_host::WarnLeftWindow("-dsf_cheb", nullptr, "site", R, W, K);
-            R.momq = dmrgx_host::SiteCosineSum(S.Lx, S.Ly, S.rx.data(), S.ry.data(), R.c, R.mom.data(), N, R.done + 1);
-            if (omega) R.grid = dmrgx_host::ChebyshevGrid(R.momq, R.done + 1, *omega, e0, W.centre, W.half_width);
-        }
-        PetscTime(&t1);
-        if (verbose) printf("  * Chebyshev correlations: %lld reference sites, %lld steps per run, window [%.6f, %.6f] from %lld Lanczos steps, %lld MatMults on %lld states, tDsfCheb %.6f s, of it the Chebyshev runs %.6f s\n",
-                            LLD(runs.size()), LLD(K), W.centre - W.half_width, W.centre + W.half_width, LLD(W.bound_steps), LLD(matmults), LLD(n), t1 - t0, t_runs);
-        ierr = dsf_cheb_file.BeginDynamical(data_dir + "ChebyshevMoments.json", GlobIdx, LoopTypeName(), e0, S.norm); CHKERRQ(ierr);
-        FILE* fp = dsf_cheb_file.fp;
-        fprintf(fp, ", \"Steps\": %lld, \"Centre\": %.17g, \"HalfWidth\": %.17g, \"BoundSteps\": %lld, \"ThetaMax\": %.17g, \"Residual\": %.17g, \"tDsfCheb\": %.9g, \"MatMults\": %lld,\n",
-                LLD(K), W.centre, W.half_width, LLD(W.bound_steps), W.theta_max, W.residual, t1 - t0, LLD(matmults));
-        dsf_cheb_file.Omega(omega);
-        fprintf(fp, "   \"Sites\": [\n");
-        for (size_t ir = 0; ir < runs.size(); ++ir) {
-            const dmrgx_host::MomentRun& R = runs[ir];
-            dsf_cheb_file.OpenSite(R.c, S.rx[(size_t)R.c], S.ry[(size_t)R.c], R.norm2);
-            fprintf(fp, ", \"StepsDone\": %d", (int)R.done);
-            dsf_cheb_file.Moments(R, N, M, omega, ir + 1 < runs.size() ? "},\n" : "}\n");
-        }
-        fprintf(fp, "   ]}");
-        fflush(fp);
-        return 0;
-    }
-
-    /** The window of a Chebyshev expansion on the planned Hamiltonian of n states, for -dsf_cheb, -dsf_dimer and -dsf_pm: -dsf_cheb_window lo,hi as given
-        (bound_steps 0, theta_min = lo, theta_max = hi), else from -dsf_cheb_bound_steps Lanczos steps from a fixed pseudo-random vector (ChebyshevBoundRun):
-        above the known bottom *E0 (ChebyshevWindow, Measurements.hpp), or, E0 null, a sector whose bottom is not known (ChebyshevWindowTwoSided). */
-    PetscErrorCode FindChebyshevWindow(Mat& H, int64_t n, const double* E0, const std::string& name, dmrgx_host::ChebyshevSpectralWindow& W)
-    {
-        const double lo = dsf_cheb_window[0], hi = dsf_cheb_window[1];
-        if (dsf_cheb_have_window) { W = dmrgx_host::ChebyshevSpectralWindow{0.5 * (lo + hi), 0.5 * (hi - lo), lo, hi, 0.0, 0.0, 0, true}; return 0; }
-        std::vector<double> a, b;
-        int32_t done = 0;
-        PetscErrorCode ierr = ChebyshevBoundRun(H, n, a, b, done); CHKERRQ(ierr);
-        W = E0 ? dmrgx_host::ChebyshevWindow(*E0, a, b, done) : dmrgx_host::ChebyshevWindowTwoSided(a, b, done);
-        W.bound_steps = dsf_cheb_bound_steps;
-        if (!W.ok) SETERRQ2(mpi_comm, 1, "%s: no spectral window from %d Lanczos steps.", name.c_str(), (int)done);
-        return 0;
-    }
-
-    /** alpha, beta and the steps done of -dsf_cheb_bound_steps Lanczos steps (dmrgx_kron_lanczos_coeffs) on the planned Hamiltonian of n states from
-        a fixed pseudo-random vector: what ChebyshevWindow and ChebyshevWindowTwoSided read. */
-    PetscErrorCode ChebyshevBoundRun(Mat& H, int64_t n, std::vector<double>& a, std::vector<double>& b, int32_t& done)
-    {
-        const PetscInt B = dsf_cheb_bound_steps;
-        dmrgx_host::DevBuffer r((size_t)n);
-        {   /* uniform(-1, 1) from a fixed seed, by integer arithmetic on the generator's 64 bits: the same vector everywhere */
-            std::mt19937_64 gen(0x63686562ull);
-            double* h = r.host();
-            for (int64_t e = 0; e < n; ++e) h[e] = (double)(gen() >> 11) * (2.0 / 9007199254740992.0) - 1.0;
-        }
-        a.assign((size_t)B, 0.0); b.assign((size_t)B, 0.0);
-        double r2 = 0.0; done = 0;
-        if (dmrgx_kron_lanczos_coeffs(H->plan, r.dev_ro(), (int32_t)B, 0.0, &r2, a.data(), b.data(), &done, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_lanczos_coeffs: %s", dmrgx_last_error());
-        return 0;
-    }
-
-    /** -dsf_pm c0,c1,... (engine extension): the Chebyshev moments of the transverse dynamical correlations of the ground state,
-            mu_n^{ic} = < O_i psi , T_n(Ht) O_c psi > / <psi|psi>,   Ht = (H' - Centre) / HalfWidth,   for ALL sites i,
-        in two channels: "MinusPlus", O = S^+, the response < S^-_i delta(w - H' + E0) S^+_c >, and "PlusMinus", O = S^- (Sp read
-        transposed), < S^+_i ... S^-_c > -- the magnons of an XXZ model or of a magnetised target, which S^zz (-dsf_cheb) does not hold.
-        O psi lives in the total-Sz sector qn_sector + 1 (- 1), so H' is the superblock Hamiltonian of THAT sector: per channel a
-        KronBlocks_t of the neighbouring sector over the same two blocks, the images of all N sites written in its layout
-        (SzFrame::AllImages, dmrgx_kron_term_apply_to) -- N x N_sb' doubles, refused with PETSC_ERR_MEM if they do not fit --, its plan
-        (KronSumConstruct with the settings of the ground-state plan), and one dmrgx_kron_chebyshev_moments run per reference site.  The
-        measurement runs after the ground-state plan is destroyed and destroys each plan before the next: one plan is resident at a time.
-        The window is -dsf_cheb_window lo,hi as given (ThetaMin = lo, ThetaMax = hi), else from -dsf_cheb_bound_steps Lanczos steps on
-        H' from the fixed pseudo-random vector of FindChebyshevWindow, both ends from the Ritz values (ChebyshevWindowTwoSided: the
-        bottom of another sector is not known from E0).  Should the window fail to hold, the library's guard ends the run: StepsDone <
-        Steps in the record and a warning here, not an error.  An empty neighbouring sector (a fully polarised target) gives a record
-        with States 0, no MatMults and StepsDone 0 for every site.
-        One record per measurement and channel in TransverseDynamics.json; Moments, MomentsQ, Diag and SqwGrid as in
-        ChebyshevMoments.json, energies measured from E0 of the target sector: (1/N) sum_c SqwGrid is the Jackson-broadened S^-+(q, w)
-        (S^+-(q, w)), non-negative.  The caveats of -dsf_sites apply, and one more: the bases of the blocks are optimised for the ONE
-        target state, not for the states of the neighbouring sector (single-target DMRG) -- exact while nothing is truncated, an
-        approximation that m controls otherwise.  One rank only (refused at start-up otherwise). */
-    PetscErrorCode CalculateTransverseDynamics(KronBlocks_t& KronBlocks, const Vec& gsv_r, const std::vector<Hamiltonians::Term>& Terms, PetscScalar E0)
-    {
-        PetscErrorCode ierr;
-        const PetscInt K = dsf_cheb_steps;
-        for (int channel = 0; channel < 2; ++channel) {
-            PetscLogDouble t0, t1;
-            PetscTime(&t0);
-            const char* cname = channel == 0 ? "MinusPlus" : "PlusMinus";
-            const PetscReal sector = qn_sector + (channel == 0 ? 1.0 : -1.0);
-            dmrgx_host::SzFrame S;
-            ierr = S.Init(KronBlocks, num_sites, Ham, gsv_r, "Transverse dynamics", channel == 0 ? OpSp : OpSm); CHKERRQ(ierr);
-            const PetscInt N = S.F.N, M = S.M;
-            KronBlocks_t KB1(KronBlocks.LeftBlockRefMod(), KronBlocks.RightBlockRefMod(), {sector}, NULL, GlobIdx);
-            const int64_t n1 = KB1.NumStates(), ld1 = n1 + (n1 & 1);
-
-            const std::vector<double>* omega = dsf_cheb_have_omega ? &dsf_cheb_omega : nullptr;
-            std::vector<dmrgx_host::MomentRun> runs(dsf_pm_sites.size());
-            for (size_t ir = 0; ir < runs.size(); ++ir) runs[ir].c = dsf_pm_sites[ir];
-            PetscInt matmults = 0;
-            dmrgx_host::ChebyshevSpectralWindow W;
-            if (n1 > 0) {
-                /* the images of all sites in the layout of KB1, row s = O_s psi */
-                std::vector<int32_t> out_il, out_ir;
-                for (PetscInt k = 0; k < KB1.size(); ++k) { out_il.push_back((int32_t)KB1.LeftIdx(k)); out_ir.push_back((int32_t)KB1.RightIdx(k)); }
-                std::unique_ptr<dmrgx_host::DevBuffer> U;
-                ierr = S.AllImages(U, n1, &out_il, &out_ir); CHKERRQ(ierr);
-                /* the plan of the neighbouring sector */
-                Mat H1 = nullptr;
-                ierr = KB1.KronSumSetRedistribute(PETSC_TRUE); CHKERRQ(ierr);
-                ierr = KB1.KronSumSetToleranceFromOptions(); CHKERRQ(ierr);
-                ierr = KB1.KronSumSetShellMatrix(do_shell); CHKERRQ(ierr);
-                ierr = KB1.KronSumConstruct(Terms, H1); CHKERRQ(ierr);
-                if (!H1) SETERRQ(mpi_comm, 1, "Transverse dynamics: H is null.");
-                /* the window: the bottom of this sector is not known */
-                ierr = FindChebyshevWindow(H1, n1, nullptr, std::string("Transverse dynamics (") + cname + ")", W); CHKERRQ(ierr);
-                matmults = W.bound_steps;
-                std::vector<double> cross;
-                for (dmrgx_host::MomentRun& R : runs) {
-                    ierr = dmrgx_host::ChebyshevMomentRun(H1->plan, U->dev_ro(), ld1, N, W, K, S.norm, cross, R, nullptr); CHKERRQ(ierr);
-                    matmults += K;
-                    if (R.norm2 == 0.0) printf("  * -dsf_pm (%s): the image of site %lld is zero in the bases of the blocks; no run.\n", cname, LLD(R.c));
-                    else dmrgx_host::WarnLeftWindow("-dsf_pm", cname, "site", R, W, K);
-                    R.momq = dmrgx_host::SiteCosineSum(S.Lx, S.Ly, S.rx.data(), S.ry.data(), R.c, R.mom.data(), N, R.done + 1);
-                    if (omega) R.grid = dmrgx_host::ChebyshevGrid(R.momq, R.done + 1, *omega, (double)E0, W.centre, W.half_width);
-                }
-                ierr = MatDestroy_KronSumShell(&H1); CHKERRQ(ierr);
-                ierr = MatDestroy(&H1); CHKERRQ(ierr);
-            }                                                       /* (the images go back to the pool here) */
-            PetscTime(&t1);
-            if (verbose) printf("  * Transverse dynamics (%s): sector %g, %lld reference sites, %lld steps per run, window [%.6f, %.6f] from %lld Lanczos steps, %lld MatMults on %lld states, tDsfPm %.6f s\n",
-                                cname, (double)sector, LLD(runs.size()), LLD(K), W.centre - W.half_width, W.centre + W.half_width, LLD(W.bound_steps), LLD(matmults), LLD(n1), t1 - t0);
-            ierr = dsf_pm_file.BeginDynamical(data_dir + "TransverseDynamics.json", GlobIdx, LoopTypeName(), (double)E0, S.norm); CHKERRQ(ierr);
-            FILE* fp = dsf_pm_file.fp;
-            fprintf(fp, ", \"Channel\": \"%s\", \"Sector\": %.17g, \"States\": %lld, \"Steps\": %lld, \"Centre\": %.17g, \"HalfWidth\": %.17g, \"BoundSteps\": %lld, \"ThetaMin\": %.17g, \"ThetaMax\": %.17g, \"tDsfPm\": %.9g, \"MatMults\": %lld,\n",
-                    cname, (double)sector, LLD(n1), LLD(K), W.centre, W.half_width, LLD(W.bound_steps), W.theta_min, W.theta_max, t1 - t0, LLD(matmults));
-            dsf_pm_file.Omega(omega);
-            fprintf(fp, "   \"Sites\": [\n");
-            for (size_t ir = 0; ir < runs.size(); ++ir) {
-                const dmrgx_host::MomentRun& R = runs[ir];
-                const char* end = ir + 1 < runs.size() ? "},\n" : "}\n";
-                dsf_pm_file.OpenSite(R.c, S.rx[(size_t)R.c], S.ry[(size_t)R.c], R.norm2);
-                fprintf(fp, ", \"StepsDone\": %d", (int)R.done);
-                if (n1 == 0) fprintf(fp, "%s", end);                       /* no run: no moments */
-                else dsf_pm_file.Moments(R, N, M, omega, end);
-            }
-            fprintf(fp, "   ]}");
-            fflush(fp);
-        }
-        return 0;
-    }
-
-    /** -dsf_dimer b0,b1,... (engine extension): the Chebyshev moments of the dynamical dimer correlations of the ground state,
-            mu_n^{bc} = < dD_b psi , T_n(Ht) dD_c psi > / <psi|psi>,   dD_b = D_b - <D_b>,   D_b = S_i . S_j,   Ht = (H - Centre) / HalfWidth,
-        for ALL nearest-neighbour bonds b, from one dmrgx_kron_chebyshev_moments run per reference bond c (its index in Bonds, the order of
-        DimerBonds(Ham) and of DimerCorrelations.json): the singlet channel -- valence-bond order against a spin liquid, what Raman
-        scattering sees -- where -dsf_cheb measures the spin channel.  The images D_b psi of all nb bonds (DimerFrame::Images: the bond
-        operators and terms of -corr_dimer) are written into one device family, and ONE dmrgx_vec_project_out call removes psi from all
-        of them: <D_b> is about -0.3 where <Sz_i> vanishes, and its delta peak at w = 0, far heavier than the inelastic part, would be
-        smeared by the Jackson kernel over the window where the singlet gap is.  The coefficients of that call are D[b] = <D_b> =
-        <psi|D_b|psi> / <psi|psi>.  Row c of the family is the start vector of run c, the whole family its U.  The window is found as for
-        -dsf_cheb (FindChebyshevWindow: -dsf_cheb_window, or -dsf_cheb_bound_steps Lanczos steps); a run that leaves it ends with
-        StepsDone < Steps and a warning.
-        Per reference bond: Norm2 = <dD_c psi, dD_c psi>; Elastic = <psi, dD_c psi> / sqrt(Norm Norm2), what is left of the elastic line
-        (rounding); Diag[m] = mu_m^{cc}, m <= 2 StepsDone; Moments (nb x (StepsDone + 1), Moments[:, 0] = Connected[:, c] of -corr_dimer);
-        MomentsQ[q][n] = sum over the bonds b of c's orientation of cos(q . (r_b - r_c)) Moments[b][n] at their Positions (row nx Ly + ny);
-        with -dsf_dimer_omega w0,w1,nw SqwGrid[q][k] = ChebyshevJackson(MomentsQ[q], StepsDone + 1, x_k) / HalfWidth at
-        x_k = (w_k + E0 - Centre) / HalfWidth: averaged over the reference bonds of one orientation the Jackson-broadened dimer structure
-        factor S_a(q, w), non-negative.  MatMults = BoundSteps + refs * Steps.
-        Memory on the device: the nb images (nb x N_sb doubles, refused with PETSC_ERR_MEM if they do not fit) plus the 34 vectors of the
-        moment run.  The block bases are ground-state bases (the caveat of -dsf_sites).  One rank only (refused at start-up otherwise). */
-    PetscErrorCode CalculateDimerDynamics(KronBlocks_t& KronBlocks, const Vec& gsv_r, Mat& H, PetscScalar E0)
-    {
-        PetscLogDouble t0, t1;
-        PetscTime(&t0);
-        dmrgx_host::DimerFrame B;
-        PetscErrorCode ierr = B.Init(KronBlocks, num_sites, Ham, gsv_r, "Dimer dynamics"); CHKERRQ(ierr);
-        const PetscInt nb = B.nb, K = dsf_dimer_steps, Lx = Ham.Lx(), Ly = Ham.Ly(), M = Lx * Ly;
-        const int64_t n = B.n, ld = n + (n & 1);
-        /* the images of all bonds, row b = D_b psi, then (D_b - <D_b>) psi */
-        std::unique_ptr<dmrgx_host::DevBuffer> U;
-        try { U.reset(new dmrgx_host::DevBuffer((size_t)(nb * ld), dmrgx_host::DevBuffer::device_only_t{})); }
-        catch (const std::exception& e) { SETERRQ4(mpi_comm, PETSC_ERR_MEM, "Dimer dynamics: no memory for the images of %lld bonds x %lld states (%.3f GB): %s", LLD(nb), LLD(n), (double)(nb * ld) * 8e-9, e.what()); }
-        ierr = B.Images(U->dev_uninitialised(), ld); CHKERRQ(ierr);
-        std::vector<double> D((size_t)nb, 0.0);
-        double norm = 0.0;
-        if (dmrgx_vec_project_out((int32_t)nb, n, U->dev_uninitialised(), ld, B.psi, D.data(), &norm, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_vec_project_out: %s", dmrgx_last_error());
-        if (!(norm > 0.0)) SETERRQ(mpi_comm, 1, "Dimer dynamics: the ground state has no norm.");
-
-        const double e0 = (double)E0;
-        const std::vector<double>* omega = dsf_dimer_have_omega ? &dsf_dimer_omega : nullptr;
-        dmrgx_host::ChebyshevSpectralWindow W;
-        ierr = FindChebyshevWindow(H, n, &e0, "Dimer dynamics", W); CHKERRQ(ierr);
-        PetscInt matmults = W.bound_steps;
-
-        const dmrgx_host::OrientedBonds oriented[2] = {dmrgx_host::BondsOfOrientation(B.bonds, 'x'), dmrgx_host::BondsOfOrientation(B.bonds, 'y')};
-        std::vector<dmrgx_host::MomentRun> runs(dsf_dimer_bonds.size());
-        std::vector<double> cross;
-        double t_runs = 0.0;
-        for (size_t ir = 0; ir < runs.size(); ++ir) {
-            dmrgx_host::MomentRun& R = runs[ir];
-            R.c = dsf_dimer_bonds[ir];
-            ierr = dmrgx_host::ChebyshevMomentRun(H->plan, U->dev_ro(), ld, nb, W, K, norm, cross, R, verbose ? &t_runs : nullptr); CHKERRQ(ierr);
-            matmults += K;
-            double overlap = 0.0;
-            if (dmrgx_dot(n, B.psi, U->dev_ro() + R.c * ld, &overlap, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
-            R.elastic = R.norm2 > 0.0 ? overlap / std::sqrt(norm * R.norm2) : 0.0;
-            dmrgx_host::WarnLeftWindow("-dsf_dimer", nullptr, "bond", R, W, K);
-            /* the cosine sum over the bonds of c's orientation, from c */
-            const PetscInt nm = R.done + 1;
-            const dmrgx_host::OrientedBonds& O = oriented[B.bonds[(size_t)R.c].orient == 'x' ? 0 : 1];
-            const PetscInt no = (PetscInt)O.of.size(), c_in = (PetscInt)(std::find(O.of.begin(), O.of.end(), R.c) - O.of.begin());
-            std::vector<double> sel((size_t)(no * nm));
-            for (PetscInt k = 0; k < no; ++k) std::copy(R.mom.begin() + O.of[(size_t)k] * nm, R.mom.begin() + (O.of[(size_t)k] + 1) * nm, sel.begin() + k * nm);
-            R.momq = dmrgx_host::SiteCosineSum(Lx, Ly, O.x.data(), O.y.data(), c_in, sel.data(), no, nm);
-            if (omega) R.grid = dmrgx_host::ChebyshevGrid(R.momq, nm, *omega, e0, W.centre, W.half_width);
-        }
-        PetscTime(&t1);
-        if (verbose) printf("  * Dimer dynamics: %lld reference bonds of %lld, %lld steps per run, window [%.6f, %.6f] from %lld Lanczos steps, %lld MatMults on %lld states, tDimerDyn %.6f s, of it the Chebyshev runs %.6f s\n",
-                            LLD(runs.size()), LLD(nb), LLD(K), W.centre - W.half_width, W.centre + W.half_width, LLD(W.bound_steps), LLD(matmults), LLD(n), t1 - t0, t_runs);
-        ierr = dsf_dimer_file.BeginDynamical(data_dir + "DimerDynamics.json", GlobIdx, LoopTypeName(), e0, norm); CHKERRQ(ierr);
-        FILE* fp = dsf_dimer_file.fp;
-        fprintf(fp, ", \"Steps\": %lld, \"Centre\": %.17g, \"HalfWidth\": %.17g, \"BoundSteps\": %lld, \"ThetaMax\": %.17g, \"Residual\": %.17g, \"tDimerDyn\": %.9g, \"MatMults\": %lld,\n",
-                LLD(K), W.centre, W.half_width, LLD(W.bound_steps), W.theta_max, W.residual, t1 - t0, LLD(matmults));
-        dsf_dimer_file.BondHeader(B.bonds, D);
-        dsf_dimer_file.Omega(omega);
-        fprintf(fp, "   \"RefBonds\": [\n");
-        for (size_t ir = 0; ir < runs.size(); ++ir) {
-            const dmrgx_host::MomentRun& R = runs[ir];
-            const dmrgx_host::DimerBond& bc = B.bonds[(size_t)R.c];
-            fprintf(fp, "   {\"Bond\": %lld, \"Sites\": [%lld, %lld], \"Orientation\": \"%c\", \"Norm2\": %.17g, \"Elastic\": %.17g, \"StepsDone\": %d",
-                    LLD(R.c), LLD(bc.i), LLD(bc.j), bc.orient, R.norm2, R.elastic, (int)R.done);
-            dsf_dimer_file.Moments(R, nb, M, omega, ir + 1 < runs.size() ? "},\n" : "}\n");
-        }
-        fprintf(fp, "   ]}");
-        fflush(fp);
-        return 0;
-    }
-
-    /** -dsf_cv c0,c1,... (engine extension): the real-space dynamical correlations of the ground state at given complex frequencies,
-            G_ic(w_k + i eta) = < Sz_i psi , 1 / (E0 + w_k + i eta - H) Sz_c psi > / <psi|psi>,   for ALL sites i,
-        by the correction-vector method: one dmrgx_kron_correction_vector call per reference site c and frequency w_k of -dsf_cv_omega
-        solves [(H - sigma)^2 + eta^2] Y = -eta Sz_c psi, sigma = E0 + w_k, by conjugate gradients on the device to the relative residual
-        -dsf_cv_tol (at most -dsf_cv_maxit iterations, two MatMults each), forms X = (H - sigma) Y / eta and takes the overlaps of both with
-        the images of all sites.  Unlike -dsf, -dsf_sites and -dsf_cheb the error at each frequency is controlled -- |ImG - exact| <=
-        |u| |v| Residual / eta -- and the broadening is a true Lorentzian of half width eta.  No warm start between frequencies.
-        The images u_i = Sz_i psi of all N sites (SzFrame::Images, lattice order) stay on the device for the whole measurement, as
-        for -dsf_cheb; beside them Y, X and the four pool vectors of the solver: N + 6 vectors of N_sb doubles.
-        The record: ImG[i][k], ReG[i][k] (the overlaps over <psi|psi>), Aw[i][k] = -ImG / pi, SqwGrid[q][k] = sum_i cos(q . (r_i - r_c))
-        Aw[i][k] (SiteCosineSum, row nx Ly + ny; (1/N) sum_c SqwGrid is the Lorentzian-broadened S^zz(q, w)), Iterations[k], Converged[k]
-        and Residual[k], the true residual |b - A Y| / |b| of the returned Y.  A frequency that did not converge within -dsf_cv_maxit is
-        written as it is, with a warning here.  The caveats of -dsf_sites apply: the block bases are optimised for the ground state alone
-        -- no correction vector is targeted in the density matrix.  One rank only (refused at start-up otherwise). */
-    PetscErrorCode CalculateCorrectionVectors(KronBlocks_t& KronBlocks, const Vec& gsv_r, Mat& H, PetscScalar E0)
-    {
-        PetscLogDouble t0, t1;
-        PetscTime(&t0);
-        dmrgx_host::SzFrame S;
-        PetscErrorCode ierr = S.Init(KronBlocks, num_sites, Ham, gsv_r, "Correction vectors"); CHKERRQ(ierr);
-        const PetscInt N = S.F.N, M = S.M, nw = (PetscInt)dsf_cv_omega.size();
-        const int64_t n = S.n, ld = S.ld;
-        /* the images of all sites, row s = Sz_s psi, and the two vectors of a solve */
-        std::unique_ptr<dmrgx_host::DevBuffer> U, YX;
-        try {
-            U.reset(new dmrgx_host::DevBuffer((size_t)(N * ld), dmrgx_host::DevBuffer::device_only_t{}));
-            YX.reset(new dmrgx_host::DevBuffer((size_t)(2 * ld), dmrgx_host::DevBuffer::device_only_t{}));
-        }
-        catch (const std::exception& e) { SETERRQ3(mpi_comm, PETSC_ERR_MEM, "Correction vectors: no memory for the images of %lld sites and two vectors of %lld states (%.3f GB): %s", LLD(N), LLD(n), (double)((N + 2) * ld) * 8e-9, e.what()); }
-        ierr = S.Images(S.op_of.data(), N, U->dev_uninitialised(), ld); CHKERRQ(ierr);
-
-        struct Run { PetscInt c = 0; double norm2 = 0.0; std::vector<double> iterations, converged, residual, im, re, aw, grid; };
-        std::vector<Run> runs(dsf_cv_sites.size());
-        std::vector<double> im((size_t)N), re((size_t)N);
-        double* Yd = YX->dev_uninitialised();
-        double* Xd = Yd + ld;
-        PetscInt matmults = 0, iterations = 0;
-        for (size_t ir = 0; ir < runs.size(); ++ir) {
-            Run& R = runs[ir];
-            R.c = dsf_cv_sites[ir];
-            R.iterations.assign((size_t)nw, 0.0); R.converged.assign((size_t)nw, 0.0); R.residual.assign((size_t)nw, 0.0);
-            R.im.assign((size_t)(N * nw), 0.0); R.re.assign((size_t)(N * nw), 0.0); R.aw.assign((size_t)(N * nw), 0.0);
-            for (PetscInt k = 0; k < nw; ++k) {
-                dmrgx_cv_stats cs;
-                if (dmrgx_kron_correction_vector(H->plan, U->dev_ro() + R.c * ld, (double)E0 + dsf_cv_omega[(size_t)k], dsf_cv_eta, dsf_cv_tol, (int32_t)dsf_cv_maxit, 0, Yd, Xd,
-                                                 (int32_t)N, U->dev_ro(), ld, &R.norm2, im.data(), re.data(), &cs, nullptr))
-                    SETERRQ1(mpi_comm, 1, "dmrgx_kron_correction_vector: %s", dmrgx_last_error());
-                matmults += cs.n_matvec; iterations += cs.iterations;
-                if (!cs.converged) printf("  * WARNING: -dsf_cv: site %lld, w = %.6f: not converged after %d iterations (residual %.3e, tol %.3e%s); the record holds the last iterate.\n",
-                                          LLD(R.c), dsf_cv_omega[(size_t)k], (int)cs.iterations, cs.true_residual, dsf_cv_tol, cs.dead ? ", the iteration broke down" : "");
-                R.iterations[(size_t)k] = (double)cs.iterations; R.converged[(size_t)k] = (double)cs.converged; R.residual[(size_t)k] = cs.true_residual;
-                for (PetscInt s = 0; s < N; ++s) {
-                    const size_t at = (size_t)(s * nw + k);
-                    R.im[at] = im[(size_t)s] / S.norm; R.re[at] = re[(size_t)s] / S.norm; R.aw[at] = -R.im[at] / (0.5 * dmrgx_host::two_pi);
-                }
-            }
-            R.grid = dmrgx_host::SiteCosineSum(S.Lx, S.Ly, S.rx.data(), S.ry.data(), R.c, R.aw.data(), N, nw);
-        }
-        PetscTime(&t1);
-        if (verbose) printf("  * Correction vectors: %lld reference sites x %lld frequencies, eta %.6f, %lld iterations, %lld MatMults on %lld states, tDsfCv %.6f s\n",
-                            LLD(runs.size()), LLD(nw), dsf_cv_eta, LLD(iterations), LLD(matmults), LLD(n), t1 - t0);
-        ierr = dsf_cv_file.BeginDynamical(data_dir + "CorrectionVectors.json", GlobIdx, LoopTypeName(), (double)E0, S.norm); CHKERRQ(ierr);
-        FILE* fp = dsf_cv_file.fp;
-        fprintf(fp, ", \"Eta\": %.17g, \"Tol\": %.17g, \"MaxIt\": %lld, \"tDsfCv\": %.9g, \"MatMults\": %lld,\n   \"Omega\": ", dsf_cv_eta, dsf_cv_tol, LLD(dsf_cv_maxit), t1 - t0, LLD(matmults));
-        dsf_cv_file.Row(dsf_cv_omega);
-        fprintf(fp, ",\n   \"Sites\": [\n");
-        for (size_t ir = 0; ir < runs.size(); ++ir) {
-            const Run& R = runs[ir];
-            dsf_cv_file.OpenSite(R.c, S.rx[(size_t)R.c], S.ry[(size_t)R.c], R.norm2);
-            fprintf(fp, ",\n   \"Iterations\": ");
-            dsf_cv_file.Row(R.iterations); fprintf(fp, ",\n   \"Converged\": ");
-            dsf_cv_file.Row(R.converged); fprintf(fp, ",\n   \"Residual\": ");
-            dsf_cv_file.Row(R.residual); fprintf(fp, ",\n");
-            dsf_cv_file.Table("ImG", R.im, N, nw, ",\n");
-            dsf_cv_file.Table("ReG", R.re, N, nw, ",\n");
-            dsf_cv_file.Table("Aw", R.aw, N, nw, ",\n");
-            dsf_cv_file.Table("SqwGrid", R.grid, M, nw, ir + 1 < runs.size() ? "},\n" : "}\n");
-        }
-        fprintf(fp, "   ]}");
-        fflush(fp);
-        return 0;
-    }
-
-    /** -corr_dimer 1 (engine extension): the dimer-dimer table < D_b D_b' > over all pairs of nearest-neighbour bonds, D_b = S_i . S_j
-        = Sz_i Sz_j + (Sp_i Sm_j + Sm_i Sp_j) / 2, its connected part and the dimer structure factors of the x and the y bonds, at every
-        measurement point.  < psi | D_b^T D_b' | psi > = < D_b psi , D_b' psi >: the whole table is ONE dmrgx_kron_term_gram call over the
-        bond images D_b psi -- vector 0 is psi itself (norm and < D_b >), vector 1 + b the image of bond b -- instead of a plan, a MatMult
-        and a dot product per pair of bonds.  The bond operators and the term list of every bond are DimerFrame's (Measurements.hpp),
-        which -dsf_dimer shares.  Site s of the right block is lattice site N - 1 - s.
-        DD[b][b'] is < psi | D_b^T D_b' | psi >: it equals < D_b D_b' > when nothing was truncated or the two bonds sit in different
-        blocks -- truncated operators of one block do not commute, the caveat of the SpSm table.  On several ranks every rank
-        computes the same table from the replicated psi (no collective); rank 0 writes one record per measurement to
-        DimerCorrelations.json. */
-    PetscErrorCode CalculateDimerCorrelations(KronBlocks_t& KronBlocks, const Vec& gsv_r)
-    {
-        PetscLogDouble t0, t1;
-        PetscTime(&t0);
-        dmrgx_host::DimerFrame B;
-        PetscErrorCode ierr = B.Init(KronBlocks, num_sites, Ham, gsv_r, "Dimer correlations"); CHKERRQ(ierr);
-        const std::vector<dmrgx_host::DimerBond>& bonds = B.bonds;
-        const PetscInt nb = B.nb, nv = nb + 1;
-        const int64_t bond_doubles = B.bond_doubles;
-        /* ---- the vectors: psi, then the image of every bond */
-        std::vector<double> G;
-        ierr = B.Gram(G); CHKERRQ(ierr);
-        const double norm = G[0];
-        std::vector<double> D((size_t)nb, 0.0), DD((size_t)(nb * nb), 0.0), Conn((size_t)(nb * nb), 0.0);
-        for (PetscInt b = 0; b < nb; ++b) {
-            D[(size_t)b] = G[(size_t)(1 + b)];
-            for (PetscInt c = 0; c < nb; ++c) DD[(size_t)(b * nb + c)] = G[(size_t)((1 + b) * nv + 1 + c)];
-        }
-        for (PetscInt b = 0; b < nb; ++b) for (PetscInt c = 0; c < nb; ++c) Conn[(size_t)(b * nb + c)] = DD[(size_t)(b * nb + c)] / norm - D[(size_t)b] * D[(size_t)c] / (norm * norm);
-        /* S_a(q) = (1/N_a) sum over the bonds b, b' of orientation a of cos(q . (r_b - r_b')) Connected[b][b'],  q = (2 pi nx / Lx, 2 pi ny / Ly) */
-        const PetscInt Lx = Ham.Lx(), Ly = Ham.Ly();
-        std::vector<double> Sq[2] = {std::vector<double>((size_t)(Lx * Ly), 0.0), std::vector<double>((size_t)(Lx * Ly), 0.0)};
-        for (int o = 0; o < 2; ++o) {
-            const dmrgx_host::OrientedBonds O = dmrgx_host::BondsOfOrientation(bonds, o == 0 ? 'x' : 'y');
-            if (O.of.empty()) continue;
-            std::vector<double> C;                                  /* Connected among the bonds of this orientation */
-            for (PetscInt b : O.of) for (PetscInt c : O.of) C.push_back(Conn[(size_t)(b * nb + c)]);
-            Sq[o] = dmrgx_host::LatticeFourier(Lx, Ly, O.x.data(), O.y.data(), C.data(), (PetscInt)O.of.size(), (double)O.of.size());
-        }
-        PetscTime(&t1);
-        if (!mpi_rank && verbose)
-            printf("  * Dimer correlations: %lld bonds, Gram of %lld vectors x %lld, %lld bytes of bond operators held, tDimer %.6f s\n", LLD(nb), LLD(nv), LLD(gsv_r->n), LLD(bond_doubles * (int64_t)sizeof(double)), t1 - t0);
-        if (mpi_rank) return 0;
-        ierr = dimer_file.Begin(data_dir + "DimerCorrelations.json"); CHKERRQ(ierr);
-        FILE* fp_dimer = dimer_file.fp;
-        fprintf(fp_dimer, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"tDimer\": %.9g, \"Norm\": %.15g,\n", LLD(GlobIdx), LoopTypeName(), t1 - t0, norm);
-        dimer_file.BondHeader(bonds, D);
-        dimer_file.Table("DD", DD, nb, nb, ",\n"); dimer_file.Table("Connected", Conn, nb, nb, ",\n"); dimer_file.Table("StructureFactorX", Sq[0], Lx, Ly, ",\n"); dimer_file.Table("StructureFactorY", Sq[1], Lx, Ly, "}");
-        fflush(fp_dimer);
-        return 0;
-    }
-
-    /** -corr_chiral 1 (engine extension): the table < chi_a chi_b > of the scalar chirality chi_ijk = S_i . (S_j x S_k) over all pairs of
-        triangles of the lattice's plaquettes, at every measurement point.  chi = i K with the real, antisymmetric
-          K_ijk = [ Sz_i (Sp_j Sm_k - Sm_j Sp_k) + Sz_j (Sp_k Sm_i - Sm_k Sp_i) + Sz_k (Sp_i Sm_j - Sm_i Sp_j) ] / 2,
-        so for the real psi < chi_a chi_b > = < K_a psi , K_b psi >: ONE dmrgx_kron_term_gram call over psi (vector 0: the norm and
-        K[a] = < psi , K_a psi >, zero in an exact basis and reported as the truncation diagnostic it is) and the images K_a psi.  The
-        triangles, their strings, the split at the cut and the composed operators are ChiralFrame's (Measurements.hpp).
-        CC[a][b] is < K_a psi , K_b psi >: it equals < chi_a chi_b > when nothing was truncated -- truncated operators of one block do
-        not commute, the caveat of the SpSm table.  PlaquetteCC[p][p'] sums CC over the four triangles of p and of p';
-        StructureFactor(q) = (1 / N_p) sum_pp' cos(q . (r_p - r_p')) PlaquetteCC[p][p'] / Norm over the plaquette positions.  One rank. */
-    PetscErrorCode CalculateChiralCorrelations(KronBlocks_t& KronBlocks, const Vec& gsv_r)
-    {
-        PetscLogDouble t0, t1;
-        PetscTime(&t0);
-        dmrgx_host::ChiralFrame B;
-        PetscErrorCode ierr = B.Init(KronBlocks, num_sites, Ham, gsv_r, "Chiral correlations"); CHKERRQ(ierr);
-        const PetscInt nt = B.nt, nv = nt + 1, np = (PetscInt)B.plaquettes.size();
-        std::vector<double> G;
-        ierr = B.Gram(G); CHKERRQ(ierr);
-        const double norm = G[0];
-        std::vector<double> K((size_t)nt, 0.0), CC((size_t)(nt * nt), 0.0), PCC((size_t)(np * np), 0.0);
-        for (PetscInt a = 0; a < nt; ++a) {
-            K[(size_t)a] = G[(size_t)(1 + a)];
-            for (PetscInt b = 0; b < nt; ++b) CC[(size_t)(a * nt + b)] = G[(size_t)((1 + a) * nv + 1 + b)];
-        }
-        for (PetscInt a = 0; a < nt; ++a) for (PetscInt b = 0; b < nt; ++b) PCC[(size_t)(B.triangles[(size_t)a].plaq * np + B.triangles[(size_t)b].plaq)] += CC[(size_t)(a * nt + b)];
-        const PetscInt Lx = Ham.Lx(), Ly = Ham.Ly();
-        std::vector<PetscInt> px, py;
-        for (const dmrgx_host::ChiralPlaquette& p : B.plaquettes) { px.push_back(p.x); py.push_back(p.y); }
-        std::vector<double> Sq((size_t)(Lx * Ly), 0.0);
-        if (np > 0) Sq = dmrgx_host::LatticeFourier(Lx, Ly, px.data(), py.data(), PCC.data(), np, norm * (double)np);
-        PetscTime(&t1);
-        if (!mpi_rank && verbose)
-            printf("  * Chiral correlations: %lld triangles, Gram of %lld vectors x %lld, %lld bytes of composed operators held, tChiral %.6f s\n", LLD(nt), LLD(nv), LLD(gsv_r->n), LLD(B.composed_doubles * (int64_t)sizeof(double)), t1 - t0);
-        if (mpi_rank) return 0;
-        ierr = chiral_file.Begin(data_dir + "ChiralCorrelations.json"); CHKERRQ(ierr);
-        FILE* fp = chiral_file.fp;
-        fprintf(fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"tChiral\": %.9g, \"Norm\": %.17g,\n", LLD(GlobIdx), LoopTypeName(), t1 - t0, norm);
-        fprintf(fp, "   \"Triangles\": [");
-        for (PetscInt a = 0; a < nt; ++a) fprintf(fp, "%s[%lld, %lld, %lld]", a ? ", " : "", LLD(B.triangles[(size_t)a].i), LLD(B.triangles[(size_t)a].j), LLD(B.triangles[(size_t)a].k));
-        fprintf(fp, "],\n   \"Kind\": [");
-        for (PetscInt a = 0; a < nt; ++a) fprintf(fp, "%s%d", a ? ", " : "", B.triangles[(size_t)a].kind);
-        fprintf(fp, "],\n   \"Position\": [");
-        for (PetscInt a = 0; a < nt; ++a) fprintf(fp, "%s[%lld, %lld]", a ? ", " : "", LLD(B.triangles[(size_t)a].x), LLD(B.triangles[(size_t)a].y));
-        fprintf(fp, "],\n   \"Side\": [");
-        for (PetscInt a = 0; a < nt; ++a) fprintf(fp, "%s%d", a ? ", " : "", B.side_of[(size_t)a]);
-        fprintf(fp, "],\n   \"Plaquettes\": [");
-        for (PetscInt p = 0; p < np; ++p) fprintf(fp, "%s[%lld, %lld, %lld, %lld]", p ? ", " : "", LLD(B.plaquettes[(size_t)p].s[0]), LLD(B.plaquettes[(size_t)p].s[1]), LLD(B.plaquettes[(size_t)p].s[2]), LLD(B.plaquettes[(size_t)p].s[3]));
-        fprintf(fp, "],\n   \"PlaquettePosition\": [");
-        for (PetscInt p = 0; p < np; ++p) fprintf(fp, "%s[%lld, %lld]", p ? ", " : "", LLD(B.plaquettes[(size_t)p].x), LLD(B.plaquettes[(size_t)p].y));
-        fprintf(fp, "],\n   \"K\": ");
-        chiral_file.Row(K); fprintf(fp, ",\n");
-        chiral_file.Table("CC", CC, nt, nt, ",\n"); chiral_file.Table("PlaquetteCC", PCC, np, np, ",\n"); chiral_file.Table("StructureFactor", Sq, Lx, Ly, "}");
-        fflush(fp);
+        if (mctx) { ierr = engine_measurements.RunAtCentre(*mctx, Ham); CHKERRQ(ierr); }      /* -corr_matrix, -corr_dimer, -corr_chiral */
         return 0;
     }
 
@@ -2442,7 +1655,7 @@ public:
             for (const Op& o : c.SysOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
             for (const Op& o : c.EnvOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
         }
-        if (use_corr_matrix || use_corr_dimer || use_corr_chiral || use_dsf || use_dsf_sites || use_dsf_cheb || use_dsf_cv || use_dsf_dimer || use_dsf_pm) corr_sites.assign((size_t)N, 1);      /* -corr_matrix, -corr_dimer, -corr_chiral, -dsf, -dsf_sites, -dsf_cheb, -dsf_cv, -dsf_dimer, -dsf_pm: Sz and Sp of every site of both centre blocks, on every rank */
+        if (engine_measurements.NeedsAllSiteOperators()) corr_sites.assign((size_t)N, 1);      /* Sz and Sp of every site of both centre blocks, on every rank */
         need_built = true;
         return 0;
     }
@@ -2512,44 +1725,6 @@ private:
     const char* LoopTypeName() const { return LoopType == WarmupStep ? "Warmup" : "Sweep"; }      /* "LoopType" in the record of a measurement */
 
     void PrintBlocks(const PetscInt& nsys, const PetscInt& nenv) const { printf("  [%lld]-* *-[%lld]\n", LLD(nsys), LLD(nenv)); }
-
-    /** A site-list option (-dsf_sites, -dsf_cheb, -dsf_cv c0,c1,...): on when present and not empty; then refused on more than one rank
-        (`what` has no collectives), and every site must be a lattice site.  With `count` (-dsf_dimer): a list of `noun`s out of [0, count). */
-    PetscErrorCode ReadSiteListOption(const char* option, const char* what, std::vector<PetscInt>& sites, PetscBool& use,
-                                      PetscInt count = -1, const char* noun = "site", const char* range = "the lattice sites in the numbering of To1D")
-    {
-        if (count < 0) count = num_sites;
-        PetscBool have_sites = PETSC_FALSE;
-        PetscInt nc = 4096;
-        sites.assign((size_t)nc, 0);
-        PetscErrorCode ierr = PetscOptionsGetIntArray(NULL, NULL, option, sites.data(), &nc, &have_sites); CHKERRQ(ierr);
-        sites.resize(have_sites ? (size_t)nc : 0);
-        use = (have_sites && nc > 0) ? PETSC_TRUE : PETSC_FALSE;
-        if (!use) return 0;
-        if (mpi_size > 1) SETERRQ3(mpi_comm, PETSC_ERR_SUP, "%s is not available on more than one rank (got %d): %s has no collectives.", option, (int)mpi_size, what);
-        for (PetscInt c : sites) if (c < 0 || c >= count) SETERRQ5(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "%s: %s %lld is outside [0, %lld), %s.", option, noun, LLD(c), LLD(count), range);
-        return 0;
-    }
-
-    /** A frequency grid w0,w1,nw (-dsf_cheb_omega, -dsf_cv_omega): `have` if the option is there, then `grid` or the refusal. */
-    PetscErrorCode ReadOmegaGridOption(const char* option, std::vector<double>& grid, PetscBool& have)
-    {
-        PetscInt no = 3;
-        PetscReal om[3] = {0.0, 0.0, 0.0};
-        PetscErrorCode ierr = PetscOptionsGetRealArray(NULL, NULL, option, om, &no, &have); CHKERRQ(ierr);
-        if (have && !dmrgx_host::OmegaGrid(om, no, grid)) SETERRQ2(mpi_comm, PETSC_ERR_ARG_WRONG, "%s needs w0,w1,nw: nw >= 1 frequencies from w0 to w1 (nw = 1: w0 = w1). Got %lld numbers.", option, LLD(no));
-        return 0;
-    }
-
-    /** -dsf_steps and -dsf_breakdown_tol, which -dsf and -dsf_sites share. */
-    PetscErrorCode ReadLanczosStepOptions()
-    {
-        PetscErrorCode ierr = PetscOptionsGetInt(NULL, NULL, "-dsf_steps", &dsf_steps, NULL); CHKERRQ(ierr);
-        if (dsf_steps < 1) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_steps must be at least 1. Got %lld.", LLD(dsf_steps));
-        ierr = PetscOptionsGetReal(NULL, NULL, "-dsf_breakdown_tol", &dsf_breakdown_tol, NULL); CHKERRQ(ierr);
-        if (!(dsf_breakdown_tol >= 0.0) || dsf_breakdown_tol >= 1.0) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "-dsf_breakdown_tol must lie in [0, 1). Got %g.", dsf_breakdown_tol);
-        return 0;
-    }
 
     PetscErrorCode SaveStepHeaders()
     {
@@ -2681,49 +1856,11 @@ private:
     PetscBool use_guess_overlap = PETSC_TRUE;   /* -wavefunction_guess_overlap 0: no start vector where the stored chain of bases is broken (round-2 behaviour) */
     PetscInt guesses_used = 0;
     PetscBool use_rdm_warm = PETSC_FALSE;       /* -rdm_warm_start: still recognised, does nothing (a line at start-up says so) */
-    PetscBool use_corr_matrix = PETSC_FALSE;    /* -corr_matrix 1: all-pairs tables through dmrgx_kron_op_gram, SpinCorrelations.json (CalculateCorrelationMatrix) */
-    dmrgx_host::JsonRecordFile spin_file{"%.15g"};      /* created at the first measurement with -corr_matrix, rank 0 only */
-    PetscBool use_corr_dimer = PETSC_FALSE;     /* -corr_dimer 1: dimer-dimer table over all bond pairs through dmrgx_kron_term_gram, DimerCorrelations.json (CalculateDimerCorrelations) */
-    dmrgx_host::JsonRecordFile dimer_file{"%.15g"};     /* created at the first measurement with -corr_dimer, rank 0 only */
-    PetscBool use_corr_chiral = PETSC_FALSE;    /* -corr_chiral 1: scalar-chirality table over all triangle pairs through dmrgx_secop_compose and dmrgx_kron_term_gram, ChiralCorrelations.json (CalculateChiralCorrelations) */
-    dmrgx_host::JsonRecordFile chiral_file{"%.17g"};    /* created at the first measurement with -corr_chiral */
-    PetscBool use_dsf = PETSC_FALSE;            /* -dsf 1: S^zz(q, w) by the Lanczos-vector method, DynamicalStructureFactor.json (CalculateDynamicalStructureFactor) */
-    std::vector<PetscInt> dsf_q;                /* -dsf_q: nx0, ny0, nx1, ny1, ... */
-    PetscInt dsf_steps = 100;                   /* -dsf_steps: Lanczos steps per run */
-    PetscReal dsf_breakdown_tol = 0.0;          /* -dsf_breakdown_tol: 0 = the library's default, 1e-7 */
-    static constexpr double dsf_no_weight = 1e-20; /* a part with |v|^2 <= dsf_no_weight <psi|psi> (rounding noise, as Sz_tot psi at q = 0) is recorded with StepsDone 0, without a run */
-    dmrgx_host::JsonRecordFile dsf_file{"%.17g"};       /* created at the first measurement with -dsf */
-    PetscBool use_dsf_sites = PETSC_FALSE;      /* -dsf_sites c0,c1,...: G_ic(w) and its Fourier transform from a kept Lanczos basis, DynamicalCorrelations.json (CalculateDynamicalCorrelations) */
-    std::vector<PetscInt> dsf_sites;            /* the reference sites c, lattice numbering of To1D; shares -dsf_steps and -dsf_breakdown_tol */
-    dmrgx_host::JsonRecordFile dsf_sites_file{"%.17g"}; /* created at the first measurement with -dsf_sites */
-    PetscBool use_dsf_cheb = PETSC_FALSE;       /* -dsf_cheb c0,c1,...: Chebyshev moments of G_ic(w), ChebyshevMoments.json (CalculateChebyshevCorrelations) */
-    std::vector<PetscInt> dsf_cheb_sites;       /* the reference sites c, lattice numbering of To1D */
-    PetscInt dsf_cheb_steps = 200;              /* -dsf_cheb_steps: MatMults per run; moments 0 .. steps between sites, 0 .. 2 steps on the diagonal */
-    PetscInt dsf_cheb_bound_steps = 40;         /* -dsf_cheb_bound_steps: Lanczos steps of the run that finds the top of the spectrum */
-    PetscBool dsf_cheb_have_window = PETSC_FALSE, dsf_cheb_have_omega = PETSC_FALSE;
-    PetscReal dsf_cheb_window[2] = {0.0, 0.0};  /* -dsf_cheb_window lo,hi: the window given, no bound run */
-    std::vector<double> dsf_cheb_omega;         /* -dsf_cheb_omega w0,w1,nw: the grid of the Jackson-broadened SqwGrid */
-    dmrgx_host::JsonRecordFile dsf_cheb_file{"%.17g"};  /* created at the first measurement with -dsf_cheb */
-    PetscBool use_dsf_dimer = PETSC_FALSE;      /* -dsf_dimer b0,b1,...: Chebyshev moments of the dimer correlations D_bc(w), DimerDynamics.json (CalculateDimerDynamics); shares -dsf_cheb_window and -dsf_cheb_bound_steps */
-    std::vector<PetscInt> dsf_dimer_bonds;      /* the reference bonds c: their index in DimerBonds(Ham), the Bonds of DimerCorrelations.json */
-    PetscInt dsf_dimer_steps = 200;             /* -dsf_dimer_steps: MatMults per run */
-    PetscBool dsf_dimer_have_omega = PETSC_FALSE;
-    std::vector<double> dsf_dimer_omega;        /* -dsf_dimer_omega w0,w1,nw: the grid of the Jackson-broadened SqwGrid */
-    dmrgx_host::JsonRecordFile dsf_dimer_file{"%.17g"}; /* created at the first measurement with -dsf_dimer */
     dmrgx_host::NoiseSchedule noise;            /* -noise a0,a1,... / -noise_warmup a: the weight of the density-matrix perturbation per sweep (Noise.hpp) */
     int64_t noise_max_bytes = 0;                /* the largest expansion a truncation held (DMRGRun.json NoiseMaxExpansionBytes) */
     PetscInt noise_ops[2] = {0, 0}, noise_expansions = 0;      /* operators per side of the largest list; expansions built */
-    PetscBool use_dsf_pm = PETSC_FALSE;         /* -dsf_pm c0,c1,...: Chebyshev moments of the transverse correlations, TransverseDynamics.json (CalculateTransverseDynamics); shares the -dsf_cheb_* options */
-    std::vector<PetscInt> dsf_pm_sites;         /* the reference sites c, lattice numbering of To1D */
-    dmrgx_host::JsonRecordFile dsf_pm_file{"%.17g"};    /* created at the first measurement with -dsf_pm */
-    PetscBool use_dsf_cv = PETSC_FALSE;         /* -dsf_cv c0,c1,...: correction vectors of G_ic(w + i eta), CorrectionVectors.json (CalculateCorrectionVectors) */
-    std::vector<PetscInt> dsf_cv_sites;         /* the reference sites c, lattice numbering of To1D */
-    std::vector<double> dsf_cv_omega;           /* -dsf_cv_omega w0,w1,nw: the frequencies, one solve per site and frequency */
-    PetscReal dsf_cv_eta = 0.1;                 /* -dsf_cv_eta: half width at half maximum of the Lorentzian */
-    PetscReal dsf_cv_tol = 1e-8;                /* -dsf_cv_tol: |r| <= tol |b| ends a solve */
-    PetscInt dsf_cv_maxit = 2000;               /* -dsf_cv_maxit: iterations per solve at most */
-    dmrgx_host::JsonRecordFile dsf_cv_file{"%.17g"};    /* created at the first measurement with -dsf_cv */
     PetscBool use_corr_batch = PETSC_TRUE;      /* -corr_batch 0: every correlator through its own MatMult + dot, as the reference does */
+    dmrgx_host::EngineMeasurements engine_measurements;      /* the nine engine-extension measurements: options, record files, runs (EngineMeasurements.hpp) */
 };
 
 #endif

@@ -1,11 +1,11 @@
 #ifndef DMRGX_HOST_MEASUREMENTS_HPP
 #define DMRGX_HOST_MEASUREMENTS_HPP
-/** What the measurements of DMRGBlockContainer.hpp share.  All of them: the two blocks as the library sees them, the site operators of
+/** What the measurements of EngineMeasurements.hpp share.  All of them: the two blocks as the library sees them, the site operators of
     one Gram / term call, the JSON record file; -corr_matrix and -corr_dimer: the bond list and the lattice Fourier sum; -corr_dimer and
-    -dsf_dimer (CalculateDimerCorrelations, CalculateDimerDynamics): DimerFrame, the bond operators as terms, BondsOfOrientation, the bond header.
-    The four dynamical ones, -dsf, -dsf_sites, -dsf_cheb and -dsf_cv (CalculateDynamicalStructureFactor, CalculateDynamicalCorrelations,
-    CalculateChebyshevCorrelations, CalculateCorrectionVectors): SzFrame, SiteCosineSum, the w0,w1,nw grid, the openings of their records;
-    the phase coefficients of -dsf; -dsf_pm (CalculateTransverseDynamics): SzFrame over Sp or Sm.  The Chebyshev three, -dsf_cheb, -dsf_pm and
+    -dsf_dimer (DimerCorrelations::Run, DimerDynamics::Run): DimerFrame, the bond operators as terms, BondsOfOrientation, the bond header.
+    The four dynamical ones, -dsf, -dsf_sites, -dsf_cheb and -dsf_cv (DynamicalStructureFactor::Run, DynamicalCorrelations::Run,
+    ChebyshevCorrelations::Run, CorrectionVectors::Run): SzFrame, SiteCosineSum, the w0,w1,nw grid, the openings of their records;
+    the phase coefficients of -dsf; -dsf_pm (TransverseDynamics::Run): SzFrame over Sp or Sm.  The Chebyshev three, -dsf_cheb, -dsf_pm and
     -dsf_dimer: the window, the moment run (MomentRun), the Jackson-damped grid and the moment part of a record.  host_tool.cpp runs the pure parts without a GPU. */
 #include <cmath>
 #include <deque>

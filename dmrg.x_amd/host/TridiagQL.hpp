@@ -4,7 +4,7 @@
     with Wilkinson shifts (EISPACK tql2 restricted to one row of the eigenvector matrix; TridiagQLVectors below keeps all of it).
     This is all a continued fraction needs:
     for the Lanczos matrix T of a start vector v, the spectral function of v has its poles at the eigenvalues of T with the weights
-    |v|^2 z_k^2 (-dsf, DMRGBlockContainer.hpp: CalculateDynamicalStructureFactor).  Orders are the number of Lanczos steps (~100):
+    |v|^2 z_k^2 (-dsf, EngineMeasurements.hpp: DynamicalStructureFactor::Run).  Orders are the number of Lanczos steps (~100):
     host work of microseconds. */
 #include <cmath>
 #include <vector>
@@ -58,8 +58,8 @@ inline bool TridiagQLFirstRow(std::vector<double>& d, std::vector<double> e, std
 
 /** The same iteration with ALL eigenvectors (EISPACK tql2): on return d holds the eigenvalues (unsorted) and vec[k * n + i] component i
     of the normalised eigenvector of d[k] -- eigenvector-major, so that a rotation walks two contiguous rows.  T = S Theta S^T with
-    S[i][k] = vec[k * n + i].  For the overlaps of other vectors with a kept Lanczos basis (-dsf_sites, DMRGBlockContainer.hpp:
-    CalculateDynamicalCorrelations), which need more of S than its first row.  Orders up to a few hundred: 3 n^3 flops, milliseconds.
+    S[i][k] = vec[k * n + i].  For the overlaps of other vectors with a kept Lanczos basis (-dsf_sites, EngineMeasurements.hpp:
+    DynamicalCorrelations::Run), which need more of S than its first row.  Orders up to a few hundred: 3 n^3 flops, milliseconds.
     false: an eigenvalue did not converge in 60 iterations. */
 inline bool TridiagQLVectors(std::vector<double>& d, std::vector<double> e, std::vector<double>& vec)
 {

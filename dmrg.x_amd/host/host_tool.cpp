@@ -11,7 +11,7 @@
 #include "DMRGKron.hpp"
 #include "CorrelatorDealing.hpp"
 #include "TridiagQL.hpp"
-#include "Measurements.hpp"
+#include "EngineMeasurements.hpp"
 #include "Noise.hpp"
 
 static void dump_mat(const char* tag, PetscInt site, const Mat& m)
@@ -311,7 +311,31 @@ int main()
                 print_numbers("noise", v);
                 printf("any %d json %s\n", (int)S.Any(), S.Json().c_str());
             }
-        } else if (cmd == "noiseops") {         /* noiseops a n, then n x (shift transposed id): plan operators, id names the stored cell set  ->  the list of NoiseOperators as shift:transposed:id, then the coefficient */
+        } else if (cmd == "measopts") {         /* measopts ranks -option value ...: the model and the measurement options as on the driver's command line ("_": no value)  ->  rc of EngineMeasurements::ReadOptions on that many ranks, then one line per measurement */
+            PetscMPIInt ranks; is >> ranks;
+            dmrgx_host::Options::Global().Clear();
+            std::string k, v;
+            while (is >> k >> v) PetscOptionsSetValue(NULL, k.c_str(), v == "_" ? "" : v.c_str());
+            ham = Hamiltonians::J1J2XXZModel_SquareLattice();
+            ierr = ham.SetFromOptions();
+            dmrgx_host::EngineMeasurements E;
+            if (!ierr) ierr = E.ReadOptions(PETSC_COMM_WORLD, 0, ranks, ham.NumSites(), ham);
+            printf("rc %d\n", ierr);
+            if (!ierr) {
+                auto ints = [](const std::vector<PetscInt>& a) { std::string s; for (PetscInt x : a) s += (s.empty() ? "" : ",") + std::to_string(x); return s.empty() ? std::string("-") : s; };
+                auto reals = [](const std::vector<double>* a) { std::string s; char b[32]; if (a) for (double x : *a) { snprintf(b, sizeof(b), "%.17g", x); s += (s.empty() ? "" : ",") + std::string(b); } return s.empty() ? std::string("-") : s; };
+                const std::vector<double> window(E.cheb.window, E.cheb.window + 2);
+                const std::string shared = " bound_steps " + std::to_string(E.cheb.bound_steps) + " window " + reals(E.cheb.have_window ? &window : nullptr);
+                const std::string cheb = " steps " + std::to_string(E.cheb.steps) + " omega " + reals(E.cheb.grid()) + shared;
+                printf("corr_matrix %d\ncorr_dimer %d\ncorr_chiral %d\n", (int)E.corr_matrix.use, (int)E.corr_dimer.use, (int)E.corr_chiral.use);
+                printf("dsf %d q %s steps %lld breakdown_tol %.17g\n", (int)E.dsf.use, ints(E.dsf.q).c_str(), LLD(E.lanczos.steps), E.lanczos.breakdown_tol);
+                printf("dsf_sites %d sites %s steps %lld breakdown_tol %.17g\n", (int)E.dsf_sites.use, ints(E.dsf_sites.sites).c_str(), LLD(E.lanczos.steps), E.lanczos.breakdown_tol);
+                printf("dsf_cheb %d sites %s%s\n", (int)E.dsf_cheb.use, ints(E.dsf_cheb.sites).c_str(), cheb.c_str());
+                printf("dsf_dimer %d bonds %s steps %lld omega %s%s\n", (int)E.dsf_dimer.use, ints(E.dsf_dimer.bonds).c_str(), LLD(E.dsf_dimer.steps), reals(E.dsf_dimer.have_omega ? &E.dsf_dimer.omega : nullptr).c_str(), shared.c_str());
+                printf("dsf_pm %d sites %s%s\n", (int)E.dsf_pm.use, ints(E.dsf_pm.sites).c_str(), cheb.c_str());
+                printf("dsf_cv %d sites %s omega %s eta %.17g tol %.17g maxit %lld\n", (int)E.dsf_cv.use, ints(E.dsf_cv.sites).c_str(), reals(&E.dsf_cv.omega).c_str(), E.dsf_cv.eta, E.dsf_cv.tol, LLD(E.dsf_cv.maxit));
+            }
+        } else if (cmd == "noiseops") {        /* noiseops a n, then n x (shift transposed id): plan operators, id names the stored cell set  ->  the list of NoiseOperators as shift:transposed:id, then the coefficient */
             double a; PetscInt n; is >> a >> n;
             std::vector<dmrgx_cell> sets(64);
             for (size_t i = 0; i < sets.size(); ++i) sets[i] = dmrgx_cell{0, 0, 0, 2, 2, DMRGX_CELL_DENSE, 0.0, reinterpret_cast<const double*>(sets.data()) + i % 32, 2};      /* (addresses never read; set 32 + i is a second descriptor of the blocks of set i) */
