@@ -131,7 +131,10 @@ extern "C" dmrgx_status dmrgx_rotate_ops(const dmrgx_sectors* old_sectors, const
             if (q < 0 || q >= old_sectors->nsec || qc < 0 || qc >= old_sectors->nsec) DMRGX_FAIL(DMRGX_ERR_OUTOFRANGE, "rotate_ops: op %d cell %d sector out of range", o, c);
             if (ce.nr <= 0 || ce.nc <= 0 || ce.r0 < 0 || ce.c0 < 0 || ce.r0 + ce.nr > old_sectors->size[q] || ce.c0 + ce.nc > old_sectors->size[qc])
                 DMRGX_FAIL(DMRGX_ERR_OUTOFRANGE, "rotate_ops: op %d cell %d exceeds its block", o, c);
+            if (ce.kind != DMRGX_CELL_DENSE && ce.kind != DMRGX_CELL_IDENT) DMRGX_FAIL(DMRGX_ERR_ARG, "rotate_ops: op %d cell %d has unknown kind %d", o, c, ce.kind);
             if (ce.kind == DMRGX_CELL_DENSE && (!ce.data || ce.ld < ce.nc)) DMRGX_FAIL(DMRGX_ERR_ARG, "rotate_ops: op %d cell %d has no data", o, c);
+            // stage A copies nc columns of RT_a from r0 on: only a square identity cell keeps them inside the row
+            if (ce.kind == DMRGX_CELL_IDENT && ce.nr != ce.nc) DMRGX_FAIL(DMRGX_ERR_ARG, "rotate_ops: op %d identity cell %d is %d x %d, not square", o, c, ce.nr, ce.nc);
             const int32_t a = new_of_old[q], ap = new_of_old[qc];
             if (a < 0 || ap < 0) continue;                      // a truncated-away sector: the block disappears
             if (!dst_blocks[o] || !dst_blocks[o][a]) DMRGX_FAIL(DMRGX_ERR_ARG, "rotate_ops: op %d has no destination for new sector %d", o, a);

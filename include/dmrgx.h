@@ -383,7 +383,8 @@ typedef struct {
 /* For every source operator o (cells in the OLD sector basis): dst_blocks[o][a] <- RT_a . O_{q -> q+shift} . RT_a'^T with
  * q = old_sector[a] and a' the new sector cut from old sector q+shift; dst_blocks[o][a] is a caller-allocated dense
  * kept[a] x kept[a'] row-major block (ignored / may be NULL when a' does not exist).  == RotateOperators
- * (src/DMRGBlock.cpp:763-772) for Sz(i), Sp(i) and H at once. */
+ * (src/DMRGBlock.cpp:763-772) for Sz(i), Sp(i) and H at once.  Identity cells are square (nr == nc); any other identity
+ * cell, and any kind other than DENSE or IDENT, is refused with DMRGX_ERR_ARG. */
 dmrgx_status dmrgx_rotate_ops(const dmrgx_sectors* old_sectors, const dmrgx_rotation* rot, int32_t nops,
                               const dmrgx_secop* src_ops, double* const* const* dst_blocks, void* stream);
 

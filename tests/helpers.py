@@ -52,6 +52,26 @@ def oracle_shell_from_superblock(sb, target=0.0):
     return ShellCtx(kb, terms)
 
 
+def secop_from(op, keep, ld_pad=0):
+    """ctypes dmrgx_secop for a workloads.SectorOperator; device tensors appended to `keep`.  ld_pad > 0: every dense cell lives in a
+    wider NaN-filled device array, ld = nc + ld_pad (in the engine every cell is a view into an arena)."""
+    import torch
+    from dmrgx_amd import _capi
+    cells = (_capi.Cell * max(len(op.cells), 1))()
+    for i, c in enumerate(op.cells):
+        cells[i].row_sector, cells[i].r0, cells[i].c0, cells[i].nr, cells[i].nc, cells[i].kind, cells[i].scale = c.row_sector, c.r0, c.c0, c.nr, c.nc, c.kind, c.scale
+        if c.kind == CELL_DENSE:
+            wide = np.full((c.nr, c.nc + ld_pad), np.nan)
+            wide[:, :c.nc] = c.array
+            t = torch.from_numpy(wide).cuda()
+            keep.append(t)
+            cells[i].data, cells[i].ld = t.data_ptr(), c.nc + ld_pad
+    keep.append(cells)
+    s = _capi.SecOp()
+    s.shift, s.transposed, s.ncells, s.cells = op.shift, 0, len(op.cells), cells
+    return s
+
+
 # ---- independent exact diagonalisation of the lattice model (correlator known answers) -------------------------------
 def lattice_ground_state(ham, spin="1/2"):
     """Dense ED of the whole lattice in the site basis (site 0 = most significant factor), from the model's own term

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import oracle_shell_from_superblock
+from helpers import oracle_shell_from_superblock, secop_from
 from oracle.kron_c import ShellApplyC
 
 pytestmark = pytest.mark.gpu
@@ -535,23 +535,6 @@ def test_persistent_tridiagonalisation_time_out_falls_back_and_stays_correct(mod
     assert "persistent tridiagonalisation timed out" in p.stderr, p.stderr[-2000:]
 
 
-def _secop_from(op, keep):
-    """ctypes dmrgx_secop for a workloads.SectorOperator; device tensors appended to `keep`."""
-    import ctypes as C
-    from dmrgx_amd import _capi
-    cells = (_capi.Cell * max(len(op.cells), 1))()
-    for i, c in enumerate(op.cells):
-        cells[i].row_sector, cells[i].r0, cells[i].c0, cells[i].nr, cells[i].nc, cells[i].kind, cells[i].scale = c.row_sector, c.r0, c.c0, c.nr, c.nc, c.kind, c.scale
-        if c.kind == 1:
-            t = torch.from_numpy(np.ascontiguousarray(c.array)).cuda()
-            keep.append(t)
-            cells[i].data, cells[i].ld = t.data_ptr(), c.nc
-    keep.append(cells)
-    s = _capi.SecOp()
-    s.shift, s.transposed, s.ncells, s.cells = op.shift, 0, len(op.cells), cells
-    return s
-
-
 def test_rdm_subset_matches_full_solve_and_refuses_unselected(mods):
     """dmrgx_rdm_create_subset (multi-GPU dealing; sides whose spectrum the engine borrows from the other side): a selected density
     matrix gets the spectrum of the full solve, an unselected one is refused with DMRGX_ERR_ARG, and the spectra of the two sides of a
@@ -591,7 +574,9 @@ def test_rdm_subset_matches_full_solve_and_refuses_unselected(mods):
 
 def test_rotate_ops_vs_numpy(mods):
     """K6 vs numpy: O' = RotMatT . O . RotMat (src/DMRGBlock.cpp:766-771) for Sz-, Sp- and H-type operators with
-    structurally sparse cells, an identity cell, and a sector dropped by the truncation."""
+    structurally sparse cells, a sector dropped by the truncation, and two identity cells on one operator of shift +1: the first has
+    its column sector truncated away (the cell is skipped, its block disappears), the second (row sector 3 -> column sector 4) lands on
+    a kept pair and goes through the scaled-copy branch of stage A."""
     import ctypes as C
     sbm, wl, capi = mods
     rng = np.random.default_rng(5)
@@ -599,14 +584,16 @@ def test_rotate_ops_vs_numpy(mods):
     sub = [(2, 3), (40, 30), (33, 0), (0, 8), (65, 65)]
     off = np.concatenate([[0], np.cumsum(sizes)])
     ops = [wl._old_site_op(rng, 0, sizes, sub), wl._old_site_op(rng, +1, sizes, sub), wl._sym_block_op(rng, sizes)]
-    ident = wl.SectorOperator(+1, [wl.OpCell(1, 40, 0, 30, 30, wl.CELL_IDENT, 0.75), wl.OpCell(0, 0, 10, 5, 5, wl.CELL_DENSE, 0.0, rng.standard_normal((5, 5)))])
+    ident = wl.SectorOperator(+1, [wl.OpCell(1, 40, 0, 30, 30, wl.CELL_IDENT, 0.75), wl.OpCell(0, 0, 10, 5, 5, wl.CELL_DENSE, 0.0, rng.standard_normal((5, 5))),
+                                   wl.OpCell(3, 1, 60, 7, 7, wl.CELL_IDENT, -1.25)])
     ops.append(ident)
     old_sector, kept = [0, 1, 3, 4], [3, 41, 8, 70]           # old sector 2 is truncated away entirely
     RT = [rng.standard_normal((m, sizes[q])) for q, m in zip(old_sector, kept)]
     keep = []
     rt_dev = [torch.from_numpy(r).cuda() for r in RT]
-    secops = (capi.SecOp * len(ops))(*[_secop_from(o, keep) for o in ops])
+    secops = (capi.SecOp * len(ops))(*[secop_from(o, keep) for o in ops])
     new_of_old = {q: a for a, q in enumerate(old_sector)}
+    assert [c.row_sector in new_of_old and c.row_sector + 1 in new_of_old for c in ident.cells if c.kind == wl.CELL_IDENT] == [False, True]
     dst, dst_arrays = [], []
     for o in ops:
         row = (C.c_void_p * len(old_sector))()

@@ -377,6 +377,16 @@ POISONED_NODES = [
     "tests/test_gpu_ggemm.py::test_tile_geometry_64_only",
     "tests/test_gpu_ggemm.py::test_launch_regimes_64",
     "tests/test_gpu_ggemm.py::test_claiming_128",
+    # rotation workspaces (UT, W of dmrgx_rotate_ops) are fully written before they are read
+    "tests/test_gpu_rotate.py::test_cells_axpy_shape_ladder",
+    "tests/test_gpu_rotate.py::test_cells_axpy_identity_source",
+    "tests/test_gpu_rotate.py::test_cells_axpy_submission_order_by_bits",
+    "tests/test_gpu_rotate.py::test_cells_axpy_many_overlapping_tasks",
+    "tests/test_gpu_rotate.py::test_rotate_ops_enlarged_block_structure",
+    "tests/test_gpu_rotate.py::test_rotate_ops_exact_rotation",
+    "tests/test_gpu_rotate.py::test_rotate_ops_size_edges",
+    "tests/test_gpu_rotate.py::test_rotate_ops_truncation_patterns",
+    "tests/test_gpu_rotate.py::test_rotate_ops_refusal_case_is_accepted_undamaged",
 ]
 
 
