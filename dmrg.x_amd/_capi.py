@@ -199,6 +199,8 @@ SIGNATURES = {
     "dmrgx_kron_correction_vector": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                                  C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                  C.POINTER(CvStats), C.c_void_p]),
+    "dmrgx_kron_static_response": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                               C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(CvStats), C.c_void_p]),
     "dmrgx_vec_project_out": (C.c_int32, [C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
     "dmrgx_eigs_comm_timing": (C.c_int32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),
     "dmrgx_eigs_lowest": (C.c_int32, [C.c_void_p, C.POINTER(EigsOpts), C.POINTER(C.c_double), C.c_void_p,

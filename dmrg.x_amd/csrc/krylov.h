@@ -1,4 +1,4 @@
-// What the device-resident Krylov calls share (lanczos.hip, corrvec.hip; the single-value sums of eigs.hip and lib.hip; the range layout,
+// What the device-resident Krylov calls share (lanczos.hip, corrvec.hip, response.hip; the single-value sums of eigs.hip and lib.hip; the range layout,
 // pair accesses and host side of project_out.hip, whose sums are pairs of doubles in the same order): the workgroup
 // sum in wave order, 16-byte pair accesses with a ragged tail, the range layout, and the host-side checks and scalar array.  Internal,
 // not part of the ABI.  Every sum here has ONE order -- lanes by shuffle-down 32..1, waves 0..3, block partials b, b + THREADS, .. per

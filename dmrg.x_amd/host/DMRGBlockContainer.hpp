@@ -1860,7 +1860,7 @@ private:
     int64_t noise_max_bytes = 0;                /* the largest expansion a truncation held (DMRGRun.json NoiseMaxExpansionBytes) */
     PetscInt noise_ops[2] = {0, 0}, noise_expansions = 0;      /* operators per side of the largest list; expansions built */
     PetscBool use_corr_batch = PETSC_TRUE;      /* -corr_batch 0: every correlator through its own MatMult + dot, as the reference does */
-    dmrgx_host::EngineMeasurements engine_measurements;      /* the nine engine-extension measurements: options, record files, runs (EngineMeasurements.hpp) */
+    dmrgx_host::EngineMeasurements engine_measurements;      /* the ten engine-extension measurements: options, record files, runs (EngineMeasurements.hpp) */
 };
 
 #endif

@@ -1,8 +1,8 @@
 #ifndef DMRGX_HOST_ENGINEMEASUREMENTS_HPP
 #define DMRGX_HOST_ENGINEMEASUREMENTS_HPP
-/** The nine engine-extension measurements of the sweep engine, on top of what they share (Measurements.hpp): -corr_matrix, -corr_dimer,
-    -corr_chiral, -dsf, -dsf_sites, -dsf_cheb, -dsf_dimer, -dsf_pm and -dsf_cv.  Each is a struct of its flag, its options, its record
-    file, a ReadOptions and a Run; EngineMeasurements holds the nine as plain members and calls them in a fixed order.  What a Run needs
+/** The ten engine-extension measurements of the sweep engine, on top of what they share (Measurements.hpp): -corr_matrix, -corr_dimer,
+    -corr_chiral, -dsf, -dsf_sites, -dsf_cheb, -dsf_dimer, -dsf_pm, -dsf_cv and -chi_sites / -chi_bonds.  Each is a struct of its flag, its options, its record
+    file, a ReadOptions and a Run; EngineMeasurements holds the ten as plain members and calls them in a fixed order.  What a Run needs
     from the step comes in a MeasurementContext, the lattice through a template parameter: nothing here depends on the block or the
     container class, so host_tool.cpp reads the options without a GPU (command measopts). */
 #include <random>
@@ -937,7 +937,157 @@ struct CorrectionVectors {
     }
 };
 
-/** The nine measurements, the options they share, and the order in which a DMRG step reads and runs them. */
+/** -chi_sites c0,c1,... and -chi_bonds b0,b1,... (engine extension): the static susceptibilities of the ground state,
+        chi_ic = d<O_i>/dh_c = 2 sum_{n>0} <0|O_i|n><n|O_c|0> / (E_n - E0),   for ALL sites (bonds) i,
+    O = Sz of a lattice site (-chi_sites, lattice numbering) or O = D_b = S_i . S_j of a nearest-neighbour bond (-chi_bonds, the index in
+    DimerBonds(Ham) as for -dsf_dimer): the linear response to a field the Hamiltonian does not have.  One dmrgx_kron_static_response call
+    per reference c solves Q (H - E0) Q X = Q O_c psi, Q = 1 - |psi><psi| / <psi|psi>, by conjugate gradients on the device to the
+    relative residual -chi_tol (at most -chi_maxit iterations, ONE MatMult each, no eta) and takes the overlaps of X with the images of
+    all sites (bonds).  The solver deflates psi itself and returns Mean = <O_c> as its coefficient: no dmrgx_vec_project_out.  The error
+    is controlled: |Chi - exact| <= 2 |u| |Q v| Residual / gap.
+    The images (SzFrame::Images of all N sites, then DimerFrame::Images of all nb bonds: one family at a time) stay on the device for
+    their solves; beside them X and the four pool vectors of the solver: max(N, nb) + 5 vectors of N_sb doubles.
+    The record: per reference Norm2 = |Q O_c psi|^2 / Norm, Mean, Iterations, Converged, Residual (the true residual |b - A X| / |b| of
+    the returned X), Chi[i] = 2 <u_i, X> / Norm, ChiQ[q] = sum_i cos(q . (r_i - r_c)) Chi[i] (SiteCosineSum, row nx Ly + ny; for a bond
+    over the bonds of c's orientation at their Positions, as MomentsQ of -dsf_dimer).  A solve that did not converge within -chi_maxit is
+    written as it is, with a warning here.  The caveat of -dsf_sites applies: the block bases are optimised for the ground state alone
+    -- X is not targeted in the density matrix, so Chi is exact while nothing is truncated and an approximation that m controls otherwise.
+    One rank only (refused at start-up otherwise). */
+struct StaticSusceptibility {
+    PetscBool use = PETSC_FALSE, use_sites = PETSC_FALSE, use_bonds = PETSC_FALSE;
+    std::vector<PetscInt> sites;                /* -chi_sites c0,c1,...: the reference sites, lattice numbering of To1D */
+    std::vector<PetscInt> bonds;                /* -chi_bonds b0,b1,...: the reference bonds, their index in DimerBonds(Ham) */
+    PetscReal tol = 1e-8;                       /* -chi_tol: |r| <= tol |b| ends a solve */
+    PetscInt maxit = 2000;                      /* -chi_maxit: iterations per solve at most */
+    JsonRecordFile file{"%.17g"};               /* created at the first measurement */
+    PetscErrorCode ReadOptions(MPI_Comm comm, PetscMPIInt size, PetscInt num_sites, PetscInt num_bonds)
+    {
+        PetscErrorCode ierr = ReadSiteListOption(comm, size, "-chi_sites", "the conjugate-gradient run", sites, use_sites, num_sites); CHKERRQ(ierr);
+        ierr = ReadSiteListOption(comm, size, "-chi_bonds", "the conjugate-gradient run", bonds, use_bonds, num_bonds, "bond",
+                                  "the nearest-neighbour bonds in the order of Bonds in DimerCorrelations.json"); CHKERRQ(ierr);
+        use = (use_sites || use_bonds) ? PETSC_TRUE : PETSC_FALSE;
+        if (!use) return 0;
+        ierr = PetscOptionsGetReal(NULL, NULL, "-chi_tol", &tol, NULL); CHKERRQ(ierr);
+        if (!(tol > 0.0) || tol >= 1.0) SETERRQ1(comm, PETSC_ERR_ARG_OUTOFRANGE, "-chi_tol must lie in (0, 1). Got %g.", tol);
+        ierr = PetscOptionsGetInt(NULL, NULL, "-chi_maxit", &maxit, NULL); CHKERRQ(ierr);
+        if (maxit < 1) SETERRQ1(comm, PETSC_ERR_ARG_OUTOFRANGE, "-chi_maxit must be at least 1. Got %lld.", LLD(maxit));
+        return 0;
+    }
+
+    struct Run_t { PetscInt c = 0; double norm2 = 0.0, mean = 0.0, residual = 0.0; int iterations = 0, converged = 0; std::vector<double> chi, chiq; };
+
+    /** The solves of one family of `count` images U (row stride ld): R.c is given, the rest of R is filled. */
+    PetscErrorCode Solve(const MeasurementContext& ctx, const char* option, const char* noun, const double* psi, double norm, const double* U, int64_t ld, PetscInt count,
+                         double* X, std::vector<Run_t>& runs, PetscInt& matmults, PetscInt& iterations) const
+    {
+        std::vector<double> chi((size_t)count);
+        for (Run_t& R : runs) {
+            dmrgx_cv_stats cs;
+            if (dmrgx_kron_static_response(ctx.plan(), psi, U + R.c * ld, (double)ctx.E0, tol, (int32_t)maxit, 0, X, (int32_t)count, U, ld, &R.mean, &R.norm2, chi.data(), &cs, nullptr))
+                SETERRQ1(ctx.mpi_comm, 1, "dmrgx_kron_static_response: %s", dmrgx_last_error());
+            matmults += cs.n_matvec; iterations += cs.iterations;
+            if (!cs.converged) printf("  * WARNING: %s: %s %lld: not converged after %d iterations (residual %.3e, tol %.3e%s); the record holds the last iterate.\n",
+                                      option, noun, LLD(R.c), (int)cs.iterations, cs.true_residual, tol, cs.dead ? ", the iteration broke down" : "");
+            R.norm2 /= norm; R.iterations = (int)cs.iterations; R.converged = (int)cs.converged; R.residual = cs.true_residual;
+            R.chi.resize((size_t)count);
+            for (PetscInt i = 0; i < count; ++i) R.chi[(size_t)i] = 2.0 * chi[(size_t)i] / norm;
+        }
+        return 0;
+    }
+
+    void WriteTail(const Run_t& R, PetscInt M, const char* end) const
+    {
+        FILE* fp = file.fp;
+        fprintf(fp, ", \"Mean\": %.17g, \"Iterations\": %d, \"Converged\": %d, \"Residual\": %.17g,\n   \"Chi\": ", R.mean, R.iterations, R.converged, R.residual);
+        file.Row(R.chi); fprintf(fp, ",\n   \"ChiQ\": ");
+        file.Row(R.chiq.data(), M); fprintf(fp, "%s", end);
+    }
+
+    template<class Hamiltonian> PetscErrorCode Run(const MeasurementContext& ctx, const Hamiltonian& Ham)
+    {
+        PetscLogDouble t0, t1;
+        PetscTime(&t0);
+        PetscErrorCode ierr;
+        const PetscInt Lx = Ham.Lx(), Ly = Ham.Ly(), M = Lx * Ly;
+        PetscInt matmults = 0, iterations = 0;
+        int64_t n = 0;
+        double norm = 0.0;
+        std::vector<Run_t> site_runs(sites.size()), bond_runs(bonds.size());
+        std::vector<PetscInt> site_x, site_y;
+        std::vector<DimerBond> all_bonds;
+        if (use_sites) {
+            SzFrame S;
+            ierr = S.Init(ctx.KronBlocks, ctx.num_sites, Ham, ctx.psi, "Static susceptibility"); CHKERRQ(ierr);
+            const PetscInt N = S.F.N;
+            const int64_t ld = S.ld;
+            n = S.n; norm = S.norm;
+            /* the images of all sites, row s = Sz_s psi, and the solution of a solve */
+            std::unique_ptr<DevBuffer> U, X;
+            try {
+                U.reset(new DevBuffer((size_t)(N * ld), DevBuffer::device_only_t{}));
+                X.reset(new DevBuffer((size_t)ld, DevBuffer::device_only_t{}));
+            }
+            catch (const std::exception& e) { SETERRQ4(ctx.mpi_comm, PETSC_ERR_MEM, "Static susceptibility: no memory for the images of %lld sites and one vector of %lld states (%.3f GB): %s", LLD(N), LLD(n), (double)((N + 1) * ld) * 8e-9, e.what()); }
+            ierr = S.Images(S.op_of.data(), N, U->dev_uninitialised(), ld); CHKERRQ(ierr);
+            for (size_t ir = 0; ir < site_runs.size(); ++ir) site_runs[ir].c = sites[ir];
+            ierr = Solve(ctx, "-chi_sites", "site", S.psi, norm, U->dev_ro(), ld, N, X->dev_uninitialised(), site_runs, matmults, iterations); CHKERRQ(ierr);
+            for (Run_t& R : site_runs) R.chiq = SiteCosineSum(S.Lx, S.Ly, S.rx.data(), S.ry.data(), R.c, R.chi.data(), N, 1);
+            site_x = S.rx; site_y = S.ry;
+        }
+        if (use_bonds) {
+            DimerFrame B;
+            ierr = B.Init(ctx.KronBlocks, ctx.num_sites, Ham, ctx.psi, "Static susceptibility"); CHKERRQ(ierr);
+            const PetscInt nb = B.nb;
+            n = B.n;
+            const int64_t ld = n + (n & 1);
+            if (dmrgx_dot(n, B.psi, B.psi, &norm, nullptr)) SETERRQ1(ctx.mpi_comm, 1, "dmrgx_dot: %s", dmrgx_last_error());
+            if (!(norm > 0.0)) SETERRQ(ctx.mpi_comm, 1, "Static susceptibility: the ground state has no norm.");
+            /* the images of all bonds, row b = D_b psi, and the solution of a solve */
+            std::unique_ptr<DevBuffer> U, X;
+            try {
+                U.reset(new DevBuffer((size_t)(nb * ld), DevBuffer::device_only_t{}));
+                X.reset(new DevBuffer((size_t)ld, DevBuffer::device_only_t{}));
+            }
+            catch (const std::exception& e) { SETERRQ4(ctx.mpi_comm, PETSC_ERR_MEM, "Static susceptibility: no memory for the images of %lld bonds and one vector of %lld states (%.3f GB): %s", LLD(nb), LLD(n), (double)((nb + 1) * ld) * 8e-9, e.what()); }
+            ierr = B.Images(U->dev_uninitialised(), ld); CHKERRQ(ierr);
+            for (size_t ir = 0; ir < bond_runs.size(); ++ir) bond_runs[ir].c = bonds[ir];
+            ierr = Solve(ctx, "-chi_bonds", "bond", B.psi, norm, U->dev_ro(), ld, nb, X->dev_uninitialised(), bond_runs, matmults, iterations); CHKERRQ(ierr);
+            /* the cosine sum over the bonds of c's orientation, from c */
+            const OrientedBonds oriented[2] = {BondsOfOrientation(B.bonds, 'x'), BondsOfOrientation(B.bonds, 'y')};
+            for (Run_t& R : bond_runs) {
+                const OrientedBonds& O = oriented[B.bonds[(size_t)R.c].orient == 'x' ? 0 : 1];
+                const PetscInt no = (PetscInt)O.of.size(), c_in = (PetscInt)(std::find(O.of.begin(), O.of.end(), R.c) - O.of.begin());
+                std::vector<double> sel((size_t)no);
+                for (PetscInt k = 0; k < no; ++k) sel[(size_t)k] = R.chi[(size_t)O.of[(size_t)k]];
+                R.chiq = SiteCosineSum(Lx, Ly, O.x.data(), O.y.data(), c_in, sel.data(), no, 1);
+            }
+            all_bonds = B.bonds;
+        }
+        PetscTime(&t1);
+        if (ctx.verbose) printf("  * Static susceptibility: %lld reference sites, %lld reference bonds, %lld iterations, %lld MatMults on %lld states, tChi %.6f s\n",
+                                LLD(site_runs.size()), LLD(bond_runs.size()), LLD(iterations), LLD(matmults), LLD(n), t1 - t0);
+        ierr = file.BeginDynamical(ctx.data_dir + "StaticSusceptibility.json", ctx.GlobIdx, ctx.loop_type, (double)ctx.E0, norm); CHKERRQ(ierr);
+        FILE* fp = file.fp;
+        fprintf(fp, ", \"Tol\": %.17g, \"MaxIt\": %lld, \"tChi\": %.9g, \"MatMults\": %lld,\n   \"Sites\": [\n", tol, LLD(maxit), t1 - t0, LLD(matmults));
+        for (size_t ir = 0; ir < site_runs.size(); ++ir) {
+            const Run_t& R = site_runs[ir];
+            file.OpenSite(R.c, site_x[(size_t)R.c], site_y[(size_t)R.c], R.norm2);
+            WriteTail(R, M, ir + 1 < site_runs.size() ? "},\n" : "}\n");
+        }
+        fprintf(fp, "   ],\n   \"Bonds\": [\n");
+        for (size_t ir = 0; ir < bond_runs.size(); ++ir) {
+            const Run_t& R = bond_runs[ir];
+            const DimerBond& bc = all_bonds[(size_t)R.c];
+            fprintf(fp, "   {\"Bond\": %lld, \"Sites\": [%lld, %lld], \"Orientation\": \"%c\", \"r\": [%lld, %lld], \"Norm2\": %.17g", LLD(R.c), LLD(bc.i), LLD(bc.j), bc.orient, LLD(bc.ix), LLD(bc.jy), R.norm2);
+            WriteTail(R, M, ir + 1 < bond_runs.size() ? "},\n" : "}\n");
+        }
+        fprintf(fp, "   ]}");
+        fflush(fp);
+        return 0;
+    }
+};
+
+/** The ten measurements, the options they share, and the order in which a DMRG step reads and runs them. */
 struct EngineMeasurements {
     CorrelationMatrix corr_matrix;
     DimerCorrelations corr_dimer;
@@ -948,6 +1098,7 @@ struct EngineMeasurements {
     DimerDynamics dsf_dimer;
     TransverseDynamics dsf_pm;
     CorrectionVectors dsf_cv;
+    StaticSusceptibility chi;
     LanczosStepOptions lanczos;                 /* -dsf, -dsf_sites */
     ChebyshevOptions cheb;                      /* -dsf_cheb, -dsf_pm; its window also -dsf_dimer */
 
@@ -965,7 +1116,8 @@ struct EngineMeasurements {
         ierr = dsf_dimer.ReadOptions(comm, size, (PetscInt)DimerBonds(Ham).size()); CHKERRQ(ierr);
         ierr = dsf_pm.ReadOptions(comm, size, num_sites); CHKERRQ(ierr);
         ierr = cheb.Read(comm, dsf_cheb.use, dsf_dimer.use, dsf_pm.use); CHKERRQ(ierr);
-        return dsf_cv.ReadOptions(comm, size, num_sites);
+        ierr = dsf_cv.ReadOptions(comm, size, num_sites); CHKERRQ(ierr);
+        return chi.ReadOptions(comm, size, num_sites, (PetscInt)DimerBonds(Ham).size());
     }
     /** Right after the eigensolve, while the plan of the superblock Hamiltonian exists. */
     template<class Hamiltonian> PetscErrorCode RunWithPlan(const MeasurementContext& ctx, const Hamiltonian& Ham)
@@ -976,6 +1128,7 @@ struct EngineMeasurements {
         if (dsf_cheb.use) { ierr = dsf_cheb.Run(ctx, Ham, cheb); CHKERRQ(ierr); }
         if (dsf_dimer.use) { ierr = dsf_dimer.Run(ctx, Ham, cheb); CHKERRQ(ierr); }
         if (dsf_cv.use) { ierr = dsf_cv.Run(ctx, Ham); CHKERRQ(ierr); }
+        if (chi.use) { ierr = chi.Run(ctx, Ham); CHKERRQ(ierr); }
         return 0;
     }
     /** After that plan is destroyed: needs psi, not H -- its plans are of other sectors, one resident at a time. */
@@ -990,8 +1143,8 @@ struct EngineMeasurements {
         return 0;
     }
     /** Every one of them reads Sz and Sp of every site of both centre blocks, on every rank. */
-    bool NeedsAllSiteOperators() const { return corr_matrix.use || corr_dimer.use || corr_chiral.use || dsf.use || dsf_sites.use || dsf_cheb.use || dsf_cv.use || dsf_dimer.use || dsf_pm.use; }
-    void Close() { corr_matrix.file.Close(); corr_dimer.file.Close(); corr_chiral.file.Close(); dsf.file.Close(); dsf_sites.file.Close(); dsf_cheb.file.Close(); dsf_cv.file.Close(); dsf_dimer.file.Close(); dsf_pm.file.Close(); }
+    bool NeedsAllSiteOperators() const { return corr_matrix.use || corr_dimer.use || corr_chiral.use || dsf.use || dsf_sites.use || dsf_cheb.use || dsf_cv.use || dsf_dimer.use || dsf_pm.use || chi.use; }
+    void Close() { corr_matrix.file.Close(); corr_dimer.file.Close(); corr_chiral.file.Close(); dsf.file.Close(); dsf_sites.file.Close(); dsf_cheb.file.Close(); dsf_cv.file.Close(); dsf_dimer.file.Close(); dsf_pm.file.Close(); chi.file.Close(); }
 };
 
 }  // namespace dmrgx_host

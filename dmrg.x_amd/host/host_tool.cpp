@@ -334,6 +334,8 @@ int main()
                 printf("dsf_dimer %d bonds %s steps %lld omega %s%s\n", (int)E.dsf_dimer.use, ints(E.dsf_dimer.bonds).c_str(), LLD(E.dsf_dimer.steps), reals(E.dsf_dimer.have_omega ? &E.dsf_dimer.omega : nullptr).c_str(), shared.c_str());
                 printf("dsf_pm %d sites %s%s\n", (int)E.dsf_pm.use, ints(E.dsf_pm.sites).c_str(), cheb.c_str());
                 printf("dsf_cv %d sites %s omega %s eta %.17g tol %.17g maxit %lld\n", (int)E.dsf_cv.use, ints(E.dsf_cv.sites).c_str(), reals(&E.dsf_cv.omega).c_str(), E.dsf_cv.eta, E.dsf_cv.tol, LLD(E.dsf_cv.maxit));
+                /* the tenth measurement prints its line when it is on: a run without its options lists the nine above, as before */
+                if (E.chi.use) printf("chi 1 sites %s bonds %s tol %.17g maxit %lld\n", ints(E.chi.sites).c_str(), ints(E.chi.bonds).c_str(), E.chi.tol, LLD(E.chi.maxit));
             }
         } else if (cmd == "noiseops") {        /* noiseops a n, then n x (shift transposed id): plan operators, id names the stored cell set  ->  the list of NoiseOperators as shift:transposed:id, then the coefficient */
             double a; PetscInt n; is >> a >> n;

@@ -213,6 +213,33 @@ class KronPlan:
         out.update({k: getattr(stats, k) for k, _ in _capi.CvStats._fields_})
         return out
 
+    def static_response(self, p, v0, sigma, tol=0.0, max_it=1000, check_every=0, U=None, X=None, stream=None):
+        """The static response X of v0 on the complement of p (dmrgx_kron_static_response): <p, X> = 0 and Q (H - sigma) Q X = Q v0 with
+        Q = 1 - p p^T / <p, p>, by conjugate gradients with one MatMult per iteration, device-resident, convergence |r| <= tol |Q v0| decided
+        on the device (tol 0: 1e-8), iterations enqueued in blocks of check_every (0: 8).  p, v0: f64 device tensors of n_states, only read.
+        U: None, or a 2-D f64 device tensor of nu rows with unit stride along the vector (its row stride is the library's ldu), only read.
+        X: None (a new tensor), or the contiguous f64 device tensor of n_states to write.  Returns a dict: X, coef = <p, v0> / <p, p>,
+        norm2 = |Q v0|^2, chi[nu] = <U[i], X>, and the fields of dmrgx_cv_stats: iterations, converged, n_matvec, dead, residual,
+        true_residual.  Not converging within max_it is no error."""
+        n = self.info.n_states
+        for w in (p, v0):
+            assert w.dtype == torch.float64 and w.is_contiguous() and w.numel() >= n
+        nu, u_ptr, ldu = 0, C.c_void_p(), 0
+        if U is not None:
+            assert U.dtype == torch.float64 and U.dim() == 2 and U.shape[1] >= n and (U.shape[1] <= 1 or U.stride(1) == 1)
+            nu, u_ptr, ldu = U.shape[0], C.c_void_p(U.data_ptr()), U.stride(0) if U.shape[0] > 1 else max(U.stride(0), U.shape[1])
+        if X is None:
+            X = torch.empty(n, dtype=torch.float64, device=v0.device)
+        assert X.dtype == torch.float64 and X.is_contiguous() and X.numel() >= n
+        coef, norm2, stats = C.c_double(0.0), C.c_double(0.0), _capi.CvStats()
+        chi = (C.c_double * max(nu, 1))()
+        _capi.check(_capi.lib().dmrgx_kron_static_response(self._handle, C.c_void_p(p.data_ptr()), C.c_void_p(v0.data_ptr()), float(sigma), float(tol), int(max_it),
+                                                           int(check_every), C.c_void_p(X.data_ptr()), int(nu), u_ptr, int(ldu), C.byref(coef), C.byref(norm2), chi,
+                                                           C.byref(stats), self._stream_ptr(stream)))
+        out = dict(X=X, coef=coef.value, norm2=norm2.value, chi=np.array(chi[:nu]))
+        out.update({k: getattr(stats, k) for k, _ in _capi.CvStats._fields_})
+        return out
+
     def timing(self, enable):
         _capi.check(_capi.lib().dmrgx_kron_plan_timing(self._handle, 1 if enable else 0))
 

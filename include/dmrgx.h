@@ -38,6 +38,8 @@
  *   dmrgx_secop_compose         sums of products of two and three operators of one block, dense per sector: the parts of S_i . (S_j x S_k)
  *                               on one side of the cut (-corr_chiral)
  *   dmrgx_vec_project_out       one vector removed from a family of vectors, coefficients returned: (D_b - <D_b>) psi for all bonds (-dsf_dimer)
+ *   dmrgx_kron_static_response  the static linear response sum_{n>0} |n><n|v0> / (E_n - E0) by a device-resident conjugate-gradient run on the
+ *                               complement of psi, and its overlaps with a family of vectors: chi_ic = d<Sz_i>/dh_c, chi_bc (-chi_sites, -chi_bonds)
  *   dmrgx_comm_*             <- the communicator of the reference's MPI path: VecScatter-to-all of x inside every MatMult
  *                               (src/DMRGKron.cpp:1833-1834) and the MPI_Allreduce behind SLEPc's VecDot / VecNorm
  *
@@ -693,6 +695,43 @@ dmrgx_status dmrgx_kron_correction_vector(dmrgx_kron_plan* plan, const double* v
  * atomics: two calls give the same bits in coef and V. */
 dmrgx_status dmrgx_vec_project_out(int32_t nv, int64_t len, double* V_dev, int64_t ldv, const double* p_dev,
                                    double* coef /* host [nv] */, double* p_norm2 /* host */, void* stream);
+
+/* ---- Static linear response on the complement of one vector (susceptibilities without eta and without pinning fields) -- */
+/* With Q = 1 - p p^T / <p, p> on the planned Hamiltonian (world_size == 1; a striped plan is refused with DMRGX_ERR_ARG) the call returns
+ *   *coef = <p, v0> / <p, p>,   *norm2 = |Q v0|^2,   X with <p, X> = 0 and Q (H - sigma) Q X = Q v0,   chi[i] = <u_i, X>.
+ * With p = psi, sigma = E0 and v0 = O_c psi:  coef = <O_c>  and  2 chi[i] = 2 sum_{n>0} <psi|O_i|n><n|O_c|psi> / (E_n - E0) = d<O_i>/dh_c,
+ * the static susceptibility, with an error bounded by |u_i| |Q v0| true_residual / gap.  (The correction vector at w = 0 is no substitute:
+ * it solves the squared operator, is broadened by eta and turns singular as eta -> 0, psi lying in the null space of H - E0.)
+ * X is found by plain conjugate gradients from x = 0 on A = Q (H - sigma) Q, positive definite on the complement of p when p is the lowest
+ * eigenvector and sigma its eigenvalue, with b = Q v0.  Per iteration ONE MatMult t = H d, then s = t - sigma d (over t) with the partial
+ * sums of d.A d = <d, s> and of <p, s>; r -= delta p + alpha (s - gamma p) with gamma = <p, s> / <p, p> (what H - sigma leaves along p) and
+ * delta = <p, r> / <p, p> of the previous update (what rounding left along p), with the partial sums of r . r and <p, r>; x += alpha d,
+ * d = r + beta d: three fused vector kernels (9 vector reads, 4 writes) and two one-workgroup scalar kernels; alpha, beta, gamma, delta,
+ * r.r, the count and the flags live in a small device array.  Convergence is decided on the device: r.r <= tol^2 b.b (tol == 0: 1e-8;
+ * outside [0, 1): DMRGX_ERR_ARG).  Iterations are enqueued in blocks of check_every (0: 8); after each block one small copy brings the
+ * count and the flags back -- the only place where the host looks at the device.  Once the run has converged, died or counted max_it
+ * iterations, the kernels that remain in the block leave every vector alone and count nothing (their MatMults still run): X, chi,
+ * iterations and both residuals do not depend on check_every, bit for bit; only n_matvec = blocks check_every + 1 does.  After the loop
+ * <p, X> / <p, p> p is taken out of X once more, and one more MatMult gives the true residual |b - A X| / |b| of the returned X.
+ * p and v0 (reference layout, n_states doubles) are only read; p, v0 and X_dev may sit on any 8-byte alignment.  X_dev is the caller's
+ * buffer of n_states doubles; every element is written.  U, ldu, nu as in dmrgx_kron_chebyshev_moments (only read; columns beyond
+ * n_states neither read nor touched); the overlaps are one dmrgx_vec_gram call after the loop.  The MatMult runs between pool vectors
+ * only, one fixed (x, y) pair; it never sees p, X or U.
+ * Not reaching tol within max_it is no error: DMRGX_OK with converged = 0 and the last iterate.  *norm2 <= 1e-24 <v0, v0>, or not positive
+ * and finite: v0 is a multiple of p to rounding (the projection leaves about eps^2 per element, far below) -- X is exact zeros, chi is 0,
+ * iterations = 0, converged = 1, dead = 0.  <p, p> not positive and finite (or a coefficient that is not finite): X and chi are zeros,
+ * *coef = *norm2 = 0, converged = 0, dead = 1.  A partial sum that is not finite, or a d.A d that is not positive and finite (sigma above
+ * the second eigenvalue), sets dead before that iteration reaches X: with a finite H and U no output is ever NaN.  (An H that is not
+ * finite shows in the closing MatMult: dead = 1 and true_residual = infinity.)
+ * Refused (DMRGX_ERR_ARG), before any device work: a null plan, p, v0, X, coef, norm2 or stats; sigma not finite; max_it < 1;
+ * check_every < 0; nu < 0; nu > 0 with U_dev or chi NULL or ldu < n_states; X overlapping p, v0 or U.  Memory from the pool: four vectors
+ * of n_states doubles (r, d, t and an aligned copy of p), 3 ceil(n_states / 2048) partial sums, 18 + nu scalars.  Fixed grids,
+ * fixed-order sums, no atomics: two runs give the same bits.  The stats are those of dmrgx_kron_correction_vector, read for this A and X. */
+dmrgx_status dmrgx_kron_static_response(dmrgx_kron_plan* plan, const double* p_dev, const double* v0_dev, double sigma,
+                                        double tol, int32_t max_it, int32_t check_every,
+                                        double* X_dev, int32_t nu, const double* U_dev, int64_t ldu,
+                                        double* coef, double* norm2, double* chi /* host [nu]: <u_i, X>; may be NULL when nu == 0 */,
+                                        dmrgx_cv_stats* stats, void* stream);
 
 #ifdef __cplusplus
 }
