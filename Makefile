@@ -5,7 +5,7 @@ ARCH       ?= gfx950
 PKG        := dmrg.x_amd
 CSRC       := $(PKG)/csrc
 HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-function -Wno-pass-failed -Wno-inline-asm
-HIP_SRCS   := $(CSRC)/lib.hip $(CSRC)/pool.hip $(CSRC)/ggemm.hip $(CSRC)/gram.hip $(CSRC)/kron_plan.hip $(CSRC)/secop_compose.hip $(CSRC)/eigs.hip $(CSRC)/lanczos.hip $(CSRC)/corrvec.hip $(CSRC)/response.hip $(CSRC)/project_out.hip $(CSRC)/rdm.hip $(CSRC)/rdm_jacobi.hip $(CSRC)/hqr.hip $(CSRC)/symeig.hip $(CSRC)/symeig_trid.hip $(CSRC)/symeig_dc.hip $(CSRC)/rotate.hip $(CSRC)/comm.hip
+HIP_SRCS   := $(CSRC)/lib.hip $(CSRC)/pool.hip $(CSRC)/ggemm.hip $(CSRC)/gram.hip $(CSRC)/kron_plan.hip $(CSRC)/secop_compose.hip $(CSRC)/eigs.hip $(CSRC)/eigs_orth.hip $(CSRC)/states_expand.hip $(CSRC)/lanczos.hip $(CSRC)/corrvec.hip $(CSRC)/response.hip $(CSRC)/project_out.hip $(CSRC)/rdm.hip $(CSRC)/rdm_jacobi.hip $(CSRC)/hqr.hip $(CSRC)/symeig.hip $(CSRC)/symeig_trid.hip $(CSRC)/symeig_dc.hip $(CSRC)/rotate.hip $(CSRC)/comm.hip
 HIP_OBJS   := $(HIP_SRCS:.hip=.o)
 
 HOST       := $(PKG)/host

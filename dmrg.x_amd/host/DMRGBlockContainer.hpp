@@ -38,6 +38,7 @@
 #include "TridiagQL.hpp"
 #include "EngineMeasurements.hpp"
 #include "Noise.hpp"
+#include "TargetStates.hpp"
 
 /** One eigenpair of a reduced-density-matrix block */
 struct Eigen_t
@@ -203,6 +204,10 @@ public:
         /* -noise a0,a1,... / -noise_warmup a: White's density-matrix perturbation, weight per sweep (GetTruncation) */
         ierr = dmrgx_host::ReadNoiseOptions(mpi_comm, noise); CHKERRQ(ierr);
         if (noise.Any() && mpi_size > 1) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-noise is not available on more than one rank (got %d): the expansion of the density matrix is not striped.", (int)mpi_size);
+        /* -nstates k / -state_weights w0,...: the k lowest states of the sector, truncated with the state-averaged density matrix (TargetStates.hpp) */
+        ierr = dmrgx_host::ReadTargetStatesOptions(mpi_comm, targets); CHKERRQ(ierr);
+        if (targets.k > 1 && mpi_size > 1) SETERRQ2(mpi_comm, PETSC_ERR_SUP, "-nstates %lld is not available on more than one rank (got %d): the deflated solve and the expansion of the density matrix are not striped.", LLD(targets.k), (int)mpi_size);
+        if (targets.k > 1 && noise.Any()) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-nstates %lld cannot be combined with -noise / -noise_warmup: both widen the input of the density matrix.", LLD(targets.k));
         /* -corr_matrix, -corr_dimer, -corr_chiral, -dsf, -dsf_sites, -dsf_cheb, -dsf_dimer, -dsf_pm, -dsf_cv and what goes with them (EngineMeasurements.hpp) */
         ierr = engine_measurements.ReadOptions(mpi_comm, mpi_rank, mpi_size, num_sites, Ham); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-step_profile", &step_profile, NULL); CHKERRQ(ierr);
@@ -453,6 +458,7 @@ public:
         if (fp_entanglement) { fprintf(fp_entanglement, "\n]\n"); fclose(fp_entanglement); fp_entanglement = NULL; }
         if (fp_kron) { fprintf(fp_kron, "\n]\n"); fclose(fp_kron); fp_kron = NULL; }
         engine_measurements.Close();
+        targets_file.Close();
         if (fp_corr) {
             if (!corr_headers_printed) { PetscErrorCode e2 = PrintCorrelationHeaders(); CHKERRQ(e2); }
             fprintf(fp_corr, "\n  ]\n}\n"); fclose(fp_corr); fp_corr = NULL;
@@ -465,6 +471,7 @@ public:
             /* the schedule of the density-matrix perturbation as given (one weight per sweep, the last one holds on), and what it cost */
             fprintf(fp_data, "],\n  \"Noise\": %s,\n  \"NoiseWarmup\": %.17g,\n  \"NoiseExpansions\": %lld,\n  \"NoiseMaxExpansionBytes\": %lld,\n  \"NoiseOperatorsLeft\": %lld,\n  \"NoiseOperatorsRight\": %lld",
                     noise.Json().c_str(), noise.warmup, LLD(noise_expansions), (long long)noise_max_bytes, LLD(noise_ops[0]), LLD(noise_ops[1]));
+            if (targets.k > 1) fprintf(fp_data, ",\n  \"TargetStates\": %lld,\n  \"TargetWeights\": %s", LLD(targets.k), dmrgx_host::TargetStates::Json(targets.weights).c_str());
             fprintf(fp_data, ",\n  \"GSEnergy\": %.16g,\n  \"MatMults\": %lld,\n  \"LastSweepSeconds\": %.9g,\n  \"LastSweepSteps\": %lld,\n  \"LastSweepMatMults\": %lld,\n  \"EigensolveSeconds\": %.9g,\n"
                              "  \"DeviceBytesResidentAfterSweep\": %zu,\n  \"DeviceBytesPeak\": %zu,\n  \"DeviceBytesCached\": %zu,\n  \"StartVectorsTransformed\": %lld,\n  \"StartVectorsThroughOverlap\": %lld,\n  \"StartVectorsRejected\": %lld,\n"
                              "  \"RdmCalls\": %lld,\n  \"RdmBlockJacobiCalls\": %lld,\n  \"TridPersistentCalls\": %lld,\n  \"TridLaunchPathCalls\": %lld,\n  \"TridFallbacks\": %lld,\n"
@@ -546,6 +553,8 @@ public:
         Vec gsv_r;
         ierr = MatCreateVecs(H, &gsv_r, nullptr); CHKERRQ(ierr);
         PetscScalar gse_r = 0.0;
+        dmrgx_eigs_stats st0;                    /* of state 0, for TargetedStates.json */
+        bool guessed0 = false;
         {
             dmrgx_eigs_opts o;
             memset(&o, 0, sizeof(o));
@@ -576,12 +585,21 @@ public:
                 SETERRQ1(mpi_comm, 1, "dmrgx_eigs_lowest: %s", dmrgx_last_error());
             if (guessed && st.start_rejected) { ++guesses_rejected; guessed = false; }
             if (guessed) ++guesses_used;
+            st0 = st; guessed0 = guessed;
             timings.nMatMult = st.n_matvec; total_matmults += st.n_matvec; total_eigs_seconds += st.seconds;
             double ms4[4] = {0, 0, 0, 0}; int64_t napp = 0;
             if (step_profile && dmrgx_kron_plan_timing_read(H->plan, ms4, &napp)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_plan_timing_read: %s", dmrgx_last_error());
             ierr = SaveKronStats(kinfo, SysBlock, EnvBlock, (PetscInt)Terms.size(), st.n_matvec, st.seconds, ms4, napp); CHKERRQ(ierr);
         }
         step.GSEnergy = gse_r;
+        /* -nstates k > 1: the states above the lowest, each on the complement of those found; everything below measures state 0 */
+        TargetStep tstep;
+        if (targets.k > 1) {
+            try { ierr = SolveExcitedStates(KronBlocks, SysBlock, EnvBlock, H, gsv_r, gse_r, st0, guessed0, tstep, timings.nMatMult); CHKERRQ(ierr); }
+            catch (const std::exception& e) { SETERRQ1(mpi_comm, 1, "wavefunction transformation: %s", e.what()); }
+            if (do_measurements) { ierr = MeasureTargetStates(KronBlocks, gsv_r, tstep); CHKERRQ(ierr); }
+        }
+        const bool averaged = tstep.more.size() > 0;
         const dmrgx_host::MeasurementContext mctx{KronBlocks, gsv_r, &H, Terms, gse_r, num_sites, qn_sector, GlobIdx, LoopTypeName(), verbose, do_shell, mpi_comm, mpi_rank, mpi_size, data_dir};
         if (do_measurements) { ierr = engine_measurements.RunWithPlan(mctx, Ham); CHKERRQ(ierr); }      /* -dsf, -dsf_sites, -dsf_cheb, -dsf_dimer, -dsf_cv: they need the plan */
         ierr = MatDestroy_KronSumShell(&H); CHKERRQ(ierr);
@@ -592,15 +610,17 @@ public:
 
         BasisTransformation BT_L, BT_R;
         /* a side whose output block no later step reads needs its spectrum (truncation error, sector table) but no eigenvectors */
-        const bool vec_sys = !(hints && hints->dead_sys && !same), vec_env = !(hints && hints->dead_env && !same);
+        /* (under a state-averaged density matrix both sides are solved: the two averaged matrices do not share their spectra) */
+        const bool vec_sys = averaged || !(hints && hints->dead_sys && !same), vec_env = averaged || !(hints && hints->dead_env && !same);
         step.Noise = noise.At(LoopType == WarmupStep, LoopIdx - 1);      /* (the warm-up is loop 0, sweep s loop s + 1: also after a restart) */
-        ierr = GetTruncation(KronBlocks, gsv_r, MStates, BT_L, BT_R, vec_sys, vec_env, step.Noise, &Terms); CHKERRQ(ierr);
+        ierr = GetTruncation(KronBlocks, gsv_r, MStates, BT_L, BT_R, vec_sys, vec_env, step.Noise, &Terms, averaged ? &tstep : nullptr); CHKERRQ(ierr);
         ierr = CalculateCorrelations_BlockDiag(KronBlocks, gsv_r, do_measurements, &mctx); CHKERRQ(ierr);
         if (use_guess) {   /* what the next step needs to carry this ground state over */
             prev.valid = false;
             prev.insys = BlockIndex(SysBlock); prev.inenv = BlockIndex(EnvBlock); prev.outsys = BlockIndex(SysBlockOut); prev.outenv = BlockIndex(EnvBlockOut);
             if (prev.insys >= 0 && prev.inenv >= 0 && prev.outsys >= 0 && prev.outenv >= 0 && BT_L.RotMatT && BT_R.RotMatT) {
                 prev.psi = gsv_r;
+                prev.more = tstep.more;
                 prev.kb.clear();
                 for (PetscInt k = 0; k < KronBlocks.size(); ++k)
                     prev.kb.push_back({KronBlocks.LeftIdx(k), KronBlocks.RightIdx(k), SysBlockEnl.Magnetization.Sizes(KronBlocks.LeftIdx(k)),
@@ -618,6 +638,8 @@ public:
             }
         }
         ierr = VecDestroy(&gsv_r); CHKERRQ(ierr);
+        for (Vec& v : tstep.more) { ierr = VecDestroy(&v); CHKERRQ(ierr); }
+        tstep.rows.reset();
         ierr = SysBlockOut.Destroy(); CHKERRQ(ierr);
         ierr = EnvBlockOut.Destroy(); CHKERRQ(ierr);
         ierr = PetscTime(&trdms); CHKERRQ(ierr);
@@ -647,6 +669,7 @@ public:
         gse = gse_r;
         trunc_err.push_back(BT_L.TruncErr);
         ierr = SaveStepData(step); CHKERRQ(ierr);
+        if (targets.k > 1) { ierr = SaveTargetStep(tstep); CHKERRQ(ierr); }
         if (mpi_size > 1) { int64_t nmv = 0; dmrgx_eigs_comm_timing(&timings.msAllGather, &timings.msApply, &nmv, 1); }      /* this step's share, totals reset */
         ierr = SaveTimingsData(timings); CHKERRQ(ierr);
         ++GlobIdx; ++StepIdx; ++rows_written;
@@ -848,11 +871,12 @@ public:
 
     /** Fills `guess` (device, layout of KronBlocks) from the previous step if the two steps are consecutive positions
         of a sweep; returns used = false (guess untouched) otherwise or when any dimension does not line up. */
-    PetscErrorCode TransformedGuess(KronBlocks_t& KronBlocks, Block& SysBlock, Block& EnvBlock, const Vec& guess, bool& used, double& min_norm2)
+    PetscErrorCode TransformedGuess(KronBlocks_t& KronBlocks, Block& SysBlock, Block& EnvBlock, const Vec& guess, bool& used, double& min_norm2, const PetscInt state = 0)
     {
         used = false;
         bool projected = false;
         if (!use_guess || !prev.valid) return 0;
+        if (state > (PetscInt)prev.more.size()) return 0;      /* the previous step did not hold that state: a random start */
         const PetscInt insys = BlockIndex(SysBlock), inenv = BlockIndex(EnvBlock);
         if (insys < 0 || inenv < 0) return 0;
         const bool grow_left = (insys == prev.outsys && inenv == prev.inenv - 1);
@@ -933,7 +957,7 @@ public:
                 for (size_t i = 0; i < ij.size(); ++i) ST[(size_t)ij[i]] = base + off[ia.size() + i];
             }
         }
-        const double* x = prev.psi->buf->dev_ro();
+        const double* x = (state == 0 ? prev.psi : prev.more[(size_t)state - 1])->buf->dev_ro();
         for (const auto& kb : prev.kb) {
             const int32_t IL = (int32_t)kb[0], IR = (int32_t)kb[1], nL = (int32_t)kb[2], nR = (int32_t)kb[3];
             const int32_t grow_sector = grow_left ? IL : IR;
@@ -1013,7 +1037,7 @@ public:
            projected step's solve. */
         min_norm2 = projected ? 0.25 : 0.0;
         used = true;
-        if (projected) ++guesses_projected;
+        if (projected && state == 0) ++guesses_projected;
         return 0;
     }
 
@@ -1050,7 +1074,7 @@ public:
         std::ofstream f(filename);
         if (!f) SETERRQ1(mpi_comm, PETSC_ERR_FILE_OPEN, "cannot write %s", filename.c_str());
         char val[4096]; PetscBool set;
-        for (const char* key : {"-spin", "-mstates", "-mwarmup", "-nsweeps", "-msweeps", "-maxnsweeps", "-min_block", "-noise", "-noise_warmup"}) {
+        for (const char* key : {"-spin", "-mstates", "-mwarmup", "-nsweeps", "-msweeps", "-maxnsweeps", "-min_block", "-noise", "-noise_warmup", "-nstates", "-state_weights"}) {
             PetscErrorCode ierr = PetscOptionsGetString(NULL, NULL, key, val, sizeof(val), &set); CHKERRQ(ierr);
             if (set) f << key << " " << (val[0] ? val : "yes") << "\n";
         }
@@ -1381,13 +1405,145 @@ public:
         return 0;
     }
 
+    /** What a step with -nstates k > 1 holds beside state 0: the states above it, all k_step states as rows of one device buffer (row stride
+        ld: the Q of the deflated solves, the Psi of dmrgx_kron_states_expand, the family of the Gram matrix), and the step's record. */
+    struct TargetStep {
+        std::vector<double> weights, energies, residuals, seconds, overlaps, spin2;
+        std::vector<PetscInt> converged, matmults, transformed, rejected;
+        std::vector<Vec> more;                                      /**< states 1 .. k_step - 1 */
+        std::shared_ptr<dmrgx_host::DevBuffer> rows;
+        int64_t ld = 0;
+    };
+
+    /** States s = 1 .. k_step - 1 of the step's superblock, k_step = min(-nstates, states of the sector): dmrgx_eigs_lowest_orth with the
+        states already found as Q, options -H_eps_tol / -H_eps_ncv / -H_eps_max_it, seed = the step's seed + s, start vector = the previous
+        step's state s carried over (TransformedGuess) or random.  MatMults and seconds count into the step's and the run's totals. */
+    PetscErrorCode SolveExcitedStates(KronBlocks_t& KronBlocks, Block& SysBlock, Block& EnvBlock, Mat& H, const Vec& gsv_r, const double e0, const dmrgx_eigs_stats& st0, const bool guessed0,
+                                      TargetStep& T, PetscInt& step_matmults)
+    {
+        PetscErrorCode ierr;
+        const int64_t n = gsv_r->n;
+        T.weights = targets.StepWeights((PetscInt)n);
+        const PetscInt ks = (PetscInt)T.weights.size();
+        T.energies = {e0}; T.residuals = {st0.residual}; T.seconds = {st0.seconds};
+        T.converged = {st0.converged}; T.matmults = {st0.n_matvec}; T.transformed = {guessed0 ? 1 : 0}; T.rejected = {st0.start_rejected};
+        if (ks < 2) return 0;
+        T.ld = n + (n & 1);
+        T.rows = std::make_shared<dmrgx_host::DevBuffer>((size_t)(ks * T.ld), dmrgx_host::DevBuffer::device_only_t{});
+        double* rows = T.rows->dev_uninitialised();
+        if (dmrgx_memcpy_d2d(rows, gsv_r->buf->dev_ro(), (size_t)n * sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
+        for (PetscInt s = 1; s < ks; ++s) {
+            Vec v;
+            ierr = MatCreateVecs(H, &v, nullptr); CHKERRQ(ierr);
+            dmrgx_eigs_opts o;
+            memset(&o, 0, sizeof(o));
+            o.ncv = (int32_t)eps_ncv; o.max_it = (int32_t)eps_max_it; o.tol = eps_tol; o.seed = 0x9E3779B9u + (uint64_t)GlobIdx + (uint64_t)s;
+            bool guessed = false;
+            double min_norm2 = 0.0;
+            ierr = TransformedGuess(KronBlocks, SysBlock, EnvBlock, v, guessed, min_norm2, s); CHKERRQ(ierr);
+            if (guessed) { o.use_initial = 1; o.min_initial_norm2 = min_norm2; }
+            dmrgx_eigs_stats st;
+            memset(&st, 0, sizeof(st));
+            double e = 0.0;
+            if (dmrgx_eigs_lowest_orth(H->plan, &o, (int32_t)s, rows, T.ld, &e, v->buf->dev_uninitialised(), &st, nullptr)) SETERRQ2(mpi_comm, 1, "dmrgx_eigs_lowest_orth (state %lld): %s", LLD(s), dmrgx_last_error());
+            if (dmrgx_memcpy_d2d(rows + s * T.ld, v->buf->dev_ro(), (size_t)n * sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
+            step_matmults += st.n_matvec; total_matmults += st.n_matvec; total_eigs_seconds += st.seconds;
+            T.energies.push_back(e); T.residuals.push_back(st.residual); T.seconds.push_back(st.seconds);
+            T.converged.push_back(st.converged); T.matmults.push_back(st.n_matvec); T.transformed.push_back(guessed && !st.start_rejected ? 1 : 0); T.rejected.push_back(st.start_rejected);
+            T.more.push_back(v);
+        }
+        return 0;
+    }
+
+    /** At a measurement step: Overlaps, the Gram matrix of the states (one dmrgx_vec_gram), and TotalSpin2[s] = |S+_tot psi_s|^2 + M (M + 1)
+        with M the target sector's Sz -- one dmrgx_kron_term_gram per state with a single vector whose terms are Sp of every site of both
+        blocks: S (S + 1) of a state of definite total spin, which tells a singlet from a triplet excitation. */
+    PetscErrorCode MeasureTargetStates(KronBlocks_t& KronBlocks, const Vec& gsv_r, TargetStep& T)
+    {
+        const PetscInt ks = (PetscInt)T.energies.size();
+        const int64_t n = gsv_r->n;
+        dmrgx_host::DevBuffer g((size_t)(ks * ks + 1), dmrgx_host::DevBuffer::device_only_t{});
+        T.overlaps.assign((size_t)(ks * ks), 1.0);
+        if (ks > 1) {
+            if (dmrgx_vec_gram((int32_t)ks, (int32_t)ks, n, T.rows->dev_ro(), T.ld, T.rows->dev_ro(), T.ld, g.dev_uninitialised(), ks, 0, nullptr, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_vec_gram: %s", dmrgx_last_error());
+            if (dmrgx_memcpy_d2h(T.overlaps.data(), g.dev_ro(), T.overlaps.size() * sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
+        }
+        dmrgx_host::CentreFrame F;
+        PetscErrorCode ierr = F.Init(KronBlocks, num_sites, "-nstates"); CHKERRQ(ierr);
+        dmrgx_host::SiteOperators ops(F);
+        std::vector<PetscInt> lattice;
+        ierr = ops.AllSites(OpSp, lattice); CHKERRQ(ierr);
+        std::vector<dmrgx_term> terms;
+        for (int32_t a = 0; a < (int32_t)ops.ops[0].size(); ++a) terms.push_back(dmrgx_term{1.0, a, -1});
+        for (int32_t b = 0; b < (int32_t)ops.ops[1].size(); ++b) terms.push_back(dmrgx_term{1.0, -1, b});
+        const int32_t vec_first[2] = {0, (int32_t)terms.size()};
+        T.spin2.assign((size_t)ks, 0.0);
+        for (PetscInt s = 0; s < ks; ++s) {
+            const double* psi = s == 0 ? gsv_r->buf->dev_ro() : T.more[(size_t)s - 1]->buf->dev_ro();
+            if (dmrgx_kron_term_gram(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)ops.ops[0].size(), ops.ops[0].data(), (int32_t)ops.ops[1].size(), ops.ops[1].data(),
+                                     1, vec_first, terms.data(), 0, g.dev_uninitialised() + ks * ks, 1, nullptr, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_gram: %s", dmrgx_last_error());
+            double up = 0.0;
+            if (dmrgx_memcpy_d2h(&up, g.dev_ro() + ks * ks, sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
+            T.spin2[(size_t)s] = up + (double)qn_sector * ((double)qn_sector + 1.0);
+        }
+        return 0;
+    }
+
+    /** One record of TargetedStates.json (rank 0; the file exists only with -nstates k > 1). */
+    PetscErrorCode SaveTargetStep(const TargetStep& T)
+    {
+        if (mpi_rank) return 0;
+        PetscErrorCode ierr = targets_file.Begin(data_dir + "TargetedStates.json"); CHKERRQ(ierr);
+        FILE* fp = targets_file.fp;
+        auto ints = [&](const char* name, const std::vector<PetscInt>& v) { fprintf(fp, ",\n   \"%s\": [", name); for (size_t i = 0; i < v.size(); ++i) fprintf(fp, "%s%lld", i ? ", " : "", LLD(v[i])); fprintf(fp, "]"); };
+        auto reals = [&](const char* name, const std::vector<double>& v) { fprintf(fp, ",\n   \"%s\": ", name); targets_file.Row(v); };
+        fprintf(fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"NStates\": %lld", LLD(GlobIdx), LoopTypeName(), LLD((PetscInt)T.energies.size()));
+        reals("Weights", T.weights); reals("Energies", T.energies); reals("Residuals", T.residuals);
+        ints("Converged", T.converged); ints("MatMults", T.matmults); reals("Seconds", T.seconds);
+        ints("StartTransformed", T.transformed); ints("StartRejected", T.rejected);
+        if (!T.spin2.empty()) {
+            fprintf(fp, ",\n");
+            targets_file.Table("Overlaps", T.overlaps, (PetscInt)T.energies.size(), (PetscInt)T.energies.size(), "");
+            reals("TotalSpin2", T.spin2);
+        }
+        fprintf(fp, "}");
+        fflush(fp);
+        return 0;
+    }
+
+    /** The state-averaged density matrices sum_s w_s rho_s of both sides: the states set side by side by dmrgx_kron_states_expand and the
+        density matrices of that side only built on the expansion by dmrgx_rdm_create_subset, one object per side, exactly as
+        NoisyDensityMatrices does it.  rdm_of[side] and expansion[side] are the caller's to release, in that order. */
+    PetscErrorCode AveragedDensityMatrices(const TargetStep& T, const dmrgx_sectors& sl, const dmrgx_sectors& sr, const std::vector<int32_t>& bil, const std::vector<int32_t>& bir,
+                                           dmrgx_rdm* rdm_of[2], std::shared_ptr<dmrgx_host::DevBuffer> expansion[2])
+    {
+        const int32_t nb = (int32_t)bil.size(), ks = (int32_t)T.weights.size();
+        std::vector<int32_t> own((size_t)nb);
+        for (int32_t k = 0; k < nb; ++k) own[(size_t)k] = k;
+        for (int side = 0; side < 2; ++side) {
+            std::vector<int32_t> extent((size_t)nb, 0);
+            int64_t n_out = 0;
+            if (dmrgx_kron_states_expand(&sl, &sr, nb, bil.data(), bir.data(), ks, nullptr, T.ld, T.weights.data(), side, extent.data(), &n_out, nullptr, nullptr))
+                SETERRQ1(mpi_comm, 1, "dmrgx_kron_states_expand: %s", dmrgx_last_error());
+            expansion[side] = std::make_shared<dmrgx_host::DevBuffer>((size_t)n_out, dmrgx_host::DevBuffer::device_only_t{});
+            if (dmrgx_kron_states_expand(&sl, &sr, nb, bil.data(), bir.data(), ks, T.rows->dev_ro(), T.ld, T.weights.data(), side, extent.data(), &n_out, expansion[side]->dev_uninitialised(), nullptr))
+                SETERRQ1(mpi_comm, 1, "dmrgx_kron_states_expand: %s", dmrgx_last_error());
+            const dmrgx_sectors se{nb, extent.data()};
+            const std::vector<uint8_t> mask((size_t)nb, (uint8_t)(1 << side));
+            if (dmrgx_rdm_create_subset(side == 0 ? &sl : &se, side == 0 ? &se : &sr, nb, side == 0 ? bil.data() : own.data(), side == 0 ? own.data() : bir.data(),
+                                        expansion[side]->dev_uninitialised(), mask.data(), nullptr, &rdm_of[side]))
+                SETERRQ1(mpi_comm, 1, "dmrgx_rdm_create_subset: %s", dmrgx_last_error());
+        }
+        return 0;
+    }
+
     /*  noise_a > 0 (engine extension, -noise; one rank): White's density-matrix perturbation.  Each side that is solved gets a density-matrix
         object of its own, built by the unchanged solver on the expansion of dmrgx_kron_noise_expand (NoisyDensityMatrices); spectra,
         selection and eigenvectors of a side are read from that side's object, and the spectra are divided by the trace of the perturbed
         matrix.  noise_a == 0 is the code path and the call sequence of before. */
     PetscErrorCode GetTruncation(const KronBlocks_t& KronBlocks, const Vec& gsv_r, const PetscInt& MStates, BasisTransformation& BT_L, BasisTransformation& BT_R,
                                  const bool need_vec_L = true, const bool need_vec_R = true,
-                                 const double noise_a = 0.0, const std::vector<Hamiltonians::Term>* noise_terms = nullptr)
+                                 const double noise_a = 0.0, const std::vector<Hamiltonians::Term>* noise_terms = nullptr, const TargetStep* states = nullptr)
     {
         PetscErrorCode ierr;
         if (gsv_r->n != KronBlocks.NumStates()) SETERRQ2(PETSC_COMM_SELF, 1, "Incorrect vector length. Expected %lld. Got %lld.", LLD(KronBlocks.NumStates()), LLD(gsv_r->n));
@@ -1403,6 +1559,8 @@ public:
         dmrgx_rdm* rdm = nullptr;
         const bool noisy = noise_a > 0.0;
         if (noisy && (!noise_terms || dmrgx_host::WorldComm())) SETERRQ(mpi_comm, PETSC_ERR_SUP, "Density-matrix noise needs the terms of the step and one rank.");
+        const bool averaged = states != nullptr;                        /* several target states: sum_s w_s rho_s, built like the perturbed matrix on an expansion */
+        if (averaged && (noisy || dmrgx_host::WorldComm() || !need_vec_L || !need_vec_R)) SETERRQ(mpi_comm, PETSC_ERR_SUP, "The state-averaged density matrix needs one rank, no noise and both sides solved.");
         dmrgx_rdm* rdm_of[2] = {nullptr, nullptr};                       /* the object a side is read from: one for both, or one each under noise */
         std::shared_ptr<dmrgx_host::DevBuffer> expansion[2];            /* under noise: what that side's object was built on */
         auto drop = [&]() { if (rdm_of[0]) dmrgx_rdm_destroy(rdm_of[0]); if (rdm_of[1] && rdm_of[1] != rdm_of[0]) dmrgx_rdm_destroy(rdm_of[1]); rdm_of[0] = rdm_of[1] = nullptr; };
@@ -1430,6 +1588,7 @@ public:
             for (const auto& u : units) { int best = 0; for (int w = 1; w < W; ++w) if (load[(size_t)w] < load[(size_t)best]) best = w; load[(size_t)best] += u.first; owner[(size_t)u.second] = best; }
         }
         if (noisy) { ierr = NoisyDensityMatrices(KronBlocks, gsv_r, noise_a, *noise_terms, sl, sr, bil, bir, need_vec, rdm_of, expansion); if (ierr) { drop(); CHKERRQ(ierr); } }
+        else if (averaged) { ierr = AveragedDensityMatrices(*states, sl, sr, bil, bir, rdm_of, expansion); if (ierr) { drop(); CHKERRQ(ierr); } }
         else if (W > 1 || partial) {
             std::vector<uint8_t> mask((size_t)nb, 0);
             for (PetscInt k = 0; k < nb; ++k) mask[(size_t)k] = (uint8_t)((owner[(size_t)(2 * k)] == me ? 1 : 0) | (owner[(size_t)(2 * k + 1)] == me ? 2 : 0));
@@ -1438,7 +1597,7 @@ public:
         }
         else if (dmrgx_rdm_create(&sl, &sr, (int32_t)nb, bil.data(), bir.data(), gsv_r->buf->dev_ro(), nullptr, &rdm))
             SETERRQ1(mpi_comm, 1, "dmrgx_rdm_create: %s", dmrgx_last_error());
-        if (!noisy) rdm_of[0] = rdm_of[1] = rdm;
+        if (!noisy && !averaged) rdm_of[0] = rdm_of[1] = rdm;
         /* spectra of every matrix on every rank */
         std::vector<int64_t> spec_off((size_t)(2 * nb + 1), 0);
         for (PetscInt k = 0; k < nb; ++k) { spec_off[(size_t)(2 * k + 1)] = spec_off[(size_t)(2 * k)] + ls[bil[k]]; spec_off[(size_t)(2 * k + 2)] = spec_off[(size_t)(2 * k + 1)] + rs[bir[k]]; }
@@ -1594,8 +1753,8 @@ public:
            eigenpairs (eigenvalues against the Rayleigh quotients of the finished vectors), which by then has long arrived -- destroying it
            here made the host wait for the GPU to drain (5 % of a configs[1] step, profiles/r05_hostprof_m512.txt) before it could queue the
            rotations.  Everything queued above is stream-ordered; the rotation rows live in buffers of their own. */
-        if (noisy) {
-            /* under noise the objects go at once, each before the expansion it was built on: the verification is read here, at the price of
+        if (noisy || averaged) {
+            /* under noise (and with several target states) the objects go at once, each before the expansion it was built on: the verification is read here, at the price of
                waiting for the queue -- paid in the noisy sweeps only, and the expansions are the largest buffers of the step */
             for (int side = 0; side < 2; ++side) {
                 dmrgx_rdm* r = rdm_of[side];
@@ -1655,7 +1814,7 @@ public:
             for (const Op& o : c.SysOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
             for (const Op& o : c.EnvOps) if (o.idx >= 0 && o.idx < N) corr_sites[(size_t)o.idx] = 1;
         }
-        if (engine_measurements.NeedsAllSiteOperators()) corr_sites.assign((size_t)N, 1);      /* Sz and Sp of every site of both centre blocks, on every rank */
+        if (engine_measurements.NeedsAllSiteOperators() || targets.k > 1) corr_sites.assign((size_t)N, 1);      /* Sz and Sp of every site of both centre blocks, on every rank */
         need_built = true;
         return 0;
     }
@@ -1836,6 +1995,7 @@ private:
         bool valid = false;
         PetscInt insys = -1, inenv = -1, outsys = -1, outenv = -1;
         Vec psi;
+        std::vector<Vec> more;                                     /**< -nstates k > 1: states 1 .. of that step */
         std::vector<std::array<PetscInt, 5>> kb;                   /**< (IL, IR, nL, nR, offset) of every KronBlock */
         std::vector<std::vector<EnlPart>> partsL, partsR;            /**< decomposition of the enlarged sectors */
         std::shared_ptr<dmrgx_host::BasisRotation> rotL, rotR;     /**< this step's truncations */
@@ -1857,6 +2017,8 @@ private:
     PetscInt guesses_used = 0;
     PetscBool use_rdm_warm = PETSC_FALSE;       /* -rdm_warm_start: still recognised, does nothing (a line at start-up says so) */
     dmrgx_host::NoiseSchedule noise;            /* -noise a0,a1,... / -noise_warmup a: the weight of the density-matrix perturbation per sweep (Noise.hpp) */
+    dmrgx_host::TargetStates targets;           /* -nstates k / -state_weights w0,...: the states a step solves and their weights in the density matrix (TargetStates.hpp) */
+    dmrgx_host::JsonRecordFile targets_file{"%.17g"};      /* TargetedStates.json: created at the first step, with -nstates k > 1 only */
     int64_t noise_max_bytes = 0;                /* the largest expansion a truncation held (DMRGRun.json NoiseMaxExpansionBytes) */
     PetscInt noise_ops[2] = {0, 0}, noise_expansions = 0;      /* operators per side of the largest list; expansions built */
     PetscBool use_corr_batch = PETSC_TRUE;      /* -corr_batch 0: every correlator through its own MatMult + dot, as the reference does */

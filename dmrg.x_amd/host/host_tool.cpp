@@ -13,6 +13,7 @@
 #include "TridiagQL.hpp"
 #include "EngineMeasurements.hpp"
 #include "Noise.hpp"
+#include "TargetStates.hpp"
 
 static void dump_mat(const char* tag, PetscInt site, const Mat& m)
 {
@@ -310,6 +311,20 @@ int main()
                 for (PetscInt s = 0; s < nsweeps; ++s) v.push_back(S.At(false, s));
                 print_numbers("noise", v);
                 printf("any %d json %s\n", (int)S.Any(), S.Json().c_str());
+            }
+        } else if (cmd == "targets") {          /* targets <-nstates value or "none"> <-state_weights value or "none"> nstates_of_sector  ->  rc, then k, k_step and the step's normalised weights */
+            std::string ns, sw; PetscInt in_sector; is >> ns >> sw >> in_sector;
+            dmrgx_host::Options::Global().Clear();
+            if (ns != "none") PetscOptionsSetValue(NULL, "-nstates", ns.c_str());
+            if (sw != "none") PetscOptionsSetValue(NULL, "-state_weights", sw == "empty" ? "" : sw.c_str());
+            dmrgx_host::TargetStates T;
+            ierr = dmrgx_host::ReadTargetStatesOptions(PETSC_COMM_WORLD, T);
+            printf("rc %d\n", ierr);
+            if (!ierr) {
+                const std::vector<double> w = T.StepWeights(in_sector);
+                printf("k %lld k_step %lld\n", LLD(T.k), LLD((PetscInt)w.size()));
+                print_numbers("weights", w);
+                print_numbers("all", T.weights);
             }
         } else if (cmd == "measopts") {         /* measopts ranks -option value ...: the model and the measurement options as on the driver's command line ("_": no value)  ->  rc of EngineMeasurements::ReadOptions on that many ranks, then one line per measurement */
             PetscMPIInt ranks; is >> ranks;

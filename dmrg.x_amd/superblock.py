@@ -143,6 +143,26 @@ class KronPlan:
             _capi.check(rc)
         return e0.value, psi, stats
 
+    def eigs_lowest_orth(self, Q, ncv=16, max_it=1000, tol=1e-8, seed=1, psi0=None, min_initial_norm2=0.0, stream=None):
+        """Lowest eigenpair of P H P on the complement of the rows of Q (dmrgx_eigs_lowest_orth): the next excited state of the sector
+        when Q holds the states already found.  Q: None (no row: the call forwards to dmrgx_eigs_lowest), or a 2-D f64 device tensor of
+        nq rows with unit stride along the vector (its row stride is the library's ldq), only read.  psi0: a start vector, projected
+        against Q by the library.  Returns (e, psi, stats); psi is orthogonal to Q."""
+        nq, q_ptr, ldq = 0, C.c_void_p(), 0
+        if Q is not None:
+            assert Q.dtype == torch.float64 and Q.dim() == 2 and Q.shape[1] >= self.info.n_states and (Q.shape[1] <= 1 or Q.stride(1) == 1)
+            nq, q_ptr, ldq = Q.shape[0], C.c_void_p(Q.data_ptr()), Q.stride(0) if Q.shape[0] > 1 else max(Q.stride(0), Q.shape[1])
+        opts = _capi.EigsOpts()
+        opts.ncv, opts.max_it, opts.tol, opts.seed, opts.min_initial_norm2 = ncv, max_it, tol, seed, min_initial_norm2
+        psi = self.new_vector()
+        if psi0 is not None:
+            psi.copy_(psi0)
+            opts.use_initial = 1
+        e, stats = C.c_double(0.0), _capi.EigsStats()
+        _capi.check(_capi.lib().dmrgx_eigs_lowest_orth(self._handle, C.byref(opts), int(nq), q_ptr, int(ldq), C.byref(e), C.c_void_p(psi.data_ptr()),
+                                                       C.byref(stats), self._stream_ptr(stream)))
+        return e.value, psi, stats
+
     def lanczos_coeffs(self, v0, nsteps, breakdown_tol=0.0, stream=None):
         """Lanczos coefficients of H from the start vector v0 (dmrgx_kron_lanczos_coeffs): plain three-term recursion, device-resident,
         breakdown decided on the device.  v0: f64 device tensor of n_states (reference layout, only read).  Returns
@@ -461,6 +481,36 @@ def noise_expand(sb_or_layout, psi, side, ops, coef, out=None):
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     _capi.check(L.dmrgx_kron_noise_expand(*head, side, n_ops, arr, cf, extent, C.byref(n_out), C.c_void_p(out.data_ptr()), st))
     torch.cuda.current_stream().synchronize()       # the operator copies in `keep` are read by the queued work
+    return out, list(extent), n_out.value
+
+
+def states_expand(sb_or_layout, Psi, weights, side, out=None):
+    """Several states of one sector side by side, each times the square root of its weight (dmrgx_kron_states_expand): side 0 sets the
+    KronBlock slices of the states beside each other as columns, side 1 stacks them as rows, so that the density matrix of the expansion
+    on that side is the weighted average of the states'.  sb_or_layout: a Superblock or (left_sizes, right_sizes, blocks); Psi: a 2-D f64
+    device tensor of one row per state with unit stride along the vector (its row stride is the library's ldpsi), only read; weights: one
+    non-negative number per state.  out: a 1-D f64 device tensor with unit stride of at least n_out elements (elements beyond n_out are left
+    alone); default: a new tensor of n_out.  Returns (Y, extent, n_out); `noise_rdm_layout` turns extent into the layout the density-matrix
+    solver takes."""
+    _capi.require_device()
+    left_sizes, right_sizes, blocks = (sb_or_layout.left_sizes, sb_or_layout.right_sizes, sb_or_layout.blocks) if hasattr(sb_or_layout, "blocks") else sb_or_layout
+    n = sum(left_sizes[il] * right_sizes[ir] for il, ir in blocks)
+    assert Psi.dtype == torch.float64 and Psi.dim() == 2 and Psi.shape[1] >= n and (Psi.shape[1] <= 1 or Psi.stride(1) == 1)
+    ns = Psi.shape[0]
+    assert len(weights) == ns
+    ldpsi = Psi.stride(0) if ns > 1 else max(Psi.stride(0), Psi.shape[1])
+    ls, rs = _i32(left_sizes), _i32(right_sizes)
+    sl, sr = _capi.Sectors(len(left_sizes), ls), _capi.Sectors(len(right_sizes), rs)
+    bil, bir = _i32([b[0] for b in blocks]), _i32([b[1] for b in blocks])
+    head = (C.byref(sl), C.byref(sr), len(blocks), bil, bir, ns, C.c_void_p(Psi.data_ptr()), int(ldpsi), (C.c_double * ns)(*[float(w) for w in weights]), int(side))
+    extent, n_out = (C.c_int32 * len(blocks))(), C.c_int64(0)
+    L = _capi.lib()
+    _capi.check(L.dmrgx_kron_states_expand(*head, extent, C.byref(n_out), None, None))
+    if out is None:
+        out = torch.empty(n_out.value, dtype=torch.float64, device=Psi.device)
+    assert out.dtype == torch.float64 and out.dim() == 1 and (out.numel() <= 1 or out.stride(0) == 1) and out.numel() >= n_out.value
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _capi.check(L.dmrgx_kron_states_expand(*head, extent, C.byref(n_out), C.c_void_p(out.data_ptr()), st))
     return out, list(extent), n_out.value
 
 

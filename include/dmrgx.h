@@ -40,6 +40,9 @@
  *   dmrgx_vec_project_out       one vector removed from a family of vectors, coefficients returned: (D_b - <D_b>) psi for all bonds (-dsf_dimer)
  *   dmrgx_kron_static_response  the static linear response sum_{n>0} |n><n|v0> / (E_n - E0) by a device-resident conjugate-gradient run on the
  *                               complement of psi, and its overlaps with a family of vectors: chi_ic = d<Sz_i>/dh_c, chi_bc (-chi_sites, -chi_bonds)
+ *   dmrgx_eigs_lowest_orth      the lowest eigenpair on the complement of states already found, and dmrgx_kron_states_expand, those states
+ *   dmrgx_kron_states_expand    side by side as the input of dmrgx_rdm_create_subset: the k lowest states of a sector under a
+ *                               state-averaged density matrix (-nstates)
  *   dmrgx_comm_*             <- the communicator of the reference's MPI path: VecScatter-to-all of x inside every MatMult
  *                               (src/DMRGKron.cpp:1833-1834) and the MPI_Allreduce behind SLEPc's VecDot / VecNorm
  *
@@ -297,6 +300,28 @@ typedef struct {
 
 dmrgx_status dmrgx_eigs_lowest(dmrgx_kron_plan* plan, const dmrgx_eigs_opts* opts, double* e0,
                                double* psi_full, dmrgx_eigs_stats* stats, void* stream);
+/* The lowest eigenpair of P H P on the complement of span(Q), P = 1 - Qt Qt^T: the excited states of one sector, found one after another,
+ * each call with the states already found as Q (-nstates).  That resolves exact degeneracies, which a single Krylov sequence cannot.
+ * Q_dev: nq rows of n_states doubles, ldq >= n_states, any 8-byte alignment, only read.  The call orthonormalises a private, 16-byte
+ * aligned copy Qt of it (CGS2 row by row, in row order).  psi_dev: n_states doubles; with opts->use_initial it holds the start vector,
+ * which is projected against Qt first; the run starts from the projected random vector instead (stats->start_rejected = 1) when the
+ * projected squared norm is not finite and positive or lies below max(min_initial_norm2, 1e-20 times the unprojected squared norm).
+ * nq == 0 forwards to dmrgx_eigs_lowest with the same options: the same bits in e, psi and stats.
+ * Read from opts as in dmrgx_eigs_lowest: ncv (0: 16; at most 64, never more than n_states - nq), max_it, tol (0: 1e-8), seed,
+ * use_initial, min_initial_norm2.  `method` is ignored for nq > 0.
+ * Refused with DMRGX_ERR_ARG before any MatMult: a null plan, opts, e or psi; nq < 0; a null Q or ldq < n_states; nq >= n_states; a row of
+ * Q that is zero or not finite; a row whose norm after the projection against the rows before it falls below 1e-10 of its own norm
+ * (linearly dependent); a striped plan (world_size > 1); non-null allgather / allreduce_sum / comm; max_matvec > 0.
+ * Method: thick-restart Lanczos with the restart rule, the look at the Ritz pair after every step and the convergence test
+ * |r| <= tol |theta| of dmrgx_eigs_lowest's Lanczos path.  Every w = H v_j is orthogonalised twice against all rows of [Qt ; v_0 .. v_j];
+ * the Krylov space never grows past n_states - nq, where the answer is exact and converged = 1.
+ * Outputs: *e = theta; psi of unit norm, projected against Qt once more before the final normalisation (|<qt_i, psi>| <= 1e-13); stats as
+ * for dmrgx_eigs_lowest, `residual` that of P H P.  Not reaching tol within max_it restarts gives DMRGX_ERR_NOTCONV with the last iterate.
+ * Memory from the pool, with ld = n_states rounded up to even: (nq + ncv + 1) rows of ld doubles in one allocation, two work vectors of
+ * ld (the MatMult's input and output), (nq + ncv + 2) (n_states / 2048 + 1) doubles of per-workgroup partial sums, and O(nq + ncv^2)
+ * scalars.  No atomics, every sum has a fixed order: two calls give the same bits in e, psi and the stats (seconds apart). */
+dmrgx_status dmrgx_eigs_lowest_orth(dmrgx_kron_plan* plan, const dmrgx_eigs_opts* opts, int32_t nq, const double* Q_dev, int64_t ldq,
+                                    double* e, double* psi_dev, dmrgx_eigs_stats* stats, void* stream);
 
 /* Distributed solves only: where the MatMults of the solves since the last reset spent their time on this rank -- the all-gather that
  * rebuilds x (the reference's VecScatter-to-all, src/DMRGKron.cpp:1833-1834) and the apply behind it -- from HIP events on the
@@ -531,6 +556,35 @@ dmrgx_status dmrgx_kron_noise_expand(const dmrgx_sectors* left, const dmrgx_sect
                                      int32_t* extent /* host [nblocks]: expanded width (side 0) / height (side 1) of block k */,
                                      int64_t* n_out /* host: total doubles of the expansion */,
                                      double* Y_dev /* NULL: sizes only */, void* stream);
+
+/* ---- several target states: the states set side by side as the input of the state-averaged density matrix -------------- */
+/* For states Psi_0 .. Psi_{nstates-1} of one sector with weights w_s, the averaged density matrices sum_s w_s rho_L,s and sum_s w_s rho_R,s
+ * without a new density-matrix build: for the left block Psi'_k = [ sqrt(w_0) Psi_0,k | sqrt(w_1) Psi_1,k | ... ] has Psi' Psi'^T =
+ * sum_s w_s rho_L,s; for the right block the panels are stacked as rows and Psi''^T Psi'' = sum_s w_s rho_R,s.  This call writes the
+ * expansion; dmrgx_rdm_create_subset then runs on it unchanged, with `extent` as the sector table of the other side exactly as for
+ * dmrgx_kron_noise_expand (side 0: right table = extent, block_ir'[k] = k, side mask bit 0; side 1: left table = extent, block_il'[k] = k,
+ * bit 1).
+ * Sector tables and KronBlocks as in dmrgx_kron_term_apply.  Psi_dev: nstates rows in the reference vector layout, row s at
+ * Psi_dev + s * ldpsi, ldpsi >= n_states, any 8-byte alignment, only read; the columns beyond n_states are neither read nor touched.
+ * weight: host array [nstates], non-negative and finite, not all zero; sqrt(w_s) is taken once on the host.
+ * Output: block k follows block k - 1 and is row-major.
+ *   side 0: n_L(IL_k) x extent[k], extent[k] = nstates * n_R(IR_k); columns [s n_R, (s + 1) n_R) are sqrt(w_s) Psi_s,k.
+ *   side 1: extent[k] x n_R(IR_k), extent[k] = nstates * n_L(IL_k); rows [s n_L, (s + 1) n_L) are sqrt(w_s) Psi_s,k.
+ * A panel of weight exactly 1 is a bit-for-bit copy; a panel of weight 0 is exact zeros whatever the state holds (it is not read).
+ * extent (host [nblocks]) and *n_out (host: nstates * n_states doubles) are always written.  Y_dev == NULL: sizes only -- nothing else is
+ * done, no device is touched, Psi_dev may be NULL.  Otherwise every element of [0, *n_out) of Y is written exactly once (Y may hold
+ * anything on entry, any 8-byte alignment).  One strided scaled-copy kernel over all blocks and panels, in 16-byte pairs where a panel's
+ * rows are 16-byte aligned on both sides.  Memory from the pool: the table of panels.
+ * Refused (DMRGX_ERR_ARG): a null sector table, KronBlock list, extent or n_out; nstates < 1 or null weights; ldpsi < n_states; a weight
+ * that is negative or not finite; all weights zero; a side that is not 0 or 1; a null Psi with Y given; Y overlapping Psi; a KronBlock
+ * listed twice; an expanded extent above 2^31 - 1.  DMRGX_ERR_OUTOFRANGE: a KronBlock outside the tables.
+ * No atomics: two calls give the same bits. */
+dmrgx_status dmrgx_kron_states_expand(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
+                                      const int32_t* block_il, const int32_t* block_ir,
+                                      int32_t nstates, const double* Psi_dev, int64_t ldpsi, const double* weight /* host [nstates] */,
+                                      int32_t side, int32_t* extent /* host [nblocks]: expanded width (side 0) / height (side 1) of block k */,
+                                      int64_t* n_out /* host: total doubles of the expansion */,
+                                      double* Y_dev /* NULL: sizes only */, void* stream);
 
 /* ---- products of sector operators of one block (observables of three site operators: the scalar chirality) ------------- */
 /* C_o = sum over the strings t of output o of  coeff_t * F_{t,1} F_{t,2} [F_{t,3}],  o < n_out:  sums of products of one, two or three
