@@ -179,6 +179,10 @@ SIGNATURES = {
     "dmrgx_kron_term_gram": (C.c_int32, [C.POINTER(Sectors), C.POINTER(Sectors), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
                                          C.c_int32, C.POINTER(SecOp), C.c_int32, C.POINTER(SecOp), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Term),
                                          C.c_size_t, C.c_void_p, C.c_int64, C.POINTER(GramReport), C.c_void_p]),
+    "dmrgx_kron_term_gram_states": (C.c_int32, [C.POINTER(Sectors), C.POINTER(Sectors), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                C.c_int32, C.c_void_p, C.c_int64,
+                                                C.c_int32, C.POINTER(SecOp), C.c_int32, C.POINTER(SecOp), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Term),
+                                                C.c_size_t, C.c_void_p, C.c_int64, C.POINTER(GramReport), C.c_void_p]),
     "dmrgx_kron_term_apply": (C.c_int32, [C.POINTER(Sectors), C.POINTER(Sectors), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
                                           C.c_int32, C.POINTER(SecOp), C.c_int32, C.POINTER(SecOp), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Term),
                                           C.c_void_p, C.c_int64, C.c_void_p]),

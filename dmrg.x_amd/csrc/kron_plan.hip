@@ -1110,7 +1110,12 @@ void emit_groups(GemmBatch& gb, GemmSet& set, double* Y, int32_t ldc, int32_t nL
 // the KronBlocks of the output list Out (a second layout over the same sector tables, never null with Y_dev; dmrgx_kron_term_apply passes L itself) at their
 // offsets in its reference layout, all in one slice whose "workspace" is the caller's Y (vector stride ldy), and no Gram matrix is
 // taken; the sources are looked up in L, and the groups, products and cell copies are emitted exactly as for the Gram matrix.
-dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* psi_dev,
+// Several states (nstates > 1, dmrgx_kron_term_gram_states; never with Y_dev): psi_dev holds nstates rows of stride ldpsi, and the family is
+// the nstates * nvec images in state-major order, member s * nvec + v built from row s.  The image blocks of a slice hold the whole family;
+// within a slice the states are built one after another, each with its own pair of GEMM sets launched in stream order, so that the
+// intermediates T of the two-sided terms are those of one state at a time and the scratch does not grow with nstates.  The operand copies
+// are made once.  With (nstates, ldpsi) = (1, 0) every table and launch is what it was before there were states.
+dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* psi_dev, int32_t nstates, int64_t ldpsi,
                              int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
                              int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
                              size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, hipStream_t st,
@@ -1119,6 +1124,7 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
     const dmrgx_sectors& SL = *L.SL;
     const dmrgx_sectors& SR = *L.SR;
     const int32_t nterms = vec_first[nvec];
+    const int64_t nfam = (int64_t)nstates * nvec;     // the vectors an image block holds
     auto shift_l = [&](const dmrgx_term& t) { return t.left_op < 0 ? 0 : left_ops[t.left_op].shift; };
     auto shift_r = [&](const dmrgx_term& t) { return t.right_op < 0 ? 0 : right_ops[t.right_op].shift; };
     std::vector<std::vector<NCell>> cellsL((size_t)n_left_ops), cellsR((size_t)n_right_ops);
@@ -1151,12 +1157,12 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
         for (int32_t k = 0; k < Out->nblocks; ++k) imgs.push_back(ImgBlock{Out->il[k], Out->ir[k], Out->ref_off[k + 1] - Out->ref_off[k], Out->ref_off[k], 0});
     if (Y_dev) slice_len.assign(1, ldy);              // one slice: the caller's vectors, stride ldy
     // slices of image blocks that fit the workspace
-    const int64_t bound = (int64_t)((workspace_bytes ? workspace_bytes : ((size_t)1 << 30)) / sizeof(double)) / nvec;
+    const int64_t bound = (int64_t)((workspace_bytes ? workspace_bytes : ((size_t)1 << 30)) / sizeof(double)) / nfam;
     for (ImgBlock& im : imgs) {
         if (Y_dev) break;
         if (im.size > bound)
-            DMRGX_FAIL(DMRGX_ERR_ARG, "%s: image block (%d,%d) of %d x %d needs %lld bytes for the %d vectors, workspace_bytes allows %lld",
-                       fn, im.a, im.b, SL.size[im.a], SR.size[im.b], (long long)(im.size * nvec * (int64_t)sizeof(double)), nvec, (long long)(bound * nvec * (int64_t)sizeof(double)));
+            DMRGX_FAIL(DMRGX_ERR_ARG, "%s: image block (%d,%d) of %d x %d needs %lld bytes for the %lld vectors, workspace_bytes allows %lld",
+                       fn, im.a, im.b, SL.size[im.a], SR.size[im.b], (long long)(im.size * nfam * (int64_t)sizeof(double)), (long long)nfam, (long long)(bound * nfam * (int64_t)sizeof(double)));
         if (slice_len.empty() || slice_len.back() + im.size > bound) slice_len.push_back(0);
         im.slice = (int32_t)slice_len.size() - 1;
         im.off = slice_len.back();
@@ -1164,7 +1170,7 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
     }
     const int32_t nslices = (int32_t)slice_len.size();
     if (nslices == 0) {                               // no shifted sector pair exists: every image is zero
-        DMRGX_CHK(dmrgx_vec_gram(nvec, nvec, 0, nullptr, 0, nullptr, 0, G_dev, ldg, 0, report, st));
+        DMRGX_CHK(dmrgx_vec_gram((int32_t)nfam, (int32_t)nfam, 0, nullptr, 0, nullptr, 0, G_dev, ldg, 0, report, st));
         return DMRGX_OK;
     }
     // the source KronBlock of term t in image block im (-1: none)
@@ -1208,37 +1214,43 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
 
     DevBuf W, trans, scratch, tab;
     if (Y_dev) W.view(Y_dev, (size_t)((nvec - 1) * ldy + Out->ref_off[Out->nblocks]) * sizeof(double));
-    else DMRGX_CHK(W.alloc_f64((size_t)(*std::max_element(slice_len.begin(), slice_len.end())) * nvec, st));
+    else DMRGX_CHK(W.alloc_f64((size_t)(*std::max_element(slice_len.begin(), slice_len.end())) * (size_t)nfam, st));
     if (ou.trans_doubles > 0) DMRGX_CHK(trans.alloc_f64((size_t)ou.trans_doubles, st));
     const int64_t scratch_max = *std::max_element(scratch_len.begin(), scratch_len.end());
     if (scratch_max > 0) DMRGX_CHK(scratch.alloc_f64((size_t)scratch_max, st));
     ou.bind(trans.as<double>());
 
     GemmBatch gb;
-    std::vector<GemmSet> sets1(nslices), sets2(nslices);      // stage 1: the intermediates of a slice; stage 2: its images
+    std::vector<GemmSet> sets1((size_t)nslices * nstates), sets2((size_t)nslices * nstates);      // per (slice, state) -- stage 1: the intermediates; stage 2: the images
     EmitScratch emit;
     std::vector<ImgContrib> lefts, rights;
-    for (const auto& kv : toff) {                              // (ordered by slice, right operator, KronBlock)
-        const int32_t s = std::get<0>(kv.first), r = std::get<1>(kv.first), k = std::get<2>(kv.first);
-        const int32_t nl = SL.size[L.il[k]], b = L.ir[k] - right_ops[r].shift, ldx = SR.size[L.ir[k]];
-        lefts.clear();
-        rights.assign(1, ImgContrib{&ou.uses.at(std::make_tuple((int)SIDE_RIGHT, r, bits_of(1.0))), psi_dev + L.ref_off[k], ldx});
-        emit_groups(gb, sets1[s], scratch.as<double>() + kv.second, SR.size[b], nl, SR.size[b], -1, b, lefts, rights, emit);
+    for (int32_t s = 0; s < nstates; ++s) {
+        const double* psi = psi_dev + (int64_t)s * ldpsi;
+        for (const auto& kv : toff) {                              // (ordered by slice, right operator, KronBlock)
+            const int32_t sl = std::get<0>(kv.first), r = std::get<1>(kv.first), k = std::get<2>(kv.first);
+            const int32_t nl = SL.size[L.il[k]], b = L.ir[k] - right_ops[r].shift, ldx = SR.size[L.ir[k]];
+            lefts.clear();
+            rights.assign(1, ImgContrib{&ou.uses.at(std::make_tuple((int)SIDE_RIGHT, r, bits_of(1.0))), psi + L.ref_off[k], ldx});
+            emit_groups(gb, sets1[(size_t)sl * nstates + s], scratch.as<double>() + kv.second, SR.size[b], nl, SR.size[b], -1, b, lefts, rights, emit);
+        }
     }
-    for (const ImgBlock& im : imgs) {
-        const int32_t nLa = SL.size[im.a], nRb = SR.size[im.b];
-        const int64_t ldw = slice_len[im.slice];
-        for (int32_t v = 0; v < nvec; ++v) {
-            lefts.clear(); rights.clear();
-            for (int32_t t = vec_first[v]; t < vec_first[v + 1]; ++t) {
-                const dmrgx_term& T = terms[t];
-                const int32_t k = source(T, im);
-                if (k < 0) continue;
-                if (T.left_op >= 0 && T.right_op >= 0) lefts.push_back(ImgContrib{tuse[t].left, scratch.as<double>() + toff.at(std::make_tuple(im.slice, T.right_op, k)), nRb});
-                else if (T.right_op >= 0) rights.push_back(ImgContrib{tuse[t].right, psi_dev + L.ref_off[k], SR.size[L.ir[k]]});
-                else lefts.push_back(ImgContrib{tuse[t].left, psi_dev + L.ref_off[k], nRb});
+    for (int32_t s = 0; s < nstates; ++s) {
+        const double* psi = psi_dev + (int64_t)s * ldpsi;
+        for (const ImgBlock& im : imgs) {
+            const int32_t nLa = SL.size[im.a], nRb = SR.size[im.b];
+            const int64_t ldw = slice_len[im.slice];
+            for (int32_t v = 0; v < nvec; ++v) {
+                lefts.clear(); rights.clear();
+                for (int32_t t = vec_first[v]; t < vec_first[v + 1]; ++t) {
+                    const dmrgx_term& T = terms[t];
+                    const int32_t k = source(T, im);
+                    if (k < 0) continue;
+                    if (T.left_op >= 0 && T.right_op >= 0) lefts.push_back(ImgContrib{tuse[t].left, scratch.as<double>() + toff.at(std::make_tuple(im.slice, T.right_op, k)), nRb});
+                    else if (T.right_op >= 0) rights.push_back(ImgContrib{tuse[t].right, psi + L.ref_off[k], SR.size[L.ir[k]]});
+                    else lefts.push_back(ImgContrib{tuse[t].left, psi + L.ref_off[k], nRb});
+                }
+                emit_groups(gb, sets2[(size_t)im.slice * nstates + s], W.as<double>() + ((int64_t)s * nvec + v) * ldw + im.off, nRb, nLa, nRb, im.a, im.b, lefts, rights, emit);
             }
-            emit_groups(gb, sets2[im.slice], W.as<double>() + (int64_t)v * ldw + im.off, nRb, nLa, nRb, im.a, im.b, lefts, rights, emit);
         }
     }
     PackedUpload pk;
@@ -1251,11 +1263,13 @@ dmrgx_status term_gram_build(const char* fn, const GramLayout& L, const double* 
     DMRGX_CHK(ou.launch_copies(tab, o_tiles, o_tasks, trans.as<double>(), st));
     dmrgx_gram_report total{0, nslices, 0};
     for (int32_t s = 0; s < nslices; ++s) {               // fixed order: slice s is added to the sum of the slices before it
-        DMRGX_CHK(gb.launch(sets1[s], tab, st));
-        DMRGX_CHK(gb.launch(sets2[s], tab, st));
+        for (int32_t j = 0; j < nstates; ++j) {           // state j's images read its T: stream order keeps the next state's T behind them
+            DMRGX_CHK(gb.launch(sets1[(size_t)s * nstates + j], tab, st));
+            DMRGX_CHK(gb.launch(sets2[(size_t)s * nstates + j], tab, st));
+        }
         if (Y_dev) continue;
         dmrgx_gram_report r{};
-        DMRGX_CHK(dmrgx_vec_gram(nvec, nvec, slice_len[s], W.as<double>(), slice_len[s], W.as<double>(), slice_len[s], G_dev, ldg, s > 0 ? 1 : 0, &r, st));
+        DMRGX_CHK(dmrgx_vec_gram((int32_t)nfam, (int32_t)nfam, slice_len[s], W.as<double>(), slice_len[s], W.as<double>(), slice_len[s], G_dev, ldg, s > 0 ? 1 : 0, &r, st));
         total.tiles = r.tiles;
         total.slab_doubles = std::max(total.slab_doubles, r.slab_doubles);
     }
@@ -1300,7 +1314,27 @@ extern "C" dmrgx_status dmrgx_kron_term_gram(const dmrgx_sectors* left, const dm
     int32_t shift = 0;
     DMRGX_CHK(term_list_check(fn, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, &shift));
     if (!G_dev || ldg < nvec) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null G or ldg %lld below the %d vectors", fn, (long long)ldg, nvec);
-    return term_gram_build(fn, L, psi_dev, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, workspace_bytes, G_dev, ldg, report, (hipStream_t)stream);
+    return term_gram_build(fn, L, psi_dev, 1, 0, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, workspace_bytes, G_dev, ldg, report, (hipStream_t)stream);
+}
+
+// dmrgx_kron_term_gram_states: the Gram matrix of the images of several states, state-major (the builder's multi-state path).
+extern "C" dmrgx_status dmrgx_kron_term_gram_states(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
+                                                    const int32_t* block_il, const int32_t* block_ir,
+                                                    int32_t nstates, const double* Psi_dev, int64_t ldpsi,
+                                                    int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
+                                                    int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
+                                                    size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, void* stream)
+{
+    const char* fn = "kron_term_gram_states";
+    GramLayout L;
+    if (nstates < 1) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: nstates %d: at least one state", fn, nstates);
+    DMRGX_CHK(gram_layout(fn, left, right, nblocks, block_il, block_ir, Psi_dev, L));
+    if (ldpsi < L.ref_off[nblocks]) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: ldpsi %lld below the %lld states of a row", fn, (long long)ldpsi, (long long)L.ref_off[nblocks]);
+    int32_t shift = 0;
+    DMRGX_CHK(term_list_check(fn, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, &shift));
+    if ((int64_t)nstates * nvec > INT32_MAX) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: %d states x %d vectors: too many", fn, nstates, nvec);
+    if (!G_dev || ldg < (int64_t)nstates * nvec) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null G or ldg %lld below the %d x %d vectors", fn, (long long)ldg, nstates, nvec);
+    return term_gram_build(fn, L, Psi_dev, nstates, ldpsi, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, workspace_bytes, G_dev, ldg, report, (hipStream_t)stream);
 }
 
 // dmrgx_kron_term_apply: the images themselves, written once each into the caller's Y (the builder's output mode).
@@ -1319,7 +1353,7 @@ extern "C" dmrgx_status dmrgx_kron_term_apply(const dmrgx_sectors* left, const d
     const int64_t N = L.ref_off[nblocks];
     if (!Y_dev || ldy < N) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null Y or ldy %lld below the %lld states", fn, (long long)ldy, (long long)N);
     if (Y_dev < psi_dev + N && psi_dev < Y_dev + (int64_t)(nvec - 1) * ldy + N) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: Y overlaps psi", fn);
-    return term_gram_build(fn, L, psi_dev, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, 0, nullptr, 0, nullptr, (hipStream_t)stream, Y_dev, ldy, &L);      // output list == input list
+    return term_gram_build(fn, L, psi_dev, 1, 0, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, 0, nullptr, 0, nullptr, (hipStream_t)stream, Y_dev, ldy, &L);      // output list == input list
 }
 
 // dmrgx_kron_term_apply_to: the same images written in the layout of a second KronBlock list (the sector the total shift leads to).
@@ -1341,7 +1375,7 @@ extern "C" dmrgx_status dmrgx_kron_term_apply_to(const dmrgx_sectors* left, cons
     const int64_t N = L.ref_off[nblocks], NO = O.ref_off[n_out];
     if (!Y_dev || ldy < NO) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: null Y or ldy %lld below the %lld output states", fn, (long long)ldy, (long long)NO);
     if (Y_dev < psi_dev + N && psi_dev < Y_dev + (int64_t)(nvec - 1) * ldy + NO) DMRGX_FAIL(DMRGX_ERR_ARG, "%s: Y overlaps psi", fn);
-    return term_gram_build(fn, L, psi_dev, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, 0, nullptr, 0, nullptr, (hipStream_t)stream, Y_dev, ldy, &O);
+    return term_gram_build(fn, L, psi_dev, 1, 0, n_left_ops, left_ops, n_right_ops, right_ops, nvec, vec_first, terms, 0, nullptr, 0, nullptr, (hipStream_t)stream, Y_dev, ldy, &O);
 }
 
 // dmrgx_kron_noise_expand: psi with the images c_a A_a psi of one side's operators set beside it (side 0: as further columns of the

@@ -208,7 +208,7 @@ public:
         ierr = dmrgx_host::ReadTargetStatesOptions(mpi_comm, targets); CHKERRQ(ierr);
         if (targets.k > 1 && mpi_size > 1) SETERRQ2(mpi_comm, PETSC_ERR_SUP, "-nstates %lld is not available on more than one rank (got %d): the deflated solve and the expansion of the density matrix are not striped.", LLD(targets.k), (int)mpi_size);
         if (targets.k > 1 && noise.Any()) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-nstates %lld cannot be combined with -noise / -noise_warmup: both widen the input of the density matrix.", LLD(targets.k));
-        /* -corr_matrix, -corr_dimer, -corr_chiral, -dsf, -dsf_sites, -dsf_cheb, -dsf_dimer, -dsf_pm, -dsf_cv and what goes with them (EngineMeasurements.hpp) */
+        /* -corr_matrix, -corr_dimer, -corr_chiral, -dsf, -dsf_sites, -dsf_cheb, -dsf_dimer, -dsf_pm, -dsf_cv, -chi_sites / -chi_bonds, -states_corr and what goes with them (EngineMeasurements.hpp) */
         ierr = engine_measurements.ReadOptions(mpi_comm, mpi_rank, mpi_size, num_sites, Ham); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-step_profile", &step_profile, NULL); CHKERRQ(ierr);
 
@@ -600,7 +600,8 @@ public:
             if (do_measurements) { ierr = MeasureTargetStates(KronBlocks, gsv_r, tstep); CHKERRQ(ierr); }
         }
         const bool averaged = tstep.more.size() > 0;
-        const dmrgx_host::MeasurementContext mctx{KronBlocks, gsv_r, &H, Terms, gse_r, num_sites, qn_sector, GlobIdx, LoopTypeName(), verbose, do_shell, mpi_comm, mpi_rank, mpi_size, data_dir};
+        const dmrgx_host::MeasurementContext mctx{KronBlocks, gsv_r, &H, Terms, gse_r, num_sites, qn_sector, GlobIdx, LoopTypeName(), verbose, do_shell, mpi_comm, mpi_rank, mpi_size, data_dir,
+                                                     averaged ? dmrgx_host::TargetedStatesView{tstep.rows->dev_ro(), tstep.ld, (PetscInt)tstep.energies.size(), tstep.energies.data()} : dmrgx_host::TargetedStatesView{}};
         if (do_measurements) { ierr = engine_measurements.RunWithPlan(mctx, Ham); CHKERRQ(ierr); }      /* -dsf, -dsf_sites, -dsf_cheb, -dsf_dimer, -dsf_cv: they need the plan */
         ierr = MatDestroy_KronSumShell(&H); CHKERRQ(ierr);
         ierr = MatDestroy(&H); CHKERRQ(ierr);
@@ -1355,7 +1356,7 @@ public:
             fprintf(fp_corr, " ]");
             fflush(fp_corr);
         }
-        if (mctx) { ierr = engine_measurements.RunAtCentre(*mctx, Ham); CHKERRQ(ierr); }      /* -corr_matrix, -corr_dimer, -corr_chiral */
+        if (mctx) { ierr = engine_measurements.RunAtCentre(*mctx, Ham); CHKERRQ(ierr); }      /* -corr_matrix, -corr_dimer, -corr_chiral, -states_corr */
         return 0;
     }
 
@@ -2022,7 +2023,7 @@ private:
     int64_t noise_max_bytes = 0;                /* the largest expansion a truncation held (DMRGRun.json NoiseMaxExpansionBytes) */
     PetscInt noise_ops[2] = {0, 0}, noise_expansions = 0;      /* operators per side of the largest list; expansions built */
     PetscBool use_corr_batch = PETSC_TRUE;      /* -corr_batch 0: every correlator through its own MatMult + dot, as the reference does */
-    dmrgx_host::EngineMeasurements engine_measurements;      /* the ten engine-extension measurements: options, record files, runs (EngineMeasurements.hpp) */
+    dmrgx_host::EngineMeasurements engine_measurements;      /* the eleven engine-extension measurements: options, record files, runs (EngineMeasurements.hpp) */
 };
 
 #endif

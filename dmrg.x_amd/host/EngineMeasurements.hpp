@@ -1,8 +1,8 @@
 #ifndef DMRGX_HOST_ENGINEMEASUREMENTS_HPP
 #define DMRGX_HOST_ENGINEMEASUREMENTS_HPP
-/** The ten engine-extension measurements of the sweep engine, on top of what they share (Measurements.hpp): -corr_matrix, -corr_dimer,
-    -corr_chiral, -dsf, -dsf_sites, -dsf_cheb, -dsf_dimer, -dsf_pm, -dsf_cv and -chi_sites / -chi_bonds.  Each is a struct of its flag, its options, its record
-    file, a ReadOptions and a Run; EngineMeasurements holds the ten as plain members and calls them in a fixed order.  What a Run needs
+/** The eleven engine-extension measurements of the sweep engine, on top of what they share (Measurements.hpp): -corr_matrix, -corr_dimer,
+    -corr_chiral, -dsf, -dsf_sites, -dsf_cheb, -dsf_dimer, -dsf_pm, -dsf_cv, -chi_sites / -chi_bonds and -states_corr.  Each is a struct of its flag, its options, its record
+    file, a ReadOptions and a Run; EngineMeasurements holds the eleven as plain members and calls them in a fixed order.  What a Run needs
     from the step comes in a MeasurementContext, the lattice through a template parameter: nothing here depends on the block or the
     container class, so host_tool.cpp reads the options without a GPU (command measopts). */
 #include <random>
@@ -10,6 +10,10 @@
 #include "Measurements.hpp"
 
 namespace dmrgx_host {
+
+/** The states of a step with -nstates k > 1: count rows of stride ld on the device, row s the state s in the layout of psi (row 0 is psi),
+    and their energies.  Empty (count 0) with -nstates 1 and in a step whose sector holds one state. */
+struct TargetedStatesView { const double* rows = nullptr; int64_t ld = 0; PetscInt count = 0; const double* energies = nullptr; };
 
 /** What a measurement reads of the DMRG step it runs in.  The step fills it once, after the eigensolve. */
 struct MeasurementContext {
@@ -22,6 +26,7 @@ struct MeasurementContext {
     PetscBool verbose, do_shell;
     MPI_Comm mpi_comm; PetscMPIInt mpi_rank, mpi_size;
     const std::string& data_dir;
+    TargetedStatesView states;                              /* -nstates k > 1: all states of the step */
     dmrgx_kron_plan* plan() const { return (*H)->plan; }
 };
 
@@ -1087,7 +1092,181 @@ struct StaticSusceptibility {
     }
 };
 
-/** The ten measurements, the options they share, and the order in which a DMRG step reads and runs them. */
+/** -states_corr 1 (engine extension, with -nstates k >= 2): what the k targeted states ARE -- the correlations of every state and the
+    transition amplitudes between them, at every measurement point.  Four dmrgx_kron_term_gram_states calls on the k_step states of the
+    step (the rows of MeasurementContext::states), each the Gram matrix of a state-major family of images O_a psi_s:
+        identity + Sz of every site (shift 0), Sp of every site (+1), Sm of every site (Sp read transposed, -1),
+        identity + the bond images D_b = S_i . S_j (DimerFrame's operators and terms, built once; shift 0).
+    The block (s, t) of a Gram matrix is < O_a psi_s , O_b psi_t > = < psi_s | O_a^T O_b | psi_t >; its identity row is the one-point
+    amplitude < psi_s | O_b | psi_t >.  The record (StateCorrelations.json, one per measurement):
+      Energies, Overlaps (k x k, the identity rows of the first family), tStates (seconds), the bond list;
+      Sz[s][t] (N numbers, lattice numbering) and D[s][t] (nb numbers) for all s, t: the transition amplitudes;
+      TransitionSz[s][t]: the Lx x Ly single-mode weights W(q) = (1/N) |sum_i e^(i q . r_i) Sz[s][t][i]|^2 (TransitionWeight, Measurements.hpp) --
+        with E_s - E_t the momentum and the weight of the pole that state s contributes to S^zz(q, w) of state t;
+      States[s]: SzSz, SmSp, SpSm, SS, StructureFactor (the tables of -corr_matrix, same formulas, SS with + Sz_i on its diagonal) and DD
+        (the table of -corr_dimer), from the diagonal blocks (s, s);
+      with -states_corr_cross 1, Cross: per pair s < t the off-diagonal blocks SzSz, SmSp, SpSm, DD.  Of an exactly degenerate pair the
+        solver returns an arbitrary rotation: only the whole 2 x 2 block over the pair has meaning, and this is where it is.
+    Every table is < psi_s | O_a^T O_b | psi_t > of TRUNCATED block operators: it equals < psi_s | O_a O_b | psi_t > (O^T for Sp: Sm) when
+    nothing was truncated or the two operators sit in different blocks -- truncated operators of one block do not commute, the caveat of
+    the SpSm table of -corr_matrix.  The signs of nondegenerate states are arbitrary: Sz[s][t] and D[s][t], s != t, carry the product of two.
+    Memory: the images of all k_step states of one family at a time (workspace slices of at least the largest image block of every member).
+    One rank, no noise: the limits of -nstates. */
+struct StateCorrelations {
+    PetscBool use = PETSC_FALSE;                /* -states_corr 1 */
+    PetscBool cross = PETSC_FALSE;              /* -states_corr_cross 1: the off-diagonal blocks too */
+    JsonRecordFile file{"%.17g"};               /* created at the first measurement */
+    PetscErrorCode ReadOptions(MPI_Comm comm)
+    {
+        PetscErrorCode ierr = PetscOptionsGetBool(NULL, NULL, "-states_corr", &use, NULL); CHKERRQ(ierr);
+        if (!use) return 0;
+        ierr = PetscOptionsGetBool(NULL, NULL, "-states_corr_cross", &cross, NULL); CHKERRQ(ierr);
+        PetscInt k = 1;
+        PetscBool set = PETSC_FALSE;
+        ierr = PetscOptionsGetInt(NULL, NULL, "-nstates", &k, &set); CHKERRQ(ierr);
+        if (!set || k < 2) SETERRQ1(comm, PETSC_ERR_ARG_WRONG, "-states_corr 1 needs -nstates k with k >= 2: it measures the targeted states against each other. Got -nstates %lld.", LLD(set ? k : 1));
+        return 0;
+    }
+
+    template<class Hamiltonian> PetscErrorCode Run(const MeasurementContext& ctx, const Hamiltonian& Ham)
+    {
+        const TargetedStatesView& V = ctx.states;
+        const PetscInt k = V.count;
+        if (k < 2) return 0;                                        /* a step whose sector holds one state: nothing between states */
+        PetscLogDouble t0, t1;
+        PetscTime(&t0);
+        PetscErrorCode ierr;
+        DimerFrame B;                                               /* (its CentreFrame serves the site families too) */
+        ierr = B.Init(ctx.KronBlocks, ctx.num_sites, Ham, ctx.psi, "State correlations"); CHKERRQ(ierr);
+        const CentreFrame& F = B.F;
+        const PetscInt N = F.N, nb = B.nb, Lx = Ham.Lx(), Ly = Ham.Ly();
+        std::vector<PetscInt> site;                                 /* lattice site of vector a of a site family (identity: -1) */
+        std::vector<double> G;
+        /* one site family over all states: [identity] + the operator of every left site + of every right site; G is (k n)^2, state-major */
+        auto family = [&](Op_t type, bool with_identity, PetscInt& n) -> PetscErrorCode {
+            SiteOperators T(F);
+            site.clear();
+            std::vector<dmrgx_term> terms;
+            if (with_identity) { terms.push_back(dmrgx_term{1.0, -1, -1}); site.push_back(-1); }
+            PetscErrorCode e = T.AllSites(type, site); CHKERRQ(e);
+            for (int32_t a = 0; a < (int32_t)T.ops[0].size(); ++a) terms.push_back(dmrgx_term{1.0, a, -1});
+            for (int32_t b = 0; b < (int32_t)T.ops[1].size(); ++b) terms.push_back(dmrgx_term{1.0, -1, b});
+            n = (PetscInt)terms.size();
+            std::vector<int32_t> first((size_t)n + 1);
+            for (PetscInt a = 0; a <= n; ++a) first[(size_t)a] = (int32_t)a;
+            /* the workspace holds at least the largest image block of every member: (IL - d, IR) and (IL, IR - d) of the family's shift d */
+            const int32_t d = type == OpSz ? 0 : (type == OpSp ? 1 : -1);
+            int64_t largest = 1;
+            for (size_t q = 0; q < F.bil.size(); ++q) {
+                const int32_t a = F.bil[q] - d, c = F.bir[q] - d;
+                if (a >= 0 && a < (int32_t)F.sizes[0].size()) largest = std::max<int64_t>(largest, (int64_t)F.sizes[0][(size_t)a] * F.sizes[1][(size_t)F.bir[q]]);
+                if (c >= 0 && c < (int32_t)F.sizes[1].size()) largest = std::max<int64_t>(largest, (int64_t)F.sizes[0][(size_t)F.bil[q]] * F.sizes[1][(size_t)c]);
+            }
+            const PetscInt nf = k * n;
+            const size_t workspace = std::max<size_t>((size_t)1 << 30, (size_t)largest * (size_t)nf * sizeof(double));
+            DevBuffer g((size_t)(nf * nf), DevBuffer::device_only_t{});
+            if (dmrgx_kron_term_gram_states(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), (int32_t)k, V.rows, V.ld, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
+                                            (int32_t)n, first.data(), terms.data(), workspace, g.dev_uninitialised(), nf, nullptr, nullptr)) SETERRQ1(ctx.mpi_comm, 1, "dmrgx_kron_term_gram_states: %s", dmrgx_last_error());
+            G.assign((size_t)(nf * nf), 0.0);
+            if (dmrgx_memcpy_d2h(G.data(), g.dev_ro(), G.size() * sizeof(double), nullptr)) SETERRQ1(ctx.mpi_comm, 1, "%s", dmrgx_last_error());
+            return 0;
+        };
+        /* the block (s, t) of a site family's G as a table over lattice sites */
+        auto block = [&](PetscInt s, PetscInt t, PetscInt n, PetscInt first) {
+            std::vector<double> table((size_t)(N * N), 0.0);
+            for (PetscInt a = first; a < n; ++a) for (PetscInt b = first; b < n; ++b)
+                table[(size_t)(site[(size_t)a] * N + site[(size_t)b])] = G[(size_t)((s * n + a) * (k * n) + t * n + b)];
+            return table;
+        };
+        typedef std::vector<std::vector<double>> Blocks;            /* [s * k + t] */
+        Blocks SzSz((size_t)(k * k)), SmSp((size_t)(k * k)), SpSm((size_t)(k * k)), DD((size_t)(k * k)), Sz((size_t)(k * k)), D((size_t)(k * k)), W((size_t)(k * k));
+        std::vector<double> overlaps((size_t)(k * k), 0.0);
+        auto wanted = [&](PetscInt s, PetscInt t) { return s == t || (cross && s < t); };
+        PetscInt n = 0;
+        ierr = family(OpSz, true, n); CHKERRQ(ierr);
+        for (PetscInt s = 0; s < k; ++s) for (PetscInt t = 0; t < k; ++t) {
+            overlaps[(size_t)(s * k + t)] = G[(size_t)((s * n) * (k * n) + t * n)];
+            Sz[(size_t)(s * k + t)].assign((size_t)N, 0.0);
+            for (PetscInt a = 1; a < n; ++a) Sz[(size_t)(s * k + t)][(size_t)site[(size_t)a]] = G[(size_t)((s * n) * (k * n) + t * n + a)];      /* < psi_s , Sz_i psi_t > */
+            if (wanted(s, t)) SzSz[(size_t)(s * k + t)] = block(s, t, n, 1);
+        }
+        ierr = family(OpSp, false, n); CHKERRQ(ierr);
+        for (PetscInt s = 0; s < k; ++s) for (PetscInt t = s; t < k; ++t) if (wanted(s, t)) SmSp[(size_t)(s * k + t)] = block(s, t, n, 0);
+        ierr = family(OpSm, false, n); CHKERRQ(ierr);
+        for (PetscInt s = 0; s < k; ++s) for (PetscInt t = s; t < k; ++t) if (wanted(s, t)) SpSm[(size_t)(s * k + t)] = block(s, t, n, 0);
+        ierr = B.GramStates(k, V.rows, V.ld, G); CHKERRQ(ierr);
+        const PetscInt nv = nb + 1;
+        for (PetscInt s = 0; s < k; ++s) for (PetscInt t = 0; t < k; ++t) {
+            std::vector<double>& d = D[(size_t)(s * k + t)];
+            d.assign((size_t)nb, 0.0);
+            for (PetscInt b = 0; b < nb; ++b) d[(size_t)b] = G[(size_t)((s * nv) * (k * nv) + t * nv + 1 + b)];                               /* < psi_s , D_b psi_t > */
+            if (!wanted(s, t)) continue;
+            std::vector<double>& dd = DD[(size_t)(s * k + t)];
+            dd.assign((size_t)(nb * nb), 0.0);
+            for (PetscInt b = 0; b < nb; ++b) for (PetscInt c = 0; c < nb; ++c) dd[(size_t)(b * nb + c)] = G[(size_t)((s * nv + 1 + b) * (k * nv) + t * nv + 1 + c)];
+        }
+        /* the single-mode weights of every transition, and per state S_i . S_j and S(q) as -corr_matrix forms them */
+        std::vector<PetscInt> rx((size_t)N), ry((size_t)N);
+        for (PetscInt i = 0; i < N; ++i) { ierr = Ham.To2D(i, rx[(size_t)i], ry[(size_t)i]); CHKERRQ(ierr); }
+        for (PetscInt st = 0; st < k * k; ++st) W[(size_t)st] = TransitionWeight(Lx, Ly, rx.data(), ry.data(), Sz[(size_t)st].data(), N);
+        Blocks SS((size_t)k), Sq((size_t)k);
+        for (PetscInt s = 0; s < k; ++s) {
+            const size_t ss = (size_t)(s * k + s);
+            SS[(size_t)s].assign((size_t)(N * N), 0.0);
+            for (PetscInt i = 0; i < N; ++i) for (PetscInt j = 0; j < N; ++j) SS[(size_t)s][(size_t)(i * N + j)] = SzSz[ss][(size_t)(i * N + j)] + SmSp[ss][(size_t)(i * N + j)] + (i == j ? Sz[ss][(size_t)i] : 0.0);
+            Sq[(size_t)s] = LatticeFourier(Lx, Ly, rx.data(), ry.data(), SS[(size_t)s].data(), N, (double)N);
+        }
+        PetscTime(&t1);
+        if (!ctx.mpi_rank && ctx.verbose)
+            printf("  * State correlations: %lld states, Gram of %lld vectors x %lld (Sz), %lld (Sp), %lld (Sm), %lld (bonds), tStates %.6f s\n", LLD(k), LLD(k * (N + 1)), LLD(ctx.psi->n), LLD(k * N), LLD(k * N), LLD(k * nv), t1 - t0);
+        if (ctx.mpi_rank) return 0;
+        ierr = file.Begin(ctx.data_dir + "StateCorrelations.json"); CHKERRQ(ierr);
+        FILE* fp = file.fp;
+        fprintf(fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"NStates\": %lld, \"tStates\": %.9g,\n   \"Energies\": ", LLD(ctx.GlobIdx), ctx.loop_type, LLD(k), t1 - t0);
+        file.Row(V.energies, k); fprintf(fp, ",\n");
+        file.Table("Overlaps", overlaps, k, k, ",\n");
+        file.BondList(B.bonds);
+        /* name[s][t]: a row of `len` numbers, or (rows > 0) a rows x len / rows table, per pair of states */
+        auto pairs = [&](const char* name, const Blocks& T, PetscInt len, PetscInt rows) {
+            fprintf(fp, "   \"%s\": [\n", name);
+            for (PetscInt s = 0; s < k; ++s) {
+                fprintf(fp, "     [");
+                for (PetscInt t = 0; t < k; ++t) {
+                    const double* v = T[(size_t)(s * k + t)].data();
+                    fprintf(fp, "%s", t ? ",\n      " : "");
+                    if (rows == 0) file.Row(v, len);
+                    else { fprintf(fp, "["); for (PetscInt r = 0; r < rows; ++r) { fprintf(fp, "%s", r ? ", " : ""); file.Row(v + r * (len / rows), len / rows); } fprintf(fp, "]"); }
+                }
+                fprintf(fp, "]%s\n", s + 1 < k ? "," : "");
+            }
+            fprintf(fp, "   ],\n");
+        };
+        pairs("Sz", Sz, N, 0); pairs("D", D, nb, 0); pairs("TransitionSz", W, Lx * Ly, Lx);
+        fprintf(fp, "   \"States\": [\n");
+        for (PetscInt s = 0; s < k; ++s) {
+            const size_t ss = (size_t)(s * k + s);
+            fprintf(fp, "   {\"State\": %lld, \"Energy\": %.17g,\n", LLD(s), V.energies[s]);
+            file.Table("SzSz", SzSz[ss], N, N, ",\n"); file.Table("SmSp", SmSp[ss], N, N, ",\n"); file.Table("SpSm", SpSm[ss], N, N, ",\n"); file.Table("SS", SS[(size_t)s], N, N, ",\n");
+            file.Table("StructureFactor", Sq[(size_t)s], Lx, Ly, ",\n"); file.Table("DD", DD[ss], nb, nb, s + 1 < k ? "},\n" : "}\n");
+        }
+        fprintf(fp, "   ]");
+        if (cross) {
+            fprintf(fp, ",\n   \"Cross\": [\n");
+            for (PetscInt s = 0; s < k; ++s) for (PetscInt t = s + 1; t < k; ++t) {
+                const size_t st = (size_t)(s * k + t);
+                fprintf(fp, "   {\"s\": %lld, \"t\": %lld,\n", LLD(s), LLD(t));
+                file.Table("SzSz", SzSz[st], N, N, ",\n"); file.Table("SmSp", SmSp[st], N, N, ",\n"); file.Table("SpSm", SpSm[st], N, N, ",\n");
+                file.Table("DD", DD[st], nb, nb, (s == k - 2 && t == k - 1) ? "}\n" : "},\n");
+            }
+            fprintf(fp, "   ]");
+        }
+        fprintf(fp, "}");
+        fflush(fp);
+        return 0;
+    }
+};
+
+/** The eleven measurements, the options they share, and the order in which a DMRG step reads and runs them. */
 struct EngineMeasurements {
     CorrelationMatrix corr_matrix;
     DimerCorrelations corr_dimer;
@@ -1099,6 +1278,7 @@ struct EngineMeasurements {
     TransverseDynamics dsf_pm;
     CorrectionVectors dsf_cv;
     StaticSusceptibility chi;
+    StateCorrelations states_corr;
     LanczosStepOptions lanczos;                 /* -dsf, -dsf_sites */
     ChebyshevOptions cheb;                      /* -dsf_cheb, -dsf_pm; its window also -dsf_dimer */
 
@@ -1117,7 +1297,8 @@ struct EngineMeasurements {
         ierr = dsf_pm.ReadOptions(comm, size, num_sites); CHKERRQ(ierr);
         ierr = cheb.Read(comm, dsf_cheb.use, dsf_dimer.use, dsf_pm.use); CHKERRQ(ierr);
         ierr = dsf_cv.ReadOptions(comm, size, num_sites); CHKERRQ(ierr);
-        return chi.ReadOptions(comm, size, num_sites, (PetscInt)DimerBonds(Ham).size());
+        ierr = chi.ReadOptions(comm, size, num_sites, (PetscInt)DimerBonds(Ham).size()); CHKERRQ(ierr);
+        return states_corr.ReadOptions(comm);
     }
     /** Right after the eigensolve, while the plan of the superblock Hamiltonian exists. */
     template<class Hamiltonian> PetscErrorCode RunWithPlan(const MeasurementContext& ctx, const Hamiltonian& Ham)
@@ -1140,11 +1321,12 @@ struct EngineMeasurements {
         if (corr_matrix.use) { ierr = corr_matrix.Run(ctx, Ham); CHKERRQ(ierr); }
         if (corr_dimer.use) { ierr = corr_dimer.Run(ctx, Ham); CHKERRQ(ierr); }
         if (corr_chiral.use) { ierr = corr_chiral.Run(ctx, Ham); CHKERRQ(ierr); }
+        if (states_corr.use) { ierr = states_corr.Run(ctx, Ham); CHKERRQ(ierr); }
         return 0;
     }
     /** Every one of them reads Sz and Sp of every site of both centre blocks, on every rank. */
-    bool NeedsAllSiteOperators() const { return corr_matrix.use || corr_dimer.use || corr_chiral.use || dsf.use || dsf_sites.use || dsf_cheb.use || dsf_cv.use || dsf_dimer.use || dsf_pm.use || chi.use; }
-    void Close() { corr_matrix.file.Close(); corr_dimer.file.Close(); corr_chiral.file.Close(); dsf.file.Close(); dsf_sites.file.Close(); dsf_cheb.file.Close(); dsf_cv.file.Close(); dsf_dimer.file.Close(); dsf_pm.file.Close(); chi.file.Close(); }
+    bool NeedsAllSiteOperators() const { return corr_matrix.use || corr_dimer.use || corr_chiral.use || dsf.use || dsf_sites.use || dsf_cheb.use || dsf_cv.use || dsf_dimer.use || dsf_pm.use || chi.use || states_corr.use; }
+    void Close() { corr_matrix.file.Close(); corr_dimer.file.Close(); corr_chiral.file.Close(); dsf.file.Close(); dsf_sites.file.Close(); dsf_cheb.file.Close(); dsf_cv.file.Close(); dsf_dimer.file.Close(); dsf_pm.file.Close(); chi.file.Close(); states_corr.file.Close(); }
 };
 
 }  // namespace dmrgx_host

@@ -182,6 +182,24 @@ inline std::vector<double> SiteCosineSum(PetscInt Lx, PetscInt Ly, const PetscIn
     return out;
 }
 
+/** The single-mode weight of a transition amplitude T_i = < s | O_i | t > over the N sites r_i = (rx[i], ry[i]):
+        W[nx Ly + ny] = (1 / N) [ (sum_i cos(q . r_i) T_i)^2 + (sum_i sin(q . r_i) T_i)^2 ] = (1 / N) | sum_i e^(i q . r_i) T_i |^2,
+    q = (2 pi nx / Lx, 2 pi ny / Ly); the result is Lx x Ly, row-major.  Both sums run over i ascending from 0.0.  Summed over all Lx Ly
+    wave vectors of a lattice whose sites are all different, W gives sum_i T_i^2 (N = Lx Ly). */
+inline std::vector<double> TransitionWeight(PetscInt Lx, PetscInt Ly, const PetscInt* rx, const PetscInt* ry, const double* T, PetscInt N)
+{
+    std::vector<double> W((size_t)(Lx * Ly), 0.0);
+    for (PetscInt nx = 0; nx < Lx; ++nx) for (PetscInt ny = 0; ny < Ly; ++ny) {
+        double c = 0.0, s = 0.0;
+        for (PetscInt i = 0; i < N; ++i) {
+            const double phase = two_pi * ((double)(nx * rx[i]) / (double)Lx + (double)(ny * ry[i]) / (double)Ly);
+            c += std::cos(phase) * T[i]; s += std::sin(phase) * T[i];
+        }
+        W[(size_t)(nx * Ly + ny)] = (c * c + s * s) / (double)N;
+    }
+    return W;
+}
+
 /** The frequencies of a w0,w1,nw option: nw >= 1 equidistant points from w0 to w1 (nw = 1: w0 = w1).  false, and no grid, unless
     om[0..count) is three such numbers. */
 inline bool OmegaGrid(const double* om, PetscInt count, std::vector<double>& grid)
@@ -374,9 +392,16 @@ struct DimerFrame {
         return 0;
     }
     /** G ((nb + 1) x (nb + 1), row-major, host): the Gram matrix of psi (vector 0) and the images D_b psi (vector 1 + b), ONE dmrgx_kron_term_gram call. */
-    PetscErrorCode Gram(std::vector<double>& G) const
+    PetscErrorCode Gram(std::vector<double>& G) const { return GramOf(0, psi, 0, G); }
+    /** The same over the `nstates` rows of Psi (row stride ldpsi), ONE dmrgx_kron_term_gram_states call: G is (nstates (nb + 1))^2, state-major,
+        member s (nb + 1) the state s itself and s (nb + 1) + 1 + b the image D_b psi_s.  The frame's own psi is not read. */
+    PetscErrorCode GramStates(PetscInt nstates, const double* Psi, int64_t ldpsi, std::vector<double>& G) const { return GramOf(nstates, Psi, ldpsi, G); }
+private:
+    /** nstates == 0: dmrgx_kron_term_gram on the one vector Psi; else dmrgx_kron_term_gram_states.  The workspace holds at least the largest
+        image block of every vector of the family. */
+    PetscErrorCode GramOf(PetscInt nstates, const double* Psi, int64_t ldpsi, std::vector<double>& G) const
     {
-        const PetscInt nv = nb + 1;
+        const PetscInt nv = nb + 1, nf = std::max<PetscInt>(nstates, 1) * nv;
         std::vector<int32_t> first{0};
         std::vector<dmrgx_term> all;
         all.push_back(dmrgx_term{1.0, -1, -1});
@@ -389,14 +414,18 @@ struct DimerFrame {
                 const int32_t a = F.bil[k] - d, c = F.bir[k] + d;
                 if (a >= 0 && a < (int32_t)F.sizes[0].size() && c >= 0 && c < (int32_t)F.sizes[1].size()) largest = std::max<int64_t>(largest, (int64_t)F.sizes[0][(size_t)a] * F.sizes[1][(size_t)c]);
             }
-        const size_t workspace = std::max<size_t>((size_t)1 << 30, (size_t)largest * (size_t)nv * sizeof(double));
-        G.assign((size_t)(nv * nv), 0.0);
-        DevBuffer g((size_t)(nv * nv), DevBuffer::device_only_t{});
-        if (dmrgx_kron_term_gram(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
-                                 (int32_t)nv, first.data(), all.data(), workspace, g.dev_uninitialised(), nv, nullptr, nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "dmrgx_kron_term_gram: %s", dmrgx_last_error());
+        const size_t workspace = std::max<size_t>((size_t)1 << 30, (size_t)largest * (size_t)nf * sizeof(double));
+        G.assign((size_t)(nf * nf), 0.0);
+        DevBuffer g((size_t)(nf * nf), DevBuffer::device_only_t{});
+        if (nstates == 0) {
+            if (dmrgx_kron_term_gram(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), Psi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
+                                     (int32_t)nv, first.data(), all.data(), workspace, g.dev_uninitialised(), nv, nullptr, nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "dmrgx_kron_term_gram: %s", dmrgx_last_error());
+        } else if (dmrgx_kron_term_gram_states(&F.sectors[0], &F.sectors[1], (int32_t)F.bil.size(), F.bil.data(), F.bir.data(), (int32_t)nstates, Psi, ldpsi, (int32_t)T.ops[0].size(), T.ops[0].data(), (int32_t)T.ops[1].size(), T.ops[1].data(),
+                                               (int32_t)nv, first.data(), all.data(), workspace, g.dev_uninitialised(), nf, nullptr, nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "dmrgx_kron_term_gram_states: %s", dmrgx_last_error());
         if (dmrgx_memcpy_d2h(G.data(), g.dev_ro(), G.size() * sizeof(double), nullptr)) SETERRQ1(PETSC_COMM_SELF, 1, "%s", dmrgx_last_error());
         return 0;
     }
+public:
     /** dst + b ld = D_b psi for all nb bonds, through dmrgx_kron_term_apply in chunks of at most 1 GiB of images (as SzFrame::Images). */
     PetscErrorCode Images(double* dst, int64_t ld) const
     {
@@ -776,6 +805,13 @@ struct JsonRecordFile {
     /** "Bonds", "Orientation", "Position" of the bonds and "D" = < D_b >, as -corr_dimer and -dsf_dimer write them, each line closed. */
     void BondHeader(const std::vector<DimerBond>& bonds, const std::vector<double>& D) const
     {
+        BondList(bonds);
+        fprintf(fp, "   \"D\": ");
+        Row(D); fprintf(fp, ",\n");
+    }
+    /** The bond list of BondHeader without "D" (-states_corr, whose D is a table per pair of states). */
+    void BondList(const std::vector<DimerBond>& bonds) const
+    {
         const size_t nb = bonds.size();
         fprintf(fp, "   \"Bonds\": [");
         for (size_t b = 0; b < nb; ++b) fprintf(fp, "%s[%lld, %lld]", b ? ", " : "", LLD(bonds[b].i), LLD(bonds[b].j));
@@ -783,8 +819,7 @@ struct JsonRecordFile {
         for (size_t b = 0; b < nb; ++b) fprintf(fp, "%s\"%c\"", b ? ", " : "", bonds[b].orient);
         fprintf(fp, "],\n   \"Position\": [");
         for (size_t b = 0; b < nb; ++b) fprintf(fp, "%s[%lld, %lld]", b ? ", " : "", LLD(bonds[b].ix), LLD(bonds[b].jy));
-        fprintf(fp, "],\n   \"D\": ");
-        Row(D); fprintf(fp, ",\n");
+        fprintf(fp, "],\n");
     }
     void Close() { if (fp) { fprintf(fp, "\n]\n"); fclose(fp); fp = NULL; } }
 };

@@ -226,6 +226,14 @@ int main()
             double norm;
             if (!(is >> norm)) norm = (double)n;
             print_numbers(cmd.c_str(), c < 0 ? dmrgx_host::LatticeFourier(Lx, Ly, x.data(), y.data(), T.data(), n, norm) : dmrgx_host::SiteCosineSum(Lx, Ly, x.data(), y.data(), c, T.data(), n, ncol));
+        } else if (cmd == "transweight") {       /* transweight Lx Ly n x_0 .. x_{n-1} y_0 .. y_{n-1} T_0 .. T_{n-1}  ->  the Lx x Ly table of TransitionWeight */
+            PetscInt Lx, Ly, n; is >> Lx >> Ly >> n;
+            std::vector<PetscInt> x((size_t)n), y((size_t)n);
+            std::vector<double> T((size_t)n);
+            for (PetscInt& v : x) is >> v;
+            for (PetscInt& v : y) is >> v;
+            for (double& v : T) is >> v;
+            print_numbers(cmd.c_str(), dmrgx_host::TransitionWeight(Lx, Ly, x.data(), y.data(), T.data(), n));
         } else if (cmd == "omegagrid") {         /* omegagrid w0 w1 nw  ->  1 and the grid, or 0 */
             std::vector<double> om, grid;
             for (double v; is >> v;) om.push_back(v);
@@ -351,6 +359,7 @@ int main()
                 printf("dsf_cv %d sites %s omega %s eta %.17g tol %.17g maxit %lld\n", (int)E.dsf_cv.use, ints(E.dsf_cv.sites).c_str(), reals(&E.dsf_cv.omega).c_str(), E.dsf_cv.eta, E.dsf_cv.tol, LLD(E.dsf_cv.maxit));
                 /* the tenth measurement prints its line when it is on: a run without its options lists the nine above, as before */
                 if (E.chi.use) printf("chi 1 sites %s bonds %s tol %.17g maxit %lld\n", ints(E.chi.sites).c_str(), ints(E.chi.bonds).c_str(), E.chi.tol, LLD(E.chi.maxit));
+                if (E.states_corr.use) printf("states_corr 1 cross %d\n", (int)E.states_corr.cross);      /* the eleventh: likewise */
             }
         } else if (cmd == "noiseops") {        /* noiseops a n, then n x (shift transposed id): plan operators, id names the stored cell set  ->  the list of NoiseOperators as shift:transposed:id, then the coefficient */
             double a; PetscInt n; is >> a >> n;

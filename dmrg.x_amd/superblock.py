@@ -410,6 +410,35 @@ def term_gram(sb_or_layout, psi, left_ops, right_ops, vectors, workspace_bytes=0
     return G, report
 
 
+def term_gram_states(sb_or_layout, Psi, left_ops, right_ops, vectors, workspace_bytes=0):
+    """G[s * n + a, t * n + b] = <v_a(psi_s), v_b(psi_t)> for the rows psi_s of Psi and the n = len(vectors) images of term_gram built from
+    each of them (dmrgx_kron_term_gram_states): the family is state-major.  Psi: a 2-D f64 device tensor (or numpy array) of one state
+    per row in the reference vector layout, unit stride along the row and a row stride >= n_states whose columns beyond n_states are never
+    read.  Layout, operators, vectors and workspace_bytes as in term_gram; the workspace holds the images of every state.
+    Returns (G, report)."""
+    _capi.require_device()
+    if not torch.is_tensor(Psi):
+        Psi = torch.from_numpy(np.ascontiguousarray(Psi, dtype=np.float64)).cuda()
+    assert Psi.dtype == torch.float64 and Psi.dim() == 2 and Psi.shape[0] >= 1 and (Psi.shape[1] <= 1 or Psi.stride(1) == 1)
+    k, ns = Psi.shape
+    ldpsi = Psi.stride(0) if k > 1 else max(Psi.stride(0), ns)
+    args, _, keep = _gram_arguments(sb_or_layout, Psi[0].contiguous(), left_ops, right_ops)        # (row 0 only sizes and places the operators)
+    n = len(vectors)
+    first = _i32(list(np.cumsum([0] + [len(v) for v in vectors])))
+    flat = [t for v in vectors for t in v]
+    terms = (_capi.Term * max(len(flat), 1))()
+    for i, (c, l, r) in enumerate(flat):
+        terms[i].a, terms[i].left_op, terms[i].right_op = float(c), (-1 if l is None else int(l)), (-1 if r is None else int(r))
+    nf = max(k * n, 1)
+    G = torch.empty((nf, nf), dtype=torch.float64, device=Psi.device)
+    report = _capi.GramReport()
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _capi.check(_capi.lib().dmrgx_kron_term_gram_states(*args[:5], k, C.c_void_p(Psi.data_ptr()), ldpsi, *args[6:], n, first, terms, workspace_bytes,
+                                                        C.c_void_p(G.data_ptr()), nf, C.byref(report), st))
+    torch.cuda.current_stream().synchronize()       # the operator copies in `keep` are read by the queued work
+    return G, report
+
+
 def term_apply(sb_or_layout, psi, left_ops, right_ops, vectors, out=None):
     """Y[a, :n_states] = v_a = sum over the terms (c, l, r) of vectors[a] of c * (left_ops[l] (x) right_ops[r]) psi, in the layout of psi
     (dmrgx_kron_term_apply).  Arguments as in term_gram; every term must have total sector shift 0.  out: a 2-D f64 device tensor with

@@ -489,6 +489,28 @@ dmrgx_status dmrgx_kron_term_gram(const dmrgx_sectors* left, const dmrgx_sectors
                                   int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
                                   int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
                                   size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, void* stream);
+/* G[(s*nvec + a)*ldg + (t*nvec + b)] = < v_a(psi_s) , v_b(psi_t) >,  s, t < nstates, a, b < nvec:  dmrgx_kron_term_gram over several states
+ * at once, with the inner products between the images of different states -- the transition amplitudes <psi_s|O_a^T O_b|psi_t> and, with
+ * an identity vector in the family, <psi_s|O_b|psi_t>.  Psi holds the states as rows in the reference vector layout, row s at
+ * Psi_dev + s*ldpsi (the convention of dmrgx_kron_states_expand): ldpsi >= n_states, any 8-byte alignment, rows only read, the columns
+ * from n_states to ldpsi never touched.  The family is the nstates * nvec images in state-major order, member s*nvec + a the image v_a of
+ * dmrgx_kron_term_gram built from psi_s; sector tables, KronBlocks, operators, vectors, terms (the (-1, -1) identity term, the one total
+ * shift), workspace_bytes, report and every check are those of dmrgx_kron_term_gram, with the same codes.  ldg >= nstates * nvec.
+ * Refused with DMRGX_ERR_ARG besides: nstates < 1, a null Psi, ldpsi < n_states, a null G, ldg < nstates * nvec.  A refused call writes
+ * nothing.
+ * Memory: the image blocks of a workspace slice hold all nstates * nvec vectors, so workspace_bytes (0: 1 GiB) bounds
+ * nstates * nvec * (doubles of a slice), and an image block whose nstates * nvec copies do not fit is refused with DMRGX_ERR_ARG.  Within a
+ * slice the states are built one after another, then one dmrgx_vec_gram over the whole family is accumulated into G, slice after
+ * slice.  The intermediates T of the two-sided terms are those of ONE state at a time: the pool memory on top of the workspace is (1)
+ * and (2) of dmrgx_kron_term_gram and does not grow with nstates; the operand copies (2) are made once per call.
+ * No atomics and a fixed summation order: G is bitwise symmetric, two calls give the same bits, and nstates == 1 gives the bits of
+ * dmrgx_kron_term_gram on that row. */
+dmrgx_status dmrgx_kron_term_gram_states(const dmrgx_sectors* left, const dmrgx_sectors* right, int32_t nblocks,
+                                         const int32_t* block_il, const int32_t* block_ir,
+                                         int32_t nstates, const double* Psi_dev, int64_t ldpsi,
+                                         int32_t n_left_ops, const dmrgx_secop* left_ops, int32_t n_right_ops, const dmrgx_secop* right_ops,
+                                         int32_t nvec, const int32_t* vec_first, const dmrgx_term* terms,
+                                         size_t workspace_bytes, double* G_dev, int64_t ldg, dmrgx_gram_report* report, void* stream);
 /* Y[a*ldy + n] = v_a[n], n < n_states:  the images v_a = sum_t c_t (A_t (x) B_t) psi of dmrgx_kron_term_gram themselves, in the reference
  * vector layout of the same KronBlocks.  Sector tables, KronBlocks, psi, operators, vectors and terms, and their checks, are those of
  * dmrgx_kron_term_gram; it is the same builder with the caller's Y in place of the workspace and no Gram matrix taken.  The images must
