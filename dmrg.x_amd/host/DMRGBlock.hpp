@@ -5,7 +5,7 @@
       - operators are SectorMat handles (HBM), copies of a block are shallow and Destroy() on one copy invalidates the
         other (reference tests/UnitTests_DMRGBlock.cpp:56-70);
       - RotateOperators is ONE call of dmrgx_rotate_ops for all 2*nsites+1 operators (reference loops MatMatMatMult,
-        src/DMRGBlock.cpp:763-772);
+        src/DMRGBlock.cpp:763-772), and for the carried total-spin operator SpTot where -spin_penalty is on;
       - the disk-spill entry points exist with the reference's names but keep the block resident (288 GB of HBM3E):
         scratch/restart files are outside the hot path. */
 #ifndef DMRGX_DMRGBLOCK_HPP
@@ -41,6 +41,10 @@ public:
     QuantumNumbers Magnetization;
     /** Block Hamiltonian (operators acting inside the block) */
     Mat H = nullptr;
+    /** Total-spin raising operator S+_blk = sum_i Sp(i) of the block's sites (shift +1), carried next to H under -spin_penalty only
+        (SpinPenalty.hpp): null, with nothing allocated, in every other run.  A one-site block gets it from CreateSpTot; KronEye_Explicit
+        builds it for an enlarged block whose two inputs carry it; RotateOperators rotates it with H; it is never pruned. */
+    Mat SpTot = nullptr;
 
     virtual ~SpinBase() {}
     virtual PetscInt loc_dim() const { return _loc_dim; }
@@ -126,8 +130,8 @@ public:
 
     /* ---- checkpoint files ----------------------------------------------------------------
        Same directory layout and text files as the reference (src/DMRGBlock.cpp:889-971): BlockInfo.dat,
-       QuantumNumbers.dat, Sz_%09d.mat, Sp_%09d.mat, H_%09d.mat.  The operator files hold this engine's sector-cell
-       form (little-endian): int64 {magic "DMRGXOP1", shift, nsec, sizes[nsec], ncells}, then per cell int64 {row
+       QuantumNumbers.dat, Sz_%09d.mat, Sp_%09d.mat, H_%09d.mat, and SpTot_%09d.mat where the block carries SpTot.  The
+       operator files hold this engine's sector-cell form (little-endian): int64 {magic "DMRGXOP1", shift, nsec, sizes[nsec], ncells}, then per cell int64 {row
        sector, r0, c0, nr, nc, kind}, double scale and, for dense cells, nr*nc doubles row-major.  (The reference writes
        PETSc's binary MatView format, which is not part of its source tree.) */
     static std::string OpFilename(const std::string& dir, const std::string& name, const size_t isite = 0)
@@ -199,6 +203,7 @@ public:
         for (PetscInt i = 0; i < num_sites; ++i) { if (!SzData[(size_t)i] && ops_pruned) continue; if (WriteOperatorFile(OpFilename(dir, "Sz", (size_t)i), SzData[(size_t)i])) SETERRQ1(mpi_comm, PETSC_ERR_FILE_OPEN, "cannot write %s", OpFilename(dir, "Sz", (size_t)i).c_str()); }
         for (PetscInt i = 0; i < num_sites; ++i) { if (!SpData[(size_t)i] && ops_pruned) continue; if (WriteOperatorFile(OpFilename(dir, "Sp", (size_t)i), SpData[(size_t)i])) SETERRQ1(mpi_comm, PETSC_ERR_FILE_OPEN, "cannot write %s", OpFilename(dir, "Sp", (size_t)i).c_str()); }
         if (H) { if (WriteOperatorFile(OpFilename(dir, "H", 0), H)) SETERRQ1(mpi_comm, PETSC_ERR_FILE_OPEN, "cannot write %s", OpFilename(dir, "H", 0).c_str()); }
+        if (SpTot) { if (WriteOperatorFile(OpFilename(dir, "SpTot", 0), SpTot)) SETERRQ1(mpi_comm, PETSC_ERR_FILE_OPEN, "cannot write %s", OpFilename(dir, "SpTot", 0).c_str()); }
         {
             FILE* fp = fopen((dir + "BlockInfo.dat").c_str(), "w");
             if (!fp) SETERRQ1(mpi_comm, PETSC_ERR_FILE_OPEN, "cannot write %sBlockInfo.dat", dir.c_str());
@@ -220,8 +225,9 @@ public:
     }
 
     /** Rebuilds a block from the files written by SaveToDisk (InitializeFromDisk of the reference,
-        src/DMRGBlock.cpp:184-300: BlockInfo.dat and QuantumNumbers.dat are cross-checked). */
-    PetscErrorCode InitializeFromDisk(const MPI_Comm& comm_in, const std::string& dir_in)
+        src/DMRGBlock.cpp:184-300: BlockInfo.dat and QuantumNumbers.dat are cross-checked).  with_sp_tot: the run carries SpTot, the
+        checkpoint must hold its file; without it the file, if there, is left unread. */
+    PetscErrorCode InitializeFromDisk(const MPI_Comm& comm_in, const std::string& dir_in, const bool with_sp_tot = false)
     {
         std::string dir = dir_in;
         if (dir.empty()) SETERRQ(comm_in, 1, "Block directory cannot be empty.");
@@ -266,6 +272,8 @@ public:
             ierr = PetscTestFile(OpFilename(dir, "H", 0).c_str(), 'r', &has_h); CHKERRQ(ierr);
             if (has_h && ReadOperatorFile(OpFilename(dir, "H", 0), H)) SETERRQ1(comm_in, PETSC_ERR_FILE_OPEN, "cannot read %s", OpFilename(dir, "H", 0).c_str());
         }
+        if (with_sp_tot && ReadOperatorFile(OpFilename(dir, "SpTot", 0), SpTot))
+            SETERRQ1(comm_in, PETSC_ERR_FILE_OPEN, "cannot read %s: -spin_penalty needs a checkpoint that was written with it.", OpFilename(dir, "SpTot", 0).c_str());
         ierr = CheckOperatorBlocks(); CHKERRQ(ierr);
         return 0;
     }
@@ -286,6 +294,7 @@ public:
         if (PetscUnlikely(!init)) return 0;
         for (PetscInt i = 0; i < num_sites; ++i) { MatDestroy(&SzData[i]); MatDestroy(&SpData[i]); }
         MatDestroy(&H);
+        MatDestroy(&SpTot);
         if (init_Sm) DestroySm();
         init = PETSC_FALSE;
         return 0;
@@ -374,9 +383,17 @@ public:
         PetscErrorCode ierr = CheckOperators(); CHKERRQ(ierr);
         for (PetscInt i = 0; i < num_sites; ++i) { ierr = MatOpCheckOperatorBlocks(OpSz, i); CHKERRQ(ierr); }
         for (PetscInt i = 0; i < num_sites; ++i) { ierr = MatOpCheckOperatorBlocks(OpSp, i); CHKERRQ(ierr); }
+        if (SpTot) { ierr = MatCheckOperatorBlocks(OpSp, SpTot); CHKERRQ(ierr); }
         return 0;
     }
     PetscErrorCode AssembleOperators() { return 0; }
+
+    /** The carried total-spin operator of a one-site block: the site's own Sp, in cells of its own. */
+    PetscErrorCode CreateSpTot()
+    {
+        if (!init || num_sites != 1) SETERRQ(mpi_comm, PETSC_ERR_ARG_WRONGSTATE, "CreateSpTot: only an initialized one-site block gets its total-spin operator this way.");
+        return MatSpinSpCreate(SpTot);
+    }
 
     PetscBool HasSm() const { return init_Sm; }
     /** Sm(i) = Sp(i)^T as a view: the kernels read Sp transposed, nothing is copied. */
@@ -424,6 +441,7 @@ public:
         std::vector<Mat> live;
         for (PetscInt i = 0; i < num_sites; ++i) { if (SzData[i]) live.push_back(SzData[i]); if (SpData[i]) live.push_back(SpData[i]); }
         if (H) live.push_back(H);
+        if (SpTot) live.push_back(SpTot);
         std::map<dmrgx_host::DevBuffer*, size_t> arena_size;
         size_t used = 0;
         for (const Mat& m : live)
@@ -464,7 +482,7 @@ public:
 
     /** this block's operators <- RotMatT . Source's operators . RotMatT^T, all of them in one device call.
         keep_sites (engine extension, default: every site): only the site operators with keep_sites[i] != 0 that Source
-        holds are rotated; the others stay absent (see PruneOperators).  H is always rotated. */
+        holds are rotated; the others stay absent (see PruneOperators).  H is always rotated, and so is SpTot where Source carries it. */
     PetscErrorCode RotateOperators(SpinBase& Source, const Mat& RotMatT_in, const std::vector<char>* keep_sites = nullptr)
     {
         if (!init) SETERRQ(mpi_comm, PETSC_ERR_ARG_CORRUPT, "Block not yet initialized.");
@@ -488,6 +506,7 @@ public:
             if (!want || !Source.SpData[i] || !Source.SzData[i]) { ops_pruned = PETSC_TRUE; continue; }
             src.push_back(Source.SpData[i]); src.push_back(Source.SzData[i]); src_site.push_back(i);
         }
+        if (Source.SpTot) src.push_back(Source.SpTot);
         src.push_back(Source.H);
         const size_t nops = src.size();
         std::vector<dmrgx_secop> ops(nops);
@@ -536,6 +555,7 @@ public:
         if (dmrgx_rotate_ops(&olds, &rot, (int32_t)nops, ops.data(), dpp.data(), nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_rotate_ops: %s", dmrgx_last_error());
         for (size_t j = 0; j < src_site.size(); ++j) { SpData[(size_t)src_site[j]] = dst[2 * j]; SzData[(size_t)src_site[j]] = dst[2 * j + 1]; }
         H = dst[nops - 1];
+        SpTot = Source.SpTot ? dst[nops - 2] : nullptr;
         num_rotated_ops = (PetscInt)nops;
         PetscErrorCode ierr = CheckOperatorBlocks(); CHKERRQ(ierr);
         return SaveAndDestroy();

@@ -39,6 +39,7 @@
 #include "EngineMeasurements.hpp"
 #include "Noise.hpp"
 #include "TargetStates.hpp"
+#include "SpinPenalty.hpp"
 
 /** One eigenpair of a reduced-density-matrix block */
 struct Eigen_t
@@ -208,6 +209,10 @@ public:
         ierr = dmrgx_host::ReadTargetStatesOptions(mpi_comm, targets); CHKERRQ(ierr);
         if (targets.k > 1 && mpi_size > 1) SETERRQ2(mpi_comm, PETSC_ERR_SUP, "-nstates %lld is not available on more than one rank (got %d): the deflated solve and the expansion of the density matrix are not striped.", LLD(targets.k), (int)mpi_size);
         if (targets.k > 1 && noise.Any()) SETERRQ1(mpi_comm, PETSC_ERR_SUP, "-nstates %lld cannot be combined with -noise / -noise_warmup: both widen the input of the density matrix.", LLD(targets.k));
+        /* -spin_penalty l0,l1,... / -spin_penalty_warmup l: H + l S-_tot S+_tot in the superblock (SpinPenalty.hpp); with a non-zero weight every
+           block carries its total-spin raising operator, starting with the one-site blocks */
+        ierr = dmrgx_host::ReadSpinPenaltyOptions(mpi_comm, mpi_size, penalty); CHKERRQ(ierr);
+        if (penalty.Any()) { ierr = SingleSite.CreateSpTot(); CHKERRQ(ierr); }
         /* -corr_matrix, -corr_dimer, -corr_chiral, -dsf, -dsf_sites, -dsf_cheb, -dsf_dimer, -dsf_pm, -dsf_cv, -chi_sites / -chi_bonds, -states_corr and what goes with them (EngineMeasurements.hpp) */
         ierr = engine_measurements.ReadOptions(mpi_comm, mpi_rank, mpi_size, num_sites, Ham); CHKERRQ(ierr);
         ierr = PetscOptionsGetBool(NULL, NULL, "-step_profile", &step_profile, NULL); CHKERRQ(ierr);
@@ -316,7 +321,7 @@ public:
             num_sys_blocks = num_sites - 1;
             sys_blocks.resize((size_t)num_sys_blocks);
             for (PetscInt ib = 0; ib < restart_sys_ninit; ++ib) {
-                ierr = sys_blocks[(size_t)ib].InitializeFromDisk(mpi_comm, restart_dir + BlockDir("Sys", ib)); CHKERRQ(ierr);
+                ierr = sys_blocks[(size_t)ib].InitializeFromDisk(mpi_comm, restart_dir + BlockDir("Sys", ib), penalty.Any()); CHKERRQ(ierr);
             }
             sys_ninit = restart_sys_ninit;
             warmed_up = PETSC_TRUE;
@@ -327,6 +332,7 @@ public:
         num_sys_blocks = num_sites - 1;
         sys_blocks.resize((size_t)num_sys_blocks);
         ierr = sys_blocks[sys_ninit++].Initialize(mpi_comm, 1, PETSC_DEFAULT); CHKERRQ(ierr);
+        if (penalty.Any()) { ierr = sys_blocks[0].CreateSpTot(); CHKERRQ(ierr); }
         if (AddSite().NumSites() != 1) SETERRQ1(mpi_comm, 1, "Routine assumes an additional site of 1. Got %lld.", LLD(AddSite().NumSites()));
         PetscInt nsites_cluster = Ham.NumEnvSites();
         if (nsites_cluster % 2) nsites_cluster *= 2;
@@ -459,6 +465,7 @@ public:
         if (fp_kron) { fprintf(fp_kron, "\n]\n"); fclose(fp_kron); fp_kron = NULL; }
         engine_measurements.Close();
         targets_file.Close();
+        penalty_file.Close();
         if (fp_corr) {
             if (!corr_headers_printed) { PetscErrorCode e2 = PrintCorrelationHeaders(); CHKERRQ(e2); }
             fprintf(fp_corr, "\n  ]\n}\n"); fclose(fp_corr); fp_corr = NULL;
@@ -471,6 +478,7 @@ public:
             /* the schedule of the density-matrix perturbation as given (one weight per sweep, the last one holds on), and what it cost */
             fprintf(fp_data, "],\n  \"Noise\": %s,\n  \"NoiseWarmup\": %.17g,\n  \"NoiseExpansions\": %lld,\n  \"NoiseMaxExpansionBytes\": %lld,\n  \"NoiseOperatorsLeft\": %lld,\n  \"NoiseOperatorsRight\": %lld",
                     noise.Json().c_str(), noise.warmup, LLD(noise_expansions), (long long)noise_max_bytes, LLD(noise_ops[0]), LLD(noise_ops[1]));
+            if (penalty.Any()) fprintf(fp_data, ",\n  \"SpinPenalty\": %s,\n  \"SpinPenaltyWarmup\": %.17g", penalty.Json().c_str(), penalty.warmup);
             if (targets.k > 1) fprintf(fp_data, ",\n  \"TargetStates\": %lld,\n  \"TargetWeights\": %s", LLD(targets.k), dmrgx_host::TargetStates::Json(targets.weights).c_str());
             fprintf(fp_data, ",\n  \"GSEnergy\": %.16g,\n  \"MatMults\": %lld,\n  \"LastSweepSeconds\": %.9g,\n  \"LastSweepSteps\": %lld,\n  \"LastSweepMatMults\": %lld,\n  \"EigensolveSeconds\": %.9g,\n"
                              "  \"DeviceBytesResidentAfterSweep\": %zu,\n  \"DeviceBytesPeak\": %zu,\n  \"DeviceBytesCached\": %zu,\n  \"StartVectorsTransformed\": %lld,\n  \"StartVectorsThroughOverlap\": %lld,\n  \"StartVectorsRejected\": %lld,\n"
@@ -528,6 +536,8 @@ public:
         ierr = KronBlocks.KronSumSetRedistribute(PETSC_TRUE); CHKERRQ(ierr);
         ierr = KronBlocks.KronSumSetToleranceFromOptions(); CHKERRQ(ierr);
         ierr = KronBlocks.KronSumSetShellMatrix(do_shell); CHKERRQ(ierr);
+        const double lambda = penalty.At(LoopType == WarmupStep, LoopIdx - 1);      /* 0: the plan of H, the calls of a run without -spin_penalty */
+        if (lambda > 0.0) { ierr = KronBlocks.KronSumSetSpinPenalty(lambda); CHKERRQ(ierr); }
         ierr = KronBlocks.KronSumConstruct(Terms, H); CHKERRQ(ierr);
         if (!H) SETERRQ(mpi_comm, 1, "H is null.");
         ierr = PetscTime(&tkron); CHKERRQ(ierr);
@@ -600,6 +610,7 @@ public:
             if (do_measurements) { ierr = MeasureTargetStates(KronBlocks, gsv_r, tstep); CHKERRQ(ierr); }
         }
         const bool averaged = tstep.more.size() > 0;
+        if (penalty.Any()) { ierr = SaveSpinPenaltyStep(KronBlocks, gsv_r, gse_r, tstep, lambda); CHKERRQ(ierr); }
         const dmrgx_host::MeasurementContext mctx{KronBlocks, gsv_r, &H, Terms, gse_r, num_sites, qn_sector, GlobIdx, LoopTypeName(), verbose, do_shell, mpi_comm, mpi_rank, mpi_size, data_dir,
                                                      averaged ? dmrgx_host::TargetedStatesView{tstep.rows->dev_ro(), tstep.ld, (PetscInt)tstep.energies.size(), tstep.energies.data()} : dmrgx_host::TargetedStatesView{}};
         if (do_measurements) { ierr = engine_measurements.RunWithPlan(mctx, Ham); CHKERRQ(ierr); }      /* -dsf, -dsf_sites, -dsf_cheb, -dsf_dimer, -dsf_cv: they need the plan */
@@ -1075,7 +1086,7 @@ public:
         std::ofstream f(filename);
         if (!f) SETERRQ1(mpi_comm, PETSC_ERR_FILE_OPEN, "cannot write %s", filename.c_str());
         char val[4096]; PetscBool set;
-        for (const char* key : {"-spin", "-mstates", "-mwarmup", "-nsweeps", "-msweeps", "-maxnsweeps", "-min_block", "-noise", "-noise_warmup", "-nstates", "-state_weights"}) {
+        for (const char* key : {"-spin", "-mstates", "-mwarmup", "-nsweeps", "-msweeps", "-maxnsweeps", "-min_block", "-noise", "-noise_warmup", "-nstates", "-state_weights", "-spin_penalty", "-spin_penalty_warmup"}) {
             PetscErrorCode ierr = PetscOptionsGetString(NULL, NULL, key, val, sizeof(val), &set); CHKERRQ(ierr);
             if (set) f << key << " " << (val[0] ? val : "yes") << "\n";
         }
@@ -1507,6 +1518,47 @@ public:
             targets_file.Table("Overlaps", T.overlaps, (PetscInt)T.energies.size(), (PetscInt)T.energies.size(), "");
             reals("TotalSpin2", T.spin2);
         }
+        fprintf(fp, "}");
+        fflush(fp);
+        return 0;
+    }
+
+    /** One record of SpinPenalty.json (the file exists only in a run with a non-zero weight, and then holds every step, also those of a
+        sweep whose weight is 0): per targeted state of a step solved with weight lambda the eigenvalue of H' = H + lambda S-_tot S+_tot,
+        RaisedNorm2 = |S+_tot psi_s|^2 -- the diagonal of one dmrgx_kron_term_gram_states over all states with the two one-sided terms
+        S+_L (x) 1 and 1 (x) S+_R of the carried operators --, Energy = Eigenvalue - lambda RaisedNorm2 = <psi_s|H|psi_s>, and
+        TotalSpin2 = RaisedNorm2 + M (M + 1): S (S + 1) of a state of definite spin. */
+    PetscErrorCode SaveSpinPenaltyStep(const KronBlocks_t& KronBlocks, const Vec& gsv_r, const double e0, const TargetStep& T, const double lambda)
+    {
+        const bool many = T.energies.size() > 1 && T.rows;
+        const PetscInt ks = many ? (PetscInt)T.energies.size() : 1;
+        const std::vector<double> eigenvalues = many ? T.energies : std::vector<double>{e0};
+        dmrgx_secop sp[2];
+        std::vector<std::vector<dmrgx_cell>> store;
+        PetscErrorCode ierr = KronBlocks.SpinRaisingOperators(sp[0], sp[1], store); CHKERRQ(ierr);
+        const std::vector<int32_t> ls = KronBlocks.LeftBlockRef().Magnetization.Sizes32(), rs = KronBlocks.RightBlockRef().Magnetization.Sizes32();
+        const dmrgx_sectors sl{(int32_t)ls.size(), ls.data()}, sr{(int32_t)rs.size(), rs.data()};
+        std::vector<int32_t> bil, bir;
+        for (PetscInt k = 0; k < KronBlocks.size(); ++k) { bil.push_back((int32_t)KronBlocks.LeftIdx(k)); bir.push_back((int32_t)KronBlocks.RightIdx(k)); }
+        const dmrgx_term terms[2] = {{1.0, 0, -1}, {1.0, -1, 0}};
+        const int32_t vec_first[2] = {0, 2};
+        dmrgx_host::DevBuffer g((size_t)(ks * ks), dmrgx_host::DevBuffer::device_only_t{});
+        if (dmrgx_kron_term_gram_states(&sl, &sr, (int32_t)bil.size(), bil.data(), bir.data(), (int32_t)ks, many ? T.rows->dev_ro() : gsv_r->buf->dev_ro(), many ? T.ld : (int64_t)gsv_r->n,
+                                        1, &sp[0], 1, &sp[1], 1, vec_first, terms, 0, g.dev_uninitialised(), ks, nullptr, nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_kron_term_gram_states: %s", dmrgx_last_error());
+        std::vector<double> G((size_t)(ks * ks));
+        if (dmrgx_memcpy_d2h(G.data(), g.dev_ro(), G.size() * sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
+        std::vector<double> raised((size_t)ks), energy((size_t)ks), spin2((size_t)ks);
+        for (PetscInt s = 0; s < ks; ++s) {
+            raised[(size_t)s] = G[(size_t)(s * ks + s)];
+            energy[(size_t)s] = eigenvalues[(size_t)s] - lambda * raised[(size_t)s];
+            spin2[(size_t)s] = raised[(size_t)s] + (double)qn_sector * ((double)qn_sector + 1.0);
+        }
+        if (mpi_rank) return 0;
+        ierr = penalty_file.Begin(data_dir + "SpinPenalty.json"); CHKERRQ(ierr);
+        FILE* fp = penalty_file.fp;
+        auto reals = [&](const char* name, const std::vector<double>& v) { fprintf(fp, ",\n   \"%s\": ", name); penalty_file.Row(v); };
+        fprintf(fp, "  {\"GlobIdx\": %lld, \"LoopType\": \"%s\", \"Lambda\": %.17g", LLD(GlobIdx), LoopTypeName(), lambda);
+        reals("Eigenvalue", eigenvalues); reals("RaisedNorm2", raised); reals("Energy", energy); reals("TotalSpin2", spin2);
         fprintf(fp, "}");
         fflush(fp);
         return 0;
@@ -2019,6 +2071,8 @@ private:
     PetscBool use_rdm_warm = PETSC_FALSE;       /* -rdm_warm_start: still recognised, does nothing (a line at start-up says so) */
     dmrgx_host::NoiseSchedule noise;            /* -noise a0,a1,... / -noise_warmup a: the weight of the density-matrix perturbation per sweep (Noise.hpp) */
     dmrgx_host::TargetStates targets;           /* -nstates k / -state_weights w0,...: the states a step solves and their weights in the density matrix (TargetStates.hpp) */
+    dmrgx_host::SpinPenaltySchedule penalty;    /* -spin_penalty l0,l1,... / -spin_penalty_warmup l: the weight of S-_tot S+_tot per sweep (SpinPenalty.hpp) */
+    dmrgx_host::JsonRecordFile penalty_file{"%.17g"};      /* SpinPenalty.json: created at the first step of a run with a non-zero weight */
     dmrgx_host::JsonRecordFile targets_file{"%.17g"};      /* TargetedStates.json: created at the first step, with -nstates k > 1 only */
     int64_t noise_max_bytes = 0;                /* the largest expansion a truncation held (DMRGRun.json NoiseMaxExpansionBytes) */
     PetscInt noise_ops[2] = {0, 0}, noise_expansions = 0;      /* operators per side of the largest list; expansions built */

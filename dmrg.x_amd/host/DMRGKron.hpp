@@ -5,7 +5,8 @@
     implementation is new:
       - enlargement is metadata only for the site operators: O (x) 1 and 1 (x) s become cell views / scaled-identity
         cells over the SAME device buffers (no copy, no flops); only the enlarged block Hamiltonian is assembled, by
-        one batch of dense-cell accumulates on the device (dmrgx_cells_axpy);
+        one batch of dense-cell accumulates on the device (dmrgx_cells_axpy) -- and, under -spin_penalty, the carried total-spin
+        operator S+_out = S+_L (x) 1 + 1 (x) s+ by the same batch, in the same allocation;
       - the superblock matrix is always matrix-free: KronSumConstruct fills a dmrgx_kron_desc and creates the HIP plan
         (grouped MFMA GEMMs), MatMult_KronSumShell applies it.  The explicit MPIAIJ superblock matrix of the reference
         (-do_shell 0) is not built. */
@@ -13,6 +14,7 @@
 #define DMRGX_DMRGKRON_HPP
 
 #include <algorithm>
+#include <cmath>
 #include <map>
 #include <set>
 #include <tuple>
@@ -88,6 +90,12 @@ public:
     }
     PetscErrorCode KronSumSetRedistribute(const PetscBool& in = PETSC_TRUE) { do_redistribute = in; return 0; }
     PetscErrorCode KronSumSetToleranceFromOptions() { return PetscOptionsGetReal(NULL, NULL, "-ks_tol", &ks_tol, NULL); }
+    /** Engine extension (-spin_penalty, SpinPenalty.hpp): KronSumConstruct builds H + lambda S-_tot S+_tot; 0 (the default): H. */
+    PetscErrorCode KronSumSetSpinPenalty(const PetscReal& lambda)
+    {
+        if (!(lambda >= 0.0) || !std::isfinite(lambda)) SETERRQ1(mpi_comm, PETSC_ERR_ARG_OUTOFRANGE, "The spin penalty must be finite and non-negative. Got %g.", (double)lambda);
+        spin_penalty = lambda; return 0;
+    }
 
     /** Keep the inter-block terms with a != 0 and renumber the right block's sites from the interface
         (L0 L1 .. R2 R1 R0): the filtering/reflection of the reference's KronSumConstruct. */
@@ -110,7 +118,10 @@ public:
     }
 
     /** Superblock Hamiltonian restricted to this object's KronBlocks as a matrix-free device plan:
-        MatOut applies  H_L (x) 1 + 1 (x) H_R + sum_t a_t A_t (x) B_t.  Release with MatDestroy_KronSumShell. */
+        MatOut applies  H_L (x) 1 + 1 (x) H_R + sum_t a_t A_t (x) B_t.  Release with MatDestroy_KronSumShell.
+        With a spin penalty lambda > 0 (KronSumSetSpinPenalty) it applies H + lambda S-_tot S+_tot instead, S+_tot = S+_L (x) 1 + 1 (x) S+_R:
+          lambda [ (S- S+)_L (x) 1 + 1 (x) (S- S+)_R ]   inside copies of H_L and H_R (PenalisedHamiltonian; the blocks' own H are not touched),
+          lambda [ S-_L (x) S+_R + S+_L (x) S-_R ]       as two more terms over the carried operators, grouped like every other term. */
     PetscErrorCode KronSumConstruct(const std::vector<Hamiltonians::Term>& Terms, Mat& MatOut)
     {
         PetscErrorCode ierr;
@@ -118,9 +129,28 @@ public:
         ierr = RightBlock.CheckOperators(); CHKERRQ(ierr); ierr = RightBlock.CheckSectors(); CHKERRQ(ierr);
         std::vector<Hamiltonians::Term> TermsLR;
         ierr = ClassifyTerms(Terms, TermsLR); CHKERRQ(ierr);
+        Mat HL = LeftBlock.H, HR = RightBlock.H;
+        if (spin_penalty > 0.0) {
+            ierr = PenalisedHamiltonian(LeftBlock, spin_penalty, HL); CHKERRQ(ierr);
+            if (LeftBlock.H == RightBlock.H && LeftBlock.SpTot == RightBlock.SpTot) HR = HL;      /* the environment is the system's reflection */
+            else { ierr = PenalisedHamiltonian(RightBlock, spin_penalty, HR); CHKERRQ(ierr); }
+            TermsLR.push_back({spin_penalty, OpSm, SiteSpTot, OpSp, SiteSpTot});
+            TermsLR.push_back({spin_penalty, OpSp, SiteSpTot, OpSm, SiteSpTot});
+        }
         /* the Hamiltonian plan is striped over the ranks of the communicator; the one-term correlator plans
            below stay whole on every rank (they act on the replicated ground state) */
-        return BuildPlan(LeftBlock.H, RightBlock.H, TermsLR, MatOut, true);
+        return BuildPlan(HL, HR, TermsLR, MatOut, true);      /* (the plan holds copies of its operators: HL and HR go with this call) */
+    }
+
+    /** The carried total-spin operators of the two blocks as the plan reads them (shift +1), for |S+_tot psi|^2 = the Gram matrix of the
+        two one-sided terms S+_L (x) 1 and 1 (x) S+_R.  `store` owns their cells. */
+    PetscErrorCode SpinRaisingOperators(dmrgx_secop& left, dmrgx_secop& right, std::vector<std::vector<dmrgx_cell>>& store) const
+    {
+        if (!LeftBlock.SpTot || !RightBlock.SpTot) SETERRQ(mpi_comm, PETSC_ERR_ARG_WRONGSTATE, "The blocks do not carry their total-spin operators (-spin_penalty).");
+        store.assign(2, std::vector<dmrgx_cell>());
+        LeftBlock.SpTot->to_secop(left, store[0]);
+        RightBlock.SpTot->to_secop(right, store[1]);
+        return 0;
     }
 
     /** Single product Mat_L (x) Mat_R on the KronBlocks (correlators), matrix-free like the Hamiltonian
@@ -159,10 +189,57 @@ public:
     }
 
 private:
+    /** "site" of a term factor that is the block's carried total-spin operator (OpSp: as stored, OpSm: read transposed) */
+    static constexpr PetscInt SiteSpTot = -2;
+
     static Mat OpOf(Block::SpinBase& blk, Op_t op, PetscInt site, const Mat& extra)
     {
+        if (site == SiteSpTot) return op == OpSz ? nullptr : blk.SpTot;
         if (site < 0) return extra;
         return op == OpSz ? blk.Sz(site) : blk.Sp(site);      /* Sm(i) is read as Sp(i) transposed */
+    }
+
+    /** out = H + lambda (S- S+) of one block, dense per sector, in storage of its own: a copy of the block's H (dmrgx_cells_axpy) to which
+        the product of the carried operator read transposed with itself (dmrgx_secop_compose, one two-factor string) is added with weight
+        lambda (dmrgx_cells_axpy): one m x m product per sector.  The block is only read. */
+    static PetscErrorCode PenalisedHamiltonian(Block::SpinBase& blk, const double lambda, Mat& out)
+    {
+        using namespace dmrgx_host;
+        const MPI_Comm comm = blk.MPIComm();
+        if (!blk.SpTot) SETERRQ(comm, PETSC_ERR_ARG_WRONGSTATE, "The spin penalty needs the block's carried total-spin operator, which this block does not have.");
+        if (!blk.H) SETERRQ(comm, PETSC_ERR_ARG_WRONGSTATE, "The spin penalty needs the block's Hamiltonian.");
+        if (SectorMatDensify(blk.H, out)) SETERRQ1(comm, 1, "copy of the block Hamiltonian: %s", dmrgx_last_error());
+        const std::vector<int32_t> sz = blk.Magnetization.Sizes32();
+        const int32_t ns = (int32_t)sz.size();
+        const dmrgx_sectors sectors{ns, sz.data()};
+        dmrgx_secop ops[2];
+        std::vector<dmrgx_cell> store[2];
+        blk.SpTot->to_secop(ops[0], store[0], true, -1);      /* S-_blk: read from S+_blk as Sm(i) is read from Sp(i) */
+        blk.SpTot->to_secop(ops[1], store[1]);
+        const int32_t out_first[2] = {0, 1};
+        const dmrgx_secop_string string{1.0, 2, {0, 1, 0}};
+        int32_t shift = 0, cell_first[2] = {0, 0};
+        std::vector<dmrgx_cell> cells((size_t)std::max(ns, 1));
+        int64_t total = 0;
+        if (dmrgx_secop_compose(&sectors, 2, ops, 1, out_first, &string, &shift, cell_first, cells.data(), &total, nullptr, nullptr)) SETERRQ1(comm, 1, "dmrgx_secop_compose: %s", dmrgx_last_error());
+        std::shared_ptr<DevBuffer> arena;
+        try { arena = std::make_shared<DevBuffer>((size_t)std::max<int64_t>(total, 1), DevBuffer::device_only_t{}); }
+        catch (const std::exception& e) { SETERRQ1(comm, PETSC_ERR_MEM, "spin penalty: %s", e.what()); }
+        if (dmrgx_secop_compose(&sectors, 2, ops, 1, out_first, &string, &shift, cell_first, cells.data(), &total, arena->dev_uninitialised(), nullptr)) SETERRQ1(comm, 1, "dmrgx_secop_compose: %s", dmrgx_last_error());
+        if (shift != 0) SETERRQ1(comm, 1, "S- S+ came out with sector shift %d.", (int)shift);
+        std::vector<dmrgx_axpy_task> tasks;
+        for (int32_t ci = cell_first[0]; ci < cell_first[1]; ++ci) {
+            const dmrgx_cell& c = cells[(size_t)ci];
+            MatCell* d = nullptr;
+            for (MatCell& o : out->cells) if (o.q == c.row_sector) d = &o;
+            if (!d || d->nr != c.nr || d->nc != c.nc) SETERRQ1(comm, 1, "S- S+ of sector %d does not fit the block Hamiltonian.", (int)c.row_sector);
+            if (c.nr == 0 || c.nc == 0) continue;
+            dmrgx_axpy_task t;
+            t.dst = d->buf->dev_uninitialised() + d->off; t.dst_base = nullptr; t.src = c.data; t.ldd = d->ld; t.lds = c.ld; t.nr = c.nr; t.nc = c.nc; t.transposed = 0; t.alpha = lambda;
+            tasks.push_back(t);
+        }
+        if (!tasks.empty() && dmrgx_cells_axpy((int32_t)tasks.size(), tasks.data(), nullptr)) SETERRQ1(comm, 1, "dmrgx_cells_axpy: %s", dmrgx_last_error());
+        return 0;      /* (the product's storage goes here: the pool is stream-ordered) */
     }
 
     /** The distinct (operator, site) operators of the classified terms on each side, in the order the terms first name them, as the plan
@@ -182,7 +259,7 @@ private:
             store.emplace_back();
             dmrgx_secop so;
             if (m->transpose_of) m->transpose_of->to_secop(so, store.back(), true, -m->transpose_of->shift);
-            else if (site >= 0 && op == OpSm) m->to_secop(so, store.back(), true, -1);   /* block operator Sp(site) read as Sm */
+            else if ((site >= 0 || site == SiteSpTot) && op == OpSm) m->to_secop(so, store.back(), true, -1);   /* block operator Sp(site) read as Sm */
             else m->to_secop(so, store.back());
             ops.push_back(so);
             idx[key] = (int32_t)ops.size() - 1;
@@ -239,7 +316,7 @@ private:
     Block::SpinBase& RightBlock;
     FILE* fp_prealloc;
     PetscBool do_redistribute = PETSC_FALSE, do_shell = PETSC_TRUE;
-    PetscReal ks_tol = 1.0e-16;
+    PetscReal ks_tol = 1.0e-16, spin_penalty = 0.0;
     Mat extra_left = nullptr, extra_right = nullptr;
 };
 
@@ -422,27 +499,54 @@ inline PetscErrorCode KronEye_Explicit(Block::SpinBase& LeftBlock, Block::SpinBa
     /* ---- block Hamiltonian: dense sector blocks assembled on the device ----------------------------------------- */
     std::vector<Hamiltonians::Term> TermsLR;
     ierr = KB.ClassifyTerms(Terms, TermsLR); CHKERRQ(ierr);
-    if (!LeftBlock.H && !RightBlock.H && TermsLR.empty()) { BlockOut.H = nullptr; return 0; }
+    /* the carried total-spin operator (-spin_penalty): S+_out = S+_L (x) 1 + 1 (x) s+, built where both inputs carry theirs */
+    if ((bool)LeftBlock.SpTot != (bool)RightBlock.SpTot) SETERRQ(mpi_comm, PETSC_ERR_ARG_WRONGSTATE, "KronEye_Explicit: only one of the two blocks carries its total-spin operator.");
+    const bool carry = (bool)LeftBlock.SpTot, have_h = LeftBlock.H || RightBlock.H || !TermsLR.empty();
+    if (!have_h && !carry) { BlockOut.H = nullptr; return 0; }
     /* all sector blocks in one device allocation, zeroed by one launch (one allocation and one launch per block before) */
     Mat Hout = std::make_shared<SectorMat>();
     Hout->shift = 0; Hout->sizes = out_sizes;
+    const int32_t nsec_out = (int32_t)out_sizes.size();
     size_t htotal = 0;
     for (int32_t sz : out_sizes) htotal += (size_t)sz * (size_t)sz;
+    if (carry) for (int32_t q = 0; q + 1 < nsec_out; ++q) htotal += (size_t)out_sizes[(size_t)q] * (size_t)out_sizes[(size_t)q + 1];      /* the blocks (q -> q + 1) of S+_out, behind H_out's */
     std::shared_ptr<dmrgx_host::DevBuffer> harena;
     try { harena = std::make_shared<dmrgx_host::DevBuffer>(htotal, dmrgx_host::DevBuffer::device_only_t{}); } catch (const std::exception& e) { SETERRQ1(mpi_comm, PETSC_ERR_MEM, "KronEye_Explicit: %s", e.what()); }
     if (htotal && dmrgx_memset_zero(harena->dev_uninitialised(), htotal * sizeof(double), nullptr)) SETERRQ1(mpi_comm, 1, "%s", dmrgx_last_error());
     std::vector<dmrgx_axpy_task> tasks;
-    std::vector<double*> blockptr(out_sizes.size());
+    std::vector<double*> blockptr(out_sizes.size()), spptr(out_sizes.size(), nullptr);
+    Mat SpOut = nullptr;
     {
         size_t cursor = 0;
-        for (int32_t q = 0; q < (int32_t)out_sizes.size(); ++q) {
+        for (int32_t q = 0; q < nsec_out; ++q) {
             dmrgx_host::MatCell c;
             c.q = q; c.nr = out_sizes[(size_t)q]; c.nc = c.nr; c.ld = c.nc; c.buf = harena; c.off = (int64_t)cursor;
             blockptr[(size_t)q] = harena->dev_uninitialised() + cursor;
             cursor += (size_t)c.nr * (size_t)c.nc;
             Hout->cells.push_back(c);
         }
+        if (carry) {
+            SpOut = std::make_shared<SectorMat>();
+            SpOut->shift = OpSp; SpOut->sizes = out_sizes;
+            for (int32_t q = 0; q + 1 < nsec_out; ++q) {
+                dmrgx_host::MatCell c;
+                c.q = q; c.nr = out_sizes[(size_t)q]; c.nc = out_sizes[(size_t)q + 1]; c.ld = c.nc; c.buf = harena; c.off = (int64_t)cursor;
+                spptr[(size_t)q] = harena->dev_uninitialised() + cursor;
+                cursor += (size_t)c.nr * (size_t)c.nc;
+                SpOut->cells.push_back(c);
+            }
+        }
     }
+    auto push_sp = [&](PetscInt k, PetscInt kc, const double* src, int64_t lds, int32_t r0, int32_t c0, int32_t nrr, int32_t ncc, double alpha) {
+        /* S+_out[sub[k] + r0.., sub[kc] + c0..] += alpha * cell (src == NULL: alpha on the diagonal), in the block (sec[k] -> sec[k] + 1) */
+        const int32_t q = sec[k];
+        const int64_t ld = out_sizes[(size_t)q + 1];
+        dmrgx_axpy_task t;
+        t.dst = spptr[q] + (int64_t)(sub[k] + r0) * ld + (sub[kc] + c0);
+        t.dst_base = spptr[q] + (int64_t)sub[k] * ld + sub[kc];      /* as for H_out: tasks into one (k,kc) sub-block are ordered */
+        t.src = src; t.alpha = alpha; t.ldd = ld; t.lds = lds; t.nr = nrr; t.nc = ncc; t.transposed = 0;
+        tasks.push_back(t);
+    };
     auto push = [&](PetscInt k, PetscInt kc, const MatCell& c, bool tr, double alpha, int32_t rmul) {
         /* out[sub[k] + r0.., sub[kc] + c0..] += alpha * cell (transposed view when tr) ; rmul: 1 (only 1-state right sectors) */
         const int32_t q = sec[k];
@@ -496,9 +600,29 @@ inline PetscErrorCode KronEye_Explicit(Block::SpinBase& LeftBlock, Block::SpinBa
                 push(k, kc, c, trA, t.a * b, 1);
             }
         }
+        if (carry) {
+            const PetscInt kl = KB.Map(IL + 1, IR), kr = KB.Map(IL, IR + 1);
+            if (kl >= 0) {                                                   /* S+_L (x) 1 */
+                if (sec[kl] != sec[k] + 1) SETERRQ(mpi_comm, 1, "KronEye_Explicit: the sectors of the enlarged block are not one unit of Sz apart.");
+                if (!one_r) SETERRQ(mpi_comm, PETSC_ERR_SUP, "KronEye_Explicit: S+_L (x) 1 needs one-state right sectors.");
+                for (const MatCell& c : LeftBlock.SpTot->cells) if (c.q == IL) {
+                    if (c.kind == DMRGX_CELL_DENSE) push_sp(k, kl, c.buf->dev_ro() + c.off, c.ld, c.r0, c.c0, c.nr, c.nc, 1.0);
+                    else push_sp(k, kl, nullptr, 0, c.r0, c.c0, c.nr, c.nc, c.scale);
+                }
+            }
+            if (kr >= 0) {                                                   /* 1 (x) s+: the 1 x 1 block (IR -> IR + 1) of the added site */
+                if (sec[kr] != sec[k] + 1) SETERRQ(mpi_comm, 1, "KronEye_Explicit: the sectors of the enlarged block are not one unit of Sz apart.");
+                if (!one_r || MR.Sizes(IR + 1) != 1) SETERRQ(mpi_comm, PETSC_ERR_SUP, "KronEye_Explicit: 1 (x) S+_R needs one-state right sectors (added site).");
+                double b = 0.0;
+                for (const MatCell& c : RightBlock.SpTot->cells) if (c.q == IR) b += (c.kind == DMRGX_CELL_DENSE) ? c.buf->host_ro()[c.off] : c.scale;
+                const int32_t n = (int32_t)ML.Sizes(IL);
+                if (b != 0.0 && n > 0) push_sp(k, kr, nullptr, 0, 0, 0, n, n, b);
+            }
+        }
     }
     if (!tasks.empty() && dmrgx_cells_axpy((int32_t)tasks.size(), tasks.data(), nullptr)) SETERRQ1(mpi_comm, 1, "dmrgx_cells_axpy: %s", dmrgx_last_error());
-    BlockOut.H = Hout;
+    BlockOut.H = have_h ? Hout : nullptr;
+    BlockOut.SpTot = SpOut;
     return 0;
 }
 

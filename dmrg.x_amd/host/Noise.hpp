@@ -36,15 +36,15 @@ struct NoiseSchedule {
     }
 };
 
-/** Reads -noise and -noise_warmup from the options database.  A value that is negative or not finite, or a token that is no number, is
-    refused with PETSC_ERR_ARG_OUTOFRANGE. */
-inline PetscErrorCode ReadNoiseOptions(MPI_Comm comm, NoiseSchedule& out)
+/** Reads a schedule of weights from the options database: `name` a0,a1,... and `name_warmup` a.  A value that is negative or not finite,
+    or a token that is no number, is refused with PETSC_ERR_ARG_OUTOFRANGE. */
+inline PetscErrorCode ReadSweepWeights(MPI_Comm comm, const char* name, const char* name_warmup, NoiseSchedule& out)
 {
     PetscErrorCode ierr;
     out = NoiseSchedule();
     PetscBool set = PETSC_FALSE;
     char raw[4096] = "";
-    ierr = PetscOptionsGetString(NULL, NULL, "-noise", raw, sizeof raw, &set); CHKERRQ(ierr);
+    ierr = PetscOptionsGetString(NULL, NULL, name, raw, sizeof raw, &set); CHKERRQ(ierr);
     if (set) {
         const std::string s(raw);
         size_t pos = 0;
@@ -54,18 +54,21 @@ inline PetscErrorCode ReadNoiseOptions(MPI_Comm comm, NoiseSchedule& out)
             char* end = nullptr;
             const double a = strtod(tok.c_str(), &end);
             if (tok.empty() || end == tok.c_str() || *end != 0 || !std::isfinite(a) || a < 0.0)
-                SETERRQ1(comm, PETSC_ERR_ARG_OUTOFRANGE, "-noise takes non-negative numbers separated by commas, one per sweep. Got \"%s\".", raw);
+                SETERRQ2(comm, PETSC_ERR_ARG_OUTOFRANGE, "%s takes non-negative numbers separated by commas, one per sweep. Got \"%s\".", name, raw);
             out.sweeps.push_back(a);
             if (c == std::string::npos) break;
             pos = c + 1;
         }
     }
     PetscReal w = 0.0;
-    ierr = PetscOptionsGetReal(NULL, NULL, "-noise_warmup", &w, &set); CHKERRQ(ierr);
-    if (set && (!std::isfinite(w) || w < 0.0)) SETERRQ1(comm, PETSC_ERR_ARG_OUTOFRANGE, "-noise_warmup takes a non-negative number. Got %g.", (double)w);
+    ierr = PetscOptionsGetReal(NULL, NULL, name_warmup, &w, &set); CHKERRQ(ierr);
+    if (set && (!std::isfinite(w) || w < 0.0)) SETERRQ2(comm, PETSC_ERR_ARG_OUTOFRANGE, "%s takes a non-negative number. Got %g.", name_warmup, (double)w);
     out.warmup = set ? (double)w : 0.0;
     return 0;
 }
+
+/** Reads -noise and -noise_warmup from the options database (ReadSweepWeights). */
+inline PetscErrorCode ReadNoiseOptions(MPI_Comm comm, NoiseSchedule& out) { return ReadSweepWeights(comm, "-noise", "-noise_warmup", out); }
 
 /** Two descriptors of the same operator: the same cells (compared field by field: the plan lists Sp(i) and Sm(i) as two views of one
     set of device blocks) read the same way. */

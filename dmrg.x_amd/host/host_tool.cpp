@@ -14,6 +14,7 @@
 #include "EngineMeasurements.hpp"
 #include "Noise.hpp"
 #include "TargetStates.hpp"
+#include "SpinPenalty.hpp"
 
 static void dump_mat(const char* tag, PetscInt site, const Mat& m)
 {
@@ -76,8 +77,9 @@ int main()
             ierr = blocks[name].SaveToDisk(dir);
             printf("rc %d\n", ierr);
         } else if (cmd == "load") {
-            std::string name, dir; is >> name >> dir;
-            ierr = blocks[name].InitializeFromDisk(PETSC_COMM_WORLD, dir);
+            std::string name, dir; int with_sp_tot = 0; is >> name >> dir;
+            if (!(is >> with_sp_tot)) with_sp_tot = 0;      /* load name dir 1: the carried total-spin operator too */
+            ierr = blocks[name].InitializeFromDisk(PETSC_COMM_WORLD, dir, with_sp_tot != 0);
             printf("rc %d\n", ierr);
         } else if (cmd == "check") {
             std::string name; is >> name;
@@ -320,6 +322,28 @@ int main()
                 print_numbers("noise", v);
                 printf("any %d json %s\n", (int)S.Any(), S.Json().c_str());
             }
+        } else if (cmd == "spinpenalty") {      /* spinpenalty <-spin_penalty value or "none"> <-spin_penalty_warmup value or "none"> nsweeps ranks  ->  as "noise", read on that many ranks */
+            std::string sched, warm; PetscInt nsweeps; PetscMPIInt ranks; is >> sched >> warm >> nsweeps >> ranks;
+            dmrgx_host::Options::Global().Clear();
+            if (sched != "none") PetscOptionsSetValue(NULL, "-spin_penalty", sched == "empty" ? "" : sched.c_str());
+            if (warm != "none") PetscOptionsSetValue(NULL, "-spin_penalty_warmup", warm.c_str());
+            dmrgx_host::SpinPenaltySchedule S;
+            ierr = dmrgx_host::ReadSpinPenaltyOptions(PETSC_COMM_WORLD, ranks, S);
+            printf("rc %d\n", ierr);
+            if (!ierr) {
+                std::vector<double> v{S.At(true, 0)};
+                for (PetscInt s = 0; s < nsweeps; ++s) v.push_back(S.At(false, s));
+                print_numbers("spinpenalty", v);
+                printf("any %d json %s\n", (int)S.Any(), S.Json().c_str());
+            }
+        } else if (cmd == "sptot") {            /* sptot name: gives a one-site block its carried total-spin operator */
+            std::string name; is >> name;
+            ierr = blocks[name].CreateSpTot();
+            printf("rc %d\n", ierr);
+        } else if (cmd == "dumpsptot") {        /* dumpsptot name: the carried operator, as "dump" prints a site operator */
+            std::string name; is >> name;
+            dump_mat("SpTot", 0, blocks[name].SpTot);
+            printf("end\n");
         } else if (cmd == "targets") {          /* targets <-nstates value or "none"> <-state_weights value or "none"> nstates_of_sector  ->  rc, then k, k_step and the step's normalised weights */
             std::string ns, sw; PetscInt in_sector; is >> ns >> sw >> in_sector;
             dmrgx_host::Options::Global().Clear();
