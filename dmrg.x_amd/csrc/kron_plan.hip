@@ -504,11 +504,11 @@ struct Tables {
     //           X_src[:, contraction range of the cell] * cellT.  A merged right operator may hold several cells with the
     //           same output columns (e.g. O (x) 1 cell (2,2) and the new site's identity cell (2,1)), so groups are built
     //           per output-column SEGMENT with a product list -- never one overwriting group per cell.
-    // T (at toff, this rank's stripe of block k) is read from the source block ksrc of x.
-    void stage1(const Layout& L, const std::vector<PCell>& cellsT, int32_t k, int32_t ksrc, int64_t toff) {
+    // T (at toff, this rank's stripe of block k) is read from the source block ksrc of x; only its rows [row0, row0 + M) are built.
+    void stage1(const Layout& L, const std::vector<PCell>& cellsT, int32_t k, int32_t ksrc, int64_t toff, int32_t row0, int32_t M) {
         const int32_t ir = L.ir[k], cs = L.cbeg(k, L.me), ce = L.cend(k, L.me), w = ce - cs;
-        if (w <= 0) return;
-        const int32_t M = L.nL[ksrc];
+        if (w <= 0 || M <= 0) return;
+        toff += (int64_t)row0 * w;
         std::set<int32_t> cuts = {cs, ce};
         auto clampc = [&](int32_t v) { return std::min(std::max(v, cs), ce); };
         for (const PCell& c : cellsT) {
@@ -529,14 +529,14 @@ struct Tables {
                     for (int32_t p = 0; p < L.W; ++p) {          // contraction index r' in [c.r0, c.r0+c.nr) split over source panels
                         const int32_t k0 = std::max(c.r0, L.cbeg(ksrc, p)), k1 = std::min(c.r0 + c.nr, L.cend(ksrc, p));
                         if (k0 >= k1) continue;
-                        add_gemm(BASE_X, L.panel_off(ksrc, p) + (k0 - L.cbeg(ksrc, p)), L.panel_ld(ksrc, p),
+                        add_gemm(BASE_X, L.panel_off(ksrc, p) + (int64_t)row0 * L.panel_ld(ksrc, p) + (k0 - L.cbeg(ksrc, p)), L.panel_ld(ksrc, p),
                                  BASE_ARENA, c.off + (int64_t)(k0 - c.r0) * c.nc + (o0 - c.c0), c.nc, k1 - k0);
                     }
                 } else {                                         // identity cell: T[:, o] += scale * X_src[:, c.r0 + (o - c.c0)]
                     const int32_t s0 = c.r0 + (o0 - c.c0);
                     int32_t p = 0;
                     for (int32_t pp = 0; pp < L.W; ++pp) if (L.cbeg(ksrc, pp) <= s0 && s0 < L.cend(ksrc, pp)) p = pp;
-                    add_axpy(BASE_X, L.panel_off(ksrc, p) + (s0 - L.cbeg(ksrc, p)), L.panel_ld(ksrc, p), c.scale);
+                    add_axpy(BASE_X, L.panel_off(ksrc, p) + (int64_t)row0 * L.panel_ld(ksrc, p) + (s0 - L.cbeg(ksrc, p)), L.panel_ld(ksrc, p), c.scale);
                 }
             }
             close(g);
@@ -702,7 +702,11 @@ struct HostPlan {
     dmrgx_kron_info info{};
 };
 
-dmrgx_status plan_on_host(const dmrgx_kron_desc* d, const Checked& in, HostPlan& hp)
+// rows_read (DMRGX_PLAN_FOLD, default on): stage 1 builds only the rows of T_{g,k} that stage 2 reads -- the rows under a cell of the group's
+// left operator in sector IL, for the Sp / Sm operators of a block's new site (one identity cell per sector block) about half of them.  The
+// other rows get no group, no tile and no zero rectangle.  Every element of y stays the same sum in the same order: y is bit for bit what
+// the plan of whole intermediates gives.
+dmrgx_status plan_on_host(const dmrgx_kron_desc* d, const Checked& in, bool rows_read, HostPlan& hp)
 {
     const Layout L(d);
     Operators O;
@@ -710,8 +714,20 @@ dmrgx_status plan_on_host(const dmrgx_kron_desc* d, const Checked& in, HostPlan&
     const int64_t T_elems = place_intermediates(L, in, O);
     Tables& B = hp.tab;
     for (const Group& g : O.G)
-        for (int32_t k = 0; k < L.nb; ++k) if (g.ksrc[k] >= 0) B.stage1(L, g.rightT, k, g.ksrc[k], g.toff[k]);
-    if (!O.HRT.empty()) for (int32_t k = 0; k < L.nb; ++k) B.stage1(L, O.HRT, k, k, O.TRoff[k]);
+        for (int32_t k = 0; k < L.nb; ++k) {
+            if (g.ksrc[k] < 0) continue;
+            if (!rows_read) { B.stage1(L, g.rightT, k, g.ksrc[k], g.toff[k], 0, L.nL[g.ksrc[k]]); continue; }
+            std::vector<std::pair<int32_t, int32_t>> read;             // [c0, c0 + nc) of the left cells of sector IL, merged into disjoint ranges
+            for (const PCell& c : g.left) if (c.q == L.il[k]) read.push_back({c.c0, c.c0 + c.nc});
+            std::sort(read.begin(), read.end());
+            for (size_t i = 0; i < read.size();) {
+                const int32_t r0 = read[i].first;
+                int32_t r1 = read[i].second;
+                for (++i; i < read.size() && read[i].first <= r1; ++i) r1 = std::max(r1, read[i].second);
+                B.stage1(L, g.rightT, k, g.ksrc[k], g.toff[k], r0, r1 - r0);
+            }
+        }
+    if (!O.HRT.empty()) for (int32_t k = 0; k < L.nb; ++k) B.stage1(L, O.HRT, k, k, O.TRoff[k], 0, L.nL[k]);
     B.stage2(L, O);
     B.finalize_stage2(O.elems + T_elems);
     ggemm_schedule(B.tiles1, B.groups);
@@ -809,7 +825,8 @@ extern "C" dmrgx_status dmrgx_kron_plan_create(const dmrgx_kron_desc* d, void* s
     Checked in;
     DMRGX_CHK(validate(d, in));
     HostPlan hp;
-    DMRGX_CHK(plan_on_host(d, in, hp));
+    const char* rows = getenv("DMRGX_PLAN_FOLD");        // A/B switch, read at plan creation: 0 builds every intermediate whole
+    DMRGX_CHK(plan_on_host(d, in, !(rows && atoi(rows) == 0), hp));
     if (const char* dump = getenv("DMRGX_PLAN_DUMP")) dump_plan(dump, hp.tab);
     std::unique_ptr<dmrgx_kron_plan> P(new (std::nothrow) dmrgx_kron_plan());
     if (!P) DMRGX_FAIL(DMRGX_ERR_MEM, "out of host memory");

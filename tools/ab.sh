@@ -7,9 +7,11 @@
 #   tools/ab.sh opts "optsA" "optsB" ...      the current build on configs[3] with several engine option sets (AB_NSWEEPS=1), twice, alternating
 #   tools/ab.sh c2opts "optsA" "optsB" ...    the same on configs[1] (12 sweeps: first sweep and the mean of sweeps 3-12)
 #   tools/ab.sh env "A=1,B=2" "-" ...         the current build on configs[3] under several environment settings ("-": none)
+#   tools/ab.sh fold                          = env "DMRGX_PLAN_FOLD=0" "-": the MatMult plan with whole stage-1 intermediates against the default (only the rows read)
 #   tools/ab.sh bench NAME1 NAME2 ... [-- bench args]   bench.py --full --no-sweep --no-cpu-baseline with the library of each saved build (DMRGX_LIB), twice, alternating
 set -o pipefail
 root=$(pwd); cmd=$1; shift
+[ "$cmd" = fold ] && { cmd=env; set -- "DMRGX_PLAN_FOLD=0" "-"; }
 c4="-Lx 20 -Ly 8 -J1 1 -Jz1 1 -J2 0.5 -Jz2 0.5 -mwarmup 2048 -nsweeps ${AB_NSWEEPS:-1} -H_eps_type gd"
 c2="-Lx 8 -Ly 4 -J1 1 -Jz1 1 -J2 0.5 -Jz2 0.5 -mwarmup 512 -nsweeps 12"
 report() {      # report DIR LABEL REP NSTEPS
@@ -49,5 +51,5 @@ bench) names=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do names+=("$1"); shift
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('[$v] rep$rep: value %.1f MatMults/s  isolated %.1f  frac %.4f  stage1 %.4f ms  stage2 %.4f ms'%(d['value'],d['matmult_isolated_per_s'],r['frac'],r['stage1_ms_per_matmult'],r['stage2_ms_per_matmult']))"
   done; done;;
-*) sed -n 2,12p $0;;
+*) sed -n 2,13p $0;;
 esac
