@@ -387,6 +387,13 @@ POISONED_NODES = [
     "tests/test_gpu_rotate.py::test_rotate_ops_size_edges",
     "tests/test_gpu_rotate.py::test_rotate_ops_truncation_patterns",
     "tests/test_gpu_rotate.py::test_rotate_ops_refusal_case_is_accepted_undamaged",
+    # general descriptors, element-wise bound: every case, named and drawn, and the patched-table cache
+    "tests/test_gpu_kron_general.py::test_apply",
+    "tests/test_gpu_kron_general.py::test_gathered_apply",
+    "tests/test_gpu_kron_general.py::test_fold_switch",
+    "tests/test_gpu_kron_general.py::test_diagonal",
+    "tests/test_gpu_kron_general.py::test_repeatability",
+    "tests/test_gpu_kron_general.py::test_patched_table_cache_past_its_capacity",
 ]
 
 
