@@ -20,7 +20,7 @@ $(CSRC)/ggemm.isa.ok: $(CSRC)/ggemm.hip $(CSRC)/ggemm.h $(CSRC)/common.h tools/c
 	python3 tools/check_staging_regs.py $(CSRC)/ggemm.isa.s
 	touch $@
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/krylov.h $(CSRC)/ggemm.h $(CSRC)/hqr.h $(CSRC)/symeig.h $(CSRC)/symeig_impl.h $(CSRC)/rdm.h include/dmrgx.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/krylov.h $(CSRC)/cg.h $(CSRC)/ritz.h $(CSRC)/ggemm.h $(CSRC)/hqr.h $(CSRC)/symeig.h $(CSRC)/symeig_impl.h $(CSRC)/rdm.h include/dmrgx.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(PKG)/libdmrgx_hip.so: $(HIP_OBJS)

@@ -17,15 +17,14 @@
 // After the loop: p = y, t = H p, s = t - sigma y = eta X, X = s / eta, u = H s, true residual |b - (u - sigma s + eta^2 y)| / |b|.
 // The MatMult sees the pairs (p, t) and (s, t) only.  Iterations are enqueued in blocks of check_every; one small copy per block brings
 // the scalars back.  Fixed grids, partials added in block order by one workgroup, no atomics: the same bits whatever check_every is.
-#include "krylov.h"
-#include <cmath>
-#include <limits>
+// What this run shares with response.hip -- the scalar slots, the direction kernel, the decisions of scalars 1 and 2, the checks, the block
+// loop, the stats -- is cg.h.
+#include "cg.h"
 
 namespace dmrgx {
 namespace {
 
-// the device scalars; the overlaps <u_i, Y>, <u_i, X> follow from CV_NS on
-enum : int { CV_NORM2 = 0, CV_BB = 1, CV_RR = 2, CV_ALPHA = 3, CV_BETA = 4, CV_ITER = 5, CV_CONV = 6, CV_DEAD = 7, CV_STOP = 8, CV_APPLY = 9, CV_TRUE2 = 10, CV_NS = 12 };
+// the device scalars are the common ones; the overlaps <u_i, Y>, <u_i, X> follow from CG_NS on
 
 // partial[b] = sum of x[e]^2 over block b's range (lanczos.hip strides the whole grid: other bits).  (x is the caller's: 8-byte loads)
 __global__ void __launch_bounds__(RANGE_THREADS) cv_norm2_kernel(const double* __restrict__ x, int64_t n, double* __restrict__ partial)
@@ -40,7 +39,7 @@ __global__ void __launch_bounds__(RANGE_THREADS) cv_norm2_kernel(const double* _
 __global__ void __launch_bounds__(RANGE_THREADS) cv_start_kernel(const double* __restrict__ v0, double* __restrict__ r, double* __restrict__ p, double* __restrict__ y, int64_t n,
                                                                 double eta, const double* __restrict__ S)
 {
-    const bool dead = S[CV_DEAD] != 0.0;
+    const bool dead = S[CG_DEAD] != 0.0;
     for (int64_t e = range_first(); e < range_end(n); e += RANGE_THREADS) {
         const double b = dead ? 0.0 : -eta * v0[e];
         r[e] = b;
@@ -53,7 +52,7 @@ __global__ void __launch_bounds__(RANGE_THREADS) cv_start_kernel(const double* _
 __global__ void __launch_bounds__(RANGE_THREADS) cv_s_kernel(const double* __restrict__ t, const double* __restrict__ p, double* __restrict__ s, int64_t n, double sigma,
                                                             const double* __restrict__ S, double* __restrict__ partial)
 {
-    if (S[CV_STOP] != 0.0) return;
+    if (S[CG_STOP] != 0.0) return;
     double2 tr[RANGE_PAIRS], pr[RANGE_PAIRS];
 #pragma unroll
     for (int i = 0; i < RANGE_PAIRS; ++i) {
@@ -81,8 +80,8 @@ __global__ void __launch_bounds__(RANGE_THREADS) cv_s_kernel(const double* __res
 __global__ void __launch_bounds__(RANGE_THREADS) cv_residual_kernel(const double* __restrict__ u, const double* __restrict__ s, const double* __restrict__ p, double* __restrict__ r,
                                                                    int64_t n, double sigma, double eta2, const double* __restrict__ S, double* __restrict__ partial)
 {
-    if (S[CV_STOP] != 0.0) return;
-    const double alpha = S[CV_ALPHA];
+    if (S[CG_STOP] != 0.0) return;
+    const double alpha = S[CG_ALPHA];
     double2 ur[RANGE_PAIRS], sr[RANGE_PAIRS], pr[RANGE_PAIRS], rr[RANGE_PAIRS];
 #pragma unroll
     for (int i = 0; i < RANGE_PAIRS; ++i) {
@@ -106,41 +105,11 @@ __global__ void __launch_bounds__(RANGE_THREADS) cv_residual_kernel(const double
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
-// the iteration counted: y += alpha p, and p = r + beta p unless that iteration converged.  YVEC: the caller's y is 16-byte aligned
-template <bool YVEC> __global__ void __launch_bounds__(RANGE_THREADS) cv_direction_kernel(const double* __restrict__ r, double* __restrict__ p, double* __restrict__ y, int64_t n,
-                                                                                         const double* __restrict__ S)
-{
-    if (S[CV_APPLY] == 0.0) return;
-    const double alpha = S[CV_ALPHA], beta = S[CV_BETA];
-    const bool turn = S[CV_CONV] == 0.0;
-    double2 rr[RANGE_PAIRS], pr[RANGE_PAIRS], yr[RANGE_PAIRS];
-#pragma unroll
-    for (int i = 0; i < RANGE_PAIRS; ++i) {
-        const int64_t e = range_pair(i);
-        if (turn) rr[i] = load2<true>(r, e, n);
-        pr[i] = load2<true>(p, e, n);
-        yr[i] = load2<YVEC>(y, e, n);
-    }
-#pragma unroll
-    for (int i = 0; i < RANGE_PAIRS; ++i) {
-        const int64_t e = range_pair(i);
-        double2 x;
-        x.x = yr[i].x + alpha * pr[i].x;
-        x.y = yr[i].y + alpha * pr[i].y;
-        store2<YVEC>(y, e, n, x);
-        if (turn) {
-            x.x = rr[i].x + beta * pr[i].x;
-            x.y = rr[i].y + beta * pr[i].y;
-            store2<true>(p, e, n, x);
-        }
-    }
-}
-
 // closing 1: s = t - sigma y = eta X (t = H y), X = s / eta when X is wanted; a refused v0: exact zeros.  (y, X: the caller's, 8-byte accesses)
 __global__ void __launch_bounds__(RANGE_THREADS) cv_x_kernel(const double* __restrict__ t, const double* __restrict__ y, double* __restrict__ s, double* __restrict__ X, int64_t n,
                                                             double sigma, double eta, const double* __restrict__ S)
 {
-    const bool none = S[CV_NORM2] == 0.0;
+    const bool none = S[CG_NORM2] == 0.0;
     for (int64_t e = range_first(); e < range_end(n); e += RANGE_THREADS) {
         const double x = none ? 0.0 : t[e] - sigma * y[e];
         s[e] = x;
@@ -152,7 +121,7 @@ __global__ void __launch_bounds__(RANGE_THREADS) cv_x_kernel(const double* __res
 __global__ void __launch_bounds__(RANGE_THREADS) cv_true_residual_kernel(const double* __restrict__ v0, const double* __restrict__ u, const double* __restrict__ s, const double* __restrict__ y,
                                                                         int64_t n, double sigma, double eta, const double* __restrict__ S, double* __restrict__ partial)
 {
-    const bool none = S[CV_NORM2] == 0.0;
+    const bool none = S[CG_NORM2] == 0.0;
     double acc = 0.0;
     for (int64_t e = range_first(); e < range_end(n); e += RANGE_THREADS) {
         const double d = none ? 0.0 : -eta * v0[e] - (u[e] - sigma * s[e] + eta * eta * y[e]);
@@ -165,9 +134,8 @@ __global__ void __launch_bounds__(RANGE_THREADS) cv_true_residual_kernel(const d
 // One workgroup: the partials added in block order, then the scalar logic of the stage.
 //   stage 0 (start):   |v0|^2; not a positive finite number (nor eta^2 |v0|^2) -> dead and stopped from the start, reported as 0
 //   stage 1 (alpha):   s.s and p.p; a sum that is not finite, p.A p not positive and finite, or an alpha that is not -> dead, stopped
-//   stage 2 (counted): r.r; not finite -> dead, stopped, the iteration does not count and y never sees it; else rr, beta, the count,
-//                      the convergence and max_it decisions.  CV_APPLY tells the direction kernel of THIS iteration whether it counted
-//   stage 3 (closing): the squared true residual; not finite (an H that is not) -> dead, reported as infinity
+//   stage 2 (counted): r.r, cg_counted
+//   stage 3 (closing): the squared true residual, cg_true_residual
 // A stopped run passes stages 1 and 2 unchanged.
 __global__ void __launch_bounds__(RANGE_THREADS) cv_scalar_kernel(const double* __restrict__ partial, int nblk, double* __restrict__ S, int stage, double eta2, double tol2, int max_it)
 {
@@ -176,37 +144,17 @@ __global__ void __launch_bounds__(RANGE_THREADS) cv_scalar_kernel(const double* 
     if (stage == 0) {
         const double bb = eta2 * a;
         const bool ok = a > 0.0 && a < INFINITY && bb > 0.0 && bb < INFINITY;
-        S[CV_NORM2] = ok ? a : 0.0;
-        S[CV_BB] = ok ? bb : 0.0;
-        S[CV_RR] = ok ? bb : 0.0;
-        S[CV_DEAD] = ok ? 0.0 : 1.0;
-        S[CV_STOP] = ok ? 0.0 : 1.0;
-        return;
-    }
-    if (stage == 3) {
-        const double bb = S[CV_BB];
-        if (!(a >= 0.0 && a < INFINITY)) { S[CV_DEAD] = 1.0; S[CV_TRUE2] = INFINITY; }
-        else S[CV_TRUE2] = bb > 0.0 ? a / bb : 0.0;
-        return;
-    }
-    const bool stopped = S[CV_STOP] != 0.0;
-    if (stage == 1) {
-        if (stopped) return;
-        const double den = a + eta2 * b, alpha = S[CV_RR] / den;
-        if (!(a >= 0.0 && a < INFINITY && b >= 0.0 && b < INFINITY && den > 0.0 && den < INFINITY && alpha >= 0.0 && alpha < INFINITY)) { S[CV_DEAD] = 1.0; S[CV_STOP] = 1.0; }
-        else S[CV_ALPHA] = alpha;
-        return;
-    }
-    S[CV_APPLY] = 0.0;
-    if (stopped) return;
-    if (!(a >= 0.0 && a < INFINITY)) { S[CV_DEAD] = 1.0; S[CV_STOP] = 1.0; return; }
-    const double it = S[CV_ITER] + 1.0;
-    S[CV_BETA] = a / S[CV_RR];                                   // (rr > 0: an iteration that left rr = 0 converged and stopped the run)
-    S[CV_RR] = a;
-    S[CV_ITER] = it;
-    S[CV_APPLY] = 1.0;
-    if (a <= tol2 * S[CV_BB]) { S[CV_CONV] = 1.0; S[CV_STOP] = 1.0; }
-    else if (it >= (double)max_it) S[CV_STOP] = 1.0;
+        S[CG_NORM2] = ok ? a : 0.0;
+        S[CG_BB] = ok ? bb : 0.0;
+        S[CG_RR] = ok ? bb : 0.0;
+        S[CG_DEAD] = ok ? 0.0 : 1.0;
+        S[CG_STOP] = ok ? 0.0 : 1.0;
+    } else if (stage == 1) {
+        if (S[CG_STOP] != 0.0) return;
+        const double den = a + eta2 * b, alpha = S[CG_RR] / den;
+        cg_accept_alpha(S, den, alpha, a >= 0.0 && a < INFINITY && b >= 0.0 && b < INFINITY);
+    } else if (stage == 2) cg_counted(S, a, tol2, max_it);
+    else cg_true_residual(S, a);
 }
 
 }  // namespace
@@ -222,61 +170,33 @@ extern "C" dmrgx_status dmrgx_kron_correction_vector(dmrgx_kron_plan* plan, cons
     if (!plan || !v0_dev || !Y_dev || !norm2 || !stats || (nu > 0 && (!im || (X_dev && !re)))) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_correction_vector: null argument");
     if (!(eta > 0.0 && eta < INFINITY) || !(fabs(sigma) < INFINITY))
         DMRGX_FAIL(DMRGX_ERR_ARG, "kron_correction_vector: sigma %g, eta %g: a finite sigma and a positive finite eta are needed", sigma, eta);
-    if (!(tol >= 0.0) || tol >= 1.0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_correction_vector: tol %g outside [0, 1)", tol);
-    if (max_it < 1) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_correction_vector: max_it %d, at least one iteration is needed", max_it);
-    if (check_every < 0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_correction_vector: check_every %d is negative", check_every);
-    if (nu < 0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_correction_vector: nu %d is negative", nu);
-    int64_t n = 0;
-    DMRGX_CHK(whole_plan_states(plan, "kron_correction_vector", "iteration", &n));
-    if (nu > 0 && (!U_dev || ldu < n)) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_correction_vector: U is null or ldu %lld is smaller than n_states %lld", (long long)ldu, (long long)n);
-    const size_t nn = (size_t)n, u_span = nu > 0 ? (size_t)(nu - 1) * (size_t)ldu + nn : 0;
+    CgRun run("kron_correction_vector", st);
+    DMRGX_CHK(run.check(plan, tol, max_it, check_every, nu, U_dev, ldu));
+    const int64_t n = run.n;
+    const size_t nn = run.nn, u_span = run.u_span;
     if (spans_overlap(Y_dev, nn, v0_dev, nn) || spans_overlap(X_dev, nn, v0_dev, nn) || spans_overlap(Y_dev, nn, X_dev, nn) || spans_overlap(Y_dev, nn, U_dev, u_span) ||
         spans_overlap(X_dev, nn, U_dev, u_span))
         DMRGX_FAIL(DMRGX_ERR_ARG, "kron_correction_vector: Y or X overlaps v0, U or the other one");
-    const double tol_ = tol > 0.0 ? tol : 1e-8, tol2 = tol_ * tol_, eta2 = eta * eta;
-    const int64_t ce = check_every > 0 ? check_every : 8;
-    const int nblk = range_blocks(n);
-    const size_t nscal = (size_t)CV_NS + 2 * (size_t)nu;
-    const bool yvec = ((uintptr_t)Y_dev & 15) == 0;
-
-    DevBuf dR, dP, dSv, dT, dPartial;
-    DevScalars dS;
-    DMRGX_CHK(dR.alloc_f64(nn, st));
-    DMRGX_CHK(dP.alloc_f64(nn, st));
-    DMRGX_CHK(dSv.alloc_f64(nn, st));
-    DMRGX_CHK(dT.alloc_f64(nn, st));
-    DMRGX_CHK(dPartial.alloc_f64((size_t)2 * nblk, st));
-    DMRGX_CHK(dS.alloc_zeroed(nscal, st));
-    double* S = dS.dev();
-    double* P = dPartial.as<double>();
-    double* r = dR.as<double>();
-    double* p = dP.as<double>();
-    double* s = dSv.as<double>();
-    double* t = dT.as<double>();
+    DMRGX_CHK(run.alloc(2, (size_t)CG_NS + 2 * (size_t)nu));
+    const double tol2 = run.tol2, eta2 = eta * eta;
+    const int nblk = run.nblk;
+    double *const S = run.S, *const P = run.P, *const r = run.vec(0), *const p = run.vec(1), *const s = run.vec(2), *const t = run.vec(3);
     const dim3 grid((unsigned)nblk), block(RANGE_THREADS), one(1);
 
     hipLaunchKernelGGL(cv_norm2_kernel, grid, block, 0, st, v0_dev, n, P);
     hipLaunchKernelGGL(cv_scalar_kernel, one, block, 0, st, (const double*)P, nblk, S, 0, eta2, tol2, (int)max_it);
     hipLaunchKernelGGL(cv_start_kernel, grid, block, 0, st, v0_dev, r, p, Y_dev, n, eta, (const double*)S);
     DMRGX_HIP(hipGetLastError());
-    std::vector<double> head(CV_NS), host(nscal);
-    int64_t blocks = 0;
-    for (;;) {
-        for (int64_t k = 0; k < ce; ++k) {
-            DMRGX_CHK(dmrgx_kron_apply(plan, p, t, st));
-            hipLaunchKernelGGL(cv_s_kernel, grid, block, 0, st, (const double*)t, (const double*)p, s, n, sigma, (const double*)S, P);
-            hipLaunchKernelGGL(cv_scalar_kernel, one, block, 0, st, (const double*)P, nblk, S, 1, eta2, tol2, (int)max_it);
-            DMRGX_CHK(dmrgx_kron_apply(plan, s, t, st));
-            hipLaunchKernelGGL(cv_residual_kernel, grid, block, 0, st, (const double*)t, (const double*)s, (const double*)p, r, n, sigma, eta2, (const double*)S, P);
-            hipLaunchKernelGGL(cv_scalar_kernel, one, block, 0, st, (const double*)P, nblk, S, 2, eta2, tol2, (int)max_it);
-            if (yvec) hipLaunchKernelGGL(cv_direction_kernel<true>, grid, block, 0, st, (const double*)r, p, Y_dev, n, (const double*)S);
-            else hipLaunchKernelGGL(cv_direction_kernel<false>, grid, block, 0, st, (const double*)r, p, Y_dev, n, (const double*)S);
-            DMRGX_HIP(hipGetLastError());
-        }
-        ++blocks;
-        DMRGX_CHK(dS.read(head, st));                                // the one place where the host looks at the device
-        if (head[CV_STOP] != 0.0) break;
-    }
+    DMRGX_CHK(run.iterate([&]() -> dmrgx_status {
+        DMRGX_CHK(dmrgx_kron_apply(plan, p, t, st));
+        hipLaunchKernelGGL(cv_s_kernel, grid, block, 0, st, (const double*)t, (const double*)p, s, n, sigma, (const double*)S, P);
+        hipLaunchKernelGGL(cv_scalar_kernel, one, block, 0, st, (const double*)P, nblk, S, 1, eta2, tol2, (int)max_it);
+        DMRGX_CHK(dmrgx_kron_apply(plan, s, t, st));
+        hipLaunchKernelGGL(cv_residual_kernel, grid, block, 0, st, (const double*)t, (const double*)s, (const double*)p, r, n, sigma, eta2, (const double*)S, P);
+        hipLaunchKernelGGL(cv_scalar_kernel, one, block, 0, st, (const double*)P, nblk, S, 2, eta2, tol2, (int)max_it);
+        run.direction(r, p, Y_dev);
+        return DMRGX_OK;
+    }));
     // closing: X and the true residual of the returned Y, through the same two (x, y) pairs
     DMRGX_HIP(hipMemcpyAsync(p, Y_dev, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
     DMRGX_CHK(dmrgx_kron_apply(plan, p, t, st));
@@ -286,21 +206,14 @@ extern "C" dmrgx_status dmrgx_kron_correction_vector(dmrgx_kron_plan* plan, cons
     hipLaunchKernelGGL(cv_scalar_kernel, one, block, 0, st, (const double*)P, nblk, S, 3, eta2, tol2, (int)max_it);
     DMRGX_HIP(hipGetLastError());
     if (nu > 0) {
-        DMRGX_CHK(dmrgx_vec_gram(nu, 1, n, U_dev, ldu, Y_dev, n, S + CV_NS, 1, 0, nullptr, st));
-        if (X_dev) DMRGX_CHK(dmrgx_vec_gram(nu, 1, n, U_dev, ldu, X_dev, n, S + CV_NS + nu, 1, 0, nullptr, st));
+        DMRGX_CHK(dmrgx_vec_gram(nu, 1, n, U_dev, ldu, Y_dev, n, S + CG_NS, 1, 0, nullptr, st));
+        if (X_dev) DMRGX_CHK(dmrgx_vec_gram(nu, 1, n, U_dev, ldu, X_dev, n, S + CG_NS + nu, 1, 0, nullptr, st));
     }
-    DMRGX_CHK(dS.read(host, st));
-    const double bb = host[CV_BB];
-    *norm2 = host[CV_NORM2];
-    stats->iterations = (int32_t)host[CV_ITER];
-    stats->converged = host[CV_CONV] != 0.0;
-    stats->dead = host[CV_DEAD] != 0.0;
-    stats->n_matvec = (int32_t)std::min<int64_t>(2 * blocks * ce + 2, std::numeric_limits<int32_t>::max());
-    stats->residual = bb > 0.0 ? std::sqrt(host[CV_RR] / bb) : 0.0;
-    stats->true_residual = std::sqrt(host[CV_TRUE2]);
+    DMRGX_CHK(run.finish(2, 2, stats));
+    *norm2 = run.host[CG_NORM2];
     for (int32_t i = 0; i < nu; ++i) {
-        im[i] = host[CV_NS + i];
-        if (X_dev) re[i] = host[CV_NS + nu + i];
+        im[i] = run.host[CG_NS + i];
+        if (X_dev) re[i] = run.host[CG_NS + nu + i];
     }
     return DMRGX_OK;
 }

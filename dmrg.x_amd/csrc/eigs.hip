@@ -14,6 +14,7 @@
 // world_size > 1: vectors are this rank's stripe segment; per Lanczos step there are exactly two fused all-reduces (of
 // j+2 doubles each) and one all-gather of the Krylov vector before the MatMult.
 #include "krylov.h"
+#include "ritz.h"
 #include <mutex>
 #include <algorithm>
 #include <chrono>
@@ -546,57 +547,10 @@ gd_reduce_look_kernel(const double* __restrict__ partial, double* __restrict__ o
     if (threadIdx.x == 0 && i == look_idx) { look[0] = t; look[1] = S->theta; look[2] = S->hv0_2; }
 }
 
-// counter-based uniform(-1,1) start vector (splitmix64 of seed + global index)
+// the random start vector: element e takes value e + index_offset of the seed's stream (splitmix_uniform, krylov.h)
 __global__ void random_fill_kernel(double* __restrict__ v, int64_t n, uint64_t seed, int64_t index_offset)
 {
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-        uint64_t z = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(e + index_offset + 1);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        z ^= z >> 31;
-        v[e] = (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
-    }
-}
-
-// symmetric eigen-decomposition of a small dense matrix by cyclic Jacobi (host); ascending eigenvalues,
-// eigenvectors in the columns of Q (row-major n x n)
-void jacobi_eigh(int n, std::vector<double>& A, std::vector<double>& w, std::vector<double>& Q)
-{
-    Q.assign((size_t)n * n, 0.0);
-    for (int i = 0; i < n; ++i) Q[(size_t)i * n + i] = 1.0;
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        double off = 0.0, diag = 0.0;
-        for (int i = 0; i < n; ++i) { diag += A[(size_t)i * n + i] * A[(size_t)i * n + i]; for (int j = i + 1; j < n; ++j) off += A[(size_t)i * n + j] * A[(size_t)i * n + j]; }
-        if (off <= 1e-32 * (diag + off) || off == 0.0) break;
-        for (int p = 0; p < n - 1; ++p)
-            for (int q = p + 1; q < n; ++q) {
-                const double apq = A[(size_t)p * n + q];
-                if (apq == 0.0) continue;
-                const double app = A[(size_t)p * n + p], aqq = A[(size_t)q * n + q];
-                const double tau = (aqq - app) / (2.0 * apq);
-                const double t = (tau >= 0 ? 1.0 : -1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
-                const double c = 1.0 / std::sqrt(1.0 + t * t), s = t * c;
-                for (int k = 0; k < n; ++k) {
-                    const double akp = A[(size_t)k * n + p], akq = A[(size_t)k * n + q];
-                    A[(size_t)k * n + p] = c * akp - s * akq; A[(size_t)k * n + q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double apk = A[(size_t)p * n + k], aqk = A[(size_t)q * n + k];
-                    A[(size_t)p * n + k] = c * apk - s * aqk; A[(size_t)q * n + k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double qkp = Q[(size_t)k * n + p], qkq = Q[(size_t)k * n + q];
-                    Q[(size_t)k * n + p] = c * qkp - s * qkq; Q[(size_t)k * n + q] = s * qkp + c * qkq;
-                }
-            }
-    }
-    std::vector<int> idx(n);
-    for (int i = 0; i < n; ++i) idx[i] = i;
-    std::sort(idx.begin(), idx.end(), [&](int a, int b) { return A[(size_t)a * n + a] < A[(size_t)b * n + b]; });
-    w.resize(n);
-    std::vector<double> Qs((size_t)n * n);
-    for (int j = 0; j < n; ++j) { w[j] = A[(size_t)idx[j] * n + idx[j]]; for (int i = 0; i < n; ++i) Qs[(size_t)i * n + j] = Q[(size_t)i * n + idx[j]]; }
-    Q.swap(Qs);
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) v[e] = splitmix_uniform(seed, e + index_offset);
 }
 
 }  // namespace
@@ -838,26 +792,6 @@ struct EigsRun {
     dmrgx_status eigs_lanczos();
     dmrgx_status eigs_davidson();
 };
-
-// Rayleigh-Ritz on the leading mm columns of a cycle's projected matrix.  The cycle began with kept.size() Ritz vectors, whose block is
-// diag(kept); the later columns come from the coefficient rows the device recorded (hbuf: `row` doubles per step, slot m + 1 beta^2).
-struct Ritz {
-    std::vector<double> th, Q;      // ascending Ritz values, their vectors in the columns (row-major mm x mm)
-    double resid;                   // residual estimate of the lowest pair: |beta_mm Q[mm - 1][0]|
-};
-Ritz ritz_of_leading(int mm, int m, int row, const std::vector<double>& hbuf, const std::vector<double>& kept)
-{
-    const int k = (int)kept.size();
-    std::vector<double> A((size_t)mm * mm, 0.0);
-    for (int j = 0; j < mm; ++j) for (int i = 0; i <= j; ++i) {
-        const double v = j >= k ? hbuf[(size_t)j * row + i] : (i == j ? kept[j] : 0.0);
-        A[(size_t)i * mm + j] = v; A[(size_t)j * mm + i] = v;
-    }
-    Ritz r;
-    jacobi_eigh(mm, A, r.th, r.Q);
-    r.resid = std::fabs(std::sqrt(std::max(0.0, hbuf[(size_t)(mm - 1) * row + m + 1])) * r.Q[(size_t)(mm - 1) * mm + 0]);
-    return r;
-}
 
 // ---- thick-restart Lanczos (opts->method == 0, and whatever the Davidson path does not take) ------------------------------------
 dmrgx_status EigsRun::eigs_lanczos()

@@ -19,6 +19,7 @@
 // step's only synchronisation), solves the projected problem by Jacobi rotations and uploads the restart rotation, which is applied
 // in place: a workgroup owns its range of every row.
 #include "krylov.h"
+#include "ritz.h"
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -36,16 +37,10 @@ __global__ void __launch_bounds__(RANGE_THREADS) eo_copy_rows_kernel(const doubl
     for (int64_t e = range_first(); e < range_end(n); e += RANGE_THREADS) d[e] = s[e];
 }
 
-// counter-based uniform(-1,1) values: the stream of eigs.hip's random start vector (splitmix64 of seed + index)
+// the random start vector of eigs.hip, in the range layout: element e takes value e of the seed's stream (splitmix_uniform, krylov.h)
 __global__ void __launch_bounds__(RANGE_THREADS) eo_random_kernel(double* __restrict__ v, int64_t n, uint64_t seed)
 {
-    for (int64_t e = range_first(); e < range_end(n); e += RANGE_THREADS) {
-        uint64_t z = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(e + 1);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        z ^= z >> 31;
-        v[e] = (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
-    }
+    for (int64_t e = range_first(); e < range_end(n); e += RANGE_THREADS) v[e] = splitmix_uniform(seed, e);
 }
 
 // Passes 1 and 2.  SUB: w -= sum_{k < nk} c[k] B[k] first, and w is stored.  Then partial[k * gridDim.x + b] = <B[k], w> over block b's
@@ -193,53 +188,6 @@ __global__ void __launch_bounds__(RANGE_THREADS) eo_combine_kernel(const double*
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-// all eigenpairs of the symmetric A (row-major order n, destroyed) by cyclic Jacobi: ascending values, vectors in the columns of Q
-void eo_eigh(int n, std::vector<double>& A, std::vector<double>& w, std::vector<double>& Q)
-{
-    auto a = [&](int i, int j) -> double& { return A[(size_t)i * n + j]; };
-    std::vector<double> U((size_t)n * n, 0.0);
-    for (int i = 0; i < n; ++i) U[(size_t)i * n + i] = 1.0;
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        double off = 0.0, diag = 0.0;
-        for (int i = 0; i < n; ++i) { diag += a(i, i) * a(i, i); for (int j = i + 1; j < n; ++j) off += a(i, j) * a(i, j); }
-        if (off <= 1e-32 * (diag + off) || off == 0.0) break;
-        for (int p = 0; p < n - 1; ++p)
-            for (int q = p + 1; q < n; ++q) {
-                const double apq = a(p, q);
-                if (apq == 0.0) continue;
-                const double tau = (a(q, q) - a(p, p)) / (2.0 * apq);
-                const double t = (tau >= 0 ? 1.0 : -1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
-                const double c = 1.0 / std::sqrt(1.0 + t * t), s = t * c;
-                for (int k = 0; k < n; ++k) { const double x = a(k, p), y = a(k, q); a(k, p) = c * x - s * y; a(k, q) = s * x + c * y; }
-                for (int k = 0; k < n; ++k) { const double x = a(p, k), y = a(q, k); a(p, k) = c * x - s * y; a(q, k) = s * x + c * y; }
-                for (int k = 0; k < n; ++k) { double& x = U[(size_t)k * n + p]; double& y = U[(size_t)k * n + q]; const double u = x, v = y; x = c * u - s * v; y = s * u + c * v; }
-            }
-    }
-    std::vector<int> idx(n);
-    for (int i = 0; i < n; ++i) idx[i] = i;
-    std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return a(x, x) < a(y, y); });
-    w.resize(n);
-    Q.assign((size_t)n * n, 0.0);
-    for (int j = 0; j < n; ++j) { w[j] = a(idx[j], idx[j]); for (int i = 0; i < n; ++i) Q[(size_t)i * n + j] = U[(size_t)i * n + idx[j]]; }
-}
-
-// Rayleigh-Ritz on the leading mm columns of a cycle's projected matrix: diag(kept) on the Ritz vectors the cycle began with, then the
-// coefficient rows the device recorded (hbuf: `row` doubles per step, slot m + 1 beta^2).  resid = |beta_mm Q[mm - 1][0]|.
-struct EoRitz { std::vector<double> th, Q; double resid; };
-EoRitz eo_ritz(int mm, int m, int row, const std::vector<double>& hbuf, const std::vector<double>& kept)
-{
-    const int k = (int)kept.size();
-    std::vector<double> A((size_t)mm * mm, 0.0);
-    for (int j = 0; j < mm; ++j) for (int i = 0; i <= j; ++i) {
-        const double v = j >= k ? hbuf[(size_t)j * row + i] : (i == j ? kept[j] : 0.0);
-        A[(size_t)i * mm + j] = v; A[(size_t)j * mm + i] = v;
-    }
-    EoRitz r;
-    eo_eigh(mm, A, r.th, r.Q);
-    r.resid = std::fabs(std::sqrt(std::max(0.0, hbuf[(size_t)(mm - 1) * row + m + 1])) * r.Q[(size_t)(mm - 1) * mm + 0]);
-    return r;
-}
-
 // One deflated solve: the device buffers and the launches of the passes
 struct OrthRun {
     hipStream_t st;
@@ -351,7 +299,7 @@ extern "C" dmrgx_status dmrgx_eigs_lowest_orth(dmrgx_kron_plan* plan, const dmrg
     int k = 0, n_matvec = 0, restarts = 0, converged = 0, mm = 0;
     double resid = 0.0, lambda = 0.0;
     while (true) {
-        EoRitz ritz;
+        Ritz ritz;
         bool early = false;
         for (int j = k; j < m; ++j) {
             DMRGX_CHK(dmrgx_kron_apply(plan, R.x, R.w, st));
@@ -361,7 +309,7 @@ extern "C" dmrgx_status dmrgx_eigs_lowest_orth(dmrgx_kron_plan* plan, const dmrg
             DMRGX_HIP(hipMemcpyAsync(hbuf.data() + (size_t)j * row, Hrow(j), (size_t)row * sizeof(double), hipMemcpyDeviceToHost, st));
             DMRGX_HIP(hipStreamSynchronize(st));
             mm = j + 1;
-            ritz = eo_ritz(mm, m, row, hbuf, kept);
+            ritz = ritz_of_leading(mm, m, row, hbuf, kept);
             if (mm < m && ritz.resid <= tol * std::max(std::fabs(ritz.th[0]), 1e-300)) { early = true; break; }
         }
         lambda = ritz.th[0];

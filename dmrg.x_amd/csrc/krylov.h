@@ -1,8 +1,15 @@
-// What the device-resident Krylov calls share (lanczos.hip, corrvec.hip, response.hip; the single-value sums of eigs.hip and lib.hip; the range layout,
-// pair accesses and host side of project_out.hip, whose sums are pairs of doubles in the same order): the workgroup
-// sum in wave order, 16-byte pair accesses with a ragged tail, the range layout, and the host-side checks and scalar array.  Internal,
-// not part of the ABI.  Every sum here has ONE order -- lanes by shuffle-down 32..1, waves 0..3, block partials b, b + THREADS, .. per
-// thread -- and the bits of every caller depend on it.  Multi-value reductions (red[wave][i]) are deliberately not covered.
+// What the device-resident Krylov calls share: the workgroup sum in wave order, 16-byte pair accesses with a ragged tail, the range layout,
+// the random start-vector stream, and the host-side checks and scalar array.  Internal, not part of the ABI.  Who uses what:
+//   lanczos.hip                  all of it but the stream
+//   corrvec.hip, response.hip    all of it but the stream, through cg.h, which adds what a conjugate-gradient run shares on top
+//   eigs_orth.hip                the sums, pair accesses and range layout, the stream, whole_plan_states, DevScalars
+//   eigs.hip                     the single-value sums and the stream (its random start vector is eigs_orth.hip's)
+//   project_out.hip              the range layout, pair accesses and host side; its sums are pairs of doubles in the same order
+//   lib.hip                      the single-value sums
+//   states_expand.hip            spans_overlap
+// The host side of a Lanczos restart cycle that eigs.hip and eigs_orth.hip share (Jacobi, Rayleigh-Ritz) is ritz.h.
+// Every sum here has ONE order -- lanes by shuffle-down 32..1, waves 0..3, block partials b, b + THREADS, .. per thread -- and the bits
+// of every caller depend on it.  Multi-value reductions (red[wave][i]) are deliberately not covered.
 #pragma once
 #include "common.h"
 
@@ -62,6 +69,16 @@ __device__ __forceinline__ int64_t range_end(int64_t n) {
     return end < n ? end : n;
 }
 inline int range_blocks(int64_t n) { return (int)std::max<int64_t>(1, (n + RANGE_LEN - 1) / RANGE_LEN); }
+
+// value `index` of the counter-based uniform(-1, 1) stream of `seed` (splitmix64 of seed + index + 1): the random start vectors.  A value
+// depends on its index alone, whatever the kernel's loop looks like.
+__device__ __forceinline__ double splitmix_uniform(uint64_t seed, int64_t index) {
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(index + 1);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+}
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 // *n = n_states of a plan that one rank holds whole; a striped plan is refused in the name of `call`, whose `noun` has no collectives

@@ -22,16 +22,15 @@
 // After the loop: <q, X> / q.q q leaves X, d = X, t = H d, s = t - sigma d, true residual |b - (s - gamma q)| / |b|; one dmrgx_vec_gram
 // for the overlaps.  The MatMult sees the pair (d, t) only.  Iterations are enqueued in blocks of check_every; one small copy per block
 // brings the scalars back.  Fixed grids, partials added in block order by one workgroup, no atomics: the same bits whatever check_every is.
-#include "krylov.h"
-#include <cmath>
-#include <limits>
+// What this run shares with corrvec.hip -- the scalar slots, the direction kernel, the decisions of scalars 1 and 2, the checks, the block
+// loop, the stats -- is cg.h.
+#include "cg.h"
 
 namespace dmrgx {
 namespace {
 
-// the device scalars; the overlaps <u_i, X> follow from RS_NS on
-enum : int { RS_PP = 0, RS_COEF = 1, RS_VV = 2, RS_NORM2 = 3, RS_BB = 4, RS_RR = 5, RS_ALPHA = 6, RS_GAMMA = 7, RS_BETA = 8, RS_DELTA = 9, RS_ITER = 10, RS_CONV = 11,
-             RS_DEAD = 12, RS_STOP = 13, RS_APPLY = 14, RS_NONE = 15, RS_TRUE2 = 16, RS_NS = 18 };
+// this solver's device scalars, after the common ones; the overlaps <u_i, X> follow from RS_NS on
+enum : int { RS_NONE = CG_NS, RS_PP, RS_DELTA, RS_COEF, RS_VV, RS_GAMMA, RS_NS };
 
 // partial[b], [nblk + b], [2 nblk + b] = p . p, p . v0, v0 . v0 over block b's range.  (p, v0 are the caller's: 8-byte loads)
 __global__ void __launch_bounds__(RANGE_THREADS) rs_start_dots_kernel(const double* __restrict__ p, const double* __restrict__ v0, int64_t n, double* __restrict__ partial)
@@ -53,7 +52,7 @@ __global__ void __launch_bounds__(RANGE_THREADS) rs_start_dots_kernel(const doub
 __global__ void __launch_bounds__(RANGE_THREADS) rs_start_kernel(const double* __restrict__ p, const double* __restrict__ v0, double* __restrict__ q, double* __restrict__ r,
                                                                 double* __restrict__ d, double* __restrict__ x, int64_t n, const double* __restrict__ S, double* __restrict__ partial)
 {
-    const bool dead = S[RS_DEAD] != 0.0;
+    const bool dead = S[CG_DEAD] != 0.0;
     const double coef = S[RS_COEF];
     double acc = 0.0;
     for (int64_t e = range_first(); e < range_end(n); e += RANGE_THREADS) {
@@ -72,7 +71,7 @@ __global__ void __launch_bounds__(RANGE_THREADS) rs_start_kernel(const double* _
 __global__ void __launch_bounds__(RANGE_THREADS) rs_dots_kernel(double* __restrict__ t, const double* __restrict__ d, const double* __restrict__ q, int64_t n, double sigma,
                                                                const double* __restrict__ S, double* __restrict__ partial)
 {
-    if (S[RS_STOP] != 0.0) return;
+    if (S[CG_STOP] != 0.0) return;
     double2 tr[RANGE_PAIRS], dr[RANGE_PAIRS], qr[RANGE_PAIRS];
 #pragma unroll
     for (int i = 0; i < RANGE_PAIRS; ++i) {
@@ -101,8 +100,8 @@ __global__ void __launch_bounds__(RANGE_THREADS) rs_dots_kernel(double* __restri
 __global__ void __launch_bounds__(RANGE_THREADS) rs_residual_kernel(const double* __restrict__ s, const double* __restrict__ q, double* __restrict__ r, int64_t n,
                                                                    const double* __restrict__ S, double* __restrict__ partial)
 {
-    if (S[RS_STOP] != 0.0) return;
-    const double alpha = S[RS_ALPHA], gamma = S[RS_GAMMA], delta = S[RS_DELTA];
+    if (S[CG_STOP] != 0.0) return;
+    const double alpha = S[CG_ALPHA], gamma = S[RS_GAMMA], delta = S[RS_DELTA];
     double2 sr[RANGE_PAIRS], qr[RANGE_PAIRS], rr[RANGE_PAIRS];
 #pragma unroll
     for (int i = 0; i < RANGE_PAIRS; ++i) {
@@ -125,36 +124,6 @@ __global__ void __launch_bounds__(RANGE_THREADS) rs_residual_kernel(const double
     acc = block_sum<RANGE_THREADS>(acc);
     qa = block_sum<RANGE_THREADS>(qa);
     if (threadIdx.x == 0) { partial[blockIdx.x] = acc; partial[gridDim.x + blockIdx.x] = qa; }
-}
-
-// the iteration counted: x += alpha d, and d = r + beta d unless that iteration converged.  XVEC: the caller's x is 16-byte aligned
-template <bool XVEC> __global__ void __launch_bounds__(RANGE_THREADS) rs_direction_kernel(const double* __restrict__ r, double* __restrict__ d, double* __restrict__ x, int64_t n,
-                                                                                         const double* __restrict__ S)
-{
-    if (S[RS_APPLY] == 0.0) return;
-    const double alpha = S[RS_ALPHA], beta = S[RS_BETA];
-    const bool turn = S[RS_CONV] == 0.0;
-    double2 rr[RANGE_PAIRS], dr[RANGE_PAIRS], xr[RANGE_PAIRS];
-#pragma unroll
-    for (int i = 0; i < RANGE_PAIRS; ++i) {
-        const int64_t e = range_pair(i);
-        if (turn) rr[i] = load2<true>(r, e, n);
-        dr[i] = load2<true>(d, e, n);
-        xr[i] = load2<XVEC>(x, e, n);
-    }
-#pragma unroll
-    for (int i = 0; i < RANGE_PAIRS; ++i) {
-        const int64_t e = range_pair(i);
-        double2 v;
-        v.x = xr[i].x + alpha * dr[i].x;
-        v.y = xr[i].y + alpha * dr[i].y;
-        store2<XVEC>(x, e, n, v);
-        if (turn) {
-            v.x = rr[i].x + beta * dr[i].x;
-            v.y = rr[i].y + beta * dr[i].y;
-            store2<true>(d, e, n, v);
-        }
-    }
 }
 
 // closing 1: partial[b] = q . x over block b.  (x: the caller's, 8-byte loads)
@@ -207,12 +176,10 @@ __global__ void __launch_bounds__(RANGE_THREADS) rs_true_residual_kernel(const d
 //   stage 0 (p, v0):   p.p, p.v0, v0.v0; p.p not positive and finite, or a coefficient that is not finite -> dead, stopped, no right-hand side
 //   stage 1 (b):       |Q v0|^2; at most 1e-24 v0.v0, or not positive and finite: v0 is a multiple of p to rounding -> converged at once
 //   stage 2 (alpha):   d.s and q.s; a sum that is not finite, d.A d not positive and finite, or an alpha that is not -> dead, stopped
-//   stage 3 (counted): r.r and q.r; not finite -> dead, stopped, the iteration does not count and x never sees it; else rr, beta,
-//                      delta, the count, the convergence and max_it decisions.  RS_APPLY tells the direction kernel of THIS iteration
-//                      whether it counted
+//   stage 3 (counted): r.r and q.r; cg_counted, and delta = q.r / q.q of an iteration that counted
 //   stage 4 (q.x):     delta = q.x / q.q for the closing clean-up (0 when it is not finite)
 //   stage 5 (q.s):     gamma = q.s / q.q of the closing MatMult (0 when it is not finite: the residual then tells)
-//   stage 6 (closing): the squared true residual; not finite (an H that is not) -> dead, reported as infinity
+//   stage 6 (closing): the squared true residual, cg_true_residual
 // A stopped run passes stages 2 and 3 unchanged.
 __global__ void __launch_bounds__(RANGE_THREADS) rs_scalar_kernel(const double* __restrict__ partial, int nblk, double* __restrict__ S, int stage, double tol2, int max_it)
 {
@@ -226,19 +193,19 @@ __global__ void __launch_bounds__(RANGE_THREADS) rs_scalar_kernel(const double* 
         S[RS_PP] = ok ? a : 0.0;
         S[RS_COEF] = ok ? coef : 0.0;
         S[RS_VV] = c;
-        S[RS_DEAD] = ok ? 0.0 : 1.0;
-        S[RS_STOP] = ok ? 0.0 : 1.0;
+        S[CG_DEAD] = ok ? 0.0 : 1.0;
+        S[CG_STOP] = ok ? 0.0 : 1.0;
         S[RS_NONE] = ok ? 0.0 : 1.0;
         return;
     }
     if (stage == 1) {
-        if (S[RS_DEAD] != 0.0) return;
+        if (S[CG_DEAD] != 0.0) return;
         const bool finite = a >= 0.0 && a < INFINITY;
         const bool ok = finite && a > 0.0 && a > 1e-24 * S[RS_VV];
-        S[RS_NORM2] = finite ? a : 0.0;
-        S[RS_BB] = ok ? a : 0.0;
-        S[RS_RR] = ok ? a : 0.0;
-        if (!ok) { S[RS_CONV] = 1.0; S[RS_STOP] = 1.0; S[RS_NONE] = 1.0; }
+        S[CG_NORM2] = finite ? a : 0.0;
+        S[CG_BB] = ok ? a : 0.0;
+        S[CG_RR] = ok ? a : 0.0;
+        if (!ok) { S[CG_CONV] = 1.0; S[CG_STOP] = 1.0; S[RS_NONE] = 1.0; }
         return;
     }
     if (stage == 4 || stage == 5) {
@@ -246,32 +213,16 @@ __global__ void __launch_bounds__(RANGE_THREADS) rs_scalar_kernel(const double* 
         S[stage == 4 ? RS_DELTA : RS_GAMMA] = fabs(v) < INFINITY ? v : 0.0;
         return;
     }
-    if (stage == 6) {
-        const double bb = S[RS_BB];
-        if (!(a >= 0.0 && a < INFINITY)) { S[RS_DEAD] = 1.0; S[RS_TRUE2] = INFINITY; }
-        else S[RS_TRUE2] = bb > 0.0 ? a / bb : 0.0;
-        return;
-    }
-    const bool stopped = S[RS_STOP] != 0.0;
+    if (stage == 6) { cg_true_residual(S, a); return; }
     if (stage == 2) {
-        if (stopped) return;
-        const double alpha = S[RS_RR] / a, gamma = b / S[RS_PP];
-        if (!(a > 0.0 && a < INFINITY && fabs(b) < INFINITY && alpha >= 0.0 && alpha < INFINITY && fabs(gamma) < INFINITY)) { S[RS_DEAD] = 1.0; S[RS_STOP] = 1.0; }
-        else { S[RS_ALPHA] = alpha; S[RS_GAMMA] = gamma; }
+        if (S[CG_STOP] != 0.0) return;
+        const double alpha = S[CG_RR] / a, gamma = b / S[RS_PP];
+        if (cg_accept_alpha(S, a, alpha, fabs(b) < INFINITY && fabs(gamma) < INFINITY)) S[RS_GAMMA] = gamma;
         return;
     }
-    S[RS_APPLY] = 0.0;
-    if (stopped) return;
+    // stage 3: a delta that is not finite kills the run as a sum that is not does -- cg_counted sees an r.r that is not finite
     const double delta = b / S[RS_PP];
-    if (!(a >= 0.0 && a < INFINITY && fabs(delta) < INFINITY)) { S[RS_DEAD] = 1.0; S[RS_STOP] = 1.0; return; }
-    const double it = S[RS_ITER] + 1.0;
-    S[RS_BETA] = a / S[RS_RR];                                   // (rr > 0: an iteration that left rr = 0 converged and stopped the run)
-    S[RS_DELTA] = delta;
-    S[RS_RR] = a;
-    S[RS_ITER] = it;
-    S[RS_APPLY] = 1.0;
-    if (a <= tol2 * S[RS_BB]) { S[RS_CONV] = 1.0; S[RS_STOP] = 1.0; }
-    else if (it >= (double)max_it) S[RS_STOP] = 1.0;
+    if (cg_counted(S, fabs(delta) < INFINITY ? a : INFINITY, tol2, max_it)) S[RS_DELTA] = delta;
 }
 
 }  // namespace
@@ -286,36 +237,16 @@ extern "C" dmrgx_status dmrgx_kron_static_response(dmrgx_kron_plan* plan, const 
     hipStream_t st = (hipStream_t)stream;
     if (!plan || !p_dev || !v0_dev || !X_dev || !coef || !norm2 || !stats || (nu > 0 && !chi)) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_static_response: null argument");
     if (!(fabs(sigma) < INFINITY)) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_static_response: sigma %g is not finite", sigma);
-    if (!(tol >= 0.0) || tol >= 1.0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_static_response: tol %g outside [0, 1)", tol);
-    if (max_it < 1) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_static_response: max_it %d, at least one iteration is needed", max_it);
-    if (check_every < 0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_static_response: check_every %d is negative", check_every);
-    if (nu < 0) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_static_response: nu %d is negative", nu);
-    int64_t n = 0;
-    DMRGX_CHK(whole_plan_states(plan, "kron_static_response", "iteration", &n));
-    if (nu > 0 && (!U_dev || ldu < n)) DMRGX_FAIL(DMRGX_ERR_ARG, "kron_static_response: U is null or ldu %lld is smaller than n_states %lld", (long long)ldu, (long long)n);
-    const size_t nn = (size_t)n, u_span = nu > 0 ? (size_t)(nu - 1) * (size_t)ldu + nn : 0;
-    if (spans_overlap(X_dev, nn, p_dev, nn) || spans_overlap(X_dev, nn, v0_dev, nn) || spans_overlap(X_dev, nn, U_dev, u_span))
+    CgRun run("kron_static_response", st);
+    DMRGX_CHK(run.check(plan, tol, max_it, check_every, nu, U_dev, ldu));
+    const int64_t n = run.n;
+    const size_t nn = run.nn;
+    if (spans_overlap(X_dev, nn, p_dev, nn) || spans_overlap(X_dev, nn, v0_dev, nn) || spans_overlap(X_dev, nn, U_dev, run.u_span))
         DMRGX_FAIL(DMRGX_ERR_ARG, "kron_static_response: X overlaps p, v0 or U");
-    const double tol_ = tol > 0.0 ? tol : 1e-8, tol2 = tol_ * tol_;
-    const int64_t ce = check_every > 0 ? check_every : 8;
-    const int nblk = range_blocks(n);
-    const size_t nscal = (size_t)RS_NS + (size_t)nu;
-    const bool xvec = ((uintptr_t)X_dev & 15) == 0;
-
-    DevBuf dR, dD, dT, dQ, dPartial;
-    DevScalars dS;
-    DMRGX_CHK(dR.alloc_f64(nn, st));
-    DMRGX_CHK(dD.alloc_f64(nn, st));
-    DMRGX_CHK(dT.alloc_f64(nn, st));
-    DMRGX_CHK(dQ.alloc_f64(nn, st));
-    DMRGX_CHK(dPartial.alloc_f64((size_t)3 * nblk, st));
-    DMRGX_CHK(dS.alloc_zeroed(nscal, st));
-    double* S = dS.dev();
-    double* P = dPartial.as<double>();
-    double* r = dR.as<double>();
-    double* d = dD.as<double>();
-    double* t = dT.as<double>();
-    double* q = dQ.as<double>();
+    DMRGX_CHK(run.alloc(3, (size_t)RS_NS + (size_t)nu));
+    const double tol2 = run.tol2;
+    const int nblk = run.nblk;
+    double *const S = run.S, *const P = run.P, *const r = run.vec(0), *const d = run.vec(1), *const t = run.vec(2), *const q = run.vec(3);
     const dim3 grid((unsigned)nblk), block(RANGE_THREADS), one(1);
 
     hipLaunchKernelGGL(rs_start_dots_kernel, grid, block, 0, st, p_dev, v0_dev, n, P);
@@ -323,23 +254,15 @@ extern "C" dmrgx_status dmrgx_kron_static_response(dmrgx_kron_plan* plan, const 
     hipLaunchKernelGGL(rs_start_kernel, grid, block, 0, st, p_dev, v0_dev, q, r, d, X_dev, n, (const double*)S, P);
     hipLaunchKernelGGL(rs_scalar_kernel, one, block, 0, st, (const double*)P, nblk, S, 1, tol2, (int)max_it);
     DMRGX_HIP(hipGetLastError());
-    std::vector<double> head(RS_NS), host(nscal);
-    int64_t blocks = 0;
-    for (;;) {
-        for (int64_t k = 0; k < ce; ++k) {
-            DMRGX_CHK(dmrgx_kron_apply(plan, d, t, st));
-            hipLaunchKernelGGL(rs_dots_kernel, grid, block, 0, st, t, (const double*)d, (const double*)q, n, sigma, (const double*)S, P);
-            hipLaunchKernelGGL(rs_scalar_kernel, one, block, 0, st, (const double*)P, nblk, S, 2, tol2, (int)max_it);
-            hipLaunchKernelGGL(rs_residual_kernel, grid, block, 0, st, (const double*)t, (const double*)q, r, n, (const double*)S, P);
-            hipLaunchKernelGGL(rs_scalar_kernel, one, block, 0, st, (const double*)P, nblk, S, 3, tol2, (int)max_it);
-            if (xvec) hipLaunchKernelGGL(rs_direction_kernel<true>, grid, block, 0, st, (const double*)r, d, X_dev, n, (const double*)S);
-            else hipLaunchKernelGGL(rs_direction_kernel<false>, grid, block, 0, st, (const double*)r, d, X_dev, n, (const double*)S);
-            DMRGX_HIP(hipGetLastError());
-        }
-        ++blocks;
-        DMRGX_CHK(dS.read(head, st));                                // the one place where the host looks at the device
-        if (head[RS_STOP] != 0.0) break;
-    }
+    DMRGX_CHK(run.iterate([&]() -> dmrgx_status {
+        DMRGX_CHK(dmrgx_kron_apply(plan, d, t, st));
+        hipLaunchKernelGGL(rs_dots_kernel, grid, block, 0, st, t, (const double*)d, (const double*)q, n, sigma, (const double*)S, P);
+        hipLaunchKernelGGL(rs_scalar_kernel, one, block, 0, st, (const double*)P, nblk, S, 2, tol2, (int)max_it);
+        hipLaunchKernelGGL(rs_residual_kernel, grid, block, 0, st, (const double*)t, (const double*)q, r, n, (const double*)S, P);
+        hipLaunchKernelGGL(rs_scalar_kernel, one, block, 0, st, (const double*)P, nblk, S, 3, tol2, (int)max_it);
+        run.direction(r, d, X_dev);
+        return DMRGX_OK;
+    }));
     // closing: what rounding left of p in X goes, then the true residual of the returned X through the same (d, t) pair
     hipLaunchKernelGGL(rs_qx_kernel, grid, block, 0, st, (const double*)q, (const double*)X_dev, n, P);
     hipLaunchKernelGGL(rs_scalar_kernel, one, block, 0, st, (const double*)P, nblk, S, 4, tol2, (int)max_it);
@@ -352,16 +275,9 @@ extern "C" dmrgx_status dmrgx_kron_static_response(dmrgx_kron_plan* plan, const 
     hipLaunchKernelGGL(rs_scalar_kernel, one, block, 0, st, (const double*)P, nblk, S, 6, tol2, (int)max_it);
     DMRGX_HIP(hipGetLastError());
     if (nu > 0) DMRGX_CHK(dmrgx_vec_gram(nu, 1, n, U_dev, ldu, X_dev, n, S + RS_NS, 1, 0, nullptr, st));
-    DMRGX_CHK(dS.read(host, st));
-    const double bb = host[RS_BB];
-    *coef = host[RS_COEF];
-    *norm2 = host[RS_NORM2];
-    stats->iterations = (int32_t)host[RS_ITER];
-    stats->converged = host[RS_CONV] != 0.0;
-    stats->dead = host[RS_DEAD] != 0.0;
-    stats->n_matvec = (int32_t)std::min<int64_t>(blocks * ce + 1, std::numeric_limits<int32_t>::max());
-    stats->residual = bb > 0.0 ? std::sqrt(host[RS_RR] / bb) : 0.0;
-    stats->true_residual = std::sqrt(host[RS_TRUE2]);
-    for (int32_t i = 0; i < nu; ++i) chi[i] = host[RS_NS + i];
+    DMRGX_CHK(run.finish(1, 1, stats));
+    *coef = run.host[RS_COEF];
+    *norm2 = run.host[CG_NORM2];
+    for (int32_t i = 0; i < nu; ++i) chi[i] = run.host[RS_NS + i];
     return DMRGX_OK;
 }

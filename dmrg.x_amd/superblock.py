@@ -21,6 +21,14 @@ def _i32(values):
     return arr
 
 
+def _rows_arg(T, n):
+    """(count, pointer, row_stride) of an optional 2-D f64 device tensor of rows of at least n elements with unit stride along the row."""
+    if T is None:
+        return 0, C.c_void_p(), 0
+    assert T.dtype == torch.float64 and T.dim() == 2 and T.shape[1] >= n and (T.shape[1] <= 1 or T.stride(1) == 1)
+    return T.shape[0], C.c_void_p(T.data_ptr()), T.stride(0) if T.shape[0] > 1 else max(T.stride(0), T.shape[1])
+
+
 class KronPlan:
     def __init__(self, sb, device="cuda:0", world_size=1, rank=0, stream=None):
         _capi.require_device()          # fails loudly without a GPU: no CPU fallback
@@ -148,10 +156,7 @@ class KronPlan:
         when Q holds the states already found.  Q: None (no row: the call forwards to dmrgx_eigs_lowest), or a 2-D f64 device tensor of
         nq rows with unit stride along the vector (its row stride is the library's ldq), only read.  psi0: a start vector, projected
         against Q by the library.  Returns (e, psi, stats); psi is orthogonal to Q."""
-        nq, q_ptr, ldq = 0, C.c_void_p(), 0
-        if Q is not None:
-            assert Q.dtype == torch.float64 and Q.dim() == 2 and Q.shape[1] >= self.info.n_states and (Q.shape[1] <= 1 or Q.stride(1) == 1)
-            nq, q_ptr, ldq = Q.shape[0], C.c_void_p(Q.data_ptr()), Q.stride(0) if Q.shape[0] > 1 else max(Q.stride(0), Q.shape[1])
+        nq, q_ptr, ldq = _rows_arg(Q, self.info.n_states)
         opts = _capi.EigsOpts()
         opts.ncv, opts.max_it, opts.tol, opts.seed, opts.min_initial_norm2 = ncv, max_it, tol, seed, min_initial_norm2
         psi = self.new_vector()
@@ -199,10 +204,7 @@ class KronPlan:
         mu_cross[n, i] = <U[i], t_n>; beyond 2 nsteps_done and beyond row nsteps_done everything is zero."""
         assert v0.dtype == torch.float64 and v0.is_contiguous() and v0.numel() >= self.info.n_states
         K = max(int(nsteps), 0)
-        nu, u_ptr, ldu = 0, C.c_void_p(), 0
-        if U is not None:
-            assert U.dtype == torch.float64 and U.dim() == 2 and U.shape[1] >= self.info.n_states and (U.shape[1] <= 1 or U.stride(1) == 1)
-            nu, u_ptr, ldu = U.shape[0], C.c_void_p(U.data_ptr()), U.stride(0) if U.shape[0] > 1 else max(U.stride(0), U.shape[1])
+        nu, u_ptr, ldu = _rows_arg(U, self.info.n_states)
         norm2, done = C.c_double(0.0), C.c_int32(0)
         diag, cross = (C.c_double * (2 * K + 1))(), (C.c_double * max((K + 1) * nu, 1))()
         _capi.check(_capi.lib().dmrgx_kron_chebyshev_moments(self._handle, C.c_void_p(v0.data_ptr()), float(centre), float(half_width), int(nsteps), int(nu), u_ptr,
@@ -218,10 +220,7 @@ class KronPlan:
         dmrgx_cv_stats: iterations, converged, n_matvec, dead, residual, true_residual.  Not converging within max_it is no error."""
         assert v0.dtype == torch.float64 and v0.is_contiguous() and v0.numel() >= self.info.n_states
         n = self.info.n_states
-        nu, u_ptr, ldu = 0, C.c_void_p(), 0
-        if U is not None:
-            assert U.dtype == torch.float64 and U.dim() == 2 and U.shape[1] >= n and (U.shape[1] <= 1 or U.stride(1) == 1)
-            nu, u_ptr, ldu = U.shape[0], C.c_void_p(U.data_ptr()), U.stride(0) if U.shape[0] > 1 else max(U.stride(0), U.shape[1])
+        nu, u_ptr, ldu = _rows_arg(U, n)
         Y = torch.empty(n, dtype=torch.float64, device=v0.device)
         X = torch.empty(n, dtype=torch.float64, device=v0.device) if want_real else None
         norm2, stats = C.c_double(0.0), _capi.CvStats()
@@ -244,10 +243,7 @@ class KronPlan:
         n = self.info.n_states
         for w in (p, v0):
             assert w.dtype == torch.float64 and w.is_contiguous() and w.numel() >= n
-        nu, u_ptr, ldu = 0, C.c_void_p(), 0
-        if U is not None:
-            assert U.dtype == torch.float64 and U.dim() == 2 and U.shape[1] >= n and (U.shape[1] <= 1 or U.stride(1) == 1)
-            nu, u_ptr, ldu = U.shape[0], C.c_void_p(U.data_ptr()), U.stride(0) if U.shape[0] > 1 else max(U.stride(0), U.shape[1])
+        nu, u_ptr, ldu = _rows_arg(U, n)
         if X is None:
             X = torch.empty(n, dtype=torch.float64, device=v0.device)
         assert X.dtype == torch.float64 and X.is_contiguous() and X.numel() >= n

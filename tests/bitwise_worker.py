@@ -136,7 +136,8 @@ def krylov(out):
     into a fresh V (ldv = n, odd: 8-byte loads) and into a view of a wider tensor with an even row stride (16-byte loads); the Chebyshev
     run of 17 steps crosses one Gram block of 16 rows; the correction vector runs with check_every 0 and 3 and into a Y 8 bytes off a
     16-byte boundary (eta and sigma as in test_gpu_corrvec.CASES[0]: 0.5 and the spectrum's lower end, -33.53 and -93.84 to four digits;
-    a numpy restatement converges to 1e-10 in 270 and 324 iterations)."""
+    a numpy restatement converges to 1e-10 in 270 and 324 iterations); the static response of v0 on the complement of the ground state runs
+    the same three ways, and the deflated solve finds the first excited state from its random start vector."""
     import ctypes as C
     from dmrgx_amd import _capi
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -171,6 +172,19 @@ def krylov(out):
         assert torch.isnan(ys[[0, n + 1]]).all()
         keep("cv_offset", ("Y", "norm2", "im"), (ys[1:n + 1], norm2.value, np.array(im[:])))
         keep("cv_offset", [k for k, _ in _capi.CvStats._fields_], [getattr(stats, k) for k, _ in _capi.CvStats._fields_])
+        # the static response on the complement of the ground state, as the correction vector above: check_every 0 and 3, and into an
+        # X 8 bytes off a 16-byte boundary; then the first excited state by the deflated solve
+        e0, p, _ = plan.eigs_lowest(tol=1e-12)
+        for ce in (0, 3):
+            rs = plan.static_response(p, v0, e0, tol=1e-10, max_it=600, check_every=ce, U=U)
+            keep("rs_ce%d" % ce, sorted(rs), [rs[k] for k in sorted(rs)])
+        xs = torch.full((n + 2,), float("nan"), dtype=torch.float64, device="cuda")
+        assert xs[1:].data_ptr() % 16 == 8
+        rs = plan.static_response(p, v0, e0, tol=1e-10, max_it=600, U=U, X=xs[1:n + 1])
+        assert torch.isnan(xs[[0, n + 1]]).all()
+        keep("rs_offset", sorted(rs), [rs[k] for k in sorted(rs)])
+        e1, psi1, s1 = plan.eigs_lowest_orth(Q=p[None, :], tol=1e-10, seed=7)
+        keep("orth", ("e", "psi", "n_matvec", "n_restart", "converged", "residual"), (e1, psi1, s1.n_matvec, s1.n_restart, s1.converged, s1.residual))
         dot = C.c_double(0.0)
         _capi.check(_capi.lib().dmrgx_dot(n, C.c_void_p(v0.data_ptr()), C.c_void_p(U[1].data_ptr()), C.byref(dot), None))
         keep("dot", ("v0_u1",), (dot.value,))
